@@ -3,10 +3,18 @@
 target names).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--circuit audit|withdraw] [--batch B] [--mode weak|strong] [--total T]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one batch of independent proofs, every row a DIFFERENT witness (spp/workload.py: audit rows sk_i = 12345 + i,
 Random(1000 + i) as SURVEY 8d Config 3; withdraw rows = distinct notes of one tree), inputs already resident in HBM, proofs
 (388 B) and public witnesses written to HBM.
+
+A plain run does only what the headline needs: setup, warm-up, the K timed steps of the headline circuit, one JSON line.
+--full adds everything else: the roofline probe, the CPU baseline, the verification of the last batch, the other legs of the
+headline circuit (single proof, host-buffer entry, strong-scaling rehearsal, clock at the secrets) and the other circuits and
+configs; the --no-* options thin a --full run out again.  --dump-outputs DIR writes what the last timed step computed (rank 0's
+proofs, public witnesses and status words, as float32 arrays of their bytes / values) to DIR/*.npy; rows and blinding factors
+are fixed, so two builds can be compared output for output.
 
 N > 1: one process per GPU.  Launched by the driver through torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment) or, when WORLD_SIZE is absent, by this script itself: `python bench.py --gpus N` starts N rank processes
@@ -15,9 +23,9 @@ RCCL (timed as pk_bcast_ms, outside the metric), and every rank proves its own r
   --mode weak   (default) B proofs per GPU per step                      -> "scaling": "weak"
   --mode strong a fixed total of T proofs per step (default 1024 = BASELINE.json configs[2]) cut into contiguous blocks with
                 spp.multi.shard_range                                    -> "scaling": "strong"
-Rank 0 prints ONE JSON line.  At N = 1 the line also carries the withdraw circuit (own shape, the reference's R1CS size, the
-depth-20 variant), the RLWE witness kernel on 2^16 instances (configs[3]) and the 2^24-point Pippenger MSM (configs[4]).
-`roofline` prices the dominant kernel (k_msm_flat<G1>, the table walk of kernels_msm.hip) against the HBM peak from a serialised probe (three steps on one
+Rank 0 prints ONE JSON line.  With --full at N = 1 the line also carries the withdraw circuit (own shape, the reference's R1CS
+size, the depth-20 variant), the RLWE witness kernel on 2^16 instances (configs[3]) and the 2^24-point Pippenger MSM (configs[4]).
+With --full, `roofline` prices the dominant kernel (k_msm_flat<G1>, the table walk of kernels_msm.hip) against the HBM peak from a serialised probe (three steps on one
 stream after the timed region, durations from the dispatches' own timestamps) -- in the pipelined timed region the same
 dispatches share the chip with the other batch and last longer; both figures are in the line.  `cpu_baseline` times the
 oracle's C/OpenMP prover on a bounded sample of the same rows on this host (reported baseline, not the target).
@@ -57,6 +65,10 @@ def parse_args(argv=None):
     ap.add_argument("--mode", default="weak", choices=["weak", "strong"])
     ap.add_argument("--total", type=int, default=1024, help="strong mode: proofs per step over all GPUs (BASELINE.json configs[2]: 1024)")
     ap.add_argument("--window", type=int, default=int(os.environ.get("SPP_WINDOW", "0")), help="MSM window bits; 0 = auto (largest tables within the HBM budget)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline, roofline probe, verification, the headline circuit's other legs "
+                                                        "and the other circuits / configs (off: the headline steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's proofs, public witnesses and status "
+                                                                        "(rank 0) as float32 .npy files under DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline circuit only (profiling runs)")
     ap.add_argument("--no-other-circuits", action="store_true", help="headline circuit with its own legs (rehearsal, end to end), none of the other circuits / configs")
@@ -118,6 +130,28 @@ def launch_ranks(args, argv):
 def libspp_sha256():
     import hashlib
     return hashlib.sha256(open(os.path.join(ROOT, "shielded-pool-pinocchio-solana_amd", "libspp.so"), "rb").read()).hexdigest()
+
+
+DUMP_MAX_BYTES = 60 * 10 ** 6
+
+
+def dump_outputs(out_dir, proofs, pws, status):
+    """--dump-outputs: what a caller of spp_prove_batch_device receives from the last timed step -- proof bytes [B, 388],
+    public-witness bytes [B, pw_len], status words [B] -- as float32 .npy files (every value is exact in float32).  A batch
+    whose arrays exceed DUMP_MAX_BYTES is cut to a fixed, seeded sample of rows, named by row_index.npy."""
+    import numpy as np
+    arrays = {"proofs": proofs, "public_witness": pws, "status": status}
+    rows = proofs.shape[0]
+    per_row = 4 * sum(t[0].numel() for t in arrays.values())
+    keep = None
+    if rows * per_row > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_MAX_BYTES // (per_row + 8), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a if keep is None else a[keep])
+    if keep is not None:
+        np.save(os.path.join(out_dir, "row_index.npy"), keep.astype(np.float64))
 
 
 def dry_run(args, rank, world, dist, coll_dev):
@@ -305,9 +339,10 @@ def main():
     from oracle import native
     rlwe_pk = json.load(open(os.path.join(ROOT, "tests", "golden", "rlwe_pk.json")))
 
-    def run_circuit(circuit, B, steps, warmup, want_cpu, strong_total=0):
-        """One circuit: setup, load, distinct rows, timed steps, checks.  Returns the result dict on rank 0, None elsewhere.
-        strong_total > 0: this rank proves rows shard_range(strong_total, rank, world) of the fixed batch."""
+    def run_circuit(circuit, B, steps, warmup, want_cpu, strong_total=0, dump_dir=None):
+        """One circuit: setup, load, distinct rows, timed steps; with --full the probes, legs and checks after them.  Returns the
+        result dict on rank 0, None elsewhere.  strong_total > 0: this rank proves rows shard_range(strong_total, rank, world) of
+        the fixed batch.  dump_dir: rank 0 writes the last timed step's outputs there."""
         tmp = tempfile.mkdtemp(prefix="spp_bench_%d_" % rank)
         sppc, pkp, vkp = (os.path.join(tmp, "c." + e) for e in ("sppc", "pk", "vk"))
         if circuit == "withdraw_acir":
@@ -406,11 +441,28 @@ def main():
             total_proofs = int(cnt.item())
         assert int(status[0].abs().sum().item()) + int(status[1].abs().sum().item()) == 0, "some synthetic proofs were refused"
         take(0)           # events of the last timed step (already complete)
+        last = (warmup + steps - 1) & 1
+        if dump_dir and rank == 0:   # before any leg below reuses the output buffers
+            dump_outputs(dump_dir, proofs[last].view(B, 388), pws[last].view(B, h.pw_len), status[last])
 
-        if rank != 0:
+        out = None
+        if rank == 0:
+            out = {"value": round(total_proofs * steps / elapsed, 3), "ms_per_step": round(elapsed / steps * 1e3, 3), "steps": steps, "warmup": warmup,
+                   "config": {"workload": "%s, batch of %d independent proofs per GPU per step, every row a distinct witness" % (WORKLOADS[circuit], B),
+                              "circuit": circuit, "n_constraints": h.n_constraints, "n_wires": h.n_wires, "domain": 1 << h.domain_log,
+                              "batch_per_gpu": B, "n_distinct_witnesses": n_distinct, "proofs_per_step_all_gpus": total_proofs,
+                              "msm_windows": dict(zip(INFO_ORDER, h.msm_windows())), "msm_sizes": dict(zip(INFO_ORDER, h.msm_sizes())),
+                              "table_bytes": h.table_bytes, "parallelism": "independent proofs x%d" % world,
+                              "pk_bcast_ms": round(bcast_ms, 3), "pk_bcast_backend": (backend if dist is not None else None), "pk_bytes": pk_bytes,
+                              "setup_s": round(setup_s, 2), "load_s": round(load_s, 2), "rows_synth_s": round(rows_s, 2)},
+                   "stage_ms_per_step_pipelined": {k: round(v / acc["n"], 3) for k, v in zip(
+                       ["solve+commit", "matrix_eval", "ntt_qap", "msm_g1", "msm_g2_side_stream_join", "assemble", "total"], acc["stage"])}}
+        if rank != 0 or not args.full:
             h.close()
             ctx.close()
-            return None
+            del inp, rs, proofs, pws, status
+            torch.cuda.empty_cache()
+            return out
 
         # ---- serialised roofline probe: one stream, one batch in flight, so a dispatch's duration is its own ----
         h.set_serial(True)
@@ -565,7 +617,6 @@ def main():
 
         # the timed batches produced real proofs: every proof of the last pipelined batch through the batched GPU verifier,
         # two of them also through the host verifier
-        last = (warmup + steps - 1) & 1
         pbytes, wbytes = proofs[last].cpu().numpy().tobytes(), pws[last].cpu().numpy().tobytes()
         vkb = open(vkp, "rb").read()
         for i in (0, B - 1):
@@ -573,10 +624,7 @@ def main():
         all_ok = ctx.verify_batch(vkb, [pbytes[388 * i:388 * (i + 1)] for i in range(B)], [wbytes[h.pw_len * i:h.pw_len * (i + 1)] for i in range(B)])
         assert all(all_ok), "%d proofs of the last timed batch do not verify" % (B - sum(all_ok))
 
-        value = total_proofs * steps / elapsed
-        ms_per_step = elapsed / steps * 1e3
-        sizes = dict(zip(INFO_ORDER, h.msm_sizes()))
-        windows = dict(zip(INFO_ORDER, h.msm_windows()))
+        sizes = out["config"]["msm_sizes"]
         # algorithmic bytes of one k_msm_flat launch over a batch (64 B per base once + one 32 B scalar per (base, proof))
         alg = {s: (128 if s.startswith("B2") else 64) * sizes[s] + 32 * sizes[s] * B for s in SETS}
         g1 = ["A", "B1", "K", "Z"]     # the four k_msm_flat<Fq> launches of a step (CB / CS: small row-per-window tables, k_msm_rows)
@@ -597,18 +645,10 @@ def main():
                 valu_util = pmc.get("k_msm_flat_g1_valu_issue_util_serialised")
         except Exception:
             pass
-        out = {
-            "value": round(value, 3), "ms_per_step": round(ms_per_step, 3), "steps": steps, "warmup": warmup,
-            "config": {"workload": "%s, batch of %d independent proofs per GPU per step, every row a distinct witness" % (WORKLOADS[circuit], B),
-                       "circuit": circuit, "n_constraints": h.n_constraints, "n_wires": h.n_wires, "domain": 1 << h.domain_log,
-                       "batch_per_gpu": B, "n_distinct_witnesses": n_distinct, "proofs_per_step_all_gpus": total_proofs,
-                       "msm_windows": windows, "msm_sizes": sizes, "table_bytes": h.table_bytes, "parallelism": "independent proofs x%d" % world,
-                       "pk_bcast_ms": round(bcast_ms, 3), "pk_bcast_backend": (backend if dist is not None else None), "pk_bytes": pk_bytes, "setup_s": round(setup_s, 2), "load_s": round(load_s, 2),
-                       "rows_synth_s": round(rows_s, 2), "host_buffer_entry_proofs_per_s": None if host_rate is None else round(host_rate, 1),
-                       "last_timed_batch_verified": "all %d proofs accepted by spp_verify_batch (GPU), two of them also by spp_verify (host)" % B,
-                       "host_buffer_entry_note": "one spp_prove_batch call with host pointers for 4 batches' worth of proofs: PCIe copies included, chunks pipelined inside libspp"},
-            "stage_ms_per_step_pipelined": {k: round(v / acc["n"], 3) for k, v in zip(
-                ["solve+commit", "matrix_eval", "ntt_qap", "msm_g1", "msm_g2_side_stream_join", "assemble", "total"], acc["stage"])},
+        out["config"].update({"host_buffer_entry_proofs_per_s": None if host_rate is None else round(host_rate, 1),
+                              "last_timed_batch_verified": "all %d proofs accepted by spp_verify_batch (GPU), two of them also by spp_verify (host)" % B,
+                              "host_buffer_entry_note": "one spp_prove_batch call with host pointers for 4 batches' worth of proofs: PCIe copies included, chunks pipelined inside libspp"})
+        out.update({
             "stage_ms_per_step_serialised": {k: round(v / probe["n"], 3) for k, v in zip(
                 ["solve+commit", "matrix_eval", "ntt_qap", "msm_g1", "msm_g2", "assemble", "total"], probe["stage"])},
             "roofline": {"bound": "hbm", "kernel": "k_msm_flat<Fq>", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -623,7 +663,7 @@ def main():
                          "msm_table_rows": dict(zip(INFO_ORDER, h.msm_table_rows())),
                          "note": "integer-VALU bound (about 2.3K instructions, 1.5K of them v_mad_u64_u32, per mixed addition; 16-17 additions per "
                                  "full-size scalar with single-row 15/16-bit tables); HBM fraction of the algorithmic bytes reported as mandated"},
-        }
+        })
         if single is not None:
             out["single_proof"] = single
         if rehearsal is not None:
@@ -854,9 +894,10 @@ def main():
         print(json.dumps({"withdraw_reference_gnark_r1cs": reference_r1cs_leg()}), flush=True)
         return
     B0 = args.batch or DEFAULT_BATCH[args.circuit]
-    main_res = run_circuit(args.circuit, B0, args.steps, args.warmup, not args.no_cpu_baseline and world == 1, args.total if strong else 0)
+    main_res = run_circuit(args.circuit, B0, args.steps, args.warmup, args.full and not args.no_cpu_baseline and world == 1,
+                           args.total if strong else 0, dump_dir=args.dump_outputs)
     extras = {}
-    if world == 1 and not args.no_extras and not args.no_other_circuits and not strong:
+    if args.full and world == 1 and not args.no_extras and not args.no_other_circuits and not strong:
         # the other circuits / configs of BASELINE.json, each at >= 10 timed steps, in the same line so that the driver times them
         want = not args.no_cpu_baseline
         other = "withdraw" if args.circuit == "audit" else "audit"

@@ -449,6 +449,34 @@ def test_committed_bench_line_follows_the_contract():
     assert pmc["circuit"] == "audit" and pmc["batch"] == 2048 and pmc["n_distinct_witnesses"] == 2048
 
 
+def test_bench_dump_outputs_writes_float32_arrays_within_the_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: the last step's proof bytes, public-witness bytes and status words as float32 .npy files, exact;
+    a batch above the cap is cut to the same seeded sample of rows on every run."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(1)
+    B, pw_len = 64, 108
+    pr = torch.randint(0, 256, (B, 388), generator=g, dtype=torch.uint8)
+    pw = torch.randint(0, 256, (B, pw_len), generator=g, dtype=torch.uint8)
+    st = torch.zeros(B, dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "all"), pr, pw, st)
+    assert sorted(os.listdir(tmp_path / "all")) == ["proofs.npy", "public_witness.npy", "status.npy"]
+    for name, t in (("proofs", pr), ("public_witness", pw), ("status", st)):
+        a = np.load(str(tmp_path / "all" / (name + ".npy")))
+        assert a.dtype == np.float32 and (a == t.numpy()).all(), name
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20 * 4 * (388 + pw_len + 1))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), pr, pw, st)
+    idx = np.load(str(tmp_path / "s1" / "row_index.npy"))
+    assert (idx == np.load(str(tmp_path / "s2" / "row_index.npy"))).all() and len(idx) < 20 and (np.diff(idx) > 0).all()
+    assert (np.load(str(tmp_path / "s1" / "proofs.npy")) == pr.numpy()[idx.astype(int)]).all()
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(tmp_path / "s1")) < 20 * 4 * (388 + pw_len + 1) + 1024
+
+
 def _depth20_rows(count):
     import random
     from oracle import hashes as H
