@@ -14,6 +14,8 @@
  *   spp_poseidon_*            client/merkle.ts:22-38,119-140,165-221 (circomlibjs Poseidon, Merkle tree)
  *   spp_grumpkin_keygen_batch client/merkle.ts:98-113 generateIdentityKeypair
  *   spp_audit_inputs_batch    scripts/generate_audit.py:468-641 (everything before `nargo execute`)
+ *   spp_prove_withdraw_notes  client/payroll-demo.ts:323-340 (getRoot / getProof / generateProof per recipient) against the
+ *                             resident tree (spp_merkle_tree_*)
  *   spp_verify                `sunspot verify` noir_circuit/prove_linux.sh:86-87, audit_circuit/prove_audit.sh:98-99
  *   spp_verify_batch          the same for many proofs on the GPU
  *   spp_shamir_reconstruct / spp_rlwe_decrypt_batch   scripts/rlwe_decrypt.py:61-132, demo-frontend/app/lib/shamir.ts:97-169
@@ -57,6 +59,7 @@ extern "C" {
 #define SPP_WITHDRAW_PW_LEN 172  /* withdraw.rs:14-16 */
 #define SPP_AUDIT_PW_LEN 76      /* submit_audit.rs:19-21 */
 #define SPP_TREE_DEPTH 16        /* noir_circuit/src/main.nr:5 */
+#define SPP_NOTE_LEN 160         /* one withdraw note: recipient | amount | secret_key | randomness | index, 5 x 32 B */
 
 typedef struct spp_ctx spp_ctx;
 typedef struct spp_circuit spp_circuit;
@@ -231,6 +234,36 @@ int spp_audit_inputs_batch_device(spp_ctx* ctx, const void* d_pk_a, const void* 
  * e1 count*64 int8, rs count*64 B), outputs as spp_prove_batch_device.  Asynchronous, pipelined like spp_prove_batch_device. */
 int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk, const void* d_r,
                                         const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs, void* d_pws, void* d_status);
+
+/* Withdraw proofs from notes against the resident tree: the withdraw counterpart of the call above.  Replaces the per-recipient
+ * loop of client/payroll-demo.ts:323-340 -- generateIdentityKeypair (client/merkle.ts:98-113), wa_commitment and nullifier
+ * (payroll-demo.ts:264-271), mt.getRoot() / mt.getProof(index) (client/merkle.ts:165-176,198-221), generateProof -- with one
+ * kernel that expands each note into a withdraw row on the device.
+ *   note = recipient | amount | secret_key | randomness | index    (SPP_NOTE_LEN = 5 x 32 B big-endian, main.nr:38-51)
+ *   row  = root | nullifier | recipient | amount | wa_commitment | secret_key | owner_x | owner_y | randomness | index |
+ *          siblings[depth]                                        (10 + depth fields, the order spp_prove_withdraw packs)
+ * owner = secret_key * G (Grumpkin), wa_commitment = H(owner_x, owner_y), nullifier = H(secret_key, index); root and siblings are
+ * the tree's (default hashes for absent nodes).  The note commitment H(owner_x, owner_y, amount, randomness) is not recomputed:
+ * a note that is not the leaf at `index` (another leaf, an empty slot, index >= 2^depth -- siblings are then the level defaults
+ * and no tree memory is read), amount >= 2^64 or recipient == 0 gives a row the circuit refuses, in place (status != 0).
+ * Refused with SPP_ERR_BAD_INPUT: a circuit that is not SPP_CIRCUIT_WITHDRAW, one whose input count is not 10 + the tree's depth,
+ * a tree of another spp_ctx, NULL pointers; by the host entry points also any note field >= r.  count == 0 is SPP_OK.
+ *
+ * Snapshot: every proof of one call is against the root of the tree at the time of the call.  The rows are gathered on the
+ * tree's stream, in stream order with spp_merkle_tree_insert, so leaves inserted after the call returns -- even while its
+ * proofs are still in flight -- are not seen by it; spp_prove_withdraw_notes builds all rows before its first chunk is proved.
+ */
+/* rows only (host buffers): notes = count * SPP_NOTE_LEN B -> rows = count * (10 + depth) * 32 B, ready for spp_prove_batch */
+int spp_withdraw_rows_from_tree(spp_merkle_tree* t, size_t count, const uint8_t* notes, uint8_t* rows);
+/* end to end on the device (device pointers: notes count * SPP_NOTE_LEN B, rs count * 64 B; outputs as spp_prove_batch_device),
+ * asynchronous until spp_sync(); pipelined and workspace-rotated like spp_prove_batch_device.  No field check on the notes (the
+ * contract of spp_prove_batch_device). */
+int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* t, size_t count, const void* d_notes, const void* d_rs, void* d_proofs,
+                                    void* d_pws, void* d_status);
+/* host convenience: proofs count*388, pws count*(12+32*n_public), status[count] (optional) as spp_prove_batch, which it uses for
+ * the proving (large batches in chunks); rs NULL = OS randomness.  Returns SPP_ERR_UNSAT if any note was refused. */
+int spp_prove_withdraw_notes(spp_circuit* c, spp_merkle_tree* t, size_t count, const uint8_t* notes, const uint8_t* rs, uint8_t* proofs,
+                             uint8_t* pws, int32_t* status);
 
 /* Batched verification on the GPU (`sunspot verify` for many proofs against one key, the checks of the
  * deployed verifier withdraw.rs:63-90 / submit_audit.rs:41-54): proofs = count * 388 B, pws = count * pw_len B (host

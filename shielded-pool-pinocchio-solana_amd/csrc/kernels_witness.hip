@@ -7,6 +7,7 @@
 //   k_merkle_path         noir_circuit/src/main.nr:11-29, client/merkle.ts:198-221
 //   k_merkle_level        client/merkle.ts:165-176 (getRoot: one tree level per launch)
 //   k_grumpkin_keygen     client/merkle.ts:98-113 (generateIdentityKeypair), main.nr:54-59
+//   k_withdraw_rows       client/payroll-demo.ts:323-340 (keygen, wa_commitment, nullifier, getRoot, getProof -> one withdraw row)
 //   k_poseidon2_sponge    ct_helper/src/main.nr:15-34 (= scripts/generate_audit.py:355-374)
 #include "kernels.hpp"
 #include "poseidon29.hpp"
@@ -353,11 +354,7 @@ void launch_fr_to_be(hipStream_t st, const Fr* in, uint8_t* out, uint32_t n) {
 // ----------------------------------------------------------------------------------------------------
 // Grumpkin key generation: pk = sk * G with a 4-bit window table T[j][d] = (d+1) * 16^j * G (64 x 15 used)
 // ----------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_grumpkin_keygen(const GkAffine* __restrict__ table, const uint8_t* __restrict__ sk_be,
-                                                        uint8_t* __restrict__ xy_be, uint32_t count) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= count) return;
-  Fr sk = load_be(sk_be + (size_t)g * 32);
+__device__ __forceinline__ GkAffine grumpkin_mul_g(const GkAffine* __restrict__ table, const Fr& sk) {
   uint32_t c[8];
   sk.to_canonical(c);
   GkXYZZ acc = GkXYZZ::infinity();
@@ -372,12 +369,72 @@ __global__ void __launch_bounds__(64) k_grumpkin_keygen(const GkAffine* __restri
     word >>= 4;
     if (d) acc.madd(table[j * 16 + d - 1]);
   }
-  GkAffine p = acc.to_affine();
+  return acc.to_affine();
+}
+__global__ void __launch_bounds__(64) k_grumpkin_keygen(const GkAffine* __restrict__ table, const uint8_t* __restrict__ sk_be,
+                                                        uint8_t* __restrict__ xy_be, uint32_t count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const GkAffine p = grumpkin_mul_g(table, load_be(sk_be + (size_t)g * 32));
   store_be(xy_be + (size_t)g * 64, p.x);
   store_be(xy_be + (size_t)g * 64 + 32, p.y);
 }
 void launch_grumpkin_keygen(hipStream_t st, const GkAffine* table, const uint8_t* sk_be, uint8_t* xy_be, uint32_t count) {
   if (count) hipLaunchKernelGGL(k_grumpkin_keygen, dim3((count + 63) / 64), dim3(64), 0, st, table, sk_be, xy_be, count);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Withdraw rows from notes against the resident tree (client/payroll-demo.ts:323-340: identity, wa_commitment, nullifier,
+// mt.getRoot(), mt.getProof(index)).  One lane per note; note = recipient | amount | secret_key | randomness | index (5 x 32 B
+// big-endian, main.nr:38-51), row = root | nullifier | recipient | amount | wa_commitment | secret_key | owner_x | owner_y |
+// randomness | index | siblings[depth] (spp_prove_withdraw's order).  The note commitment is not part of the row: a note that is
+// not the leaf at `index` yields a row whose Merkle root differs from the public one, and the solver's check refuses it.
+// ----------------------------------------------------------------------------------------------------
+static constexpr uint32_t NOTE_BYTES = 160;
+__device__ __forceinline__ void copy32(uint8_t* __restrict__ o, const uint8_t* __restrict__ p) {
+  for (int i = 0; i < 32; i++) o[i] = p[i];
+}
+__global__ void __launch_bounds__(64) k_withdraw_rows(const GkAffine* __restrict__ table, HashConsts hc, const MerkleTreeDev* __restrict__ t,
+                                                      const uint8_t* __restrict__ notes, uint8_t* __restrict__ rows, uint32_t count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const uint32_t depth = t->depth;
+  const uint8_t* nt = notes + (size_t)g * NOTE_BYTES;
+  uint8_t* o = rows + (size_t)g * (10 + depth) * 32;
+  const Fr sk = load_be(nt + 64);
+  const GkAffine pk = grumpkin_mul_g(table, sk);                     // merkle.ts:98-113, main.nr:54-62
+  // wa_commitment = H(owner_x, owner_y) (main.nr:64-67), then nullifier = H(secret_key, index) (:72-74): one permutation inlined
+  // in a two-trip loop.  Through the out-of-line poseidon_permute the kernel had 200 VGPRs and a 224-byte stack frame per lane
+  // (as every caller of poseidon_hash2 here); inlined: 154 VGPRs, 112 bytes (the permutation's state array), no spills.
+#pragma unroll 1
+  for (int k = 0; k < 2; k++) {
+    Fr s[3] = {Fr::zero(), k ? sk : pk.x, k ? load_be(nt + 128) : pk.y};
+    poseidon_permute29<3, false>(s, hc.pos3_rc, hc.pos3_mds29, 57, PoseidonNoEmit{});
+    store_be(o + (k ? 1 : 4) * 32, s[0]);
+  }
+  copy32(o + 2 * 32, nt);                                            // recipient
+  copy32(o + 3 * 32, nt + 32);                                       // amount
+  copy32(o + 5 * 32, nt + 64);                                       // secret_key
+  store_be(o + 6 * 32, pk.x);
+  store_be(o + 7 * 32, pk.y);
+  copy32(o + 8 * 32, nt + 96);                                       // randomness
+  copy32(o + 9 * 32, nt + 128);                                      // index
+  // the leaf index as an integer; an index >= 2^depth never touches tree memory: its siblings are the level defaults
+  bool in_range = true;
+  uint64_t idx = 0;
+  for (int i = 0; i < 24; i++) in_range &= nt[128 + i] == 0;
+  for (int i = 24; i < 32; i++) idx = (idx << 8) | nt[128 + i];
+  in_range &= (idx >> depth) == 0;
+  // root at call time (spp_merkle_tree_root), siblings as k_merkle_gather
+  store_be(o, t->count[depth] ? t->level[depth][0] : t->dflt[depth]);
+  for (uint32_t l = 0; l < depth; l++) {
+    const uint64_t sib = (idx >> l) ^ 1;
+    store_be(o + (10 + l) * 32, in_range && sib < t->count[l] ? t->level[l][sib] : t->dflt[l]);
+  }
+}
+void launch_withdraw_rows(hipStream_t st, const GkAffine* table, HashConsts hc, const MerkleTreeDev* t, const uint8_t* notes, uint8_t* rows,
+                          uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_withdraw_rows, dim3((count + 63) / 64), dim3(64), 0, st, table, hc, t, notes, rows, count);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -31,6 +31,9 @@ struct Workspace {
   hipStream_t own_st2p = nullptr;                    // side stream with a priority of its own: used by batches (see its creation)
   std::pair<hipEvent_t, hipEvent_t> g2_ev{nullptr, nullptr};   // dispatch timestamps of the G2 MSM kernel
   hipEvent_t ev_w = nullptr, ev_b2 = nullptr;
+  // withdraw rows from notes (spp_prove_withdraw_notes_device): ev_in is recorded on `st` once a batch has loaded its input rows
+  // (d_inputs may then be overwritten), ev_rows on the tree's stream once the next rows are written
+  hipEvent_t ev_in = nullptr, ev_rows = nullptr;
   size_t cap = 0, last_P = 0;
   Fr *W = nullptr, *abc = nullptr, *scratch = nullptr;
   G1Affine* commit_affine = nullptr;
@@ -1411,6 +1414,9 @@ static int load_circuit_impl(spp_ctx* ctx, const char* circuit_path, const char*
     HIP_TRY(hipEventCreate(&w.g2_ev.second));
     HIP_TRY(hipEventCreateWithFlags(&w.ev_w, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&w.ev_b2, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&w.ev_in, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&w.ev_rows, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(w.ev_in, w.st));
     for (auto& evt : w.ev) HIP_TRY(hipEventCreate(&evt));
     w.msm_ev.resize(8);
     for (auto& pr : w.msm_ev) {
@@ -1443,6 +1449,8 @@ static void destroy_circuit(spp_circuit* c) {
     if (w.g2_ev.second) hipEventDestroy(w.g2_ev.second);
     if (w.ev_w) hipEventDestroy(w.ev_w);
     if (w.ev_b2) hipEventDestroy(w.ev_b2);
+    if (w.ev_in) hipEventDestroy(w.ev_in);
+    if (w.ev_rows) hipEventDestroy(w.ev_rows);
     free_workspace(w);
     for (auto& evt : w.ev) if (evt) hipEventDestroy(evt);
     for (auto& pr : w.msm_ev) {
@@ -1596,6 +1604,7 @@ static int prove_on_device(spp_circuit* c, Workspace& w, uint32_t P, const uint8
   hipEventRecord(w.ev[0], st);
   // 1. inputs, solver phase 1, commitment, challenge, solver phase 2
   launch_load_inputs(st, d_inputs, d_rs, w.W, circ.n_inputs(), circ.n_wires, P);
+  hipEventRecord(w.ev_in, st);
   for (const SolveStep& s : c->schedule) {
     switch (s.kind) {
       case SolveStep::SEQ:
@@ -1770,6 +1779,69 @@ extern "C" int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count,
                                        (const uint8_t*)d_sk, (const int8_t*)d_r, (const int8_t*)d_e1, (const int8_t*)d_e2, w.d_inputs))
     return e;
   return prove_on_device(c, w, (uint32_t)count, w.d_inputs, (const uint8_t*)d_rs, (uint8_t*)d_proofs, (uint8_t*)d_pws, (uint32_t*)d_status);
+}
+// Withdraw proofs from notes against the resident tree (include/spp.h).  The rows are gathered on the TREE's stream (ctx->stream),
+// not on the proving stream: spp_merkle_tree_insert runs there and may reallocate the level arrays (mt_reserve), so an insert
+// made right after this call is stream-ordered behind the gather and every proof of the call is against the root at call time.
+// Under the context lock: (1) ctx->stream waits until the workspace's previous batch has loaded its rows (ev_in), (2) the rows
+// kernel writes into the workspace's d_inputs, (3) the proving stream waits for it (ev_rows).  A batch that is not a multiple
+// of the wave width is split into body and tail as in spp_prove_batch_device; the tail's rows go to the tail workspace's own
+// d_inputs, so each workspace's rows are only ever read by its own stream.
+static int withdraw_notes_args(spp_circuit* c, spp_merkle_tree* t) {
+  if (c->circ.id != SPP_CIRCUIT_WITHDRAW) return fail(SPP_ERR_BAD_INPUT, "not a withdraw circuit");
+  if (t->ctx != c->ctx) return fail(SPP_ERR_BAD_INPUT, "the tree belongs to another context");
+  if (c->circ.n_inputs() != 10 + t->depth)
+    return fail(SPP_ERR_BAD_INPUT, "the circuit takes %u inputs, a withdraw row over a depth-%u tree has %u", c->circ.n_inputs(), t->depth,
+                10 + t->depth);
+  return SPP_OK;
+}
+extern "C" int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* t, size_t count, const void* d_notes, const void* d_rs,
+                                               void* d_proofs, void* d_pws, void* d_status) {
+  if (!c || !t || !d_notes || !d_rs || !d_proofs || !d_pws || !d_status) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int e = withdraw_notes_args(c, t)) return e;
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 20)) return fail(SPP_ERR_BAD_INPUT, "batch too large");
+  spp_ctx* ctx = c->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  const int depth = ws_depth(count, c->generic_solver);
+  if (c->next_ws >= depth) c->next_ws = 0;
+  const int wi = c->next_ws, wo = (wi + 1) % depth;
+  Workspace& w = c->ws[wi];
+  c->prev_ws = c->last_ws;
+  c->last_ws = wi;
+  c->next_ws = wo;
+  for (int k = 0; k < depth; k++)
+    if (int e = ensure_workspace(c, c->ws[k], count)) return e;
+  static const bool no_split = getenv("SPP_NO_SPLIT") != nullptr;
+  const size_t tail = count > 64 && !no_split ? count % 64 : 0, body = count - tail;
+  Workspace& wt = c->ws[wo];
+  const uint8_t* notes = (const uint8_t*)d_notes;
+  HIP_TRY(hipStreamWaitEvent(ctx->stream, w.ev_in, 0));
+  if (tail) HIP_TRY(hipStreamWaitEvent(ctx->stream, wt.ev_in, 0));
+  launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes, w.d_inputs, (uint32_t)body);
+  if (tail) launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes + body * SPP_NOTE_LEN, wt.d_inputs, (uint32_t)tail);
+  HIP_TRY(hipEventRecord(w.ev_rows, ctx->stream));
+  HIP_TRY(hipStreamWaitEvent(w.st, w.ev_rows, 0));
+  if (tail) HIP_TRY(hipStreamWaitEvent(wt.st, w.ev_rows, 0));
+  if (int e = prove_on_device(c, w, (uint32_t)body, w.d_inputs, (const uint8_t*)d_rs, (uint8_t*)d_proofs, (uint8_t*)d_pws, (uint32_t*)d_status))
+    return e;
+  if (!tail) return SPP_OK;
+  const size_t pwl = 12 + 32 * (size_t)(c->circ.n_public - 1);
+  return prove_on_device(c, wt, (uint32_t)tail, wt.d_inputs, (const uint8_t*)d_rs + body * 64, (uint8_t*)d_proofs + body * SPP_PROOF_LEN,
+                         (uint8_t*)d_pws + body * pwl, (uint32_t*)d_status + body);
+}
+// Host form: all rows are built (one gather, one root) before spp_prove_batch proves them in chunks.
+extern "C" int spp_prove_withdraw_notes(spp_circuit* c, spp_merkle_tree* t, size_t count, const uint8_t* notes, const uint8_t* rs, uint8_t* proofs,
+                                        uint8_t* pws, int32_t* status) {
+  if (!c || !t || !notes || !proofs || !pws) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int e = withdraw_notes_args(c, t)) return e;
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many notes in one call");
+  std::vector<uint8_t> rows(count * c->circ.n_inputs() * 32);
+  if (int e = spp_withdraw_rows_from_tree(t, count, notes, rows.data())) return e;
+  return spp_prove_batch(c, count, rows.data(), rs, proofs, pws, status);
 }
 extern "C" int spp_commitment_challenge(spp_circuit* c, size_t count, const uint8_t* inputs, uint8_t* challenges) {
   if (!c || !inputs || !challenges) return fail(SPP_ERR_BAD_INPUT, "NULL argument");

@@ -147,6 +147,15 @@ struct spp_ctx {
   size_t audit_scratch_cap = 0;
   std::vector<void*> owned;
 };
+// incremental tree: ShieldedPoolMerkleTree (client/merkle.ts:146-222) with the levels kept in HBM (spp_witness_api.cpp)
+struct spp_merkle_tree {
+  spp_ctx* ctx = nullptr;
+  uint32_t depth = 0;
+  uint64_t n_leaves = 0, cap_leaves = 0;       // capacity of level 0 (level l holds cap_leaves >> l, + 1)
+  MerkleTreeDev host{};                        // host mirror of the device descriptor
+  MerkleTreeDev* dev = nullptr;
+  Fr* d_dflt = nullptr;                        // depth + 1 default hashes
+};
 template <class T>
 inline int ctx_upload(spp_ctx* ctx, T** dst, const std::vector<T>& src) {
   HIP_TRY(dev_upload(dst, src));
@@ -175,6 +184,8 @@ struct DevBuf {
 size_t spp_audit_scratch_bytes(size_t count);
 int spp_audit_inputs_enqueue(spp_ctx* ctx, hipStream_t st, void* scratch, const uint32_t* d_pk_a, const uint32_t* d_pk_b, uint32_t count,
                              const uint8_t* d_sk, const int8_t* d_r, const int8_t* d_e1, const int8_t* d_e2, uint8_t* d_rows);
+// withdraw notes (spp_witness_api.cpp): SPP_ERR_BAD_INPUT unless every field of every note is canonical
+int spp_check_notes(size_t count, const uint8_t* notes);
 // lazily built per-context constants (spp_witness_api.cpp)
 int spp_ensure_ctx_consts(spp_ctx* ctx);   // Poseidon / Poseidon2 constants, Grumpkin window table
 int spp_ensure_rlwe(spp_ctx* ctx);         // NTT tables of the RLWE witness kernel

@@ -219,14 +219,7 @@ extern "C" int spp_merkle_build(spp_ctx* ctx, size_t n_leaves, uint32_t depth, c
 // incremental tree: ShieldedPoolMerkleTree (client/merkle.ts:146-222) with the levels kept in HBM.  insert() appends leaves and
 // recomputes only the touched path(s): O(count + depth) hashes instead of the reference's O(2^depth) per getRoot / getProof.
 // -----------------------------------------------------------------------------------------------------
-struct spp_merkle_tree {
-  spp_ctx* ctx = nullptr;
-  uint32_t depth = 0;
-  uint64_t n_leaves = 0, cap_leaves = 0;       // capacity of level 0 (level l holds cap_leaves >> l, + 1)
-  MerkleTreeDev host{};                        // host mirror of the device descriptor
-  MerkleTreeDev* dev = nullptr;
-  Fr* d_dflt = nullptr;                        // depth + 1 default hashes
-};
+// struct spp_merkle_tree: spp_internal.hpp (the withdraw-from-notes path of spp_api.cpp reads its descriptor)
 static size_t mt_level_cap(uint64_t cap_leaves, uint32_t l) { return (size_t)(cap_leaves >> l) + 1; }
 static int mt_reserve(spp_merkle_tree* t, uint64_t want_leaves) {
   if (want_leaves <= t->cap_leaves) return 0;
@@ -340,6 +333,36 @@ extern "C" int spp_merkle_tree_proofs(spp_merkle_tree* t, size_t n, const uint64
   HIP_TRY(dout.alloc(n * t->depth * 32));
   launch_merkle_gather(st, t->dev, t->depth, di.as<uint64_t>(), (uint32_t)n, dout.as<uint8_t>());
   HIP_TRY(hipMemcpyAsync(siblings_out, dout.p, n * t->depth * 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// Withdraw rows from notes (client/payroll-demo.ts:323-340 for every recipient: identity, wa_commitment, nullifier, getRoot,
+// getProof) against the tree as it stands: one k_withdraw_rows launch on the tree's stream.
+int spp_check_notes(size_t count, const uint8_t* notes) {
+  for (size_t i = 0; i < count; i++)
+    for (int f = 0; f < 5; f++)
+      if (!be_is_canonical<FrParams>(notes + SPP_NOTE_LEN * i + 32 * f))
+        return fail(SPP_ERR_BAD_INPUT, "note %zu: field %d is not a canonical field element", i, f);
+  return SPP_OK;
+}
+extern "C" int spp_withdraw_rows_from_tree(spp_merkle_tree* t, size_t count, const uint8_t* notes, uint8_t* rows) {
+  if (!t || !notes || !rows) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many notes in one call");
+  if (int e = spp_check_notes(count, notes)) return e;
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  const size_t row_bytes = (size_t)(10 + t->depth) * 32;
+  DevBuf dn, dr;
+  UP(dn, notes, count * SPP_NOTE_LEN);
+  HIP_TRY(dr.alloc(count * row_bytes));
+  launch_withdraw_rows(st, ctx->gk_table, ctx->hc, t->dev, dn.as<uint8_t>(), dr.as<uint8_t>(), (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(rows, dr.p, count * row_bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   return SPP_OK;

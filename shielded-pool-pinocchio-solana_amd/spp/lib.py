@@ -13,6 +13,7 @@ SPP_CIRCUIT_AUDIT = 2
 SPP_CIRCUIT_WITHDRAW_DEPTH20 = 4     # build only: withdraw over a depth-20 tree (synthetic variant)
 SPP_CIRCUIT_WITHDRAW_REFSHAPE = 3   # build only: withdraw padded to the reference's R1CS size (12 452 constraints)
 PROOF_LEN = 388
+NOTE_LEN = 160                      # withdraw note: recipient | amount | secret_key | randomness | index
 
 
 class SppError(RuntimeError):
@@ -96,6 +97,9 @@ def load_library():
     L.spp_audit_inputs_batch.argtypes = [vp, vp, vp, sz, cp, vp, vp, vp, vp]
     L.spp_audit_inputs_batch_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.spp_prove_audit_from_secrets_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.spp_withdraw_rows_from_tree.argtypes = [vp, sz, cp, vp]
+    L.spp_prove_withdraw_notes_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    L.spp_prove_withdraw_notes.argtypes = [vp, vp, sz, cp, cp, vp, vp, vp]
     L.spp_shamir_reconstruct.argtypes = [vp, u32, vp, cp, sz, vp, vp]
     L.spp_rlwe_decrypt_batch.argtypes = [vp, vp, sz, vp, vp, vp]
     L.spp_ntt_fr.argtypes = [vp, vp, u32, i32]

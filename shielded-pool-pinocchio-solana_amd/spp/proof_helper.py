@@ -136,6 +136,32 @@ def generateProofBatch(config: CircuitConfig, inputs_list, rs=None):
 
 generate_proof_batch = generateProofBatch
 
+
+def helper_context(config: CircuitConfig):
+    """The Context the helper loaded `config`'s circuit in: a tree for generateProofsFromTree must live there
+    (ShieldedPoolMerkleTree(helper_context(config)))."""
+    return _handle(config).ctx
+
+
+def generateProofsFromTree(config: CircuitConfig, tree, notes, rs=None):
+    """Withdraw proofs from notes against a resident tree: what client/payroll-demo.ts:323-340 does per recipient
+    (mt.getRoot(), mt.getProof(index), generateProof) for the whole batch.  notes: (recipient, amount, secret_key, randomness,
+    index) tuples; tree: a ShieldedPoolMerkleTree of helper_context(config).  Every proof is against the tree's root at the time
+    of the call.  Same return shape and errors as generateProofBatch."""
+    if not notes:
+        return []
+    h = _handle(config)
+    if h.circuit_id != SPP_CIRCUIT_WITHDRAW:
+        raise ValueError("generateProofsFromTree expects the withdraw circuit")
+    proofs, pws, status = h.prove_withdraw_notes(tree, notes, rs)
+    for k, st in enumerate(status):
+        if st != 0:
+            raise SppError(st, "note %d is not a spendable note of the tree (inputs do not satisfy the circuit)" % k)
+    return [{"proof": p, "publicWitness": w} for p, w in zip(proofs, pws)]
+
+
+generate_proofs_from_tree = generateProofsFromTree
+
 BN254_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 _AUDIT_ORDER = ("secret_key", "wa_commitment", "ct_commitment", "c0_packed", "c1_packed", "r", "e1_sparse", "e2", "k0", "k1")
 

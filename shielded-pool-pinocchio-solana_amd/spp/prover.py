@@ -225,6 +225,30 @@ class CircuitHandle:
         scripts/generate_audit.py:468-641 runs on the proving stream in front of the solver.  Raw device pointers (ints)."""
         check(self.L.spp_prove_audit_from_secrets_device(self.h, count, d_pk_a, d_pk_b, d_sk, d_r, d_e1, d_e2, d_rs, d_proofs, d_pws, d_status))
 
+    def prove_withdraw_notes(self, tree, notes, rs=None):
+        """Withdraw proofs from notes (spp.witness.pack_withdraw_notes tuples) against the resident tree `tree`
+        (ShieldedPoolMerkleTree of this handle's Context): spp_prove_withdraw_notes.  Same return shape as prove_batch."""
+        from .witness import pack_withdraw_notes
+        count = len(notes)
+        buf = pack_withdraw_notes(notes)
+        rsb = None
+        if rs is not None:
+            rsb = b"".join(int(r).to_bytes(32, "big") + int(s).to_bytes(32, "big") for r, s in rs)
+        proofs = ctypes.create_string_buffer(PROOF_LEN * max(count, 1))
+        pws = ctypes.create_string_buffer(self.pw_len * max(count, 1))
+        status = (ctypes.c_int32 * max(count, 1))()
+        rc = self.L.spp_prove_withdraw_notes(self.h, tree.h, count, buf, rsb, ctypes.cast(proofs, ctypes.c_void_p),
+                                             ctypes.cast(pws, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p))
+        if rc != 0 and rc != SPP_ERR_UNSAT:
+            check(rc)
+        return ([proofs.raw[PROOF_LEN * i:PROOF_LEN * (i + 1)] for i in range(count)],
+                [pws.raw[self.pw_len * i:self.pw_len * (i + 1)] for i in range(count)], list(status)[:count])
+
+    def prove_withdraw_notes_device(self, tree, count, d_notes, d_rs, d_proofs, d_pws, d_status):
+        """Withdraw proofs from notes resident on the device against the resident tree (spp_prove_withdraw_notes_device):
+        asynchronous until sync(), every proof against the root at call time.  Raw device pointers (ints)."""
+        check(self.L.spp_prove_withdraw_notes_device(self.h, tree.h, count, d_notes, d_rs, d_proofs, d_pws, d_status))
+
     def sync(self):
         check(self.L.spp_sync(self.h))
 

@@ -4,14 +4,18 @@
     poseidon_hash2/4(...)    client/merkle.ts:22-38
     ShieldedPoolMerkleTree   client/merkle.ts:146-222
     identity_public_key(...) client/merkle.ts:98-113
+    pack_withdraw_notes(...) the five values a withdrawer supplies (noir_circuit/src/main.nr:38-51), for the rows / proofs
+                             from notes against the resident tree (ShieldedPoolMerkleTree.withdraw_rows)
     ct_commitment(...)       ct_helper/src/main.nr:15-34
 All of them take and return Python ints / lists; field elements cross the C ABI as 32-byte big-endian.
 """
 import ctypes
 import numpy as np
-from .lib import check
+from .lib import check, NOTE_LEN
 
 TREE_DEPTH = 16
+FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+NOTE_FIELDS = ("recipient", "amount", "secret_key", "randomness", "index")
 RLWE_N, MSG_SLOTS = 1024, 64
 
 
@@ -59,6 +63,23 @@ def poseidon_hash2(ctx, a, b):
 
 def poseidon_hash4(ctx, a, b, c, d):
     return poseidon_hash_batch(ctx, [[a, b, c, d]])[0]
+
+
+def pack_withdraw_notes(notes):
+    """notes: (recipient, amount, secret_key, randomness, index) tuples -> NOTE_LEN bytes per note, 32-byte big-endian fields in
+    that order (spp_withdraw_rows_from_tree / spp_prove_withdraw_notes).  Host only; raises ValueError on a tuple of another
+    length or a value outside [0, r)."""
+    out = bytearray()
+    for k, note in enumerate(notes):
+        if len(note) != len(NOTE_FIELDS):
+            raise ValueError("note %d: expected %d values %s, got %d" % (k, len(NOTE_FIELDS), NOTE_FIELDS, len(note)))
+        for name, v in zip(NOTE_FIELDS, note):
+            v = int(v)
+            if not 0 <= v < FR_MODULUS:
+                raise ValueError("note %d: %s is not a canonical field element" % (k, name))
+            out += v.to_bytes(32, "big")
+    assert len(out) == NOTE_LEN * len(notes)
+    return bytes(out)
 
 
 def merkle_roots(ctx, leaves, indices, siblings, depth=TREE_DEPTH):
@@ -128,6 +149,16 @@ class ShieldedPoolMerkleTree:
 
     def getProof(self, index):
         return self.getProofs([index])[0]
+
+    def withdraw_rows(self, notes):
+        """Withdraw input rows for notes (pack_withdraw_notes) against the tree as it stands (spp_withdraw_rows_from_tree):
+        per note [root, nullifier, recipient, amount, wa_commitment, secret_key, owner_x, owner_y, randomness, index,
+        *siblings] -- what client/payroll-demo.ts:323-340 assembles for generateProof, computed on the device."""
+        buf = pack_withdraw_notes(notes)
+        n_in = 10 + self.depth
+        rows = ctypes.create_string_buffer(32 * n_in * max(len(notes), 1))
+        check(self.ctx.L.spp_withdraw_rows_from_tree(self.h, len(notes), buf, ctypes.cast(rows, ctypes.c_void_p)))
+        return [_unbe(rows.raw[32 * n_in * i:], n_in) for i in range(len(notes))]
 
 
 def merkle_build(ctx, leaves, queries, depth=TREE_DEPTH):
