@@ -16,6 +16,8 @@
  *   spp_audit_inputs_batch    scripts/generate_audit.py:468-641 (everything before `nargo execute`)
  *   spp_prove_withdraw_notes  client/payroll-demo.ts:323-340 (getRoot / getProof / generateProof per recipient) against the
  *                             resident tree (spp_merkle_tree_*)
+ *   spp_merkle_tree_deposit   client/payroll-demo.ts:264-292 (generateIdentityKeypair / calculateCommitment / insert / getRoot
+ *                             per deposit) into the same tree
  *   spp_verify                `sunspot verify` noir_circuit/prove_linux.sh:86-87, audit_circuit/prove_audit.sh:98-99
  *   spp_verify_batch          the same for many proofs on the GPU
  *   spp_shamir_reconstruct / spp_rlwe_decrypt_batch   scripts/rlwe_decrypt.py:61-132, demo-frontend/app/lib/shamir.ts:97-169
@@ -60,6 +62,7 @@ extern "C" {
 #define SPP_AUDIT_PW_LEN 76      /* submit_audit.rs:19-21 */
 #define SPP_TREE_DEPTH 16        /* noir_circuit/src/main.nr:5 */
 #define SPP_NOTE_LEN 160         /* one withdraw note: recipient | amount | secret_key | randomness | index, 5 x 32 B */
+#define SPP_DEPOSIT_LEN 96       /* one deposit: secret_key | amount | randomness, 3 x 32 B big-endian (main.nr:38-51) */
 
 typedef struct spp_ctx spp_ctx;
 typedef struct spp_circuit spp_circuit;
@@ -212,6 +215,24 @@ int spp_merkle_tree_insert(spp_merkle_tree* t, size_t count, const uint8_t* leav
 int spp_merkle_tree_root(spp_merkle_tree* t, uint8_t root[32]);
 /* getProof for n leaf indices (any index below 2^depth, inserted or not): siblings_out = n * depth * 32 B */
 int spp_merkle_tree_proofs(spp_merkle_tree* t, size_t n, const uint64_t* indices, uint8_t* siblings_out);
+/* Deposits from secrets: generateIdentityKeypair, calculateCommitment, mt.insert and mt.getRoot for every deposit
+ * (client/payroll-demo.ts:264-292, client/test-shielded-pool.ts:218-231), whose instruction then carries
+ * amount u64 LE | commitment | new_root (shielded_pool_program/src/instructions/deposit.rs:21-37; the program pushes new_root
+ * into its root ring, state.rs:28-46).  For deposit k of the call, leaf i = *first_index + k:
+ *   owner       = secret_key * G on Grumpkin, the key used as given (generateIdentityKeypair reduces it mod 2^128 first,
+ *                 client/merkle.ts:98-113; spp_withdraw_rows_from_tree does not, so a deposit and its withdrawal see one key)
+ *   commitment  = H(owner_x, owner_y, amount, randomness) (client/merkle.ts:126-133, main.nr:69-70) becomes leaf i
+ *   roots[k]    = the root after leaves 0..i: what spp_merkle_tree_root returns if the deposits are inserted one at a time
+ * deposits = count * SPP_DEPOSIT_LEN B; commitments and roots = count * 32 B big-endian; first_index, commitments and roots are
+ * optional (NULL = not wanted).  Afterwards the tree, its root, size and proofs, and the withdraw-notes path see the new leaves
+ * exactly as if spp_merkle_tree_insert had appended the commitments.
+ * Refused with SPP_ERR_BAD_INPUT before any device work, the tree unchanged, the offending deposit named in spp_last_error():
+ * a field >= r, amount >= 2^64 (main.nr's `amount: pub u64`, deposit.rs's u64), secret_key == 0, count > 2^24, more deposits
+ * than the tree has room for (2^depth - size), NULL t, NULL deposits with count > 0.  count == 0 is SPP_OK and sets
+ * *first_index = size.  Synchronous; holds the context lock for its whole length, like spp_merkle_tree_insert, so concurrent
+ * depositors get disjoint, contiguous index ranges. */
+int spp_merkle_tree_deposit(spp_merkle_tree* t, size_t count, const uint8_t* deposits, uint64_t* first_index, uint8_t* commitments,
+                            uint8_t* roots);
 
 /* generateIdentityKeypair's sk * G on Grumpkin (client/merkle.ts:98-113; scalar = the canonical field element,
  * as noir_circuit/src/main.nr:54-59): sk count * 32 B -> (x, y) count * 64 B */

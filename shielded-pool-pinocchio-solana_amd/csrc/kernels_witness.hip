@@ -8,6 +8,8 @@
 //   k_merkle_level        client/merkle.ts:165-176 (getRoot: one tree level per launch)
 //   k_grumpkin_keygen     client/merkle.ts:98-113 (generateIdentityKeypair), main.nr:54-59
 //   k_withdraw_rows       client/payroll-demo.ts:323-340 (keygen, wa_commitment, nullifier, getRoot, getProof -> one withdraw row)
+//   k_deposit_leaves      client/payroll-demo.ts:264-292 (keygen, calculateCommitment, mt.insert)
+//   k_deposit_roots       the same deposits' mt.getRoot() after each insert
 //   k_poseidon2_sponge    ct_helper/src/main.nr:15-34 (= scripts/generate_audit.py:355-374)
 #include "kernels.hpp"
 #include "poseidon29.hpp"
@@ -435,6 +437,53 @@ __global__ void __launch_bounds__(64) k_withdraw_rows(const GkAffine* __restrict
 void launch_withdraw_rows(hipStream_t st, const GkAffine* table, HashConsts hc, const MerkleTreeDev* t, const uint8_t* notes, uint8_t* rows,
                           uint32_t count) {
   if (count) hipLaunchKernelGGL(k_withdraw_rows, dim3((count + 63) / 64), dim3(64), 0, st, table, hc, t, notes, rows, count);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Deposits into the resident tree (client/payroll-demo.ts:264-292, client/test-shielded-pool.ts:218-231: generateIdentityKeypair,
+// calculateCommitment, mt.insert, mt.getRoot per deposit).  deposit = secret_key | amount | randomness (3 x 32 B big-endian).
+// k_deposit_leaves: one lane per deposit; the commitment H4(owner_x, owner_y, amount, randomness) (merkle.ts:126-133,
+// main.nr:69-70) goes straight into level 0 of the tree.  Both Poseidon permutations below are inlined (see k_withdraw_rows).
+// k_deposit_roots: after the level update, the root of the prefix tree of leaves 0..i for every deposited leaf i (what getRoot
+// returns after that leaf's insert).  Walking up from leaf i, a left sibling covers only leaves < i, so it is final in the
+// prefix tree and is read from the tree; a right sibling covers only leaves > i, so it is empty there: the level default.
+// ----------------------------------------------------------------------------------------------------
+static constexpr uint32_t DEPOSIT_BYTES = 96;
+__global__ void __launch_bounds__(64) k_deposit_leaves(const GkAffine* __restrict__ table, HashConsts hc, const uint8_t* __restrict__ deposits,
+                                                       Fr* __restrict__ leaves, uint32_t count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const uint8_t* d = deposits + (size_t)g * DEPOSIT_BYTES;
+  const GkAffine pk = grumpkin_mul_g(table, load_be(d));             // merkle.ts:98-113 (the key as given, see spp.h)
+  Fr s[5] = {Fr::zero(), pk.x, pk.y, load_be(d + 32), load_be(d + 64)};
+  poseidon_permute29<5, false>(s, hc.pos5_rc, hc.pos5_mds29, 60, PoseidonNoEmit{});
+  leaves[g] = s[0];
+}
+__global__ void __launch_bounds__(64) k_deposit_roots(HashConsts hc, const MerkleTreeDev* __restrict__ t, uint64_t first, uint32_t count,
+                                                      uint8_t* __restrict__ roots_be, uint8_t* __restrict__ commitments_be) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const uint64_t i = first + g;
+  Fr v = t->level[0][i];
+  if (commitments_be) store_be(commitments_be + (size_t)g * 32, v);
+  if (!roots_be) return;
+  const uint32_t depth = t->depth;
+#pragma unroll 1
+  for (uint32_t l = 0; l < depth; l++) {
+    const uint64_t p = i >> l;
+    const bool odd = p & 1;
+    Fr s[3] = {Fr::zero(), odd ? t->level[l][p - 1] : v, odd ? v : t->dflt[l]};
+    poseidon_permute29<3, false>(s, hc.pos3_rc, hc.pos3_mds29, 57, PoseidonNoEmit{});
+    v = s[0];
+  }
+  store_be(roots_be + (size_t)g * 32, v);
+}
+void launch_deposit_leaves(hipStream_t st, const GkAffine* table, HashConsts hc, const uint8_t* deposits, Fr* leaves, uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_deposit_leaves, dim3((count + 63) / 64), dim3(64), 0, st, table, hc, deposits, leaves, count);
+}
+void launch_deposit_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first, uint32_t count, uint8_t* roots_be,
+                          uint8_t* commitments_be) {
+  if (count) hipLaunchKernelGGL(k_deposit_roots, dim3((count + 63) / 64), dim3(64), 0, st, hc, t, first, count, roots_be, commitments_be);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -244,6 +244,21 @@ static int mt_push_descriptor(spp_merkle_tree* t) {
   HIP_TRY(hipMemcpyAsync(t->dev, &t->host, sizeof(MerkleTreeDev), hipMemcpyHostToDevice, t->ctx->stream));
   return 0;
 }
+// append `count` leaves already written into level 0 at [n_leaves, n_leaves + count) (insert, deposit): the touched parents of
+// every level are recomputed on the context's stream, then the descriptor is pushed; no synchronise
+static int mt_append(spp_merkle_tree* t, uint64_t count) {
+  spp_ctx* ctx = t->ctx;
+  const uint64_t first = t->n_leaves, last = first + count - 1;
+  t->n_leaves += count;
+  t->host.count[0] = t->n_leaves;
+  for (uint32_t l = 0; l < t->depth; l++) {
+    const uint64_t p0 = first >> (l + 1), p1 = last >> (l + 1);
+    launch_merkle_update(ctx->stream, ctx->hc, t->host.level[l], t->host.count[l], t->d_dflt + l, t->host.level[l + 1], p0,
+                         (uint32_t)(p1 - p0 + 1));
+    t->host.count[l + 1] = (t->host.count[l] + 1) / 2;
+  }
+  return mt_push_descriptor(t);
+}
 extern "C" int spp_merkle_tree_new(spp_ctx* ctx, uint32_t depth, spp_merkle_tree** out) {
   if (!ctx || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   if (depth == 0 || depth > 32) return fail(SPP_ERR_BAD_INPUT, "depth must be 1..32");
@@ -293,16 +308,54 @@ extern "C" int spp_merkle_tree_insert(spp_merkle_tree* t, size_t count, const ui
   if (int e = mt_reserve(t, t->n_leaves + count)) return e;
   DevBuf dl;
   UP(dl, leaves, count * 32);
-  const uint64_t first = t->n_leaves, last = first + count - 1;
-  launch_fr_from_be(st, dl.as<uint8_t>(), t->host.level[0] + first, (uint32_t)count);
-  t->n_leaves += count;
-  t->host.count[0] = t->n_leaves;
-  for (uint32_t l = 0; l < t->depth; l++) {
-    const uint64_t p0 = first >> (l + 1), p1 = last >> (l + 1);
-    launch_merkle_update(st, ctx->hc, t->host.level[l], t->host.count[l], t->d_dflt + l, t->host.level[l + 1], p0, (uint32_t)(p1 - p0 + 1));
-    t->host.count[l + 1] = (t->host.count[l] + 1) / 2;
+  launch_fr_from_be(st, dl.as<uint8_t>(), t->host.level[0] + t->n_leaves, (uint32_t)count);
+  if (int e = mt_append(t, count)) return e;
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+// calculateCommitment + insert + getRoot for every deposit (client/payroll-demo.ts:264-292) in one call: k_deposit_leaves writes
+// level 0, the level update of insert runs once for the whole range, k_deposit_roots gives every deposit's prefix root
+extern "C" int spp_merkle_tree_deposit(spp_merkle_tree* t, size_t count, const uint8_t* deposits, uint64_t* first_index,
+                                       uint8_t* commitments, uint8_t* roots) {
+  static const char* const field_name[3] = {"secret_key", "amount", "randomness"};
+  if (!t || (count && !deposits)) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many deposits in one call (%zu; at most 2^24)", count);
+  for (size_t i = 0; i < count; i++) {
+    const uint8_t* d = deposits + SPP_DEPOSIT_LEN * i;
+    for (int f = 0; f < 3; f++)
+      if (!be_is_canonical<FrParams>(d + 32 * f))
+        return fail(SPP_ERR_BAD_INPUT, "deposit %zu: %s is not a canonical field element", i, field_name[f]);
+    bool sk_zero = true, amount_u64 = true;
+    for (int b = 0; b < 32; b++) sk_zero &= d[b] == 0;
+    for (int b = 0; b < 24; b++) amount_u64 &= d[32 + b] == 0;
+    if (sk_zero) return fail(SPP_ERR_BAD_INPUT, "deposit %zu: secret_key is 0", i);
+    if (!amount_u64) return fail(SPP_ERR_BAD_INPUT, "deposit %zu: amount does not fit 64 bits", i);
   }
-  if (int e = mt_push_descriptor(t)) return e;
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);   // as insert: the first index handed out and the room check are read under the lock
+  const uint64_t room = ((uint64_t)1 << t->depth) - t->n_leaves;
+  if (count > room)
+    return fail(SPP_ERR_BAD_INPUT, "deposit %llu: the tree is full (%llu of %llu leaves used)", (unsigned long long)room,
+                (unsigned long long)t->n_leaves, (unsigned long long)1 << t->depth);
+  if (first_index) *first_index = t->n_leaves;
+  if (count == 0) return SPP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  if (int e = mt_reserve(t, t->n_leaves + count)) return e;
+  const uint64_t first = t->n_leaves;
+  DevBuf dd, dout;
+  UP(dd, deposits, count * SPP_DEPOSIT_LEN);
+  launch_deposit_leaves(st, ctx->gk_table, ctx->hc, dd.as<uint8_t>(), t->host.level[0] + first, (uint32_t)count);
+  if (int e = mt_append(t, count)) return e;
+  if (commitments || roots) {
+    HIP_TRY(dout.alloc(count * 64));
+    uint8_t *d_com = dout.as<uint8_t>(), *d_roots = d_com + count * 32;
+    launch_deposit_roots(st, ctx->hc, t->dev, first, (uint32_t)count, roots ? d_roots : nullptr, commitments ? d_com : nullptr);
+    if (commitments) HIP_TRY(hipMemcpyAsync(commitments, d_com, count * 32, hipMemcpyDeviceToHost, st));
+    if (roots) HIP_TRY(hipMemcpyAsync(roots, d_roots, count * 32, hipMemcpyDeviceToHost, st));
+  }
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   return SPP_OK;

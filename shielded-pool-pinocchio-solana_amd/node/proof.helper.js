@@ -78,6 +78,71 @@ function generateProofBatch(config, inputsList) {
   return inputsList.map((_, i) => ({ proof: r.proofs.slice(388 * i, 388 * (i + 1)), publicWitness: r.publicWitnesses.slice(pwLen * i, pwLen * (i + 1)) }));
 }
 
+// ---- the pool's Merkle tree resident in HBM (client/merkle.ts:146-222): deposits into it, withdrawals from notes against it.
+// The tree lives in the addon's context, the one generateProof's circuits are loaded in.
+const DEPOSIT_FIELDS = ["secret_key", "amount", "randomness"];
+const NOTE_FIELDS = ["recipient", "amount", "secret_key", "randomness", "index"];
+
+function fromField32(buf, off) {
+  return BigInt("0x" + buf.slice(off, off + 32).toString("hex"));
+}
+
+// the 72-byte body of the deposit instruction (shielded_pool_program/src/instructions/deposit.rs:21-37): amount u64 LE | commitment |
+// new_root; the 1-byte instruction tag in front of it is the caller's (client/payroll-demo.ts:288-292)
+function depositInstructionData(amount, commitment, root) {
+  let a = BigInt(amount);
+  if (a < 0n || a >= 1n << 64n) throw new Error("libspp error -1: amount does not fit a u64");
+  const out = Buffer.alloc(72);
+  for (let i = 0; i < 8; i++) { out[i] = Number(a & 0xffn); a >>= 8n; }
+  toField32(commitment).copy(out, 8);
+  toField32(root).copy(out, 40);
+  return out;
+}
+
+class ShieldedPoolMerkleTree {
+  constructor(depth = 16) {
+    addon.init(parseInt(process.env.SPP_DEVICE || "0", 10));
+    this.depth = depth;
+    this.handle = addon.treeNew(depth);
+  }
+  get size() { return addon.treeSize(this.handle); }
+  insert(commitment) { return addon.treeInsert(this.handle, toField32(commitment)); }
+  getRoot() { return fromField32(addon.treeRoot(this.handle), 0); }
+  getProof(index) {
+    const sib = addon.treeProofs(this.handle, [Number(index)]);
+    const out = [];
+    for (let l = 0; l < this.depth; l++) out.push(fromField32(sib, 32 * l));
+    return out;
+  }
+  // generateIdentityKeypair, calculateCommitment, insert and getRoot for every deposit (client/payroll-demo.ts:264-292) in one
+  // call: deposits are {secret_key, amount, randomness}; returns per deposit its leaf index, its commitment, the root right after
+  // it and the instruction body that carries them.  A field >= r, amount >= 2^64 or secret_key == 0 throws; the tree is unchanged.
+  deposit(deposits) {
+    if (!Array.isArray(deposits)) throw new Error("deposit expects an array of {secret_key, amount, randomness}");
+    const buf = Buffer.concat(deposits.map((d) => Buffer.concat(DEPOSIT_FIELDS.map((k) => toField32(d[k])))));
+    const r = addon.treeDeposit(this.handle, buf);
+    return deposits.map((d, k) => {
+      const commitment = fromField32(r.commitments, 32 * k);
+      const root = fromField32(r.roots, 32 * k);
+      return { index: r.first + k, commitment, root, instructionData: depositInstructionData(d.amount, commitment, root) };
+    });
+  }
+}
+
+// Withdraw proofs from notes against a resident tree: what client/payroll-demo.ts:323-340 does per recipient (mt.getRoot(),
+// mt.getProof(index), generateProof) for the whole batch.  notes: {recipient, amount, secret_key, randomness, index}; every proof
+// is against the tree's root at the time of the call.  Same return shape and errors as generateProofBatch.
+function generateProofsFromTree(config, tree, notes) {
+  if (!Array.isArray(notes)) throw new Error("generateProofsFromTree expects an array of notes");
+  if (notes.length === 0) return [];
+  const buf = Buffer.concat(notes.map((n) => Buffer.concat(NOTE_FIELDS.map((k) => toField32(n[k])))));
+  const r = addon.proveWithdrawNotes(circuitHandle(config), tree.handle, buf, null);
+  const bad = r.status.findIndex((s) => s !== 0);
+  if (bad >= 0) throw new Error(`libspp error ${r.status[bad]}: note ${bad} is not a spendable note of the tree (inputs do not satisfy the circuit)`);
+  const pwLen = r.publicWitnesses.length / notes.length;
+  return notes.map((_, i) => ({ proof: r.proofs.slice(388 * i, 388 * (i + 1)), publicWitness: r.publicWitnesses.slice(pwLen * i, pwLen * (i + 1)) }));
+}
+
 // ---- audit circuit: the reference proves it from scripts (audit_circuit/prove_audit.sh:74-99, scripts/generate_audit.py:668-685)
 const BN254_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
 const AUDIT_ORDER = ["secret_key", "wa_commitment", "ct_commitment", "c0_packed", "c1_packed", "r", "e1_sparse", "e2", "k0", "k1"];
@@ -115,4 +180,5 @@ function generateAuditProof(config, inputs) {
   return { proof: r.proofs, publicWitness: r.publicWitnesses };
 }
 
-module.exports = { generateProof, generateProofBatch, generateAuditProof, proverToml, auditProverToml, toField32, addon };
+module.exports = { generateProof, generateProofBatch, generateAuditProof, proverToml, auditProverToml, toField32, addon,
+                   ShieldedPoolMerkleTree, generateProofsFromTree, depositInstructionData };

@@ -101,6 +101,91 @@ export function generateProofBatch(config: CircuitConfig, inputsList: ShieldedPo
   }));
 }
 
+// ---- the pool's Merkle tree resident in HBM (client/merkle.ts:146-222): deposits into it, withdrawals from notes against it.
+// The tree lives in the addon's context, the one generateProof's circuits are loaded in.
+export interface Deposit {
+  secret_key: FieldLike;
+  amount: FieldLike;
+  randomness: FieldLike;
+}
+export interface DepositResult {
+  index: number;
+  commitment: bigint;
+  root: bigint; // the tree's root right after this deposit: the new_root of its instruction
+  instructionData: Buffer;
+}
+export interface WithdrawNote {
+  recipient: FieldLike;
+  amount: FieldLike;
+  secret_key: FieldLike;
+  randomness: FieldLike;
+  index: FieldLike;
+}
+const DEPOSIT_FIELDS = ["secret_key", "amount", "randomness"] as const;
+const NOTE_FIELDS = ["recipient", "amount", "secret_key", "randomness", "index"] as const;
+
+function fromField32(buf: Buffer, off: number): bigint {
+  return BigInt("0x" + buf.slice(off, off + 32).toString("hex"));
+}
+
+// the 72-byte body of the deposit instruction (shielded_pool_program/src/instructions/deposit.rs:21-37): amount u64 LE | commitment |
+// new_root; the 1-byte instruction tag in front of it is the caller's (client/payroll-demo.ts:288-292)
+export function depositInstructionData(amount: FieldLike, commitment: FieldLike, root: FieldLike): Buffer {
+  let a = BigInt(amount);
+  if (a < 0n || a >= 1n << 64n) throw new Error("libspp error -1: amount does not fit a u64");
+  const out = Buffer.alloc(72);
+  for (let i = 0; i < 8; i++) { out[i] = Number(a & 0xffn); a >>= 8n; }
+  toField32(commitment).copy(out, 8);
+  toField32(root).copy(out, 40);
+  return out;
+}
+
+export class ShieldedPoolMerkleTree {
+  readonly depth: number;
+  readonly handle: unknown;
+  constructor(depth = 16) {
+    addon.init(parseInt(process.env.SPP_DEVICE || "0", 10));
+    this.depth = depth;
+    this.handle = addon.treeNew(depth);
+  }
+  get size(): number { return addon.treeSize(this.handle); }
+  insert(commitment: FieldLike): number { return addon.treeInsert(this.handle, toField32(commitment)); }
+  getRoot(): bigint { return fromField32(addon.treeRoot(this.handle), 0); }
+  getProof(index: number): bigint[] {
+    const sib: Buffer = addon.treeProofs(this.handle, [Number(index)]);
+    const out: bigint[] = [];
+    for (let l = 0; l < this.depth; l++) out.push(fromField32(sib, 32 * l));
+    return out;
+  }
+  // generateIdentityKeypair, calculateCommitment, insert and getRoot for every deposit (client/payroll-demo.ts:264-292) in one
+  // call.  A field >= r, amount >= 2^64 or secret_key == 0 throws; the tree is then unchanged.
+  deposit(deposits: Deposit[]): DepositResult[] {
+    const buf = Buffer.concat(deposits.map((d) => Buffer.concat(DEPOSIT_FIELDS.map((k) => toField32(d[k])))));
+    const r = addon.treeDeposit(this.handle, buf);
+    return deposits.map((d, k) => {
+      const commitment = fromField32(r.commitments, 32 * k);
+      const root = fromField32(r.roots, 32 * k);
+      return { index: r.first + k, commitment, root, instructionData: depositInstructionData(d.amount, commitment, root) };
+    });
+  }
+}
+
+// Withdraw proofs from notes against a resident tree: what client/payroll-demo.ts:323-340 does per recipient (mt.getRoot(),
+// mt.getProof(index), generateProof) for the whole batch.  Every proof is against the tree's root at the time of the call.
+// Same return shape and errors as generateProofBatch.
+export function generateProofsFromTree(config: CircuitConfig, tree: ShieldedPoolMerkleTree, notes: WithdrawNote[]): { proof: Buffer; publicWitness: Buffer }[] {
+  if (notes.length === 0) return [];
+  const buf = Buffer.concat(notes.map((n) => Buffer.concat(NOTE_FIELDS.map((k) => toField32(n[k])))));
+  const r = addon.proveWithdrawNotes(circuitHandle(config), tree.handle, buf, null);
+  const bad = (r.status as number[]).findIndex((s) => s !== 0);
+  if (bad >= 0) throw new Error(`libspp error ${r.status[bad]}: note ${bad} is not a spendable note of the tree (inputs do not satisfy the circuit)`);
+  const pwLen = r.publicWitnesses.length / notes.length;
+  return notes.map((_, i) => ({
+    proof: (r.proofs as Buffer).slice(388 * i, 388 * (i + 1)),
+    publicWitness: (r.publicWitnesses as Buffer).slice(pwLen * i, pwLen * (i + 1)),
+  }));
+}
+
 // ---- audit circuit: the reference proves it from scripts (audit_circuit/prove_audit.sh:74-99, scripts/generate_audit.py:668-685)
 type FieldLike = string | number | bigint;
 export interface AuditInputs {

@@ -14,6 +14,7 @@ SPP_CIRCUIT_WITHDRAW_DEPTH20 = 4     # build only: withdraw over a depth-20 tree
 SPP_CIRCUIT_WITHDRAW_REFSHAPE = 3   # build only: withdraw padded to the reference's R1CS size (12 452 constraints)
 PROOF_LEN = 388
 NOTE_LEN = 160                      # withdraw note: recipient | amount | secret_key | randomness | index
+DEPOSIT_LEN = 96                    # deposit: secret_key | amount | randomness
 
 
 class SppError(RuntimeError):
@@ -92,6 +93,7 @@ def load_library():
     L.spp_merkle_tree_insert.argtypes = [vp, sz, cp, ctypes.POINTER(ctypes.c_uint64)]
     L.spp_merkle_tree_root.argtypes = [vp, vp]
     L.spp_merkle_tree_proofs.argtypes = [vp, sz, vp, vp]
+    L.spp_merkle_tree_deposit.argtypes = [vp, sz, cp, ctypes.POINTER(ctypes.c_uint64), vp, vp]
     L.spp_grumpkin_keygen_batch.argtypes = [vp, sz, cp, vp]
     L.spp_poseidon2_sponge_batch.argtypes = [vp, sz, u32, cp, vp]
     L.spp_audit_inputs_batch.argtypes = [vp, vp, vp, sz, cp, vp, vp, vp, vp]

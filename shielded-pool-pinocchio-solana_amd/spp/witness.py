@@ -6,16 +6,19 @@
     identity_public_key(...) client/merkle.ts:98-113
     pack_withdraw_notes(...) the five values a withdrawer supplies (noir_circuit/src/main.nr:38-51), for the rows / proofs
                              from notes against the resident tree (ShieldedPoolMerkleTree.withdraw_rows)
+    pack_deposits(...)       the three values a depositor supplies, for ShieldedPoolMerkleTree.deposit
+    deposit_instruction_data shielded_pool_program/src/instructions/deposit.rs:21-37
     ct_commitment(...)       ct_helper/src/main.nr:15-34
 All of them take and return Python ints / lists; field elements cross the C ABI as 32-byte big-endian.
 """
 import ctypes
 import numpy as np
-from .lib import check, NOTE_LEN
+from .lib import check, NOTE_LEN, DEPOSIT_LEN
 
 TREE_DEPTH = 16
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 NOTE_FIELDS = ("recipient", "amount", "secret_key", "randomness", "index")
+DEPOSIT_FIELDS = ("secret_key", "amount", "randomness")
 RLWE_N, MSG_SLOTS = 1024, 64
 
 
@@ -80,6 +83,36 @@ def pack_withdraw_notes(notes):
             out += v.to_bytes(32, "big")
     assert len(out) == NOTE_LEN * len(notes)
     return bytes(out)
+
+
+def pack_deposits(deposits):
+    """deposits: (secret_key, amount, randomness) tuples -> DEPOSIT_LEN bytes per deposit, 32-byte big-endian fields in that order
+    (spp_merkle_tree_deposit).  Host only; raises ValueError on a tuple of another length or a value outside [0, 2^256).  The
+    library refuses the rest (a field >= r, amount >= 2^64, secret_key == 0) and names the deposit."""
+    out = bytearray()
+    for k, dep in enumerate(deposits):
+        if len(dep) != len(DEPOSIT_FIELDS):
+            raise ValueError("deposit %d: expected %d values %s, got %d" % (k, len(DEPOSIT_FIELDS), DEPOSIT_FIELDS, len(dep)))
+        for name, v in zip(DEPOSIT_FIELDS, dep):
+            v = int(v)
+            if not 0 <= v < 1 << 256:
+                raise ValueError("deposit %d: %s does not fit 32 bytes" % (k, name))
+            out += v.to_bytes(32, "big")
+    assert len(out) == DEPOSIT_LEN * len(deposits)
+    return bytes(out)
+
+
+def deposit_instruction_data(amount, commitment, root):
+    """The 72-byte body of the pool program's deposit instruction (shielded_pool_program/src/instructions/deposit.rs:21-37):
+    amount u64 little-endian | commitment 32 B big-endian | new root 32 B big-endian.  The 1-byte instruction tag in front of it
+    is the caller's (client/payroll-demo.ts:288-292)."""
+    amount, commitment, root = int(amount), int(commitment), int(root)
+    if not 0 <= amount < 1 << 64:
+        raise ValueError("amount does not fit a u64")
+    for name, v in (("commitment", commitment), ("root", root)):
+        if not 0 <= v < FR_MODULUS:
+            raise ValueError("%s is not a canonical field element" % name)
+    return amount.to_bytes(8, "little") + commitment.to_bytes(32, "big") + root.to_bytes(32, "big")
 
 
 def merkle_roots(ctx, leaves, indices, siblings, depth=TREE_DEPTH):
@@ -149,6 +182,20 @@ class ShieldedPoolMerkleTree:
 
     def getProof(self, index):
         return self.getProofs([index])[0]
+
+    def deposit(self, deposits):
+        """generateIdentityKeypair, calculateCommitment, insert and getRoot for every deposit (client/payroll-demo.ts:264-292) in
+        one call on the device (spp_merkle_tree_deposit).  deposits: (secret_key, amount, randomness) tuples.  Returns
+        (first_index, commitments, roots): deposit k is leaf first_index + k and roots[k] is the root right after it, the new_root
+        of its deposit instruction (deposit_instruction_data)."""
+        n = len(deposits)
+        buf = pack_deposits(deposits)
+        first = ctypes.c_uint64(0)
+        com = ctypes.create_string_buffer(32 * max(n, 1))
+        roots = ctypes.create_string_buffer(32 * max(n, 1))
+        check(self.ctx.L.spp_merkle_tree_deposit(self.h, n, buf, ctypes.byref(first), ctypes.cast(com, ctypes.c_void_p),
+                                                 ctypes.cast(roots, ctypes.c_void_p)))
+        return int(first.value), _unbe(com.raw, n), _unbe(roots.raw, n)
 
     def withdraw_rows(self, notes):
         """Withdraw input rows for notes (pack_withdraw_notes) against the tree as it stands (spp_withdraw_rows_from_tree):
