@@ -1,4 +1,4 @@
-// Launch wrappers of the HIP kernels (one .hip file per kernel family), shared by spp_api.cpp.
+// Launch wrappers of the HIP kernels (one .hip file per kernel family), shared by the spp_*.cpp units.
 // Data layout in HBM, used by every kernel of the proving path ("batch-minor"):
 //   witness   W   [rows][P]      Fr Montgomery, 32 B; row = wire (plus 3 blinding rows r, s, rs)
 //   abc           [3][n][P]      constraint evaluations <A_k,w>, <B_k,w>, <C_k,w>, zero padded to n
@@ -40,7 +40,7 @@ struct DevCircuit {
   // identical to the B row (a square).  A solver lane that has just evaluated row k - 1 reuses the value instead of walking
   // the same linear form again: the rows of a power map share their B side, and compiled (ACIR) circuits have long forms.
   const uint8_t* row_flags;
-  // "small rows" of the matrix evaluation (spp_api.cpp, small_rows_plan): rows whose every term is a small integer coefficient
+  // "small rows" of the matrix evaluation (spp_plan.cpp, small_rows_plan): rows whose every term is a small integer coefficient
   // times a wire that the lookup argument bounds to a byte-sized range (the audit circuit's 1 088 quotient equations: 1 024
   // public-key coefficients < 2^28 times noise values in [-3, 3], generate_audit.py:57-66,236-243, plus ciphertext bytes).  The
   // bounded wires are extracted once per batch as int16 (k_small_extract), the rows are summed as 64-bit integers

@@ -680,7 +680,7 @@ __global__ void __launch_bounds__(64) k_g1_to_affine(const G1XYZZ* __restrict__ 
   if (i < n) out[i] = x[i].to_affine();
 }
 // term t: coeff[t] * base[row[t]]; then segment s = sum of terms [seg[s], seg[s+1]) as an affine point (the column sums
-// X_wire = sum_i C[i][wire] * W_i of the product form of computeH, spp_api.cpp)
+// X_wire = sum_i C[i][wire] * W_i of the product form of computeH, spp_load.cpp)
 __global__ void __launch_bounds__(64) k_g1_terms(const G1Affine* __restrict__ base, const uint32_t* __restrict__ row, const Fr* __restrict__ coeff,
                                                  uint32_t nterms, G1XYZZ* __restrict__ out) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;

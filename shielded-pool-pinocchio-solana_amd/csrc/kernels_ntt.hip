@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(256) k_qap_pointwise(Fr* __restrict__ abc, uin
   for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (uint64_t)gridDim.x * blockDim.x)
     a[g] = (a[g] * b[g] - c[g]) * zinv;
 }
-// a <- a * b over [n][P]: the values of A(X) B(X) on the coset zeta * H (product form of computeH, spp_api.cpp)
+// a <- a * b over [n][P]: the values of A(X) B(X) on the coset zeta * H (product form of computeH, spp_load.cpp)
 __global__ void __launch_bounds__(256) k_qap_product(Fr* __restrict__ abc, uint64_t total) {
   Fr* a = abc;
   const Fr* b = abc + total;

@@ -516,7 +516,7 @@ void launch_solve(hipStream_t st, DevCircuit dc, Fr* W, Fr* scratch, uint32_t pc
 // With one lane per proof a single proof is one lane's serial work: 14 ms for the withdraw circuit, 29 ms for the audit
 // circuit, three quarters of the drop-in generateProof latency, almost all of it inside the hash permutations (a lone wave
 // issues one dependent multiplication after the other on one of the chip's 1024 SIMDs).  Here the 64 lanes of a wave belong
-// to ONE proof and the host-built item list (spp_api.cpp, coop_plan) says how each stretch of the program uses them:
+// to ONE proof and the host-built item list (spp_plan.cpp, coop_plan) says how each stretch of the program uses them:
 //   COOP_SEQ       [pc_a, pc_b) on lane 0 (whatever has no parallel form)
 //   COOP_PAR       independent BITS / LIMBS8 / INV_H instructions, one per lane
 //   COOP_LEVELS    a run of SOLVE_C rows in dependency levels: the rows of a level are solved by different lanes

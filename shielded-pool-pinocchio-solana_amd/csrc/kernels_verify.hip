@@ -1,7 +1,7 @@
 // Batched Groth16 (+ BSB22 commitment) verification, one lane per proof -- SURVEY 8f-4: the GPU counterpart of
 // `sunspot verify <vk> <proof> <pw>` (noir_circuit/prove_linux.sh:86-87, audit_circuit/prove_audit.sh:98-99) and of the
 // checks the deployed verifier makes (withdraw.rs:13-16,63-90: 388-byte proof, 12-byte witness header + 32 B inputs).
-// Same decisions, in the same order, as the host verifier spp_verify (csrc/spp_api.cpp), which tests compare it with:
+// Same decisions, in the same order, as the host verifier spp_verify (csrc/spp_verify_api.cpp), which tests compare it with:
 //   1. format: commitment count == 1; G1 points on the curve, Bs on the twist AND in the order-r subgroup;
 //   2. Pedersen proof of knowledge:  e(Cm, GSigmaNeg) * e(PoK, G) == 1;
 //   3. challenge = fr.Hash(Cm, "bsb22-commitment");  ksum = K0 + sum pub_i K_i + challenge K_last + Cm;

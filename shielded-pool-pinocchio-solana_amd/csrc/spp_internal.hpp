@@ -1,6 +1,13 @@
-// Internals shared by the translation units of libspp's C ABI (spp_api.cpp: contexts, circuits, setup, proving;
-// spp_witness_api.cpp: witness-input kernels, Merkle trees, auditor side; spp_verify_api.cpp: verification and pairing checks;
-// spp_micro_api.cpp: the NTT / MSM / Pippenger unit and micro-benchmark entry points).  Not installed; include/spp.h is the ABI.
+// Internals shared by the translation units of libspp's C ABI.  Not installed; include/spp.h is the ABI.
+//   spp_api.cpp          error channel, contexts, the stream-concurrency probe
+//   spp_circuit.hpp      (private, on top of this header) struct spp_circuit, its workspaces and what the four units below share
+//   spp_plan.cpp         load-time planners: cooperative-solver items, small and long rows of the matrix evaluation
+//   spp_load.cpp         proving-key container, window plan and tables, circuit loading and queries, fixed-base MSM unit calls
+//   spp_prove.cpp        workspaces, the proving pipeline and its batch entry points, timing queries
+//   spp_setup.cpp        circuit construction (host only) and the trusted setup on the GPU
+//   spp_witness_api.cpp  witness-input kernels, Merkle trees, auditor side
+//   spp_verify_api.cpp   verification and pairing checks
+//   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points
 #pragma once
 #include "../../include/spp.h"
 
@@ -189,3 +196,5 @@ int spp_check_notes(size_t count, const uint8_t* notes);
 // lazily built per-context constants (spp_witness_api.cpp)
 int spp_ensure_ctx_consts(spp_ctx* ctx);   // Poseidon / Poseidon2 constants, Grumpkin window table
 int spp_ensure_rlwe(spp_ctx* ctx);         // NTT tables of the RLWE witness kernel
+// a new stream that really runs beside `ref` (spp_api.cpp)
+__attribute__((visibility("hidden"))) int pick_concurrent_stream(hipStream_t ref, hipStream_t* out);

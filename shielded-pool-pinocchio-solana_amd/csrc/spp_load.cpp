@@ -1,0 +1,916 @@
+// libspp C ABI, circuit loading: the proving-key container, the window plan and the window tables in HBM, load_circuit_impl as
+// a list of steps, the circuit queries, and the fixed-base MSM unit calls (they share the table builder).
+#include "spp_circuit.hpp"
+
+static std::vector<PendingTable<Fq>>& pending(spp_circuit* c, Fq*) { return c->pending1; }
+static std::vector<PendingTable<Fq2>>& pending(spp_circuit* c, Fq2*) { return c->pending2; }
+
+static int upload_sparse(spp_circuit* c, const Circuit& circ, const Sparse& m, DevSparse* out) {
+  std::vector<uint32_t> wire(m.terms.size()), coeff(m.terms.size()), lit(m.terms.size(), 0);
+  Fr one = Fr::one(), mone = Fr::one().neg();
+  // small literals, per coefficient-table entry: canonical value v < 2^28, or p - v < 2^28
+  std::vector<uint32_t> small(circ.coeffs.size(), 0);
+  for (size_t ci = 0; ci < circ.coeffs.size(); ci++) {
+    uint32_t v[8], nv[8];
+    circ.coeffs[ci].to_canonical(v);
+    bool hi0 = true;
+    for (int k = 1; k < 8; k++) hi0 = hi0 && v[k] == 0;
+    if (hi0 && v[0] != 0 && v[0] < (1u << 28)) { small[ci] = v[0]; continue; }
+    circ.coeffs[ci].neg().to_canonical(nv);
+    hi0 = true;
+    for (int k = 1; k < 8; k++) hi0 = hi0 && nv[k] == 0;
+    if (hi0 && nv[0] != 0 && nv[0] < (1u << 28)) small[ci] = nv[0] | 0x80000000u;
+  }
+  for (size_t i = 0; i < m.terms.size(); i++) {
+    wire[i] = m.terms[i].wire;
+    uint32_t ci = m.terms[i].coeff;
+    uint32_t flag = 0;
+    if (circ.coeffs[ci] == one) flag = COEFF_ONE;
+    else if (circ.coeffs[ci] == mone) flag = COEFF_MINUS_ONE;
+    else lit[i] = small[ci];
+    coeff[i] = ci | flag;
+  }
+  uint32_t *rp, *w, *co, *li;
+  if (int e = own_upload(c, &li, lit)) return e;
+  out->lit = li;
+  if (int e = own_upload(c, &rp, m.rowptr)) return e;
+  if (int e = own_upload(c, &w, wire)) return e;
+  if (int e = own_upload(c, &co, coeff)) return e;
+  out->rowptr = rp;
+  out->wire = w;
+  out->coeff = co;
+  return 0;
+}
+
+// window tables: allocate first (all sets), then build with temporaries sized from the HBM that is left, so that
+// each launch has enough rows (>= tens of thousands of lanes) to fill the chip
+template <class F>
+static int alloc_table(spp_circuit* c, size_t N, uint32_t cbits, uint32_t Wt, Affine<F>** table_out) {
+  size_t table_elems = std::max<size_t>(msm_table_elems((uint32_t)N, cbits, Wt), 1);
+  Affine<F>* table;
+  HIP_TRY(hipMalloc((void**)&table, table_elems * sizeof(Affine<F>)));
+  c->owned.push_back(table);
+  c->table_bytes += table_elems * sizeof(Affine<F>);
+  *table_out = table;
+  return 0;
+}
+template <class F>
+static int build_table(spp_circuit* c, const std::vector<Affine<F>>& pts, uint32_t cbits, uint32_t Wt, Affine<F>* table, size_t temp_budget) {
+  hipStream_t st = c->ctx->stream;
+  const uint32_t Wn = Wt, E = 1u << (cbits - 1);
+  const size_t N = pts.size();
+  if (N == 0) return 0;
+  const size_t rows_total = ((N * Wn + 63) / 64) * 64;
+  const size_t per_row = (size_t)E * (sizeof(XYZZ<F>) + sizeof(F));
+  size_t chunk = std::max<size_t>(64, ((temp_budget / per_row) / 64) * 64);
+  chunk = std::min(chunk, (size_t)65536);   // larger launches only add TLB misses (the d-stride is chunk * 128 B)
+  chunk = std::min(chunk, rows_total);
+  DevBuf d_bases, tmp, tmp_pre;   // released on every return path
+  HIP_TRY(d_bases.alloc(N * sizeof(Affine<F>)));
+  HIP_TRY(hipMemcpy(d_bases.p, pts.data(), N * sizeof(Affine<F>), hipMemcpyHostToDevice));
+  HIP_TRY(tmp.alloc(chunk * E * sizeof(XYZZ<F>)));
+  HIP_TRY(tmp_pre.alloc(chunk * E * sizeof(F)));
+  for (size_t r0 = 0; r0 < rows_total; r0 += chunk) {
+    uint32_t cnt = (uint32_t)std::min(chunk, rows_total - r0);
+    launch_build_table<F>(st, d_bases.as<Affine<F>>(), (uint32_t)N, cbits, Wt, (uint32_t)r0, cnt, table, tmp.as<XYZZ<F>>(), tmp_pre.as<F>());
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+static size_t table_temp_budget() {
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return (size_t)2 << 30;
+  size_t b = free_b / 2;                       // leave room for the batch workspaces
+  b = std::min(b, (size_t)48 << 30);
+  return std::max(b, (size_t)1 << 28);
+}
+template <class F>
+static int build_table_chunked(spp_circuit* c, const std::vector<Affine<F>>& pts, uint32_t cbits, uint32_t Wt, Affine<F>** table_out) {
+  if (int e = alloc_table<F>(c, pts.size(), cbits, Wt, table_out)) return e;
+  return build_table<F>(c, pts, cbits, Wt, *table_out, std::min(table_temp_budget(), (size_t)2 << 30));
+}
+
+
+template <class F>
+static int make_set(spp_circuit* c, MsmSet<F>* set, const std::vector<uint32_t>& rows, const std::vector<Affine<F>>& pts, bool from_h,
+                    uint32_t cbits, bool flat) {
+  set->N = (uint32_t)pts.size();
+  set->from_h = from_h;
+  set->c = cbits;
+  set->Wt = flat ? 1 : msm_windows(cbits);
+  if (int e = own_upload(c, &set->rows, rows)) return e;
+  if (int e = alloc_table<F>(c, pts.size(), cbits, set->Wt, &set->table)) return e;
+  pending(c, (F*)nullptr).push_back({pts, set->table, cbits, set->Wt});
+  return 0;
+}
+static int build_pending(spp_circuit* c) {
+  const size_t budget = table_temp_budget();
+  int e = 0;
+  for (auto& p : pending(c, (Fq*)nullptr)) if (!e) e = build_table<Fq>(c, p.pts, p.c, p.Wt, p.table, budget);
+  for (auto& p : pending(c, (Fq2*)nullptr)) if (!e) e = build_table<Fq2>(c, p.pts, p.c, p.Wt, p.table, budget);
+  pending(c, (Fq*)nullptr).clear();
+  pending(c, (Fq2*)nullptr).clear();
+  return e;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// pk container
+// -----------------------------------------------------------------------------------------------------
+namespace {
+struct PkFile {
+  uint32_t circuit_id, n_wires, domain_log, n_public, challenge_wire;
+  G1Affine alpha1, beta1, delta1;
+  G2Affine beta2, delta2;
+  std::vector<uint32_t> A_w, B1_w, B2_w, K_w, CB_w, CS_w;
+  std::vector<G1Affine> A, B1, K, Z, CB, CS;
+  std::vector<G2Affine> B2;
+};
+struct Rd {
+  const uint8_t* p;
+  const uint8_t* end;
+  bool ok = true;
+  uint32_t u32() {
+    if (p + 4 > end) { ok = false; return 0; }
+    uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    p += 4;
+    return v;
+  }
+  const uint8_t* take(size_t n) {
+    if (p + n > end) { ok = false; return nullptr; }
+    const uint8_t* q = p;
+    p += n;
+    return q;
+  }
+};
+bool rd_g1_section(Rd& r, std::vector<uint32_t>* wires, std::vector<G1Affine>& pts) {
+  uint32_t n = r.u32();
+  if (!r.ok || (size_t)n * 64 > (size_t)(r.end - r.p)) return false;
+  if (wires) {
+    wires->resize(n);
+    for (auto& w : *wires) w = r.u32();
+  }
+  pts.resize(n);
+  for (auto& pt : pts) {
+    const uint8_t* b = r.take(64);
+    if (!b) return false;
+    pt = g1_from_raw(b);
+  }
+  return r.ok;
+}
+bool parse_pk(const std::vector<uint8_t>& buf, PkFile& k) {
+  Rd r{buf.data(), buf.data() + buf.size()};
+  if (r.u32() != 0x4b505053u || r.u32() != 1) return false;
+  k.circuit_id = r.u32(); k.n_wires = r.u32(); k.domain_log = r.u32(); k.n_public = r.u32(); k.challenge_wire = r.u32();
+  const uint8_t* b;
+  if (!(b = r.take(64))) return false; k.alpha1 = g1_from_raw(b);
+  if (!(b = r.take(64))) return false; k.beta1 = g1_from_raw(b);
+  if (!(b = r.take(64))) return false; k.delta1 = g1_from_raw(b);
+  if (!(b = r.take(128))) return false; k.beta2 = g2_from_raw(b);
+  if (!(b = r.take(128))) return false; k.delta2 = g2_from_raw(b);
+  if (!rd_g1_section(r, &k.A_w, k.A)) return false;
+  if (!rd_g1_section(r, &k.B1_w, k.B1)) return false;
+  uint32_t n2 = r.u32();
+  if (!r.ok || (size_t)n2 * 128 > (size_t)(r.end - r.p)) return false;
+  k.B2_w.resize(n2);
+  for (auto& w : k.B2_w) w = r.u32();
+  k.B2.resize(n2);
+  for (auto& pt : k.B2) {
+    if (!(b = r.take(128))) return false;
+    pt = g2_from_raw(b);
+  }
+  if (!rd_g1_section(r, &k.K_w, k.K)) return false;
+  if (!rd_g1_section(r, nullptr, k.Z)) return false;
+  if (!rd_g1_section(r, &k.CB_w, k.CB)) return false;
+  if (!rd_g1_section(r, &k.CS_w, k.CS)) return false;
+  return r.ok && r.p == r.end;
+}
+}  // namespace
+
+
+// merge `extra` into the entry of `wire` (or append one)
+template <class F>
+static void merge_point(std::vector<uint32_t>& wires, std::vector<Affine<F>>& pts, uint32_t wire, const Affine<F>& extra) {
+  for (size_t i = 0; i < wires.size(); i++)
+    if (wires[i] == wire) {
+      pts[i] = host_add(pts[i], extra);
+      return;
+    }
+  wires.push_back(wire);
+  pts.push_back(extra);
+}
+
+// Greedy split of an HBM budget over the throughput-layout (one table row per base) MSM sets of one OR SEVERAL circuits: start
+// every set at 6 bits and repeatedly widen the set whose next window bit removes the most mixed-addition work per extra byte
+// (a G2 addition is weighted 3 G1 additions, as measured); `fixed` sets keep their bits.  With several circuits the unit of work
+// is one proof of each (the relayer's pair: an audit proof and a withdraw proof per withdrawal,
+// demo-frontend/app/api/relay/withdraw/route.ts:238-276), so their sets simply compete in one list.
+namespace {
+struct PlanSet {
+  double n, esz, wgt;   // bases, bytes per table entry, weight of an addition (0: fixed)
+  bool flat;            // one row per base (else one row per window)
+  int bits;
+};
+double plan_bytes(const PlanSet& s, int cb) { return s.n * s.esz * (s.flat ? 1.0 : (double)msm_windows((uint32_t)cb)) * (double)(1u << (cb - 1)); }
+void plan_greedy(std::vector<PlanSet>& sets, double budget, int cmax) {
+  double used = 0;
+  for (auto& s : sets) used += plan_bytes(s, s.bits);
+  for (;;) {
+    int best = -1;
+    double best_gain = 0;
+    for (size_t i = 0; i < sets.size(); i++) {
+      const PlanSet& s = sets[i];
+      if (s.wgt == 0 || s.bits >= cmax || s.n == 0) continue;
+      const double extra = plan_bytes(s, s.bits + 1) - plan_bytes(s, s.bits);
+      if (used + extra > budget) continue;
+      const double saved = s.wgt * s.n * ((double)msm_windows((uint32_t)s.bits) - (double)msm_windows((uint32_t)s.bits + 1));
+      double gain = saved / extra;
+      if (saved <= 0) gain = 1e-30;   // a bit that does not change the window count yet may enable the next one
+      if (gain > best_gain) { best_gain = gain; best = (int)i; }
+    }
+    if (best < 0) break;
+    used += plan_bytes(sets[best], sets[best].bits + 1) - plan_bytes(sets[best], sets[best].bits);
+    sets[best].bits++;
+  }
+}
+const double PLAN_ESZ[7] = {64, 64, 64, 64, 64, 64, 128}, PLAN_WGT[7] = {1, 1, 1, 1, 0, 0, 3.0};   // A, B1, K, Z, CB, CS, B2
+}  // namespace
+
+// What the steps of load_circuit_impl share beyond the circuit itself.
+struct LoadState {
+  PkFile pk;
+  uint32_t cw[7];   // window bits per MSM set: A, B1, K, Z, CB, CS, B2
+  bool flat[7] = {false, false, false, false, false, false, false};   // one table row per base (else one per window)
+  // the H bases as rows / points of the Z set and, in the product form, the per-wire column sums that join the K set
+  std::vector<uint32_t> z_w, xk_w;
+  std::vector<G1Affine> z_p, xk_p;
+};
+
+// the experiment switches of the proving path, from the environment (see Switches, spp_circuit.hpp)
+static Switches read_switches() {
+  Switches sw;
+  const char* hm = getenv("SPP_H_MODE");
+  sw.h_mode = hm ? atoi(hm) : (getenv("SPP_Z_COEFF") ? 0 : 2);
+  if (sw.h_mode < 0 || sw.h_mode > 2) sw.h_mode = 2;
+  sw.no_coop = getenv("SPP_NO_COOP") != nullptr;
+  sw.trace_items = getenv("SPP_COOP_TRACE") != nullptr;
+  sw.one_track = getenv("SPP_COOP_ONE_TRACK") != nullptr;
+  sw.no_level_stream = getenv("SPP_NO_LEVEL_STREAM") != nullptr;
+  if (const char* e = getenv("SPP_COOP_MAX")) sw.coop_max_batch = (uint32_t)atoi(e);
+  sw.no_side = getenv("SPP_NO_SIDE") != nullptr;
+  const char* de = getenv("SPP_DEPTH");
+  const int depth = de ? atoi(de) : 0;
+  sw.forced_depth = depth >= 1 && depth <= SPP_NWS ? depth : 0;
+  sw.no_split = getenv("SPP_NO_SPLIT") != nullptr;
+  return sw;
+}
+
+// Window bits and table layout per MSM set.
+//  * window_bits given: every set gets one table row per window (msm_windows(c) rows of 2^(c-1) multiples per base) -- small
+//    tables, a single pass, no Horner step: the layout of the one-proof latency path (the drop-in helpers load 8 bits).
+//  * window_bits = 0 (throughput): the five big sets keep ONE row per base and walk it once per window ("flat", see
+//    kernels_msm.hip); the window of every set is a greedy split of the HBM budget (env SPP_TABLE_BUDGET_GB, default 240 of the
+//    288 GB, capped at 85 % of the free HBM): repeatedly widen the set whose next window bit removes the most mixed-addition
+//    work per extra byte (a G2 addition is weighted 3 G1 additions, as measured).  A flat G1 row at 16 bits is 2 MB per base
+//    and costs 16 additions per full-size scalar; the row-per-window layout of rounds 1-2 afforded 11-12 bits (22-24
+//    additions) in the same bytes (SPP_FLAT=0 brings it back for comparison).  The two commitment sets only ever see bytes /
+//    small counters and sit on the critical path of the challenge: row-per-window tables at 9 bits, no passes.
+static int plan_load_windows(const PkFile& pk, int window_bits, const uint32_t* forced_bits, uint32_t cw[7], bool flat[7]) {
+  const double nset[7] = {(double)pk.A.size() + 2, (double)pk.B1.size() + 2, (double)pk.K.size() + 1, (double)pk.Z.size(),
+                          (double)pk.CB.size(), (double)pk.CS.size(), (double)pk.B2.size() + 2};
+  if (forced_bits) {           // spp_load_circuit_with_windows: the caller planned the windows (spp_plan_windows), throughput layout
+    for (int s = 0; s < 7; s++) {
+      cw[s] = forced_bits[s];
+      flat[s] = PLAN_WGT[s] != 0;
+    }
+  } else if (window_bits != 0) {
+    for (int s = 0; s < 7; s++) cw[s] = (uint32_t)window_bits;
+  } else {
+    const char* fe = getenv("SPP_FLAT");
+    const bool use_flat = !(fe && fe[0] == '0');
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    double budget = 240e9;
+    if (const char* env = getenv("SPP_TABLE_BUDGET_GB")) budget = atof(env) * 1e9;
+    budget = std::min(budget, 0.85 * (double)free_b);
+    std::vector<PlanSet> sets;
+    for (int s = 0; s < 7; s++) {
+      flat[s] = use_flat && PLAN_WGT[s] != 0;
+      sets.push_back({nset[s], PLAN_ESZ[s], PLAN_WGT[s], flat[s], PLAN_WGT[s] != 0 ? 6 : 9});
+    }
+    plan_greedy(sets, budget, use_flat ? 16 : 15);
+    for (int s = 0; s < 7; s++) cw[s] = (uint32_t)sets[s].bits;
+  }
+  return 0;
+}
+
+static int load_r1cs(spp_circuit* c) {
+  const Circuit& circ = c->circ;
+  int e;
+  if ((e = upload_sparse(c, circ, circ.A, &c->dc.A)) || (e = upload_sparse(c, circ, circ.B, &c->dc.B)) ||
+      (e = upload_sparse(c, circ, circ.C, &c->dc.C)) || (e = upload_sparse(c, circ, circ.H, &c->dc.H)))
+    return e;
+  Fr* d_coeffs;
+  Fr* d_aux;
+  uint32_t* d_prog;
+  if ((e = own_upload(c, &d_coeffs, circ.coeffs)) || (e = own_upload(c, &d_prog, circ.program)) || (e = own_upload(c, &d_aux, circ.aux))) return e;
+  c->dc.coeffs = d_coeffs;
+  c->dc.aux = d_aux;
+  c->dc.program = d_prog;
+  c->dc.n_wires = circ.n_wires;
+  c->dc.n_constraints = circ.n_constraints;
+  {
+    // runs of consecutive constraints with identical B rows (at most 8 long, so lanes stay comparable in cost)
+    std::vector<uint32_t> runs;
+    auto same_b = [&](uint32_t k) {
+      const uint32_t a0 = circ.B.rowptr[k - 1], a1 = circ.B.rowptr[k], b1 = circ.B.rowptr[k + 1];
+      if (a1 - a0 != b1 - a1 || a1 == a0) return false;
+      for (uint32_t t = 0; t < a1 - a0; t++)
+        if (circ.B.terms[a0 + t].wire != circ.B.terms[a1 + t].wire || circ.B.terms[a0 + t].coeff != circ.B.terms[a1 + t].coeff) return false;
+      return true;
+    };
+    uint32_t len = 0;
+    for (uint32_t k = 0; k < circ.n_constraints; k++) {
+      if (k == 0 || len >= 8 || !same_b(k)) { runs.push_back(k); len = 0; }
+      len++;
+    }
+    const uint32_t n_runs = (uint32_t)runs.size();
+    runs.push_back(circ.n_constraints);
+    uint32_t* d_runs;
+    if ((e = own_upload(c, &d_runs, runs))) return e;
+    c->dc.run_start = d_runs;
+    c->dc.n_runs = n_runs;
+    uint32_t longest = 0;
+    for (const Sparse* m : {&circ.A, &circ.B, &circ.C})
+      for (uint32_t k = 0; k < circ.n_constraints; k++) longest = std::max(longest, m->rowptr[k + 1] - m->rowptr[k]);
+    c->dc.max_row_terms = longest;
+    std::vector<uint8_t> flags(std::max<uint32_t>(circ.n_constraints, 1), 0);
+    for (uint32_t k = 0; k < circ.n_constraints; k++) {
+      if (k > 0 && same_b(k)) flags[k] |= 1;
+      const uint32_t a0 = circ.A.rowptr[k], a1 = circ.A.rowptr[k + 1], b0 = circ.B.rowptr[k], b1 = circ.B.rowptr[k + 1];
+      bool eq = a1 - a0 == b1 - b0 && a1 != a0;
+      for (uint32_t t = 0; eq && t < a1 - a0; t++)
+        eq = circ.A.terms[a0 + t].wire == circ.B.terms[b0 + t].wire && circ.A.terms[a0 + t].coeff == circ.B.terms[b0 + t].coeff;
+      if (eq) flags[k] |= 2;
+    }
+    uint8_t* d_flags;
+    if ((e = own_upload(c, &d_flags, flags))) return e;
+    c->dc.row_flags = d_flags;
+  }
+  c->dc.n_public = circ.n_public;
+  c->dc.n_inputs = circ.n_inputs();
+  c->dc.challenge_wire = circ.challenge_wire;
+  {
+    auto flat = [](const PoseidonParams& pp) {
+      std::vector<Fr> m;
+      for (auto& row : pp.mds)
+        for (auto& v : row) m.push_back(v);
+      return m;
+    };
+    const PoseidonParams& p3 = poseidon_params(3);
+    const PoseidonParams& p5 = poseidon_params(5);
+    const Poseidon2Params& p2 = poseidon2_params();
+    Fr *a, *b, *cc, *d, *f, *g;
+    std::vector<Fr> mu(p2.mu, p2.mu + 4);
+    auto canon = [](std::vector<Fr> v) {   // words < p: dev_poseidon29's value bounds rely on it
+      for (auto& x : v) x = x.canonical();
+      return v;
+    };
+    if ((e = own_upload(c, &a, canon(p3.rc))) || (e = own_upload(c, &b, flat(p3))) || (e = own_upload(c, &cc, canon(p5.rc))) ||
+        (e = own_upload(c, &d, flat(p5))) || (e = own_upload(c, &f, p2.rc)) || (e = own_upload(c, &g, mu)))
+      return e;
+    std::vector<Fr> bytes(256);
+    for (int i = 0; i < 256; i++) bytes[i] = Fr::from_u64((uint64_t)i);
+    Fr* bm;
+    if ((e = own_upload(c, &bm, bytes))) return e;
+    c->dc.byte_mont = bm;
+    auto flat29 = [](const PoseidonParams& pp) {
+      std::vector<uint32_t> m;
+      for (auto& row : pp.mds)
+        for (auto& v : row) {
+          const F29<FrParams> x = F29<FrParams>::from_fp(v);     // v * 2^261, normalised, < 1.1 p
+          for (int k = 0; k < 9; k++) m.push_back(x.l[k]);
+        }
+      return m;
+    };
+    uint32_t *m3, *m5;
+    if ((e = own_upload(c, &m3, flat29(p3))) || (e = own_upload(c, &m5, flat29(p5)))) return e;
+    c->dc.pos3_mds29 = m3;
+    c->dc.pos5_mds29 = m5;
+    c->dc.pos3_rc = a; c->dc.pos3_mds = b; c->dc.pos5_rc = cc; c->dc.pos5_mds = d; c->dc.p2_rc = f; c->dc.p2_mu = g;
+  }
+  return 0;
+}
+
+static int load_program(spp_circuit* c) {
+  const Circuit& circ = c->circ;
+  // program scan: split into sequential segments (one lane per proof) and wide steps (data-parallel instructions
+  // that get their own kernels: batch divisions and lookup histograms), with the commitment boundary in between
+  bool generic_ops = false;
+  {
+    const auto& pr = circ.program;
+    size_t pc = 0, seg = 0;
+    auto flush = [&](size_t end) {
+      if (end > seg) c->schedule.push_back({SolveStep::SEQ, (uint32_t)seg, (uint32_t)end, 0});
+    };
+    // SPP_SOLVE_TRACE=1 (diagnostic): one launch per instruction class run, so a kernel trace of a proof shows where the
+    // sequential solver spends its time
+    const bool trace_ops = getenv("SPP_SOLVE_TRACE") != nullptr;
+    if (trace_ops) c->sw.no_coop = true;
+    uint32_t prev_op = OP_END;
+    while (pc < pr.size() && pr[pc] != OP_END) {
+      if (trace_ops && pr[pc] != prev_op) {
+        flush(pc);
+        seg = std::max(seg, pc);
+      }
+      prev_op = pr[pc];
+      switch (pr[pc]) {
+        case OP_SOLVE_C: case OP_SOLVE_A: case OP_MASK: pc += 2; break;
+        case OP_BATCH_DIV:
+          c->max_batch_div = std::max(c->max_batch_div, pr[pc + 2]);
+          if (pr[pc + 2] >= 64) {
+            flush(pc);
+            c->schedule.push_back({SolveStep::BATCH_DIV, pr[pc + 1], pr[pc + 2], 0});
+            seg = pc + 3;
+          }
+          pc += 3;
+          break;
+        case OP_COUNT8:
+          flush(pc);
+          c->schedule.push_back({SolveStep::COUNT8, pr[pc + 1], pr[pc + 2], pr[pc + 3]});
+          seg = pc + 4;
+          pc += 4;
+          break;
+        case OP_BITS: case OP_LIMBS8: case OP_POSEIDON: pc += 4; break;
+        case OP_POSEIDON2: case OP_INV_H: pc += 3; break;
+        case OP_COMMIT:
+          flush(pc);
+          c->schedule.push_back({SolveStep::COMMIT, 0, 0, 0});
+          pc += 1;
+          seg = pc;
+          break;
+        case OP_GRUMPKIN: pc += 5 + pr[pc + 4]; break;
+        // the solver of a decoded gnark system (spp/ccs.py to_sppc_solved): one lane per proof, whatever the batch size -- the
+        // cooperative planner knows nothing of these instructions
+        case OP_SOLVE_ROW: case OP_LIMBS: case OP_COUNTN: pc += 5; generic_ops = true; break;
+        case OP_GK_MUL: pc += 7; generic_ops = true; break;
+        case OP_GLV: pc += 3 + 28; generic_ops = true; break;
+        case OP_EMUL: pc += 3 + 16; generic_ops = true; break;
+        default: return fail(SPP_ERR_FORMAT, "bad opcode %u in solver program", pr[pc]);
+      }
+    }
+    flush(pc);
+  }
+
+  c->generic_solver = generic_ops;
+  if (generic_ops) c->sw.no_coop = true;
+  else if (int e = coop_plan(c)) return e;
+  if (int e = row_paths_plan(c)) return e;
+  return 0;
+}
+
+static int load_ntt_tables(spp_circuit* c) {
+  int e;
+  const uint32_t n = c->n, logn = c->logn;
+  Fr w = fr_root_of_unity(logn), wi = w.inv();
+  std::vector<Fr> tf(n / 2), ti(n / 2), cb(n), cib(n);
+  Fr a = Fr::one(), b = Fr::one();
+  for (uint32_t k = 0; k < n / 2; k++) {
+    tf[k] = a;
+    ti[k] = b;
+    a = a * w;
+    b = b * wi;
+  }
+  // the coset: gnark's multiplicative generator 5, or -- product form -- zeta, the primitive 2n-th root of unity with
+  // zeta^2 = w, so that H u zeta*H are the 2n-th roots of unity
+  Fr g = c->sw.h_mode == 2 ? fr_root_of_unity(logn + 1) : Fr::from_u64(5), gi = g.inv(), ninv = Fr::from_u64(n).inv();
+  std::vector<Fr> gp(n), gip(n);
+  Fr x = ninv, y = ninv;
+  for (uint32_t i = 0; i < n; i++) {
+    gp[i] = x;
+    gip[i] = y;
+    x = x * g;
+    y = y * gi;
+  }
+  for (uint32_t pos = 0; pos < n; pos++) {
+    uint32_t i = bitrev(pos, logn);
+    cb[pos] = gp[i];
+    cib[pos] = gip[i];
+  }
+  if ((e = own_upload(c, &c->tw_fwd, tf)) || (e = own_upload(c, &c->tw_inv, ti)) || (e = own_upload(c, &c->coset_br, cb)) ||
+      (e = own_upload(c, &c->coset_inv_br, cib)))
+    return e;
+  Fr gn = g.pow_u64(n);
+  c->zinv = (gn - Fr::one()).inv();
+  return 0;
+}
+
+// the sets whose bases come straight from the key: A, B1, B2
+static int load_key_sets(spp_circuit* c, const LoadState& s) {
+  const PkFile& pk = s.pk;
+  const uint32_t* cw = s.cw;
+  const bool* flat = s.flat;
+  int e;
+  {
+    std::vector<uint32_t> w = pk.A_w;
+    std::vector<G1Affine> p = pk.A;
+    merge_point(w, p, 0u, pk.alpha1);
+    w.push_back(c->row_r); p.push_back(pk.delta1);
+    if ((e = make_set(c, &c->A, w, p, false, cw[0], flat[0]))) return e;
+  }
+  {
+    std::vector<uint32_t> w = pk.B1_w;
+    std::vector<G1Affine> p = pk.B1;
+    merge_point(w, p, 0u, pk.beta1);
+    w.push_back(c->row_s); p.push_back(pk.delta1);
+    if ((e = make_set(c, &c->B1, w, p, false, cw[1], flat[1]))) return e;
+  }
+  {
+    std::vector<uint32_t> w = pk.B2_w;
+    std::vector<G2Affine> p = pk.B2;
+    merge_point(w, p, 0u, pk.beta2);
+    w.push_back(c->row_s); p.push_back(pk.delta2);
+    if ((e = make_set(c, &c->B2, w, p, false, cw[6], flat[6]))) return e;
+  }
+  return 0;
+}
+
+// the H bases (and, in the product form, the per-wire column sums that join the K set)
+static int load_h_bases(spp_circuit* c, LoadState& s) {
+  const PkFile& pk = s.pk;
+  const Circuit& circ = c->circ;
+  spp_ctx* ctx = c->ctx;
+  std::vector<uint32_t>&z_w = s.z_w, &xk_w = s.xk_w;
+  std::vector<G1Affine>&z_p = s.z_p, &xk_p = s.xk_p;
+  int e;
+  if (pk.Z.size() != (size_t)c->n - 1) return fail(SPP_ERR_FORMAT, "Z section has %zu points, expected %u", pk.Z.size(), c->n - 1);
+  const uint32_t n = c->n;
+  hipStream_t st = ctx->stream;
+  // out[i] = sum_j scale[j] w^(-ij) Z_j, natural order (group DFT on the device, kernels_msm.hip)
+  auto eval_basis = [&](const std::vector<Fr>& scale, std::vector<G1Affine>& out) -> int {
+    DevBuf d_pts, d_scale, d_work, d_out;
+    HIP_TRY(d_pts.alloc(pk.Z.size() * sizeof(G1Affine)));
+    HIP_TRY(d_scale.alloc((size_t)n * sizeof(Fr)));
+    HIP_TRY(d_work.alloc((size_t)n * sizeof(G1XYZZ)));
+    HIP_TRY(d_out.alloc((size_t)n * sizeof(G1Affine)));
+    HIP_TRY(hipMemcpyAsync(d_pts.p, pk.Z.data(), pk.Z.size() * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_scale.p, scale.data(), (size_t)n * sizeof(Fr), hipMemcpyHostToDevice, st));
+    launch_g1_eval_basis(st, d_pts.as<G1Affine>(), (uint32_t)pk.Z.size(), c->logn, d_scale.as<Fr>(), c->tw_inv, d_work.as<G1XYZZ>(),
+                         d_out.as<G1Affine>());
+    std::vector<G1Affine> br(n);
+    HIP_TRY(hipMemcpyAsync(br.data(), d_out.p, (size_t)n * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    out.resize(n);
+    for (uint32_t pos = 0; pos < n; pos++) out[bitrev(pos, c->logn)] = br[pos];     // the DIF stages leave element i at bitrev(i)
+    return 0;
+  };
+  if (c->sw.h_mode == 0) {
+    // h comes out of the last DIF pass in bit-reversed order: row `pos` holds h_{bitrev(pos)}
+    for (uint32_t pos = 0; pos < n; pos++) {
+      uint32_t i = bitrev(pos, c->logn);
+      if (i == n - 1) continue;
+      z_w.push_back(pos);
+      z_p.push_back(pk.Z[i]);
+    }
+  } else if (c->sw.h_mode == 1) {
+    // sum_j h_j Z_j = sum_i h(g w^i) Z'_i with Z'_i = sum_j (g^-j / n) w^(-ij) Z_j; row i of the a-slot holds h(g w^i)
+    Fr gi = Fr::from_u64(5).inv(), x = Fr::from_u64(n).inv();
+    std::vector<Fr> scale(n);
+    for (uint32_t j = 0; j < n; j++) { scale[j] = x; x = x * gi; }
+    if ((e = eval_basis(scale, z_p))) return e;
+    for (uint32_t i = 0; i < n; i++) z_w.push_back(i);
+  } else {
+    // Product form.  P = A B has degree <= 2n - 2 and h_j = P_{n+j}; over D = the 2n-th roots of unity P_k = (1/2n) sum_{x in D}
+    // P(x) x^-k, hence  sum_j h_j Z_j = sum_{x in D} P(x) W_x  with  W_x = (1/2n) sum_j x^-(n+j) Z_j:
+    //   x = w^i        (x^-n = 1):   W_i  =  (1/2n) sum_j w^(-ij) Z_j,              P(x) = a_i b_i = c_i = <C_i, witness>
+    //   x = zeta w^i   (x^-n = -1):  W'_i = -(1/2n) sum_j zeta^-j w^(-ij) Z_j,      P(x) = A(x) B(x) from two coset transforms
+    // The first sum is linear in the witness: sum_i c_i W_i = sum_wire w_wire X_wire, X_wire = sum_i C[i][wire] W_i -- a point per
+    // wire, computed here once and added to the wire's base in the K set (wires without one -- public, committed, the
+    // challenge -- join the set with X_wire alone: the sum is part of Krs whatever the wire's class).
+    const Fr inv2n = Fr::from_u64(2 * (uint64_t)n).inv();
+    std::vector<Fr> scale(n, inv2n);
+    std::vector<G1Affine> WH;
+    if ((e = eval_basis(scale, WH))) return e;
+    Fr zi = fr_root_of_unity(c->logn + 1).inv(), x = inv2n.neg();
+    for (uint32_t j = 0; j < n; j++) { scale[j] = x; x = x * zi; }
+    if ((e = eval_basis(scale, z_p))) return e;
+    for (uint32_t i = 0; i < n; i++) z_w.push_back(i);
+    // column sums of C against W
+    struct Tm { uint32_t wire, row; Fr cf; };
+    std::vector<Tm> tms;
+    for (uint32_t k = 0; k < circ.n_constraints; k++)
+      for (uint32_t t = circ.C.rowptr[k]; t < circ.C.rowptr[k + 1]; t++) tms.push_back({circ.C.terms[t].wire, k, circ.coeffs[circ.C.terms[t].coeff]});
+    std::stable_sort(tms.begin(), tms.end(), [](const Tm& a, const Tm& b) { return a.wire < b.wire; });
+    std::vector<uint32_t> rows(tms.size()), seg{0};
+    std::vector<Fr> cfs(tms.size());
+    for (size_t t = 0; t < tms.size(); t++) {
+      rows[t] = tms[t].row;
+      cfs[t] = tms[t].cf;
+      if (t + 1 == tms.size() || tms[t + 1].wire != tms[t].wire) {
+        xk_w.push_back(tms[t].wire);
+        seg.push_back((uint32_t)t + 1);
+      }
+    }
+    if (!tms.empty()) {
+      DevBuf d_base, d_rows, d_cfs, d_seg, d_work, d_out;
+      HIP_TRY(d_base.alloc((size_t)n * sizeof(G1Affine)));
+      HIP_TRY(d_rows.alloc(rows.size() * 4));
+      HIP_TRY(d_cfs.alloc(cfs.size() * sizeof(Fr)));
+      HIP_TRY(d_seg.alloc(seg.size() * 4));
+      HIP_TRY(d_work.alloc(tms.size() * sizeof(G1XYZZ)));
+      HIP_TRY(d_out.alloc(xk_w.size() * sizeof(G1Affine)));
+      HIP_TRY(hipMemcpyAsync(d_base.p, WH.data(), (size_t)n * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_cfs.p, cfs.data(), cfs.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_seg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, st));
+      launch_g1_column_sums(st, d_base.as<G1Affine>(), d_rows.as<uint32_t>(), d_cfs.as<Fr>(), (uint32_t)tms.size(), d_seg.as<uint32_t>(),
+                            (uint32_t)xk_w.size(), d_work.as<G1XYZZ>(), d_out.as<G1Affine>());
+      xk_p.resize(xk_w.size());
+      HIP_TRY(hipMemcpyAsync(xk_p.data(), d_out.p, xk_p.size() * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return 0;
+}
+
+// the sets that depend on the H bases (K, Z) and the two commitment sets; then every table is built
+static int load_h_sets(spp_circuit* c, const LoadState& s) {
+  const PkFile& pk = s.pk;
+  const uint32_t* cw = s.cw;
+  const bool* flat = s.flat;
+  int e;
+  const Circuit& circ = c->circ;
+  const std::vector<uint32_t>&z_w = s.z_w, &xk_w = s.xk_w;
+  const std::vector<G1Affine>&z_p = s.z_p, &xk_p = s.xk_p;
+  {
+    std::vector<uint32_t> w = pk.K_w;
+    std::vector<G1Affine> p = pk.K;
+    if (!xk_w.empty()) {   // product form: K_wire + X_wire (one pass over a wire -> position map; merge_point is linear per call)
+      std::vector<int32_t> at(circ.n_wires + 3, -1);
+      for (size_t i = 0; i < w.size(); i++) at[w[i]] = (int32_t)i;
+      for (size_t i = 0; i < xk_w.size(); i++) {
+        if (xk_p[i].is_inf()) continue;
+        if (at[xk_w[i]] >= 0) p[at[xk_w[i]]] = host_add(p[at[xk_w[i]]], xk_p[i]);
+        else {
+          at[xk_w[i]] = (int32_t)w.size();
+          w.push_back(xk_w[i]);
+          p.push_back(xk_p[i]);
+        }
+      }
+    }
+    w.push_back(c->row_rs); p.push_back(pk.delta1.neg());
+    if ((e = make_set(c, &c->K, w, p, false, cw[2], flat[2]))) return e;
+  }
+  if ((e = make_set(c, &c->Z, z_w, z_p, true, cw[3], flat[3]))) return e;
+  if ((e = make_set(c, &c->CB, pk.CB_w, pk.CB, false, cw[4], false))) return e;
+  if ((e = make_set(c, &c->CS, pk.CS_w, pk.CS, false, cw[5], false))) return e;
+  return build_pending(c);
+}
+
+// streams and events of the batch workspaces
+static int load_streams(spp_circuit* c) {
+  spp_ctx* ctx = c->ctx;
+  for (int k = 0; k < SPP_NWS; k++) {
+    Workspace& w = c->ws[k];
+    // SPP_SERIAL=1 (profiling aid): one stream for everything, so per-stage / per-kernel times are not stretched by
+    // the other batch or by the G2 side stream
+    const bool serial = getenv("SPP_SERIAL") != nullptr;
+    w.own_st = ctx->pstream[k];
+    if (int e = pick_concurrent_stream(w.own_st, &w.own_st2)) return e;
+    {
+      // Batches run the G2 sum on a side stream with a priority of its own.  Streams of one priority share a few hardware queues
+      // round-robin; when st and st2 land on the same one the G2 sum runs in front of the matrix evaluation instead of beside it.
+      // Measured on 2048-proof audit batches (same box, alternating): 4 747-4 760 proofs/s with the priority stream, 4 662-4 707
+      // without.  Small batches keep the default-priority side stream: with a second queue class in use every dispatch of a single
+      // proof's ~120 short kernels started later (audit 12.3 -> 13.6 ms).  SPP_ST2_PRIORITY=0 (diagnostic): never use it.
+      int lo = 0, hi = 0;
+      HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+      const char* pe = getenv("SPP_ST2_PRIORITY");
+      if (!(pe && pe[0] == '0') && hi < lo) HIP_TRY(hipStreamCreateWithPriority(&w.own_st2p, hipStreamDefault, hi));
+    }
+    w.st = serial ? ctx->pstream[0] : w.own_st;
+    w.st2 = serial ? w.st : w.own_st2;
+    HIP_TRY(hipEventCreate(&w.g2_ev.first));
+    HIP_TRY(hipEventCreate(&w.g2_ev.second));
+    HIP_TRY(hipEventCreateWithFlags(&w.ev_w, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&w.ev_b2, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&w.ev_in, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&w.ev_rows, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(w.ev_in, w.st));
+    for (auto& evt : w.ev) HIP_TRY(hipEventCreate(&evt));
+    w.msm_ev.resize(8);
+    for (auto& pr : w.msm_ev) {
+      HIP_TRY(hipEventCreate(&pr.first));
+      HIP_TRY(hipEventCreate(&pr.second));
+    }
+  }
+  return 0;
+}
+
+static int load_circuit_impl(spp_ctx* ctx, const char* circuit_path, const char* pk_path, int window_bits, const uint32_t* forced_bits,
+                             spp_circuit** out) {
+  if (!ctx || !circuit_path || !pk_path || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (window_bits != 0 && (window_bits < 4 || window_bits > 16)) return fail(SPP_ERR_BAD_INPUT, "window_bits %d outside [4,16]", window_bits);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  spp_circuit* c = new spp_circuit();
+  c->ctx = ctx;
+  c->c_bits = (uint32_t)window_bits;
+  // every early return below releases what has been allocated so far
+  struct Guard {
+    spp_circuit* c;
+    ~Guard() { if (c) destroy_circuit(c); }
+  } guard{c};
+  if (!c->circ.load(circuit_path)) return fail(SPP_ERR_IO, "cannot read circuit %s", circuit_path);
+  std::vector<uint8_t> pkbuf;
+  LoadState s;
+  PkFile& pk = s.pk;
+  if (!read_file(pk_path, pkbuf)) return fail(SPP_ERR_IO, "cannot read proving key %s", pk_path);
+  if (!parse_pk(pkbuf, pk)) return fail(SPP_ERR_FORMAT, "malformed proving key %s", pk_path);
+  const Circuit& circ = c->circ;
+  if (pk.circuit_id != circ.id || pk.n_wires != circ.n_wires || pk.domain_log != circ.domain_log)
+    return fail(SPP_ERR_FORMAT, "proving key does not match the circuit");
+  c->sw = read_switches();
+  if (int e = plan_load_windows(pk, window_bits, forced_bits, s.cw, s.flat)) return e;
+  c->c_bits = s.cw[3];   // reported window = that of the largest set (Z)
+  c->logn = circ.domain_log;
+  c->n = 1u << c->logn;
+  c->row_r = circ.n_wires;
+  c->row_s = circ.n_wires + 1;
+  c->row_rs = circ.n_wires + 2;
+  c->n_rows = circ.n_wires + 3;
+  c->in_stride = (size_t)circ.n_inputs() * 32;
+  c->pw_stride = 12 + 32 * (size_t)(circ.n_public - 1);
+  int e;
+  if ((e = load_r1cs(c)) || (e = load_program(c)) || (e = load_ntt_tables(c)) || (e = load_key_sets(c, s)) || (e = load_h_bases(c, s)) ||
+      (e = load_h_sets(c, s)) || (e = load_streams(c)))
+    return e;
+  guard.c = nullptr;
+  *out = c;
+  return SPP_OK;
+}
+extern "C" int spp_load_circuit(spp_ctx* ctx, const char* circuit_path, const char* pk_path, int window_bits, spp_circuit** out) {
+  return load_circuit_impl(ctx, circuit_path, pk_path, window_bits, nullptr, out);
+}
+extern "C" int spp_load_circuit_with_windows(spp_ctx* ctx, const char* circuit_path, const char* pk_path, const uint32_t bits[7],
+                                             spp_circuit** out) {
+  if (!bits) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  for (int s = 0; s < 7; s++)
+    if (bits[s] < 4 || bits[s] > 16) return fail(SPP_ERR_BAD_INPUT, "window bits %u of set %d outside [4,16]", bits[s], s);
+  return load_circuit_impl(ctx, circuit_path, pk_path, 0, bits, out);
+}
+
+void free_workspace(Workspace& w) {
+  if (w.audit_scratch) hipFree(w.audit_scratch);
+  w.audit_scratch = nullptr;
+  w.audit_scratch_cap = 0;
+  for (void* p : w.owned) hipFree(p);
+  w.owned.clear();
+  w.cap = 0;
+}
+void destroy_circuit(spp_circuit* c) {
+  if (!c) return;
+  hipSetDevice(c->ctx->device);
+  hipStreamSynchronize(c->ctx->stream);
+  for (auto& w : c->ws) {
+    if (w.st) hipStreamSynchronize(w.st);
+    if (w.own_st2) { hipStreamSynchronize(w.own_st2); hipStreamDestroy(w.own_st2); }
+    if (w.own_st2p) { hipStreamSynchronize(w.own_st2p); hipStreamDestroy(w.own_st2p); }
+    if (w.g2_ev.first) hipEventDestroy(w.g2_ev.first);
+    if (w.g2_ev.second) hipEventDestroy(w.g2_ev.second);
+    if (w.ev_w) hipEventDestroy(w.ev_w);
+    if (w.ev_b2) hipEventDestroy(w.ev_b2);
+    if (w.ev_in) hipEventDestroy(w.ev_in);
+    if (w.ev_rows) hipEventDestroy(w.ev_rows);
+    free_workspace(w);
+    for (auto& evt : w.ev) if (evt) hipEventDestroy(evt);
+    for (auto& pr : w.msm_ev) {
+      if (pr.first) hipEventDestroy(pr.first);
+      if (pr.second) hipEventDestroy(pr.second);
+    }
+  }
+  for (void* p : c->owned) hipFree(p);
+  delete c;
+}
+extern "C" void spp_free_circuit(spp_circuit* c) { destroy_circuit(c); }
+extern "C" int spp_circuit_info(const spp_circuit* c, uint32_t info[8]) {
+  if (!c || !info) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  info[0] = c->circ.id; info[1] = c->circ.n_public - 1; info[2] = c->circ.n_secret; info[3] = c->circ.n_wires;
+  info[4] = c->circ.n_constraints; info[5] = c->circ.domain_log; info[6] = c->circ.n_inputs(); info[7] = c->c_bits;
+  return SPP_OK;
+}
+extern "C" uint64_t spp_circuit_table_bytes(const spp_circuit* c) { return c ? c->table_bytes : 0; }
+extern "C" int spp_circuit_small_rows(const spp_circuit* c, uint32_t out[2]) {
+  if (!c || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  out[0] = c->dc.sm_nrows;
+  out[1] = c->dc.sm_nslots;
+  return SPP_OK;
+}
+extern "C" int spp_circuit_msm_windows(const spp_circuit* c, uint32_t bits[7]) {
+  if (!c || !bits) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  bits[0] = c->A.c; bits[1] = c->B1.c; bits[2] = c->K.c; bits[3] = c->Z.c; bits[4] = c->CB.c; bits[5] = c->CS.c; bits[6] = c->B2.c;
+  return SPP_OK;
+}
+extern "C" int spp_circuit_msm_table_rows(const spp_circuit* c, uint32_t rows[7]) {
+  if (!c || !rows) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  rows[0] = c->A.Wt; rows[1] = c->B1.Wt; rows[2] = c->K.Wt; rows[3] = c->Z.Wt; rows[4] = c->CB.Wt; rows[5] = c->CS.Wt; rows[6] = c->B2.Wt;
+  return SPP_OK;
+}
+extern "C" int spp_circuit_msm_sizes(const spp_circuit* c, uint32_t sizes[7]) {
+  if (!c || !sizes) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  sizes[0] = c->A.N; sizes[1] = c->B1.N; sizes[2] = c->K.N; sizes[3] = c->Z.N; sizes[4] = c->CB.N; sizes[5] = c->CS.N; sizes[6] = c->B2.N;
+  return SPP_OK;
+}
+
+// bases per MSM set of a proving key file, as spp_circuit_msm_sizes reports them after loading (A, B1, K, Z, CB, CS, B2): what
+// spp_plan_windows needs before anything is loaded
+extern "C" int spp_pk_msm_sizes(const char* pk_path, uint32_t sizes[7]) {
+  if (!pk_path || !sizes) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  std::vector<uint8_t> pkbuf;
+  PkFile pk;
+  if (!read_file(pk_path, pkbuf)) return fail(SPP_ERR_IO, "cannot read proving key %s", pk_path);
+  if (!parse_pk(pkbuf, pk)) return fail(SPP_ERR_FORMAT, "malformed proving key %s", pk_path);
+  sizes[0] = (uint32_t)pk.A.size() + 2; sizes[1] = (uint32_t)pk.B1.size() + 2; sizes[2] = (uint32_t)pk.K.size() + 1;
+  sizes[3] = (uint32_t)pk.Z.size(); sizes[4] = (uint32_t)pk.CB.size(); sizes[5] = (uint32_t)pk.CS.size(); sizes[6] = (uint32_t)pk.B2.size() + 2;
+  return SPP_OK;
+}
+// window bits for the sets of n_circuits circuits that are to live on one GPU TOGETHER: sizes / bits = n_circuits x 7 (the order
+// above); one greedy split of budget_bytes over the union of their sets (see plan_greedy).  Host only.
+extern "C" int spp_plan_windows(uint32_t n_circuits, const uint32_t* sizes, double budget_bytes, uint32_t* bits) {
+  if (!sizes || !bits || n_circuits == 0 || n_circuits > 16) return fail(SPP_ERR_BAD_INPUT, "bad argument");
+  std::vector<PlanSet> sets;
+  for (uint32_t k = 0; k < n_circuits; k++)
+    for (int s = 0; s < 7; s++) sets.push_back({(double)sizes[7 * k + s], PLAN_ESZ[s], PLAN_WGT[s], PLAN_WGT[s] != 0, PLAN_WGT[s] != 0 ? 6 : 9});
+  double floor_bytes = 0;
+  for (auto& ps : sets) floor_bytes += plan_bytes(ps, ps.bits);
+  if (floor_bytes > budget_bytes) return fail(SPP_ERR_BAD_INPUT, "the budget does not hold even 6-bit tables (%.1f GB needed)", floor_bytes / 1e9);
+  plan_greedy(sets, budget_bytes, 16);
+  for (size_t i = 0; i < sets.size(); i++) bits[i] = (uint32_t)sets[i].bits;
+  return SPP_OK;
+}
+// -----------------------------------------------------------------------------------------------------
+// table-based MSM over caller-supplied bases (unit entry point; uses the table builder above)
+// -----------------------------------------------------------------------------------------------------
+template <class F> static Affine<F> point_from_raw(const uint8_t* b);
+template <> Affine<Fq> point_from_raw<Fq>(const uint8_t* b) { return g1_from_raw(b); }
+template <> Affine<Fq2> point_from_raw<Fq2>(const uint8_t* b) { return g2_from_raw(b); }
+static void point_to_raw(const G1Affine& p, uint8_t* b) { g1_to_raw(p, b); }
+static void point_to_raw(const G2Affine& p, uint8_t* b) { g2_to_raw(p, b); }
+template <class F, size_t PT_BYTES>
+static int msm_fixed_unit(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, int window_bits, uint8_t* out) {
+  if (!ctx || !out || (n && (!bases || !scalars))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (window_bits == 0) window_bits = 8;
+  if (window_bits < 4 || window_bits > 16) return fail(SPP_ERR_BAD_INPUT, "window_bits outside [4,16]");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const uint32_t cb = (uint32_t)window_bits, Wn = msm_windows(cb), E = 1u << (cb - 1);
+  (void)E;
+  if ((uint64_t)msm_table_elems((uint32_t)n, cb, Wn) * PT_BYTES > ((uint64_t)64 << 30)) return fail(SPP_ERR_BAD_INPUT, "table would exceed 64 GiB; use a smaller window");
+  std::vector<Affine<F>> pts(n);
+  std::vector<Fr> sc(n);
+  std::vector<uint32_t> rows(n);
+  for (size_t i = 0; i < n; i++) {
+    pts[i] = point_from_raw<F>(bases + PT_BYTES * i);
+    sc[i] = Fr::from_bytes_be(scalars + 32 * i);
+    rows[i] = (uint32_t)i;
+  }
+  spp_circuit tmpc;   // only used as an owner of device allocations
+  tmpc.ctx = ctx;
+  tmpc.c_bits = cb;
+  Affine<F>* table = nullptr;
+  int e = build_table_chunked<F>(&tmpc, pts, cb, Wn, &table);
+  Fr* d_sc = nullptr;
+  uint32_t* d_rows = nullptr;
+  XYZZ<F> *partial = nullptr, *d_out = nullptr;
+  DevBuf dig;
+  const MsmPlan pl = msm_plan((uint32_t)n, 1, cb, Wn);
+  if (!e) e = own_upload(&tmpc, &d_sc, sc);
+  if (!e) e = own_upload(&tmpc, &d_rows, rows);
+  if (!e && hipMalloc((void**)&partial, sizeof(XYZZ<F>) * std::max<size_t>(pl.partial_elems(1), 1)) != hipSuccess) e = fail(SPP_ERR_HIP, "hipMalloc");
+  if (!e && hipMalloc((void**)&d_out, sizeof(XYZZ<F>)) != hipSuccess) e = fail(SPP_ERR_HIP, "hipMalloc");
+  if (!e && dig.alloc(sizeof(int16_t) * std::max<size_t>(msm_digit_elems((uint32_t)n, 1, cb), 1)) != hipSuccess) e = fail(SPP_ERR_HIP, "hipMalloc");
+  XYZZ<F> res = XYZZ<F>::infinity();
+  if (!e) {
+    launch_msm_digits(st, d_rows, d_sc, dig.as<int16_t>(), (uint32_t)n, 1, cb);
+    launch_msm_accumulate<F>(st, table, dig.as<int16_t>(), partial, (uint32_t)n, 1, cb, pl);
+    launch_msm_reduce<F>(st, partial, d_out, 1, pl, cb, n == 0);
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) e = fail(SPP_ERR_HIP, "msm kernels failed");
+    else if (hipMemcpy(&res, d_out, sizeof res, hipMemcpyDeviceToHost) != hipSuccess) e = fail(SPP_ERR_HIP, "copy back failed");
+  }
+  for (void* p : tmpc.owned) hipFree(p);
+  if (partial) hipFree(partial);
+  if (d_out) hipFree(d_out);
+  if (e) return e;
+  point_to_raw(res.to_affine(), out);
+  return SPP_OK;
+}
+extern "C" int spp_msm_g1(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, int window_bits, uint8_t out[64]) {
+  return msm_fixed_unit<Fq, 64>(ctx, bases, scalars, n, window_bits, out);
+}
+// the same walk over G2 bases (128 B, gnark raw X.A1|X.A0|Y.A1|Y.A0): what Bs of a proof comes from (k_msm_fixed<Fq2>)
+extern "C" int spp_msm_g2(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, int window_bits, uint8_t out[128]) {
+  return msm_fixed_unit<Fq2, 128>(ctx, bases, scalars, n, window_bits, out);
+}

@@ -1,0 +1,530 @@
+// libspp C ABI, proving: the batch workspaces, the proving pipeline of one batch (prove_on_device) and the entry points that
+// schedule batches over the workspaces and proving streams of a circuit; timing queries.  Nothing here reads the environment:
+// the experiment switches are fields of the circuit (Switches, spp_circuit.hpp).
+#include "spp_circuit.hpp"
+
+template <class T>
+static int ws_alloc(Workspace& w, T** p, size_t count) {
+  HIP_TRY(hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1)));
+  w.owned.push_back((void*)*p);
+  return 0;
+}
+template <class F>
+static int ws_set(Workspace& w, const MsmSet<F>* s, MsmBuf<F>* b, size_t P) {
+  // R * Sg(P') * P' <= lane target + R * P' for every P' <= P (msm_plan); small batches: up to 64K (item, pass) lanes
+  const uint32_t occ = sizeof(F) > sizeof(Fq) ? 1 : 2;
+  const uint32_t R = msm_plan(s->N, (uint32_t)P, s->c, s->Wt, occ).R;
+  b->partial_cap = (size_t)256 * 4 * 8 * 64 + 65536 + (size_t)(R + 1) * (P + 64);
+  for (size_t q = P; q >= 1; q /= 2)   // and the exact need at the sizes most likely to be used
+    b->partial_cap = std::max(b->partial_cap, msm_plan(s->N, (uint32_t)q, s->c, s->Wt, occ).partial_elems((uint32_t)q));
+  int e;
+  if ((e = ws_alloc(w, &b->partial, b->partial_cap))) return e;
+  return ws_alloc(w, &b->out, P);
+}
+static int ensure_workspace(spp_circuit* c, Workspace& w, size_t P) {
+  if (P <= w.cap) return 0;
+  HIP_TRY(hipStreamSynchronize(w.st));
+  free_workspace(w);
+  int e;
+  if ((e = ws_alloc(w, &w.W, (size_t)c->n_rows * P)) || (e = ws_alloc(w, &w.abc, (size_t)3 * c->n * P)) ||
+      (e = ws_alloc(w, &w.scratch, (size_t)c->max_batch_div * P)) || (e = ws_alloc(w, &w.commit_affine, P)) ||
+      (e = ws_alloc(w, &w.d_inputs, c->in_stride * P)) || (e = ws_alloc(w, &w.d_rs, 64 * P)) ||
+      (e = ws_alloc(w, &w.d_proofs, (size_t)SPP_PROOF_LEN * P)) || (e = ws_alloc(w, &w.d_pws, c->pw_stride * P)) ||
+      (e = ws_alloc(w, &w.d_status, P)) || (e = ws_alloc(w, &w.counters, 256 * P)))
+    return e;
+  if ((e = ws_set(w, &c->A, &w.A, P)) || (e = ws_set(w, &c->B1, &w.B1, P)) || (e = ws_set(w, &c->B2, &w.B2, P)) ||
+      (e = ws_set(w, &c->K, &w.K, P)) || (e = ws_set(w, &c->Z, &w.Z, P)) || (e = ws_set(w, &c->CB, &w.CB, P)) ||
+      (e = ws_set(w, &c->CS, &w.CS, P)))
+    return e;
+  {
+    const size_t Ps = std::min<size_t>(P, scaled_blind_max_batch(c->A.N, c->B1.N));
+    if ((e = ws_set(w, &c->A, &w.sA, Ps)) || (e = ws_set(w, &c->B1, &w.rB, Ps)) || (e = ws_alloc(w, &w.Ws, (size_t)c->n_rows * Ps)) ||
+        (e = ws_alloc(w, &w.Wr, (size_t)c->n_rows * Ps)))
+      return e;
+  }
+  {
+    // digit planes: the G1 sets share one buffer (they run one after the other on `st`), the G2 set has its own
+    size_t d1 = 0;
+    for (const MsmSet<Fq>* s : {&c->A, &c->B1, &c->K, &c->Z, &c->CB, &c->CS}) d1 = std::max(d1, msm_digit_elems(s->N, (uint32_t)P, s->c));
+    w.dig1_cap = d1;
+    w.dig2_cap = msm_digit_elems(c->B2.N, (uint32_t)P, c->B2.c);
+    if ((e = ws_alloc(w, &w.dig1, w.dig1_cap)) || (e = ws_alloc(w, &w.dig2, w.dig2_cap))) return e;
+    if (c->dc.sm_nrows && (e = ws_alloc(w, &w.small, (size_t)c->dc.sm_nslots * P))) return e;
+  }
+  w.cap = P;
+  return 0;
+}
+
+static int16_t* ws_dig(Workspace& w, Fq*) { return w.dig1; }
+static int16_t* ws_dig(Workspace& w, Fq2*) { return w.dig2; }
+// digits + accumulate of one set; the caller folds (several sets share the fold launches): b.plan holds the lane layout
+template <class F>
+static void run_msm(spp_circuit* c, Workspace& w, const MsmSet<F>& s, MsmBuf<F>& b, uint32_t P, bool timed, hipStream_t st_override = nullptr,
+                    std::pair<hipEvent_t, hipEvent_t>* ev_override = nullptr, bool fold = true, const Fr* scal_override = nullptr) {
+  hipStream_t st = st_override ? st_override : w.st;
+  const Fr* scal = scal_override ? scal_override : s.from_h ? w.abc : w.W;
+  MsmPlan pl = msm_plan(s.N, P, s.c, s.Wt, sizeof(F) > sizeof(Fq) ? 1 : 2);
+  while (pl.Sg > 1 && pl.partial_elems(P) > b.partial_cap) pl.Sg--;  // never exceed the allocated partial buffer
+  b.plan = pl;
+  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+  if (timed && w.msm_ev_used < w.msm_ev.size()) ev = &w.msm_ev[w.msm_ev_used++];
+  if (ev_override) ev = ev_override;
+  int16_t* dig = ws_dig(w, (F*)nullptr);
+  launch_msm_digits(st, s.rows, scal, dig, s.N, P, s.c);
+  // the event pair receives the dispatch's own start/stop timestamps (what rocprofv3 reports as the kernel's duration)
+  launch_msm_accumulate<F>(st, s.table, dig, b.partial, s.N, P, s.c, pl, ev ? ev->first : nullptr, ev ? ev->second : nullptr);
+  if (fold) launch_msm_reduce<F>(st, b.partial, b.out, P, pl, s.c, s.N == 0);
+}
+
+static int prove_on_device(spp_circuit* c, Workspace& w, uint32_t P, const uint8_t* d_inputs, const uint8_t* d_rs, uint8_t* d_proofs,
+                           uint8_t* d_pws, uint32_t* d_status) {
+  hipStream_t st = w.st;
+  const Circuit& circ = c->circ;
+  const uint32_t n = c->n;
+  w.msm_ev_used = 0;
+  w.last_P = P;
+  const bool scaled_blind = P <= scaled_blind_max_batch(c->A.N, c->B1.N) && !c->sw.no_coop;
+  HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(uint32_t) * P, st));
+  hipEventRecord(w.ev[0], st);
+  // 1. inputs, solver phase 1, commitment, challenge, solver phase 2
+  launch_load_inputs(st, d_inputs, d_rs, w.W, circ.n_inputs(), circ.n_wires, P);
+  hipEventRecord(w.ev_in, st);
+  for (const SolveStep& s : c->schedule) {
+    switch (s.kind) {
+      case SolveStep::SEQ:
+        if (P <= c->sw.coop_max_batch && !c->sw.no_coop && c->sw.trace_items) {
+          for (uint32_t t = 0; t < s.ntracks; t++)
+            for (uint32_t it = s.tr_begin[t]; it < s.tr_end[t]; it++) {
+              CoopTracks one{};
+              one.n = 1; one.begin[0] = it; one.end[0] = it + 1;
+              launch_solve_coop(st, c->dc, c->coop, w.W, w.scratch, one, P);
+            }
+        } else if (P <= c->sw.coop_max_batch && !c->sw.no_coop) {
+          CoopTracks tr{};
+          tr.n = c->sw.one_track ? 1 : s.ntracks;
+          for (uint32_t t = 0; t < s.ntracks; t++) { tr.begin[t] = s.tr_begin[t]; tr.end[t] = s.tr_end[t]; }
+          if (c->sw.one_track) {   // SPP_COOP_ONE_TRACK=1 (diagnostic): the tracks one after the other
+            for (uint32_t t = 0; t < s.ntracks; t++) {
+              CoopTracks one{};
+              one.n = 1; one.begin[0] = s.tr_begin[t]; one.end[0] = s.tr_end[t];
+              launch_solve_coop(st, c->dc, c->coop, w.W, w.scratch, one, P);
+            }
+          } else launch_solve_coop(st, c->dc, c->coop, w.W, w.scratch, tr, P);
+        }
+        else launch_solve(st, c->dc, w.W, w.scratch, s.a, s.b, P);
+        break;
+      case SolveStep::BATCH_DIV: launch_batch_div(st, c->dc, w.W, w.scratch, s.a, s.b, P); break;
+      case SolveStep::COUNT8: launch_count8(st, c->dc, w.W, w.counters, s.a, s.b, s.c, P); break;
+      case SolveStep::COMMIT:
+        run_msm(c, w, c->CB, w.CB, P, true);
+        launch_challenge(st, w.CB.out, w.W, circ.challenge_wire, P, w.commit_affine, d_status);
+        break;
+    }
+  }
+  hipEventRecord(w.ev[1], st);
+  // the G2 MSM depends on the witness only: start it now on the side stream
+  hipEventRecord(w.ev_w, st);
+  hipStream_t side = (w.st2 != w.st && w.own_st2p && P > c->sw.coop_max_batch) ? w.own_st2p : w.st2;
+  if (c->sw.no_side && P <= c->sw.coop_max_batch) side = st;   // experiment: the G2 sum on the batch's own stream
+  hipStreamWaitEvent(side, w.ev_w, 0);
+  run_msm(c, w, c->B2, w.B2, P, false, side, &w.g2_ev);
+  hipEventRecord(w.ev_b2, side);
+  // 2. constraint evaluations + satisfaction check
+  launch_spmv_check(st, c->dc, w.W, w.abc, n, P, d_status, w.small);
+  hipEventRecord(w.ev[2], st);
+  // 3. h = (a*b - c)/Z  (coefficients land bit-reversed in the a-slot of abc)
+  const size_t bs = (size_t)n * P;
+  // the coset shifts ride on the stores of the inverse transforms' last pass (no separate pass over the arrays)
+  const uint32_t nt = c->sw.h_mode == 2 ? 2 : 3;      // product form: A and B only
+  launch_ntt(st, w.abc, c->logn, P, c->tw_inv, true, nt, bs, c->coset_br);
+  launch_ntt(st, w.abc, c->logn, P, c->tw_fwd, false, nt, bs);
+  if (c->sw.h_mode == 2) launch_qap_product(st, w.abc, n, P);
+  else launch_qap_pointwise(st, w.abc, n, P, c->zinv);
+  if (c->sw.h_mode == 0) launch_ntt(st, w.abc, c->logn, P, c->tw_inv, true, 1, bs, c->coset_inv_br);   // else: the Z bases are in the evaluation basis
+  hipEventRecord(w.ev[3], st);
+  // 4. MSMs
+  {
+    MsmFoldSets<Fq> fs{};
+    const MsmSet<Fq>* sets[7] = {&c->A, &c->B1, &c->K, &c->Z, &c->CS, &c->A, &c->B1};
+    MsmBuf<Fq>* bufs[7] = {&w.A, &w.B1, &w.K, &w.Z, &w.CS, &w.sA, &w.rB};
+    const Fr* scal[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, w.Ws, w.Wr};
+    const int nsets = scaled_blind ? 7 : 5;
+    if (scaled_blind) launch_scale_witness(st, w.W, w.Ws, w.Wr, c->n_rows, c->row_r, c->row_s, P);
+    for (int i = 0; i < nsets; i++) {
+      run_msm(c, w, *sets[i], *bufs[i], P, i < 5, nullptr, nullptr, false, scal[i]);
+      fs.partial[i] = bufs[i]->partial;
+      fs.out[i] = bufs[i]->out;
+      fs.Sg[i] = sets[i]->N ? bufs[i]->plan.Sg : 0;
+      fs.R[i] = bufs[i]->plan.R;
+      fs.c[i] = sets[i]->c;
+    }
+    launch_msm_reduce_multi<Fq>(st, fs, nsets, P);   // the slice sums are folded level by level in shared launches, then Horner
+  }
+  hipEventRecord(w.ev[4], st);
+  hipStreamWaitEvent(st, w.ev_b2, 0);   // join the G2 MSM
+  hipEventRecord(w.ev[5], st);
+  // 5. assembly
+  AssembleArgs a;
+  a.mA = w.A.out; a.mB1 = w.B1.out; a.mB2 = w.B2.out; a.mK = w.K.out; a.mZ = w.Z.out; a.mPok = w.CS.out;
+  a.commit_affine = w.commit_affine;
+  a.W = w.W; a.row_r = c->row_r; a.row_s = c->row_s; a.n_public = circ.n_public;
+  a.sAr = scaled_blind ? w.sA.out : nullptr;
+  a.rBs1 = scaled_blind ? w.rB.out : nullptr;
+  a.proofs = d_proofs; a.pws = d_pws; a.P = P;
+  launch_assemble(st, a);
+  hipEventRecord(w.ev[6], st);
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// scheduling: which workspace a batch takes, where a batch is cut, where its outputs go
+// -----------------------------------------------------------------------------------------------------
+// Batches in flight: two for big batches (more adds nothing once the latency-bound phases are covered: DESIGN 8.3); small
+// batches -- 128 proofs are one of 8 ranks' share of BASELINE.json configs[2] -- spend a larger part of their time in
+// latency-bound kernels (11 ms of sponge chain in the solver, the Horner combines), so up to six take turns
+// (128-proof audit batches, ms per step on one box: 25.3 with four in flight, 23.3 with five, 23.1 with six).
+static int ws_depth(const spp_circuit* c, size_t count, bool generic_solver) {
+  if (c->sw.forced_depth) return c->sw.forced_depth;
+  return count <= 256 ? 6 : count <= 768 ? 4 : generic_solver ? 3 : 2;
+}
+// the next workspace of the rotation over the first `depth`; c->ws[c->next_ws] is then the one after it
+static Workspace& take_workspace(spp_circuit* c, int depth) {
+  if (c->next_ws >= depth) c->next_ws = 0;
+  const int wi = c->next_ws;
+  c->prev_ws = c->last_ws;
+  c->last_ws = wi;
+  c->next_ws = (wi + 1) % depth;
+  return c->ws[wi];
+}
+// The start of a device call: the batch's workspace, with every workspace of the depth sized to `count` on the first call, so
+// that no allocation ever lands inside a caller's timed / pipelined region.
+static int take_sized_workspace(spp_circuit* c, size_t count, bool generic_solver, Workspace** w) {
+  const int depth = ws_depth(c, count, generic_solver);
+  *w = &take_workspace(c, depth);
+  for (int k = 0; k < depth; k++)
+    if (int e = ensure_workspace(c, c->ws[k], count)) return e;
+  return 0;
+}
+// A batch that is not a multiple of the wave width is cut into a 64-aligned body and a tail of < 64 proofs: the size of the tail.
+// Every kernel of the path maps 64 proofs to a wave, so 1025 proofs used to cost a 17th wave per (slice, window) everywhere -- and
+// before the lanes were padded to waves, every wave of the MSM straddled two slices (1024 -> 1025 proofs: +23 % time, profiles/
+// round2_batch_size_sweep.txt).  The tail takes the small-batch paths (cooperative solver, lanes per (base, proof)) on the
+// NEXT workspace of the rotation and its proving stream, beside the body; the next call starts on that stream, behind the short
+// tail.  SPP_NO_SPLIT=1: off.
+static size_t batch_tail(const spp_circuit* c, size_t count) { return count > 64 && !c->sw.no_split ? count % 64 : 0; }
+// where a batch reads its blinding and writes its outputs, in device memory
+struct BatchIO {
+  const uint8_t* rs;
+  uint8_t *proofs, *pws;
+  uint32_t* status;
+  BatchIO at(const spp_circuit* c, size_t off) const {   // the same for the batch that starts at proof `off`
+    return {rs + off * 64, proofs + off * SPP_PROOF_LEN, pws + off * c->pw_stride, status + off};
+  }
+};
+static int prove_on_device(spp_circuit* c, Workspace& w, size_t P, const uint8_t* d_inputs, const BatchIO& io) {
+  return prove_on_device(c, w, (uint32_t)P, d_inputs, io.rs, io.proofs, io.pws, io.status);
+}
+
+// -----------------------------------------------------------------------------------------------------
+// entry points: argument checks, the input stage that is their own, the shared tail
+// -----------------------------------------------------------------------------------------------------
+extern "C" int spp_prove_batch_device(spp_circuit* c, size_t count, const void* d_inputs, const void* d_rs, void* d_proofs, void* d_pws,
+                                      void* d_status) {
+  if (!c || !d_inputs || !d_rs || !d_proofs || !d_pws || !d_status) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 20)) return fail(SPP_ERR_BAD_INPUT, "batch too large");
+  std::lock_guard<std::mutex> lk(c->ctx->mu);
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  Workspace* w;
+  if (int e = take_sized_workspace(c, count, c->generic_solver, &w)) return e;
+  const BatchIO io{(const uint8_t*)d_rs, (uint8_t*)d_proofs, (uint8_t*)d_pws, (uint32_t*)d_status};
+  const size_t tail = batch_tail(c, count), body = count - tail;
+  if (int e = prove_on_device(c, *w, body, (const uint8_t*)d_inputs, io)) return e;
+  if (!tail) return SPP_OK;
+  return prove_on_device(c, c->ws[c->next_ws], tail, (const uint8_t*)d_inputs + body * c->in_stride, io.at(c, body));
+}
+// End to end: the audit proof from the prover's raw secrets.  The input pipeline of scripts/generate_audit.py:468-641 (keygen,
+// wa_commitment, RLWE encryption, quotients, packing, ct_commitment) is enqueued on the batch's own proving stream in front of the
+// solver, into the workspace's input rows: nothing returns to the host between the secrets and the proof bytes, and the
+// pipelining of consecutive calls is that of spp_prove_batch_device.
+extern "C" int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk,
+                                                   const void* d_r, const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs,
+                                                   void* d_pws, void* d_status) {
+  if (!c || !d_pk_a || !d_pk_b || !d_sk || !d_r || !d_e1 || !d_e2 || !d_rs || !d_proofs || !d_pws || !d_status)
+    return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (c->circ.id != SPP_CIRCUIT_AUDIT || c->circ.n_inputs() != 3360) return fail(SPP_ERR_BAD_INPUT, "not the audit circuit");
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 20)) return fail(SPP_ERR_BAD_INPUT, "batch too large");
+  std::lock_guard<std::mutex> lk(c->ctx->mu);
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  if (int e = spp_ensure_ctx_consts(c->ctx)) return e;
+  Workspace* wp;
+  if (int e = take_sized_workspace(c, count, false, &wp)) return e;
+  Workspace& w = *wp;
+  const size_t need = spp_audit_scratch_bytes(count);
+  if (need > w.audit_scratch_cap) {
+    HIP_TRY(hipStreamSynchronize(w.st));
+    if (w.audit_scratch) HIP_TRY(hipFree(w.audit_scratch));
+    w.audit_scratch = nullptr;
+    w.audit_scratch_cap = 0;
+    HIP_TRY(hipMalloc(&w.audit_scratch, need));
+    w.audit_scratch_cap = need;
+  }
+  if (int e = spp_audit_inputs_enqueue(c->ctx, w.st, w.audit_scratch, (const uint32_t*)d_pk_a, (const uint32_t*)d_pk_b, (uint32_t)count,
+                                       (const uint8_t*)d_sk, (const int8_t*)d_r, (const int8_t*)d_e1, (const int8_t*)d_e2, w.d_inputs))
+    return e;
+  // one piece, no cut into body and tail (batch_tail): the cut would change which kernels a 2 049-proof audit batch runs
+  return prove_on_device(c, w, count, w.d_inputs, BatchIO{(const uint8_t*)d_rs, (uint8_t*)d_proofs, (uint8_t*)d_pws, (uint32_t*)d_status});
+}
+// Withdraw proofs from notes against the resident tree (include/spp.h).  The rows are gathered on the TREE's stream (ctx->stream),
+// not on the proving stream: spp_merkle_tree_insert runs there and may reallocate the level arrays (mt_reserve), so an insert
+// made right after this call is stream-ordered behind the gather and every proof of the call is against the root at call time.
+// Under the context lock: (1) ctx->stream waits until the workspace's previous batch has loaded its rows (ev_in), (2) the rows
+// kernel writes into the workspace's d_inputs, (3) the proving stream waits for it (ev_rows).  A batch that is not a multiple
+// of the wave width is split into body and tail as in spp_prove_batch_device; the tail's rows go to the tail workspace's own
+// d_inputs, so each workspace's rows are only ever read by its own stream.
+static int withdraw_notes_args(spp_circuit* c, spp_merkle_tree* t) {
+  if (c->circ.id != SPP_CIRCUIT_WITHDRAW) return fail(SPP_ERR_BAD_INPUT, "not a withdraw circuit");
+  if (t->ctx != c->ctx) return fail(SPP_ERR_BAD_INPUT, "the tree belongs to another context");
+  if (c->circ.n_inputs() != 10 + t->depth)
+    return fail(SPP_ERR_BAD_INPUT, "the circuit takes %u inputs, a withdraw row over a depth-%u tree has %u", c->circ.n_inputs(), t->depth,
+                10 + t->depth);
+  return SPP_OK;
+}
+extern "C" int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* t, size_t count, const void* d_notes, const void* d_rs,
+                                               void* d_proofs, void* d_pws, void* d_status) {
+  if (!c || !t || !d_notes || !d_rs || !d_proofs || !d_pws || !d_status) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int e = withdraw_notes_args(c, t)) return e;
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 20)) return fail(SPP_ERR_BAD_INPUT, "batch too large");
+  spp_ctx* ctx = c->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  Workspace* wp;
+  if (int e = take_sized_workspace(c, count, c->generic_solver, &wp)) return e;
+  Workspace &w = *wp, &wt = c->ws[c->next_ws];
+  const size_t tail = batch_tail(c, count), body = count - tail;
+  const uint8_t* notes = (const uint8_t*)d_notes;
+  HIP_TRY(hipStreamWaitEvent(ctx->stream, w.ev_in, 0));
+  if (tail) HIP_TRY(hipStreamWaitEvent(ctx->stream, wt.ev_in, 0));
+  launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes, w.d_inputs, (uint32_t)body);
+  if (tail) launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes + body * SPP_NOTE_LEN, wt.d_inputs, (uint32_t)tail);
+  HIP_TRY(hipEventRecord(w.ev_rows, ctx->stream));
+  HIP_TRY(hipStreamWaitEvent(w.st, w.ev_rows, 0));
+  if (tail) HIP_TRY(hipStreamWaitEvent(wt.st, w.ev_rows, 0));
+  const BatchIO io{(const uint8_t*)d_rs, (uint8_t*)d_proofs, (uint8_t*)d_pws, (uint32_t*)d_status};
+  if (int e = prove_on_device(c, w, body, w.d_inputs, io)) return e;
+  if (!tail) return SPP_OK;
+  return prove_on_device(c, wt, tail, wt.d_inputs, io.at(c, body));
+}
+// Host form: all rows are built (one gather, one root) before spp_prove_batch proves them in chunks.
+extern "C" int spp_prove_withdraw_notes(spp_circuit* c, spp_merkle_tree* t, size_t count, const uint8_t* notes, const uint8_t* rs, uint8_t* proofs,
+                                        uint8_t* pws, int32_t* status) {
+  if (!c || !t || !notes || !proofs || !pws) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int e = withdraw_notes_args(c, t)) return e;
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many notes in one call");
+  std::vector<uint8_t> rows(count * c->in_stride);
+  if (int e = spp_withdraw_rows_from_tree(t, count, notes, rows.data())) return e;
+  return spp_prove_batch(c, count, rows.data(), rs, proofs, pws, status);
+}
+extern "C" int spp_commitment_challenge(spp_circuit* c, size_t count, const uint8_t* inputs, uint8_t* challenges) {
+  if (!c || !inputs || !challenges) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count == 0) return SPP_OK;
+  if (count > 4096) return fail(SPP_ERR_BAD_INPUT, "at most 4096 rows per call");
+  if (c->CB.N == 0) return fail(SPP_ERR_BAD_INPUT, "the circuit has no commitment");
+  std::lock_guard<std::mutex> lk(c->ctx->mu);
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  Workspace& w = c->ws[c->next_ws];
+  if (int e = ensure_workspace(c, w, count)) return e;
+  hipStream_t st = w.st;
+  const uint32_t P = (uint32_t)count;
+  HIP_TRY(hipMemcpyAsync(w.d_inputs, inputs, c->in_stride * count, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(w.d_rs, 0, 64 * count, st));
+  launch_load_inputs(st, w.d_inputs, w.d_rs, w.W, c->circ.n_inputs(), c->circ.n_wires, P);
+  // whatever the program computes before the commitment (nothing for an all-inputs system), then commit and hash
+  for (const SolveStep& s : c->schedule) {
+    if (s.kind == SolveStep::COMMIT) break;
+    switch (s.kind) {
+      case SolveStep::SEQ: launch_solve(st, c->dc, w.W, w.scratch, s.a, s.b, P); break;
+      case SolveStep::BATCH_DIV: launch_batch_div(st, c->dc, w.W, w.scratch, s.a, s.b, P); break;
+      case SolveStep::COUNT8: launch_count8(st, c->dc, w.W, w.counters, s.a, s.b, s.c, P); break;
+      default: break;
+    }
+  }
+  run_msm(c, w, c->CB, w.CB, P, false);
+  launch_challenge(st, w.CB.out, w.W, c->circ.challenge_wire, P, w.commit_affine, w.d_status);
+  std::vector<Fr> out(count);
+  HIP_TRY(hipMemcpyAsync(out.data(), w.W + (size_t)c->circ.challenge_wire * P, sizeof(Fr) * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (size_t i = 0; i < count; i++) out[i].to_bytes_be(challenges + 32 * i);
+  return SPP_OK;
+}
+extern "C" int spp_sync(spp_circuit* c) {
+  if (!c) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  for (auto& w : c->ws)
+    if (w.st) HIP_TRY(hipStreamSynchronize(w.st));
+  return SPP_OK;
+}
+extern "C" int spp_last_timings(spp_circuit* c, float ms[9]) { return spp_timings(c, 0, ms); }
+extern "C" int spp_timings(spp_circuit* c, int which, float ms[9]) {
+  if (!c || !ms) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  Workspace& w = c->ws[which ? c->prev_ws : c->last_ws];
+  if (w.cap == 0) return fail(SPP_ERR_BAD_INPUT, "no such batch");
+  HIP_TRY(hipStreamSynchronize(w.st));
+  for (int i = 0; i < 6; i++) {
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, w.ev[i], w.ev[i + 1]));
+    ms[i] = t;
+  }
+  float tot = 0;
+  HIP_TRY(hipEventElapsedTime(&tot, w.ev[0], w.ev[6]));
+  ms[6] = tot;
+  float sum = 0;
+  for (size_t i = 0; i < w.msm_ev_used; i++) {
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, w.msm_ev[i].first, w.msm_ev[i].second));
+    sum += t;
+  }
+  ms[7] = w.msm_ev_used ? sum / (float)w.msm_ev_used : 0.f;
+  ms[8] = (float)w.msm_ev_used;
+  return SPP_OK;
+}
+
+// per-launch durations of the MSM kernels of one batch, in launch order: commitment (CB), A, B1, K, Z, PoK (CS), then the G2 set
+extern "C" int spp_msm_kernel_ms(spp_circuit* c, int which, float ms[7]) {
+  if (!c || !ms) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  Workspace& w = c->ws[which ? c->prev_ws : c->last_ws];
+  if (w.cap == 0) return fail(SPP_ERR_BAD_INPUT, "no such batch");
+  HIP_TRY(hipStreamSynchronize(w.st));
+  HIP_TRY(hipStreamSynchronize(w.st2));
+  if (w.own_st2p) HIP_TRY(hipStreamSynchronize(w.own_st2p));
+  for (int i = 0; i < 7; i++) ms[i] = 0.f;
+  for (size_t i = 0; i < w.msm_ev_used && i < 6; i++) HIP_TRY(hipEventElapsedTime(&ms[i], w.msm_ev[i].first, w.msm_ev[i].second));
+  if (c->B2.N) HIP_TRY(hipEventElapsedTime(&ms[6], w.g2_ev.first, w.g2_ev.second));
+  return SPP_OK;
+}
+// on = 1: both batch workspaces and the G2 MSM run on ONE stream (kernel durations are then not stretched by another stream
+// sharing the chip: what a roofline figure needs); on = 0: the pipelined default.  Drains the device first.
+extern "C" int spp_set_serial(spp_circuit* c, int on) {
+  if (!c) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  std::lock_guard<std::mutex> lk(c->ctx->mu);
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  HIP_TRY(hipDeviceSynchronize());
+  for (int k = 0; k < SPP_NWS; k++) {
+    Workspace& w = c->ws[k];
+    w.st = on ? c->ws[0].own_st : w.own_st;
+    w.st2 = on ? w.st : w.own_st2;
+  }
+  return SPP_OK;
+}
+
+extern "C" int spp_prove_batch(spp_circuit* c, size_t count, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs, uint8_t* pws,
+                               int32_t* status) {
+  if (!c || !inputs || !proofs || !pws) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count == 0) return SPP_OK;
+  std::vector<uint8_t> rnd;
+  if (!rs) {
+    rnd.resize(64 * count);
+    FILE* f = fopen("/dev/urandom", "rb");
+    if (!f || fread(rnd.data(), 1, rnd.size(), f) != rnd.size()) {
+      if (f) fclose(f);
+      return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+    }
+    fclose(f);
+    rs = rnd.data();
+  }
+  std::vector<uint32_t> st(count);
+  {
+    // Large host batches are cut into chunks that alternate between the two workspaces / proving streams, so the
+    // copies and the solver of chunk k+1 overlap the MSMs of chunk k exactly as consecutive spp_prove_batch_device calls
+    // do, and the workspaces never grow beyond one chunk.
+    std::lock_guard<std::mutex> lk(c->ctx->mu);
+    HIP_TRY(hipSetDevice(c->ctx->device));
+    const size_t pref = c->circ.n_wires <= 16384 ? 4096 : 2048;  // batch sizes at which the per-launch overheads are amortised
+    const size_t chunk = count <= pref + pref / 2 ? count : pref;
+    const size_t inl = c->in_stride, pwl = c->pw_stride;
+    // copies back to pageable host memory block the caller until their stream has drained, so the results of chunk k are
+    // fetched only after chunk k+1 has been enqueued on the other stream
+    auto fetch = [&](Workspace& w, size_t off, size_t n) -> int {
+      hipStream_t s = w.st;
+      HIP_TRY(hipMemcpyAsync(proofs + (size_t)SPP_PROOF_LEN * off, w.d_proofs, (size_t)SPP_PROOF_LEN * n, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(pws + pwl * off, w.d_pws, pwl * n, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(st.data() + off, w.d_status, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      return 0;
+    };
+    Workspace* prev_w = nullptr;
+    size_t prev_off = 0, prev_n = 0;
+    // chunk list: a last chunk that is not a multiple of the wave width is cut into a 64-aligned body and a tail (see
+    // batch_tail); the two alternate workspaces like any other pair of chunks
+    std::vector<std::pair<size_t, size_t>> chunks;
+    for (size_t off = 0; off < count; off += chunk) {
+      const size_t n = std::min(chunk, count - off), t = batch_tail(c, n);
+      if (t) {
+        chunks.push_back({off, n - t});
+        chunks.push_back({off + n - t, t});
+      } else chunks.push_back({off, n});
+    }
+    for (const auto& ch : chunks) {
+      const size_t off = ch.first, n = ch.second;
+      Workspace& w = take_workspace(c, 2);
+      if (int e = ensure_workspace(c, w, n)) return e;   // the chunk's own workspace only, sized to the chunk
+      hipStream_t s = w.st;
+      HIP_TRY(hipMemcpyAsync(w.d_inputs, inputs + inl * off, inl * n, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(w.d_rs, rs + 64 * off, 64 * n, hipMemcpyHostToDevice, s));
+      if (int e = prove_on_device(c, w, (uint32_t)n, w.d_inputs, w.d_rs, w.d_proofs, w.d_pws, w.d_status)) return e;
+      if (prev_w)
+        if (int e = fetch(*prev_w, prev_off, prev_n)) return e;
+      prev_w = &w;
+      prev_off = off;
+      prev_n = n;
+    }
+    if (prev_w)
+      if (int e = fetch(*prev_w, prev_off, prev_n)) return e;
+    for (auto& w : c->ws)
+      if (w.st) HIP_TRY(hipStreamSynchronize(w.st));
+  }
+  int rc = SPP_OK;
+  for (size_t i = 0; i < count; i++) {
+    int32_t v = st[i] ? SPP_ERR_UNSAT : SPP_OK;
+    if (status) status[i] = v;
+    if (v && rc == SPP_OK) rc = fail(SPP_ERR_UNSAT, "proof %zu: inputs do not satisfy the circuit", i);
+    if (v) memset(proofs + (size_t)SPP_PROOF_LEN * i, 0, SPP_PROOF_LEN);
+  }
+  return rc;
+}
+
+extern "C" int spp_prove_withdraw(spp_circuit* c, const spp_withdraw_inputs* in, const uint8_t rs_seed[64], uint8_t proof[SPP_PROOF_LEN],
+                                  uint8_t pw[SPP_WITHDRAW_PW_LEN]) {
+  if (!c || !in || !proof || !pw) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (c->circ.id != SPP_CIRCUIT_WITHDRAW) return fail(SPP_ERR_BAD_INPUT, "not a withdraw circuit");
+  if (c->circ.n_inputs() != 10 + SPP_TREE_DEPTH) return fail(SPP_ERR_BAD_INPUT, "this entry point serves the depth-16 circuit; use spp_prove_batch");
+  std::vector<uint8_t> buf(26 * 32, 0);
+  auto put = [&](int i, const uint8_t* v) { memcpy(buf.data() + 32 * i, v, 32); };
+  auto put64 = [&](int i, uint64_t v) { for (int k = 0; k < 8; k++) buf[32 * i + 31 - k] = (uint8_t)(v >> (8 * k)); };
+  put(0, in->root); put(1, in->nullifier); put(2, in->recipient); put64(3, in->amount); put(4, in->wa_commitment);
+  put(5, in->secret_key); put(6, in->owner_x); put(7, in->owner_y); put(8, in->randomness); put64(9, in->index);
+  for (int i = 0; i < SPP_TREE_DEPTH; i++) put(10 + i, in->siblings[i]);
+  int32_t st = 0;
+  return spp_prove_batch(c, 1, buf.data(), rs_seed, proof, pw, &st);
+}
+
+extern "C" int spp_debug_witness(spp_circuit* c, uint8_t* out, size_t n_wires) {
+  if (!c || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  std::lock_guard<std::mutex> lk(c->ctx->mu);
+  Workspace& w = c->ws[c->last_ws];
+  if (w.cap == 0) return fail(SPP_ERR_BAD_INPUT, "no batch has been proved yet");
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  HIP_TRY(hipStreamSynchronize(w.st));
+  size_t P = w.last_P;   // column 0 of W at the stride of the last batch
+  std::vector<Fr> col(std::min<size_t>(n_wires, c->circ.n_wires));
+  for (size_t i = 0; i < col.size(); i++) HIP_TRY(hipMemcpy(&col[i], w.W + i * P, sizeof(Fr), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < col.size(); i++) col[i].to_bytes_be(out + 32 * i);
+  return SPP_OK;
+}

@@ -219,7 +219,7 @@ extern "C" int spp_merkle_build(spp_ctx* ctx, size_t n_leaves, uint32_t depth, c
 // incremental tree: ShieldedPoolMerkleTree (client/merkle.ts:146-222) with the levels kept in HBM.  insert() appends leaves and
 // recomputes only the touched path(s): O(count + depth) hashes instead of the reference's O(2^depth) per getRoot / getProof.
 // -----------------------------------------------------------------------------------------------------
-// struct spp_merkle_tree: spp_internal.hpp (the withdraw-from-notes path of spp_api.cpp reads its descriptor)
+// struct spp_merkle_tree: spp_internal.hpp (the withdraw-from-notes path of spp_prove.cpp reads its descriptor)
 static size_t mt_level_cap(uint64_t cap_leaves, uint32_t l) { return (size_t)(cap_leaves >> l) + 1; }
 static int mt_reserve(spp_merkle_tree* t, uint64_t want_leaves) {
   if (want_leaves <= t->cap_leaves) return 0;

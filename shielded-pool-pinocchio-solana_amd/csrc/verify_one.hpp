@@ -1,6 +1,6 @@
 // One Groth16 (+ BSB22 commitment) verification against a prepared key, host + gfx950: the body of k_verify
 // (kernels_verify.hip, one lane per proof) and of the host check in tests/host/pairing_check.cpp.
-// Same decisions, in the same order, as the host verifier spp_verify (csrc/spp_api.cpp), i.e. `sunspot verify`
+// Same decisions, in the same order, as the host verifier spp_verify (csrc/spp_verify_api.cpp), i.e. `sunspot verify`
 // (noir_circuit/prove_linux.sh:86-87) and the byte layout withdraw.rs:13-16,63-90 fixes:
 //   1. format: commitment count == 1, witness header; every coordinate < q and every public word < r (canonical encodings); G1 points on the curve, Bs on the twist AND in the order-r subgroup;
 //   2. Pedersen proof of knowledge (gnark-crypto pedersen.VerifyingKey.Verify):  e(Cm, GSigmaNeg) * e(PoK, G) == 1;

@@ -6,7 +6,7 @@ gnark's computeH (groth16/bn254/prove.go, the step `sunspot prove` runs at clien
 sum_j h_j Z_j with h = (A*B - C) / (X^n - 1).  libspp computes the same element as
     sum_wire w_wire * X_wire  +  sum_i A(zeta w^i) B(zeta w^i) * W'_i
 with X_wire = sum_i C[i][wire] W_i, W_i = (1/2n) sum_j w^(-ij) Z_j, W'_i = -(1/2n) sum_j zeta^(-j) w^(-ij) Z_j, zeta^2 = w
-(spp_api.cpp load_circuit_impl, h_mode 2).  The GPU tests assert the proof BYTES against the oracle's seven-transform prover;
+(spp_load.cpp load_h_bases, h_mode 2).  The GPU tests assert the proof BYTES against the oracle's seven-transform prover;
 this test pins the identity itself, and what becomes of it when the witness does not satisfy the system."""
 import random
 

@@ -388,7 +388,12 @@ def test_no_return_address_clobber_in_device_code(tmp_path):
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     csrc = os.path.join(ROOT, "shielded-pool-pinocchio-solana_amd", "csrc")
-    units = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, f) for f in ("spp_api.cpp", "circuit.cpp", "circuit_audit.cpp")]
+    # the list follows the build: every .hip file, and every .cpp whose object is in the Makefile's OBJS
+    objs = re.search(r"^OBJS\s*=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
+    cpps = [os.path.join(csrc, os.path.basename(o)[:-2] + ".cpp") for o in objs]
+    cpps = sorted(p for p in cpps if os.path.exists(p))
+    assert {"spp_api.cpp", "circuit.cpp", "circuit_audit.cpp"} <= {os.path.basename(p) for p in cpps}
+    units = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + cpps
     assert len(units) >= 10
 
     def scan(src):
