@@ -1,4 +1,5 @@
-// Launch wrappers of the HIP kernels (one .hip file per kernel family), shared by the spp_*.cpp units.
+// Launch wrappers of the HIP kernels (one .hip file per kernel family; the table-walk MSM is msm_table.hpp, instantiated by
+// kernels_msm.hip and kernels_msm_g2.hip, with its host-side planning in msm_plan.hpp), shared by the spp_*.cpp units.
 // Data layout in HBM, used by every kernel of the proving path ("batch-minor"):
 //   witness   W   [rows][P]      Fr Montgomery, 32 B; row = wire (plus 3 blinding rows r, s, rs)
 //   abc           [3][n][P]      constraint evaluations <A_k,w>, <B_k,w>, <C_k,w>, zero padded to n
@@ -10,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bn254.hpp"
+#include "msm_plan.hpp"
 #include "rlwe_ntt.hpp"
 
 namespace spp {
@@ -175,28 +177,31 @@ void launch_scale_rows(hipStream_t st, Fr* data, const Fr* table, uint32_t n, ui
 void launch_qap_pointwise(hipStream_t st, Fr* abc, uint32_t n, uint32_t P, Fr zinv);
 void launch_qap_product(hipStream_t st, Fr* abc, uint32_t n, uint32_t P);   // a <- a * b
 
-// ---- MSM with precomputed window tables (kernels_msm.hip) ----
+// ---- MSM with precomputed window tables (msm_table.hpp: the kernels, templates over the coordinate field, instantiated by
+// kernels_msm.hip for G1 and kernels_msm_g2.hip for G2; msm_plan.hpp: windows, padding, buffer sizes, the lane layout MsmPlan) ----
 // A base carries Wt table rows of 2^(c-1) affine multiples; row m = multiples of 2^(c*R*m) * Base, R = ceil(W / Wt) window passes
 // (W = ceil(254 / c) windows per scalar).  Wt = W: one row per window, no passes (the small-table latency layout).  Wt = 1: one row
 // per base and W passes whose sums are combined by Horner (the throughput layout: widest window for the bytes).
-uint32_t msm_windows(uint32_t c);
-struct MsmPlan {
-  uint32_t W;        // windows per scalar
-  uint32_t Wt, R;    // table rows per base, passes
-  uint32_t Q, Wq;    // small batches: Q lanes share the rows of a base, Wq rows each
-  uint32_t Sg;       // slices of the item range per pass
-  uint32_t Pp;       // proofs per slice row: P rounded up to a wave (P >= 64), else P
-  size_t partial_elems(uint32_t P) const { return (size_t)R * Sg * P; }
+// What tells the G1 walk from the G2 walk, in one place: k_msm_flat takes its launch bound and its loop form from here, and the
+// host passes waves_per_simd to msm_plan / msm_partial_cap as `occ`, so the planner counts the waves the launch bound allows.
+template <class F>
+struct MsmWalk;
+template <>
+struct MsmWalk<Fq> {
+  static constexpr uint32_t waves_per_simd = 2;    // at most 256 VGPRs
+  static constexpr bool gather_ahead = false;      // the other resident wave hides a gather
 };
-MsmPlan msm_plan(uint32_t N, uint32_t P, uint32_t c, uint32_t Wt, uint32_t occ = 2);   // occ: resident waves per SIMD of the kernel (G1 2, G2 1)
+template <>
+struct MsmWalk<Fq2> {
+  static constexpr uint32_t waves_per_simd = 1;    // up to 512 VGPRs
+  static constexpr bool gather_ahead = true;       // one-deep software pipeline of the table gathers (k_msm_flat)
+};
 // builds rows [row0, row0 + nrows) (row = base * Wt + m; row0 a multiple of 64) of the table of N bases;
-// tmp / tmp_pre: nrows * 2^(c-1) elements each.  Layout: see kernels_msm.hip.
+// tmp / tmp_pre: nrows * 2^(c-1) elements each.  Layout: see msm_table.hpp.
 template <class F>
 void launch_build_table(hipStream_t st, const Affine<F>* bases, uint32_t N, uint32_t c, uint32_t Wt, uint32_t row0, uint32_t nrows,
                         Affine<F>* table, XYZZ<F>* tmp, F* tmp_pre);
-size_t msm_table_elems(uint32_t N, uint32_t c, uint32_t Wt);
-// signed c-bit digits of scalars[rows[i]][p] as int16 planes dig[j][i][p] (Pp per row); msm_digit_elems = W * N * Pp
-size_t msm_digit_elems(uint32_t N, uint32_t P, uint32_t c);
+// signed c-bit digits of scalars[rows[i]][p] as int16 planes dig[j][i][p] (Pp = msm_padded_batch(P) per row; msm_digit_elems)
 void launch_msm_digits(hipStream_t st, const uint32_t* rows, const Fr* scalars, int16_t* dig, uint32_t N, uint32_t P, uint32_t c);
 // lane g -> (pass, slice, proof); partial[R * Sg][P]
 template <class F>
@@ -257,7 +262,6 @@ void launch_scale_witness(hipStream_t st, const Fr* W, Fr* Ws, Fr* Wr, uint32_t 
 // ---- setup helpers ----
 // out[i] = scalars[i] * G for a generator table built with launch_build_table (N=1)
 template <class F>
-void launch_fixed_base_mul(hipStream_t st, const Affine<F>* gen_table, uint32_t c, const Fr* scalars, uint32_t n, Affine<F>* out,
-                           XYZZ<F>* tmp);
+void launch_fixed_base_mul(hipStream_t st, const Affine<F>* gen_table, uint32_t c, const Fr* scalars, uint32_t n, Affine<F>* out);
 
 }  // namespace spp

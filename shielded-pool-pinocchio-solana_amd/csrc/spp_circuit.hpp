@@ -39,7 +39,7 @@ struct Workspace {
   MsmBuf<Fq> sA, rB;                  // small batches: s*Ar and r*Bs1 as table sums over the scaled witness (Ws, Wr)
   Fr *Ws = nullptr, *Wr = nullptr;
   MsmBuf<Fq2> B2;
-  // signed-digit planes of the scalars of one MSM (kernels_msm.hip): dig1 is shared by the G1 sets, which run one after the
+  // signed-digit planes of the scalars of one MSM (k_msm_digits): dig1 is shared by the G1 sets, which run one after the
   // other on `st`; the G2 set runs beside them on the side stream and has its own
   int16_t *dig1 = nullptr, *dig2 = nullptr;
   size_t dig1_cap = 0, dig2_cap = 0;
@@ -85,6 +85,7 @@ struct Switches {
   bool no_side = false;           // SPP_NO_SIDE=1 (experiment): the G2 sum of a small batch on the batch's own stream
   int forced_depth = 0;           // SPP_DEPTH (experiment): batches in flight, 1 .. SPP_NWS; 0: by batch size (ws_depth)
   bool no_split = false;          // SPP_NO_SPLIT=1 (experiment): no cut of a batch into a 64-aligned body and a tail
+  MsmTuning msm;                  // SPP_MSM_WAVES, SPP_MSM_WAVES_SMALL (experiment): rounds of resident waves per table walk (msm_plan.hpp)
 };
 // Up to a batch size that depends on the circuit s*Ar and r*Bs1 are two more fixed-base sums (sets A and B1 over the witness scaled by s and r) instead of
 // 254 doublings on one lane each: 3 ms of a single proof's 9.  The sums cost a third of a proof's table additions, so a batch

@@ -2,7 +2,8 @@
 //   spp_api.cpp          error channel, contexts, the stream-concurrency probe
 //   spp_circuit.hpp      (private, on top of this header) struct spp_circuit, its workspaces and what the four units below share
 //   spp_plan.cpp         load-time planners: cooperative-solver items, small and long rows of the matrix evaluation
-//   spp_load.cpp         proving-key container, window plan and tables, circuit loading and queries, fixed-base MSM unit calls
+//   spp_load.cpp         proving-key container, window plan and tables, circuit loading and queries, fixed-base MSM unit calls,
+//                        the experiment switches of the proving path from the environment (read_switches)
 //   spp_prove.cpp        workspaces, the proving pipeline and its batch entry points, timing queries
 //   spp_setup.cpp        circuit construction (host only) and the trusted setup on the GPU
 //   spp_witness_api.cpp  witness-input kernels, Merkle trees, auditor side
@@ -179,6 +180,22 @@ struct DevBuf {
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
   template <class T> T* as() { return (T*)p; }
 };
+// the window table of the single generator g for c-bit windows, one row per window (what launch_fixed_base_mul reads), into
+// `table`; waits for the stream before the temporaries of the construction are released
+template <class F>
+int build_generator_table(hipStream_t st, const Affine<F>& g, uint32_t c, DevBuf& table) {
+  const uint32_t Wn = msm_windows(c);
+  const size_t rows = msm_table_rows(1, Wn), E = (size_t)1 << (c - 1);
+  DevBuf d_g, tmp, pre;
+  HIP_TRY(d_g.alloc(sizeof g));
+  HIP_TRY(hipMemcpy(d_g.p, &g, sizeof g, hipMemcpyHostToDevice));
+  HIP_TRY(table.alloc(sizeof(Affine<F>) * msm_table_elems(1, c, Wn)));
+  HIP_TRY(tmp.alloc(sizeof(XYZZ<F>) * rows * E));
+  HIP_TRY(pre.alloc(sizeof(F) * rows * E));
+  launch_build_table<F>(st, d_g.as<Affine<F>>(), 1, c, Wn, 0, (uint32_t)rows, table.as<Affine<F>>(), tmp.as<XYZZ<F>>(), pre.as<F>());
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
 }  // namespace
 #define UP(buf, src, bytes)                                                              \
   do {                                                                                    \

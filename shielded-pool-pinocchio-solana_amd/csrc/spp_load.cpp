@@ -60,7 +60,7 @@ static int build_table(spp_circuit* c, const std::vector<Affine<F>>& pts, uint32
   const uint32_t Wn = Wt, E = 1u << (cbits - 1);
   const size_t N = pts.size();
   if (N == 0) return 0;
-  const size_t rows_total = ((N * Wn + 63) / 64) * 64;
+  const size_t rows_total = msm_table_rows(N, Wn);
   const size_t per_row = (size_t)E * (sizeof(XYZZ<F>) + sizeof(F));
   size_t chunk = std::max<size_t>(64, ((temp_budget / per_row) / 64) * 64);
   chunk = std::min(chunk, (size_t)65536);   // larger launches only add TLB misses (the d-stride is chunk * 128 B)
@@ -262,6 +262,7 @@ static Switches read_switches() {
   const int depth = de ? atoi(de) : 0;
   sw.forced_depth = depth >= 1 && depth <= SPP_NWS ? depth : 0;
   sw.no_split = getenv("SPP_NO_SPLIT") != nullptr;
+  sw.msm = msm_tuning_from_env(getenv("SPP_MSM_WAVES"), getenv("SPP_MSM_WAVES_SMALL"));
   return sw;
 }
 
@@ -269,7 +270,7 @@ static Switches read_switches() {
 //  * window_bits given: every set gets one table row per window (msm_windows(c) rows of 2^(c-1) multiples per base) -- small
 //    tables, a single pass, no Horner step: the layout of the one-proof latency path (the drop-in helpers load 8 bits).
 //  * window_bits = 0 (throughput): the five big sets keep ONE row per base and walk it once per window ("flat", see
-//    kernels_msm.hip); the window of every set is a greedy split of the HBM budget (env SPP_TABLE_BUDGET_GB, default 240 of the
+//    msm_table.hpp); the window of every set is a greedy split of the HBM budget (env SPP_TABLE_BUDGET_GB, default 240 of the
 //    288 GB, capped at 85 % of the free HBM): repeatedly widen the set whose next window bit removes the most mixed-addition
 //    work per extra byte (a G2 addition is weighted 3 G1 additions, as measured).  A flat G1 row at 16 bits is 2 MB per base
 //    and costs 16 additions per full-size scalar; the row-per-window layout of rounds 1-2 afforded 11-12 bits (22-24
@@ -866,8 +867,7 @@ static int msm_fixed_unit(spp_ctx* ctx, const uint8_t* bases, const uint8_t* sca
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const uint32_t cb = (uint32_t)window_bits, Wn = msm_windows(cb), E = 1u << (cb - 1);
-  (void)E;
+  const uint32_t cb = (uint32_t)window_bits, Wn = msm_windows(cb);
   if ((uint64_t)msm_table_elems((uint32_t)n, cb, Wn) * PT_BYTES > ((uint64_t)64 << 30)) return fail(SPP_ERR_BAD_INPUT, "table would exceed 64 GiB; use a smaller window");
   std::vector<Affine<F>> pts(n);
   std::vector<Fr> sc(n);
@@ -886,7 +886,7 @@ static int msm_fixed_unit(spp_ctx* ctx, const uint8_t* bases, const uint8_t* sca
   uint32_t* d_rows = nullptr;
   XYZZ<F> *partial = nullptr, *d_out = nullptr;
   DevBuf dig;
-  const MsmPlan pl = msm_plan((uint32_t)n, 1, cb, Wn);
+  const MsmPlan pl = msm_plan((uint32_t)n, 1, cb, Wn, MsmWalk<F>::waves_per_simd, read_switches().msm);
   if (!e) e = own_upload(&tmpc, &d_sc, sc);
   if (!e) e = own_upload(&tmpc, &d_rows, rows);
   if (!e && hipMalloc((void**)&partial, sizeof(XYZZ<F>) * std::max<size_t>(pl.partial_elems(1), 1)) != hipSuccess) e = fail(SPP_ERR_HIP, "hipMalloc");

@@ -150,21 +150,16 @@ extern "C" int spp_msm_g1_pippenger_bench_shard(spp_ctx* ctx, size_t n_total, si
     if (small) s = Fr::from_u64(w[0] & 0xffu);
     sc[i] = scale_be ? s * scale : s;   // both are fixed representations of the same field element family
   }
-  DevBuf dk, ds, dp, dw, dt, dg, dtmp, dpre;
+  DevBuf dk, ds, dp, dw, dt;
   UP(dk, ks.data(), n * sizeof(Fr));
   UP(ds, sc.data(), n * sizeof(Fr));
   HIP_TRY(dp.alloc(n * sizeof(G1Affine)));
   HIP_TRY(dw.alloc(pippenger_workspace_bytes((uint32_t)n)));
   // bases = k_i * G through the generator's window table
-  const uint32_t cb = 8, Wn = msm_windows(cb), E = 1u << (cb - 1);
-  G1Affine g1{Fq::from_u64(1), Fq::from_u64(2)};
-  UP(dg, &g1, sizeof g1);
-  const size_t gr = ((size_t)Wn + 63) / 64 * 64;
-  HIP_TRY(dt.alloc(sizeof(G1Affine) * msm_table_elems(1, cb, Wn)));
-  HIP_TRY(dtmp.alloc(sizeof(G1XYZZ) * gr * E));
-  HIP_TRY(dpre.alloc(sizeof(Fq) * gr * E));
-  launch_build_table<Fq>(st, dg.as<G1Affine>(), 1, cb, Wn, 0, (uint32_t)gr, dt.as<G1Affine>(), dtmp.as<G1XYZZ>(), dpre.as<Fq>());
-  launch_fixed_base_mul<Fq>(st, dt.as<G1Affine>(), cb, dk.as<Fr>(), (uint32_t)n, dp.as<G1Affine>(), nullptr);
+  const uint32_t cb = 8;
+  const G1Affine g1{Fq::from_u64(1), Fq::from_u64(2)};
+  if (int e = build_generator_table<Fq>(st, g1, cb, dt)) return e;
+  launch_fixed_base_mul<Fq>(st, dt.as<G1Affine>(), cb, dk.as<Fr>(), (uint32_t)n, dp.as<G1Affine>());
   HIP_TRY(hipStreamSynchronize(st));
   hipEvent_t e0, e1, k0, k1;
   HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1));

@@ -10,13 +10,8 @@ static int ws_alloc(Workspace& w, T** p, size_t count) {
   return 0;
 }
 template <class F>
-static int ws_set(Workspace& w, const MsmSet<F>* s, MsmBuf<F>* b, size_t P) {
-  // R * Sg(P') * P' <= lane target + R * P' for every P' <= P (msm_plan); small batches: up to 64K (item, pass) lanes
-  const uint32_t occ = sizeof(F) > sizeof(Fq) ? 1 : 2;
-  const uint32_t R = msm_plan(s->N, (uint32_t)P, s->c, s->Wt, occ).R;
-  b->partial_cap = (size_t)256 * 4 * 8 * 64 + 65536 + (size_t)(R + 1) * (P + 64);
-  for (size_t q = P; q >= 1; q /= 2)   // and the exact need at the sizes most likely to be used
-    b->partial_cap = std::max(b->partial_cap, msm_plan(s->N, (uint32_t)q, s->c, s->Wt, occ).partial_elems((uint32_t)q));
+static int ws_set(const spp_circuit* c, Workspace& w, const MsmSet<F>* s, MsmBuf<F>* b, size_t P) {
+  b->partial_cap = msm_partial_cap(s->N, P, s->c, s->Wt, MsmWalk<F>::waves_per_simd, c->sw.msm);
   int e;
   if ((e = ws_alloc(w, &b->partial, b->partial_cap))) return e;
   return ws_alloc(w, &b->out, P);
@@ -32,13 +27,13 @@ static int ensure_workspace(spp_circuit* c, Workspace& w, size_t P) {
       (e = ws_alloc(w, &w.d_proofs, (size_t)SPP_PROOF_LEN * P)) || (e = ws_alloc(w, &w.d_pws, c->pw_stride * P)) ||
       (e = ws_alloc(w, &w.d_status, P)) || (e = ws_alloc(w, &w.counters, 256 * P)))
     return e;
-  if ((e = ws_set(w, &c->A, &w.A, P)) || (e = ws_set(w, &c->B1, &w.B1, P)) || (e = ws_set(w, &c->B2, &w.B2, P)) ||
-      (e = ws_set(w, &c->K, &w.K, P)) || (e = ws_set(w, &c->Z, &w.Z, P)) || (e = ws_set(w, &c->CB, &w.CB, P)) ||
-      (e = ws_set(w, &c->CS, &w.CS, P)))
+  if ((e = ws_set(c, w, &c->A, &w.A, P)) || (e = ws_set(c, w, &c->B1, &w.B1, P)) || (e = ws_set(c, w, &c->B2, &w.B2, P)) ||
+      (e = ws_set(c, w, &c->K, &w.K, P)) || (e = ws_set(c, w, &c->Z, &w.Z, P)) || (e = ws_set(c, w, &c->CB, &w.CB, P)) ||
+      (e = ws_set(c, w, &c->CS, &w.CS, P)))
     return e;
   {
     const size_t Ps = std::min<size_t>(P, scaled_blind_max_batch(c->A.N, c->B1.N));
-    if ((e = ws_set(w, &c->A, &w.sA, Ps)) || (e = ws_set(w, &c->B1, &w.rB, Ps)) || (e = ws_alloc(w, &w.Ws, (size_t)c->n_rows * Ps)) ||
+    if ((e = ws_set(c, w, &c->A, &w.sA, Ps)) || (e = ws_set(c, w, &c->B1, &w.rB, Ps)) || (e = ws_alloc(w, &w.Ws, (size_t)c->n_rows * Ps)) ||
         (e = ws_alloc(w, &w.Wr, (size_t)c->n_rows * Ps)))
       return e;
   }
@@ -63,8 +58,8 @@ static void run_msm(spp_circuit* c, Workspace& w, const MsmSet<F>& s, MsmBuf<F>&
                     std::pair<hipEvent_t, hipEvent_t>* ev_override = nullptr, bool fold = true, const Fr* scal_override = nullptr) {
   hipStream_t st = st_override ? st_override : w.st;
   const Fr* scal = scal_override ? scal_override : s.from_h ? w.abc : w.W;
-  MsmPlan pl = msm_plan(s.N, P, s.c, s.Wt, sizeof(F) > sizeof(Fq) ? 1 : 2);
-  while (pl.Sg > 1 && pl.partial_elems(P) > b.partial_cap) pl.Sg--;  // never exceed the allocated partial buffer
+  MsmPlan pl = msm_plan(s.N, P, s.c, s.Wt, MsmWalk<F>::waves_per_simd, c->sw.msm);
+  pl.fit(P, b.partial_cap);   // never exceed the allocated partial buffer
   b.plan = pl;
   std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
   if (timed && w.msm_ev_used < w.msm_ev.size()) ev = &w.msm_ev[w.msm_ev_used++];

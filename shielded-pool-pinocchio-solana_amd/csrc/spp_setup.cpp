@@ -135,7 +135,7 @@ extern "C" int spp_setup(spp_ctx* ctx, const char* circuit_path, const uint8_t s
   s2.push_back(beta); s2.push_back(gamma); s2.push_back(delta); s2.push_back(rho); s2.push_back((rho * sigma).neg());
 
   // generator tables (c = 8) and the batched fixed-base multiplications on the GPU
-  const uint32_t cb = 8, Wn = msm_windows(cb), E = 1u << (cb - 1);
+  const uint32_t cb = 8;
   G1Affine g1{Fq::from_u64(1), Fq::from_u64(2)};
   auto fq_dec = [](const char* dec) {
     Fq acc = Fq::zero(), ten = Fq::from_u64(10);
@@ -147,21 +147,15 @@ extern "C" int spp_setup(spp_ctx* ctx, const char* circuit_path, const uint8_t s
   g2.x.c1 = fq_dec("11559732032986387107991004021392285783925812861821192530917403151452391805634");
   g2.y.c0 = fq_dec("8495653923123431417604973247489272438418190587263600148770280649306958101930");
   g2.y.c1 = fq_dec("4082367875863433681332203403145435568316851327593401208105741076214120093531");
-  DevBuf d_g1, d_g2, t1, t2, tmp1, tmp2, pre1, pre2, d_s1, d_s2, o1, o2;   // released on every return path
-  HIP_TRY(d_g1.alloc(sizeof g1)); HIP_TRY(hipMemcpy(d_g1.p, &g1, sizeof g1, hipMemcpyHostToDevice));
-  HIP_TRY(d_g2.alloc(sizeof g2)); HIP_TRY(hipMemcpy(d_g2.p, &g2, sizeof g2, hipMemcpyHostToDevice));
-  const size_t ge = msm_table_elems(1, cb, Wn), gr = ((size_t)Wn + 63) / 64 * 64;
-  HIP_TRY(t1.alloc(sizeof(G1Affine) * ge)); HIP_TRY(t2.alloc(sizeof(G2Affine) * ge));
-  HIP_TRY(tmp1.alloc(sizeof(G1XYZZ) * gr * E)); HIP_TRY(tmp2.alloc(sizeof(G2XYZZ) * gr * E));
-  HIP_TRY(pre1.alloc(sizeof(Fq) * gr * E)); HIP_TRY(pre2.alloc(sizeof(Fq2) * gr * E));
+  DevBuf t1, t2, d_s1, d_s2, o1, o2;   // released on every return path
+  if (int e = build_generator_table<Fq>(st, g1, cb, t1)) return e;
+  if (int e = build_generator_table<Fq2>(st, g2, cb, t2)) return e;
   HIP_TRY(d_s1.alloc(sizeof(Fr) * s1.size())); HIP_TRY(d_s2.alloc(sizeof(Fr) * s2.size()));
   HIP_TRY(o1.alloc(sizeof(G1Affine) * s1.size())); HIP_TRY(o2.alloc(sizeof(G2Affine) * s2.size()));
   HIP_TRY(hipMemcpyAsync(d_s1.p, s1.data(), sizeof(Fr) * s1.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(d_s2.p, s2.data(), sizeof(Fr) * s2.size(), hipMemcpyHostToDevice, st));
-  launch_build_table<Fq>(st, d_g1.as<G1Affine>(), 1, cb, Wn, 0, (uint32_t)gr, t1.as<G1Affine>(), tmp1.as<G1XYZZ>(), pre1.as<Fq>());
-  launch_build_table<Fq2>(st, d_g2.as<G2Affine>(), 1, cb, Wn, 0, (uint32_t)gr, t2.as<G2Affine>(), tmp2.as<G2XYZZ>(), pre2.as<Fq2>());
-  launch_fixed_base_mul<Fq>(st, t1.as<G1Affine>(), cb, d_s1.as<Fr>(), (uint32_t)s1.size(), o1.as<G1Affine>(), nullptr);
-  launch_fixed_base_mul<Fq2>(st, t2.as<G2Affine>(), cb, d_s2.as<Fr>(), (uint32_t)s2.size(), o2.as<G2Affine>(), nullptr);
+  launch_fixed_base_mul<Fq>(st, t1.as<G1Affine>(), cb, d_s1.as<Fr>(), (uint32_t)s1.size(), o1.as<G1Affine>());
+  launch_fixed_base_mul<Fq2>(st, t2.as<G2Affine>(), cb, d_s2.as<Fr>(), (uint32_t)s2.size(), o2.as<G2Affine>());
   std::vector<G1Affine> p1(s1.size());
   std::vector<G2Affine> p2(s2.size());
   HIP_TRY(hipMemcpyAsync(p1.data(), o1.p, sizeof(G1Affine) * p1.size(), hipMemcpyDeviceToHost, st));

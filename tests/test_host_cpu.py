@@ -294,6 +294,22 @@ def test_rlwe_lds_ntt_phases_host_check(tmp_path):
     assert out.strip().splitlines()[-1].startswith("OK rlwe_ntt"), out
 
 
+def test_msm_planner_matches_recorded_plans(tmp_path):
+    """csrc/msm_plan.hpp (host only: windows, the two padding rules, the lane layout of a table walk, the capacity of the
+    partial-sum buffer and the trim to it) against tests/golden/msm_plan.json -- the answers of the planner before it became a
+    header, on the set sizes of the audit and withdraw circuits, the edge sizes and three tunings -- and the clamps of
+    SPP_MSM_WAVES / SPP_MSM_WAVES_SMALL."""
+    import json
+    fixture = os.path.join(ROOT, "tests", "golden", "msm_plan.json")
+    doc = json.load(open(fixture))
+    assert len(doc["rows"]) >= 900 and all(len(r) == len(doc["columns"]) == 17 for r in doc["rows"]) and os.path.getsize(fixture) < 64 * 1024
+    exe = str(tmp_path / "msm_plan_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "shielded-pool-pinocchio-solana_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "host", "msm_plan_check.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe, fixture], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip().splitlines()[-1] == "OK msm_plan %d rows" % len(doc["rows"]), out.stdout
+
+
 def test_f29_limb_bounds_certificate():
     """Interval arithmetic over the generated constants: no 64-bit column can overflow, every lifted subtraction
     constant dominates its subtrahend, and the accumulator's value bounds are inductive."""
