@@ -103,13 +103,15 @@ void spp_free_ctx(spp_ctx* ctx);
 int spp_setup(spp_ctx* ctx, const char* circuit_path, const uint8_t seed[32], const char* pk_path, const char* vk_path);
 
 /* Loads R1CS + proving key, builds the window tables in HBM. window_bits in [4,16] = the same window for every MSM set;
- * 0 = per-set windows chosen greedily within env SPP_TABLE_BUDGET_GB (default 240) and 85 % of the free HBM, single-row tables walked once per window (16 bits = 16 additions per scalar); env SPP_SERIAL=1 (profiling aid) puts both batch workspaces and the G2 MSM on one stream. */
+ * 0 = per-set windows chosen greedily within env SPP_TABLE_BUDGET_GB (default 240) and 85 % of the free HBM, single-row tables walked once per window (16 bits = 16 additions per scalar), the row of a base whose wire the circuit bounds to a bit or a byte (solver decompositions, looked-up inputs) only as long as that range (env SPP_RAGGED=0: full rows for every base, for comparison); env SPP_SERIAL=1 (profiling aid) puts both batch workspaces and the G2 MSM on one stream. */
 int spp_load_circuit(spp_ctx* ctx, const char* circuit_path, const char* pk_path, int window_bits, spp_circuit** out);
 /* Several circuits on ONE GPU at the same time (the reference's relayer submits an audit proof AND a withdraw proof per withdrawal,
  * demo-frontend/app/api/relay/withdraw/route.ts:238-276): plan the windows of all their MSM sets under one HBM budget, then load
  * each circuit with its share.  sizes / bits: n_circuits x 7 in the order of spp_circuit_msm_sizes; spp_pk_msm_sizes reads the
  * sizes from a proving-key file; both are host-only.  spp_load_circuit_with_windows = spp_load_circuit(window_bits = 0) with
- * the planned bits instead of a budget of its own (single-row tables; the two commitment sets keep one row per window). */
+ * the planned bits instead of a budget of its own (single-row tables; the two commitment sets keep one row per window).
+ * spp_plan_windows has no circuit to read ranges from: it prices every base at a full row, so the loaded tables take at most the
+ * planned bytes (spp_circuit_table_bytes tells what they took). */
 int spp_pk_msm_sizes(const char* pk_path, uint32_t sizes[7]);
 int spp_plan_windows(uint32_t n_circuits, const uint32_t* sizes, double budget_bytes, uint32_t* bits);
 int spp_load_circuit_with_windows(spp_ctx* ctx, const char* circuit_path, const char* pk_path, const uint32_t bits[7], spp_circuit** out);
@@ -120,13 +122,13 @@ int spp_circuit_info(const spp_circuit* c, uint32_t info[8]);
 int spp_circuit_msm_sizes(const spp_circuit* c, uint32_t sizes[7]);
 /* window bits of the table of each of those sets (same order) */
 int spp_circuit_msm_windows(const spp_circuit* c, uint32_t bits[7]);
-/* table rows per base of each of those sets (same order): 1 = one row of 2^(bits-1) multiples, walked once per window
+/* table rows per base of each of those sets (same order): 1 = one row of up to 2^(bits-1) multiples, walked once per window
  * (the throughput layout chosen with window_bits = 0); ceil(254 / bits) = one row per window (explicit window_bits) */
 int spp_circuit_msm_table_rows(const spp_circuit* c, uint32_t rows[7]);
 /* out[0] = rows of A / B / C that the matrix evaluation sums in integer arithmetic (every term a small coefficient times a wire the
  * lookup argument bounds to a byte range: the audit circuit's 1 088 quotient equations), out[1] = such wires (+1: the constant) */
 int spp_circuit_small_rows(const spp_circuit* c, uint32_t out[2]);
-/* exact bytes of HBM held by the window tables */
+/* exact bytes of HBM held by the window tables, as allocated (rows sized by range included) */
 uint64_t spp_circuit_table_bytes(const spp_circuit* c);
 
 /* ---- proving ---- */

@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "bn254.hpp"
 #include "msm_plan.hpp"
+#include "msm_ragged.hpp"
 #include "rlwe_ntt.hpp"
 
 namespace spp {
@@ -196,17 +197,18 @@ struct MsmWalk<Fq2> {
   static constexpr uint32_t waves_per_simd = 1;    // up to 512 VGPRs
   static constexpr bool gather_ahead = true;       // one-deep software pipeline of the table gathers (k_msm_flat)
 };
-// builds rows [row0, row0 + nrows) (row = base * Wt + m; row0 a multiple of 64) of the table of N bases;
-// tmp / tmp_pre: nrows * 2^(c-1) elements each.  Layout: see msm_table.hpp.
+// builds rows [row0, row0 + nrows) (row = base * Wt + m; row0 a multiple of 64) of the table of N bases, E entries each;
+// tmp / tmp_pre: nrows * E elements each.  blocks = nullptr: the uniform layout, E = 2^(c-1) for every row; else the ragged layout
+// of a flat set (msm_ragged.hpp), the launch covering blocks of E entries.  Layout: see msm_table.hpp.
 template <class F>
 void launch_build_table(hipStream_t st, const Affine<F>* bases, uint32_t N, uint32_t c, uint32_t Wt, uint32_t row0, uint32_t nrows,
-                        Affine<F>* table, XYZZ<F>* tmp, F* tmp_pre);
+                        Affine<F>* table, XYZZ<F>* tmp, F* tmp_pre, const MsmBlock* blocks = nullptr, uint32_t E = 0);
 // signed c-bit digits of scalars[rows[i]][p] as int16 planes dig[j][i][p] (Pp = msm_padded_batch(P) per row; msm_digit_elems)
 void launch_msm_digits(hipStream_t st, const uint32_t* rows, const Fr* scalars, int16_t* dig, uint32_t N, uint32_t P, uint32_t c);
-// lane g -> (pass, slice, proof); partial[R * Sg][P]
+// lane g -> (pass, slice, proof); partial[R * Sg][P].  blocks: the block table of a flat set (pl.Wt == 1), required there
 template <class F>
-void launch_msm_accumulate(hipStream_t st, const Affine<F>* table, const int16_t* dig, XYZZ<F>* partial, uint32_t N, uint32_t P, uint32_t c,
-                           const MsmPlan& pl, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_msm_accumulate(hipStream_t st, const Affine<F>* table, const MsmBlock* blocks, const int16_t* dig, XYZZ<F>* partial, uint32_t N, uint32_t P,
+                           uint32_t c, const MsmPlan& pl, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // out[p] = sum over slices and passes (empty: out[p] = infinity); folds in place: `partial` is scratch afterwards
 template <class F>
 void launch_msm_reduce(hipStream_t st, XYZZ<F>* partial, XYZZ<F>* out, uint32_t P, const MsmPlan& pl, uint32_t c, bool empty);

@@ -5,7 +5,8 @@
 // inside `sunspot prove` (client/proof.helper.ts:64) on CPU threads, one proof at a time.
 //
 // MI355X design: the proving key is constant across a batch and there are 288 GB of HBM, so every base
-// carries a precomputed table of its multiples (affine, signed c-bit digits: 2^(c-1) entries per row).  An MSM
+// carries a precomputed table of its multiples (affine, signed c-bit digits: 2^(c-1) entries per row; fewer for a base of the
+// throughput layout whose scalar the circuit bounds to a bit or a byte, msm_ragged.hpp).  An MSM
 // then needs no buckets, no sorting and no bucket reduction: each lane owns one proof of the batch and folds
 // +-T[base][|digit|] into a private XYZZ accumulator with mixed additions (8M+2S).  The scalars are recoded once
 // into int16 digit planes (k_msm_digits); all 64 lanes of a wave walk the SAME (base, window) sequence, so digit
@@ -18,7 +19,7 @@
 //
 // This header holds every kernel of the walk that is a template over the coordinate field F, with its launcher.  Two translation
 // units instantiate it: kernels_msm.hip for Fq (G1), built with the scheduler strategy max-ilp -- the G1 walk is 2 % faster for
-// it, 247 registers, still two waves per SIMD -- and kernels_msm_g2.hip for Fq2 (G2) with the default scheduler: max-ilp makes
+// it, 203 registers, two waves per SIMD -- and kernels_msm_g2.hip for Fq2 (G2) with the default scheduler: max-ilp makes
 // the 512-register G2 walk spill and 4 % slower.  What differs between the two walks is MsmWalk<F> (kernels.hpp); the host-side
 // planning is msm_plan.hpp.
 #pragma once
@@ -34,19 +35,23 @@ static constexpr unsigned MSM_WALK_BLOCK = 64;           // lanes per workgroup 
 
 // ----------------------------------------------------------------------------------------------------
 // table construction: one lane per (base, window) row.
-// Table layout: rows are grouped in blocks of 64; entry d of row `row` lives at ((row/64)*E + d)*64 + row%64, so the
+// Table layout: rows are grouped in blocks of 64; entry d of row `row` lives at (off_{row/64} + d)*64 + row%64, so the
 // 64 lanes of a wave that build 64 consecutive rows write 64 consecutive points (coalesced 4 KiB per step), and so do
 // the XYZZ temporaries.  The MSM kernels gather single entries at random d anyway, so they lose nothing.
+// Uniform layout (row-per-window tables, single-base tables; blocks = nullptr): every block holds E = 2^(c-1) entries per row,
+// off_b = b*E.  Ragged layout (the flat sets, msm_ragged.hpp): block b holds E_b entries per row -- 2^(c-1) if one of its bases
+// has a full-range scalar, else what the range class of its bases needs (1 for bits, 256 for bytes) -- and starts at blocks[b].off.
+// A launch builds blocks of ONE length E.
 // ----------------------------------------------------------------------------------------------------
 template <class F>
-__global__ void __launch_bounds__(64) k_build_table(const Affine<F>* __restrict__ bases, uint32_t N, uint32_t c, uint32_t Wn,
+__global__ void __launch_bounds__(64) k_build_table(const Affine<F>* __restrict__ bases, uint32_t N, uint32_t E, uint32_t Wn,
                                                     uint32_t step_bits, uint32_t row0, uint32_t nrows, Affine<F>* __restrict__ table,
-                                                    XYZZ<F>* __restrict__ tmp, F* __restrict__ tmp_pre) {
+                                                    XYZZ<F>* __restrict__ tmp, F* __restrict__ tmp_pre, const MsmBlock* __restrict__ blocks) {
   const uint32_t rl = blockIdx.x * blockDim.x + threadIdx.x;   // row within this launch (row0 is a multiple of 64)
   if (rl >= nrows) return;
   const uint32_t row = row0 + rl;
-  const uint32_t E = 1u << (c - 1);
-  Affine<F>* out = table + ((size_t)(row >> 6) * E) * 64 + (row & 63);   // entry d at out[d * 64]
+  const size_t off = blocks ? (size_t)blocks[row >> 6].off : (size_t)(row >> 6) * E;
+  Affine<F>* out = table + off * 64 + (row & 63);                         // entry d at out[d * 64]
   XYZZ<F>* t = tmp + rl;                                                  // entry d at t[d * nrows]
   F* pre = tmp_pre + rl;
   if (row >= N * Wn) {   // padding rows of the last block
@@ -82,12 +87,13 @@ __global__ void __launch_bounds__(64) k_build_table(const Affine<F>* __restrict_
 }
 template <class F>
 void launch_build_table(hipStream_t st, const Affine<F>* bases, uint32_t N, uint32_t c, uint32_t Wt, uint32_t row0, uint32_t nrows,
-                        Affine<F>* table, XYZZ<F>* tmp, F* tmp_pre) {
+                        Affine<F>* table, XYZZ<F>* tmp, F* tmp_pre, const MsmBlock* blocks, uint32_t E) {
   if (nrows == 0) return;
   const uint32_t W = msm_windows(c);
   if (Wt == 0 || Wt > W) Wt = W;
   const uint32_t R = (W + Wt - 1) / Wt;   // row m of a base holds the multiples of 2^(c*R*m) * Base (pass rho takes windows rho + R*m)
-  hipLaunchKernelGGL(k_build_table<F>, dim3((nrows + 63) / 64), dim3(64), 0, st, bases, N, c, Wt, c * R, row0, nrows, table, tmp, tmp_pre);
+  if (!blocks) E = 1u << (c - 1);
+  hipLaunchKernelGGL(k_build_table<F>, dim3((nrows + 63) / 64), dim3(64), 0, st, bases, N, E, Wt, c * R, row0, nrows, table, tmp, tmp_pre, blocks);
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -182,14 +188,13 @@ struct MsmAcc<Fq2> {
 // on average where 2 fit.  (The second launch-bound, MsmWalk<F>::waves_per_simd, keeps the G1 walk within 256 registers = two waves per SIMD; the planner
 // reads the same figure.)
 template <class F>
-__global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_msm_flat(const Affine<F>* __restrict__ table, const int16_t* __restrict__ dig,
-                                                  XYZZ<F>* __restrict__ partial, uint32_t N, uint32_t P, uint32_t Pp, uint32_t c,
-                                                  uint32_t R, uint32_t Sg) {
+__global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_msm_flat(const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
+                                                  const int16_t* __restrict__ dig, XYZZ<F>* __restrict__ partial, uint32_t N, uint32_t P,
+                                                  uint32_t Pp, uint32_t R, uint32_t Sg) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t p = g % Pp, t = g / Pp;
   if (t >= R * Sg || p >= P) return;
   const uint32_t rho = t / Sg, sl = t % Sg;
-  const uint32_t E = 1u << (c - 1);
   const int16_t* __restrict__ dg = dig + ((size_t)rho * N) * Pp + p;
   MsmAcc<F> acc;
   acc.init();
@@ -212,15 +217,16 @@ __global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_
       }
 #pragma unroll 1
       for (uint32_t k = 0; k < 4; k++) {
-        const int d = (int)(int16_t)(uint16_t)(pack >> (16 * k));
+        int d = (int)(int16_t)(uint16_t)(pack >> (16 * k));
         const bool flush = last && k == 0;
+        const uint32_t i = i0 + k * Sg;
+        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+        MsmBlock blk{};
+        if (d != 0) blk = blocks[i >> 6];
+        if (mag > blk.E) d = 0;   // see the G1 loop below
         if (d != 0 || flush) {
           Affine<F> e;
-          if (d != 0) {
-            const uint32_t i = i0 + k * Sg;
-            const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-            e = table[((size_t)(i >> 6) * E + (mag - 1)) * 64 + (i & 63)];
-          }
+          if (d != 0) e = table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)];
           if (d_next != 0) acc.madd(e_next, d_next < 0);
           d_next = d;
           if (d != 0) e_next = e;
@@ -241,9 +247,15 @@ __global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_
       for (uint32_t k = 0; k < 4; k++) {
         const int d = (int)(int16_t)(uint16_t)(pack >> (16 * k));
         if (d != 0) {
+          // The block of base i: where its rows start and how many entries they hold (the base index is the same for the whole
+          // wave once a wave holds one slice, so this is one 16-byte line for all lanes).  A digit above the block's entry count
+          // is skipped: the range class of a narrow block's wires (msm_classes.hpp) makes it impossible for a row that satisfies
+          // its lookup constraints, and a row that does not is refused through its status word whatever is summed here -- the
+          // compare keeps the gather inside the table.
           const uint32_t i = i0 + k * Sg;
           const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-          acc.madd(table[((size_t)(i >> 6) * E + (mag - 1)) * 64 + (i & 63)], d < 0);
+          const MsmBlock blk = blocks[i >> 6];
+          if (mag <= blk.E) acc.madd(table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)], d < 0);
         }
       }
     }
@@ -293,8 +305,8 @@ __global__ void __launch_bounds__(256) k_msm_rows(const Affine<F>* __restrict__ 
 // kernel's duration as a profiler reports it -- an event pair recorded around the launch would also count the time the
 // launch waits for kernels of the other proving stream.
 template <class F>
-void launch_msm_accumulate(hipStream_t st, const Affine<F>* table, const int16_t* dig, XYZZ<F>* partial, uint32_t N, uint32_t P, uint32_t c,
-                           const MsmPlan& pl, hipEvent_t ev_start, hipEvent_t ev_stop) {
+void launch_msm_accumulate(hipStream_t st, const Affine<F>* table, const MsmBlock* blocks, const int16_t* dig, XYZZ<F>* partial, uint32_t N, uint32_t P,
+                           uint32_t c, const MsmPlan& pl, hipEvent_t ev_start, hipEvent_t ev_stop) {
   if (N == 0 || P == 0) {
     if (ev_start) hipEventRecord(ev_start, st);
     if (ev_stop) hipEventRecord(ev_stop, st);
@@ -302,7 +314,7 @@ void launch_msm_accumulate(hipStream_t st, const Affine<F>* table, const int16_t
   }
   const uint64_t lanes = (uint64_t)pl.R * pl.Sg * pl.Pp;
   if (pl.Wt == 1)
-    hipExtLaunchKernelGGL(k_msm_flat<F>, dim3((uint32_t)((lanes + MSM_WALK_BLOCK - 1) / MSM_WALK_BLOCK)), dim3(MSM_WALK_BLOCK), 0, st, ev_start, ev_stop, 0, table, dig, partial, N, P, pl.Pp, c, pl.R, pl.Sg);
+    hipExtLaunchKernelGGL(k_msm_flat<F>, dim3((uint32_t)((lanes + MSM_WALK_BLOCK - 1) / MSM_WALK_BLOCK)), dim3(MSM_WALK_BLOCK), 0, st, ev_start, ev_stop, 0, table, blocks, dig, partial, N, P, pl.Pp, pl.R, pl.Sg);
   else
     hipExtLaunchKernelGGL(k_msm_rows<F>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, ev_start, ev_stop, 0, table, dig, partial, N, P, pl.Pp, c,
                           pl.Wt, pl.R, pl.W, pl.Sg, pl.Q, pl.Wq);

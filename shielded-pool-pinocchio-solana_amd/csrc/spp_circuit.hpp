@@ -2,6 +2,7 @@
 // its MSM sets and batch workspaces, the experiment switches.  Private, like spp_internal.hpp.
 #pragma once
 #include "spp_internal.hpp"
+#include "msm_classes.hpp"
 
 template <class F>
 struct MsmSet {
@@ -11,6 +12,10 @@ struct MsmSet {
   bool from_h = false;   // scalars come from the h array instead of the witness
   uint32_t c = 0;        // window bits of this set's table
   uint32_t Wt = 0;       // table rows per base: msm_windows(c) = one per window (no passes), 1 = one row and msm_windows(c) passes
+  // flat sets (Wt = 1): start and entry count of every 64-row block of the table (msm_ragged.hpp); `narrow`: some block is shorter
+  // than 2^(c-1) entries, i.e. the table only serves scalars within the classes of the set's wires
+  MsmBlock* blocks = nullptr;
+  bool narrow = false;
 };
 template <class F>
 struct MsmBuf {
@@ -57,6 +62,8 @@ struct PendingTable {
   std::vector<Affine<F>> pts;
   Affine<F>* table;
   uint32_t c, Wt;
+  MsmRagged layout;              // flat sets; empty: the uniform layout
+  const MsmBlock* blocks;        // its copy on the device
 };
 struct SolveStep {
   enum Kind { SEQ, BATCH_DIV, COUNT8, COMMIT } kind;
@@ -85,6 +92,7 @@ struct Switches {
   bool no_side = false;           // SPP_NO_SIDE=1 (experiment): the G2 sum of a small batch on the batch's own stream
   int forced_depth = 0;           // SPP_DEPTH (experiment): batches in flight, 1 .. SPP_NWS; 0: by batch size (ws_depth)
   bool no_split = false;          // SPP_NO_SPLIT=1 (experiment): no cut of a batch into a 64-aligned body and a tail
+  bool ragged = true;             // SPP_RAGGED=0 (comparison, fallback): every base wide -- full table rows for all, the windows that affords
   MsmTuning msm;                  // SPP_MSM_WAVES, SPP_MSM_WAVES_SMALL (experiment): rounds of resident waves per table walk (msm_plan.hpp)
 };
 // Up to a batch size that depends on the circuit s*Ar and r*Bs1 are two more fixed-base sums (sets A and B1 over the witness scaled by s and r) instead of

@@ -45,34 +45,52 @@ static int upload_sparse(spp_circuit* c, const Circuit& circ, const Sparse& m, D
 // window tables: allocate first (all sets), then build with temporaries sized from the HBM that is left, so that
 // each launch has enough rows (>= tens of thousands of lanes) to fill the chip
 template <class F>
-static int alloc_table(spp_circuit* c, size_t N, uint32_t cbits, uint32_t Wt, Affine<F>** table_out) {
-  size_t table_elems = std::max<size_t>(msm_table_elems((uint32_t)N, cbits, Wt), 1);
+static int alloc_table_elems(spp_circuit* c, size_t table_elems, Affine<F>** table_out) {
+  table_elems = std::max<size_t>(table_elems, 1);
   Affine<F>* table;
   HIP_TRY(hipMalloc((void**)&table, table_elems * sizeof(Affine<F>)));
   c->owned.push_back(table);
-  c->table_bytes += table_elems * sizeof(Affine<F>);
+  c->table_bytes += table_elems * sizeof(Affine<F>);   // the bytes really allocated
   *table_out = table;
   return 0;
 }
 template <class F>
-static int build_table(spp_circuit* c, const std::vector<Affine<F>>& pts, uint32_t cbits, uint32_t Wt, Affine<F>* table, size_t temp_budget) {
+static int alloc_table(spp_circuit* c, size_t N, uint32_t cbits, uint32_t Wt, Affine<F>** table_out) {
+  return alloc_table_elems<F>(c, msm_table_elems((uint32_t)N, cbits, Wt), table_out);
+}
+// layout / blocks: the ragged layout of a flat set and its device copy (null: the uniform layout).  Blocks of equal length are
+// built together, in launches of at most `chunk` rows; the rows of narrow blocks cost at most 256 additions each.
+template <class F>
+static int build_table(spp_circuit* c, const std::vector<Affine<F>>& pts, uint32_t cbits, uint32_t Wt, Affine<F>* table, size_t temp_budget,
+                       const MsmRagged* layout = nullptr, const MsmBlock* blocks = nullptr) {
   hipStream_t st = c->ctx->stream;
-  const uint32_t Wn = Wt, E = 1u << (cbits - 1);
+  const uint32_t Wn = Wt, Efull = 1u << (cbits - 1);
   const size_t N = pts.size();
   if (N == 0) return 0;
+  if (!layout || layout->blocks.empty()) { layout = nullptr; blocks = nullptr; }
   const size_t rows_total = msm_table_rows(N, Wn);
-  const size_t per_row = (size_t)E * (sizeof(XYZZ<F>) + sizeof(F));
+  uint32_t Emax = layout ? 1 : Efull;
+  if (layout) for (const MsmBlock& b : layout->blocks) Emax = std::max(Emax, b.E);
+  const size_t per_row = (size_t)Emax * (sizeof(XYZZ<F>) + sizeof(F));
   size_t chunk = std::max<size_t>(64, ((temp_budget / per_row) / 64) * 64);
   chunk = std::min(chunk, (size_t)65536);   // larger launches only add TLB misses (the d-stride is chunk * 128 B)
   chunk = std::min(chunk, rows_total);
   DevBuf d_bases, tmp, tmp_pre;   // released on every return path
   HIP_TRY(d_bases.alloc(N * sizeof(Affine<F>)));
   HIP_TRY(hipMemcpy(d_bases.p, pts.data(), N * sizeof(Affine<F>), hipMemcpyHostToDevice));
-  HIP_TRY(tmp.alloc(chunk * E * sizeof(XYZZ<F>)));
-  HIP_TRY(tmp_pre.alloc(chunk * E * sizeof(F)));
-  for (size_t r0 = 0; r0 < rows_total; r0 += chunk) {
-    uint32_t cnt = (uint32_t)std::min(chunk, rows_total - r0);
-    launch_build_table<F>(st, d_bases.as<Affine<F>>(), (uint32_t)N, cbits, Wt, (uint32_t)r0, cnt, table, tmp.as<XYZZ<F>>(), tmp_pre.as<F>());
+  HIP_TRY(tmp.alloc(chunk * Emax * sizeof(XYZZ<F>)));
+  HIP_TRY(tmp_pre.alloc(chunk * Emax * sizeof(F)));
+  for (size_t r0 = 0; r0 < rows_total;) {
+    size_t r1 = rows_total;   // end of the run of blocks as long as the one at r0
+    uint32_t E = Efull;
+    if (layout) {
+      E = layout->blocks[r0 >> 6].E;
+      r1 = r0 + 64;
+      while (r1 < rows_total && layout->blocks[r1 >> 6].E == E) r1 += 64;
+    }
+    uint32_t cnt = (uint32_t)std::min(chunk, r1 - r0);
+    launch_build_table<F>(st, d_bases.as<Affine<F>>(), (uint32_t)N, cbits, Wt, (uint32_t)r0, cnt, table, tmp.as<XYZZ<F>>(), tmp_pre.as<F>(), blocks, E);
+    r0 += cnt;
   }
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
@@ -92,23 +110,46 @@ static int build_table_chunked(spp_circuit* c, const std::vector<Affine<F>>& pts
 }
 
 
+// bound: range class of every base (msm_classes.hpp; empty: all wide).  A flat set is put in class-major order and gets the ragged
+// table layout (msm_ragged.hpp); with every base wide both leave the set as it is, the uniform layout bit for bit.
 template <class F>
-static int make_set(spp_circuit* c, MsmSet<F>* set, const std::vector<uint32_t>& rows, const std::vector<Affine<F>>& pts, bool from_h,
-                    uint32_t cbits, bool flat) {
+static int make_set(spp_circuit* c, MsmSet<F>* set, std::vector<uint32_t> rows, std::vector<Affine<F>> pts, bool from_h, uint32_t cbits,
+                    bool flat, std::vector<uint32_t> bound = {}) {
   set->N = (uint32_t)pts.size();
   set->from_h = from_h;
   set->c = cbits;
   set->Wt = flat ? 1 : msm_windows(cbits);
-  if (int e = own_upload(c, &set->rows, rows)) return e;
-  if (int e = alloc_table<F>(c, pts.size(), cbits, set->Wt, &set->table)) return e;
-  pending(c, (F*)nullptr).push_back({pts, set->table, cbits, set->Wt});
+  if (!flat) {
+    if (int e = own_upload(c, &set->rows, rows)) return e;
+    if (int e = alloc_table<F>(c, pts.size(), cbits, set->Wt, &set->table)) return e;
+    pending(c, (F*)nullptr).push_back({std::move(pts), set->table, cbits, set->Wt, MsmRagged{}, nullptr});
+    return 0;
+  }
+  bound.resize(pts.size(), 0);
+  if (!c->sw.ragged) std::fill(bound.begin(), bound.end(), 0u);
+  const std::vector<uint32_t> perm = msm_class_major_order(bound.data(), bound.size(), cbits);
+  std::vector<uint32_t> rows_o(perm.size()), bound_o(perm.size());
+  std::vector<Affine<F>> pts_o(perm.size());
+  for (size_t k = 0; k < perm.size(); k++) {
+    rows_o[k] = rows[perm[k]];
+    pts_o[k] = pts[perm[k]];
+    bound_o[k] = bound[perm[k]];
+  }
+  MsmRagged layout = msm_ragged_layout(bound_o.data(), bound_o.size(), cbits);
+  set->narrow = layout.narrow(cbits);
+  if (int e = own_upload(c, &set->rows, rows_o)) return e;
+  if (layout.blocks.empty()) layout.blocks.push_back({0, 1u << (cbits - 1), 0});   // an empty set: nothing is read, the upload is not empty
+  if (int e = own_upload(c, &set->blocks, layout.blocks)) return e;
+  if (int e = alloc_table_elems<F>(c, layout.elems(), &set->table)) return e;
+  if (pts_o.empty()) layout.blocks.clear();
+  pending(c, (F*)nullptr).push_back({std::move(pts_o), set->table, cbits, set->Wt, std::move(layout), set->blocks});
   return 0;
 }
 static int build_pending(spp_circuit* c) {
   const size_t budget = table_temp_budget();
   int e = 0;
-  for (auto& p : pending(c, (Fq*)nullptr)) if (!e) e = build_table<Fq>(c, p.pts, p.c, p.Wt, p.table, budget);
-  for (auto& p : pending(c, (Fq2*)nullptr)) if (!e) e = build_table<Fq2>(c, p.pts, p.c, p.Wt, p.table, budget);
+  for (auto& p : pending(c, (Fq*)nullptr)) if (!e) e = build_table<Fq>(c, p.pts, p.c, p.Wt, p.table, budget, &p.layout, p.blocks);
+  for (auto& p : pending(c, (Fq2*)nullptr)) if (!e) e = build_table<Fq2>(c, p.pts, p.c, p.Wt, p.table, budget, &p.layout, p.blocks);
   pending(c, (Fq*)nullptr).clear();
   pending(c, (Fq2*)nullptr).clear();
   return e;
@@ -200,46 +241,11 @@ static void merge_point(std::vector<uint32_t>& wires, std::vector<Affine<F>>& pt
   pts.push_back(extra);
 }
 
-// Greedy split of an HBM budget over the throughput-layout (one table row per base) MSM sets of one OR SEVERAL circuits: start
-// every set at 6 bits and repeatedly widen the set whose next window bit removes the most mixed-addition work per extra byte
-// (a G2 addition is weighted 3 G1 additions, as measured); `fixed` sets keep their bits.  With several circuits the unit of work
-// is one proof of each (the relayer's pair: an audit proof and a withdraw proof per withdrawal,
-// demo-frontend/app/api/relay/withdraw/route.ts:238-276), so their sets simply compete in one list.
-namespace {
-struct PlanSet {
-  double n, esz, wgt;   // bases, bytes per table entry, weight of an addition (0: fixed)
-  bool flat;            // one row per base (else one row per window)
-  int bits;
-};
-double plan_bytes(const PlanSet& s, int cb) { return s.n * s.esz * (s.flat ? 1.0 : (double)msm_windows((uint32_t)cb)) * (double)(1u << (cb - 1)); }
-void plan_greedy(std::vector<PlanSet>& sets, double budget, int cmax) {
-  double used = 0;
-  for (auto& s : sets) used += plan_bytes(s, s.bits);
-  for (;;) {
-    int best = -1;
-    double best_gain = 0;
-    for (size_t i = 0; i < sets.size(); i++) {
-      const PlanSet& s = sets[i];
-      if (s.wgt == 0 || s.bits >= cmax || s.n == 0) continue;
-      const double extra = plan_bytes(s, s.bits + 1) - plan_bytes(s, s.bits);
-      if (used + extra > budget) continue;
-      const double saved = s.wgt * s.n * ((double)msm_windows((uint32_t)s.bits) - (double)msm_windows((uint32_t)s.bits + 1));
-      double gain = saved / extra;
-      if (saved <= 0) gain = 1e-30;   // a bit that does not change the window count yet may enable the next one
-      if (gain > best_gain) { best_gain = gain; best = (int)i; }
-    }
-    if (best < 0) break;
-    used += plan_bytes(sets[best], sets[best].bits + 1) - plan_bytes(sets[best], sets[best].bits);
-    sets[best].bits++;
-  }
-}
-const double PLAN_ESZ[7] = {64, 64, 64, 64, 64, 64, 128}, PLAN_WGT[7] = {1, 1, 1, 1, 0, 0, 3.0};   // A, B1, K, Z, CB, CS, B2
-}  // namespace
-
 // What the steps of load_circuit_impl share beyond the circuit itself.
 struct LoadState {
   PkFile pk;
   uint32_t cw[7];   // window bits per MSM set: A, B1, K, Z, CB, CS, B2
+  WireClasses wc;   // range class of every wire (msm_classes.hpp; all wide under SPP_RAGGED=0)
   bool flat[7] = {false, false, false, false, false, false, false};   // one table row per base (else one per window)
   // the H bases as rows / points of the Z set and, in the product form, the per-wire column sums that join the K set
   std::vector<uint32_t> z_w, xk_w;
@@ -262,6 +268,8 @@ static Switches read_switches() {
   const int depth = de ? atoi(de) : 0;
   sw.forced_depth = depth >= 1 && depth <= SPP_NWS ? depth : 0;
   sw.no_split = getenv("SPP_NO_SPLIT") != nullptr;
+  const char* rg = getenv("SPP_RAGGED");
+  sw.ragged = !(rg && rg[0] == '0');
   sw.msm = msm_tuning_from_env(getenv("SPP_MSM_WAVES"), getenv("SPP_MSM_WAVES_SMALL"));
   return sw;
 }
@@ -276,7 +284,9 @@ static Switches read_switches() {
 //    and costs 16 additions per full-size scalar; the row-per-window layout of rounds 1-2 afforded 11-12 bits (22-24
 //    additions) in the same bytes (SPP_FLAT=0 brings it back for comparison).  The two commitment sets only ever see bytes /
 //    small counters and sit on the critical path of the challenge: row-per-window tables at 9 bits, no passes.
-static int plan_load_windows(const PkFile& pk, int window_bits, const uint32_t* forced_bits, uint32_t cw[7], bool flat[7]) {
+//    A bit is priced at what it costs (plan_greedy, msm_ragged.hpp): the bases of A, B1, B2 and K whose wire is a bit or a byte
+//    (wc) keep rows of 1 / 256 entries whatever the window, so only the wide bases pay for a bit and only they gain by it.
+static int plan_load_windows(const PkFile& pk, const WireClasses& wc, int window_bits, const uint32_t* forced_bits, uint32_t cw[7], bool flat[7]) {
   const double nset[7] = {(double)pk.A.size() + 2, (double)pk.B1.size() + 2, (double)pk.K.size() + 1, (double)pk.Z.size(),
                           (double)pk.CB.size(), (double)pk.CS.size(), (double)pk.B2.size() + 2};
   if (forced_bits) {           // spp_load_circuit_with_windows: the caller planned the windows (spp_plan_windows), throughput layout
@@ -297,8 +307,12 @@ static int plan_load_windows(const PkFile& pk, int window_bits, const uint32_t* 
     std::vector<PlanSet> sets;
     for (int s = 0; s < 7; s++) {
       flat[s] = use_flat && PLAN_WGT[s] != 0;
-      sets.push_back({nset[s], PLAN_ESZ[s], PLAN_WGT[s], flat[s], PLAN_WGT[s] != 0 ? 6 : 9});
+      sets.push_back(plan_set(s, nset[s], flat[s]));
     }
+    const std::vector<uint32_t>* keyed[7] = {&pk.A_w, &pk.B1_w, &pk.K_w, nullptr, nullptr, nullptr, &pk.B2_w};
+    for (int s = 0; s < 7; s++)
+      if (keyed[s] && flat[s])
+        for (uint32_t b : msm_base_bounds(wc, *keyed[s])) plan_count(sets[s], b);
     plan_greedy(sets, budget, use_flat ? 16 : 15);
     for (int s = 0; s < 7; s++) cw[s] = (uint32_t)sets[s].bits;
   }
@@ -517,21 +531,21 @@ static int load_key_sets(spp_circuit* c, const LoadState& s) {
     std::vector<G1Affine> p = pk.A;
     merge_point(w, p, 0u, pk.alpha1);
     w.push_back(c->row_r); p.push_back(pk.delta1);
-    if ((e = make_set(c, &c->A, w, p, false, cw[0], flat[0]))) return e;
+    if ((e = make_set(c, &c->A, w, p, false, cw[0], flat[0], msm_base_bounds(s.wc, w)))) return e;
   }
   {
     std::vector<uint32_t> w = pk.B1_w;
     std::vector<G1Affine> p = pk.B1;
     merge_point(w, p, 0u, pk.beta1);
     w.push_back(c->row_s); p.push_back(pk.delta1);
-    if ((e = make_set(c, &c->B1, w, p, false, cw[1], flat[1]))) return e;
+    if ((e = make_set(c, &c->B1, w, p, false, cw[1], flat[1], msm_base_bounds(s.wc, w)))) return e;
   }
   {
     std::vector<uint32_t> w = pk.B2_w;
     std::vector<G2Affine> p = pk.B2;
     merge_point(w, p, 0u, pk.beta2);
     w.push_back(c->row_s); p.push_back(pk.delta2);
-    if ((e = make_set(c, &c->B2, w, p, false, cw[6], flat[6]))) return e;
+    if ((e = make_set(c, &c->B2, w, p, false, cw[6], flat[6], msm_base_bounds(s.wc, w)))) return e;
   }
   return 0;
 }
@@ -662,7 +676,10 @@ static int load_h_sets(spp_circuit* c, const LoadState& s) {
       }
     }
     w.push_back(c->row_rs); p.push_back(pk.delta1.neg());
-    if ((e = make_set(c, &c->K, w, p, false, cw[2], flat[2]))) return e;
+    // the key's own K bases inherit the class of their wire (a column sum added to the point does not change the scalar); the
+    // wires that join the set through their column sum alone stay wide, like the blinding row
+    std::vector<uint32_t> kb = msm_base_bounds(s.wc, pk.K_w);
+    if ((e = make_set(c, &c->K, w, p, false, cw[2], flat[2], kb))) return e;
   }
   if ((e = make_set(c, &c->Z, z_w, z_p, true, cw[3], flat[3]))) return e;
   if ((e = make_set(c, &c->CB, pk.CB_w, pk.CB, false, cw[4], false))) return e;
@@ -734,7 +751,9 @@ static int load_circuit_impl(spp_ctx* ctx, const char* circuit_path, const char*
   if (pk.circuit_id != circ.id || pk.n_wires != circ.n_wires || pk.domain_log != circ.domain_log)
     return fail(SPP_ERR_FORMAT, "proving key does not match the circuit");
   c->sw = read_switches();
-  if (int e = plan_load_windows(pk, window_bits, forced_bits, s.cw, s.flat)) return e;
+  s.wc = msm_wire_classes(circ);
+  if (!c->sw.ragged) s.wc = WireClasses{std::vector<uint32_t>(circ.n_wires, 0), std::vector<uint8_t>(circ.n_wires, WIRE_WIDE)};
+  if (int e = plan_load_windows(pk, s.wc, window_bits, forced_bits, s.cw, s.flat)) return e;
   c->c_bits = s.cw[3];   // reported window = that of the largest set (Z)
   c->logn = circ.domain_log;
   c->n = 1u << c->logn;
@@ -843,7 +862,7 @@ extern "C" int spp_plan_windows(uint32_t n_circuits, const uint32_t* sizes, doub
   if (!sizes || !bits || n_circuits == 0 || n_circuits > 16) return fail(SPP_ERR_BAD_INPUT, "bad argument");
   std::vector<PlanSet> sets;
   for (uint32_t k = 0; k < n_circuits; k++)
-    for (int s = 0; s < 7; s++) sets.push_back({(double)sizes[7 * k + s], PLAN_ESZ[s], PLAN_WGT[s], PLAN_WGT[s] != 0, PLAN_WGT[s] != 0 ? 6 : 9});
+    for (int s = 0; s < 7; s++) sets.push_back(plan_set(s, (double)sizes[7 * k + s], PLAN_WGT[s] != 0));
   double floor_bytes = 0;
   for (auto& ps : sets) floor_bytes += plan_bytes(ps, ps.bits);
   if (floor_bytes > budget_bytes) return fail(SPP_ERR_BAD_INPUT, "the budget does not hold even 6-bit tables (%.1f GB needed)", floor_bytes / 1e9);
@@ -895,7 +914,7 @@ static int msm_fixed_unit(spp_ctx* ctx, const uint8_t* bases, const uint8_t* sca
   XYZZ<F> res = XYZZ<F>::infinity();
   if (!e) {
     launch_msm_digits(st, d_rows, d_sc, dig.as<int16_t>(), (uint32_t)n, 1, cb);
-    launch_msm_accumulate<F>(st, table, dig.as<int16_t>(), partial, (uint32_t)n, 1, cb, pl);
+    launch_msm_accumulate<F>(st, table, nullptr, dig.as<int16_t>(), partial, (uint32_t)n, 1, cb, pl);
     launch_msm_reduce<F>(st, partial, d_out, 1, pl, cb, n == 0);
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) e = fail(SPP_ERR_HIP, "msm kernels failed");
     else if (hipMemcpy(&res, d_out, sizeof res, hipMemcpyDeviceToHost) != hipSuccess) e = fail(SPP_ERR_HIP, "copy back failed");

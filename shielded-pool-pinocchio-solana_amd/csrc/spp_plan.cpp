@@ -375,19 +375,7 @@ static int small_rows_plan(spp_circuit* c, std::vector<uint8_t>& flags_out) {
   c->dc.sm_nslots = 0;
   c->dc.row_small = nullptr;
   if (getenv("SPP_NO_SMALL_ROWS")) return 0;
-  // signed small value of a coefficient-table entry, if it has one
-  auto small_of = [&](uint32_t ci, int64_t* out) {
-    uint32_t v[8];
-    circ.coeffs[ci].to_canonical(v);
-    bool hi0 = true;
-    for (int k = 1; k < 8; k++) hi0 = hi0 && v[k] == 0;
-    if (hi0 && v[0] < (1u << 30)) { *out = (int64_t)v[0]; return true; }
-    circ.coeffs[ci].neg().to_canonical(v);
-    hi0 = true;
-    for (int k = 1; k < 8; k++) hi0 = hi0 && v[k] == 0;
-    if (hi0 && v[0] < (1u << 30)) { *out = -(int64_t)v[0]; return true; }
-    return false;
-  };
+  auto small_of = [&](uint32_t ci, int64_t* out) { return fr_small_signed(circ.coeffs[ci], out); };
   std::vector<int32_t> slot_of(circ.n_wires, -1);
   std::vector<uint32_t> wires{0};
   std::vector<int32_t> lo{0};
@@ -395,18 +383,9 @@ static int small_rows_plan(spp_circuit* c, std::vector<uint8_t>& flags_out) {
   for (const SolveStep& st : c->schedule) {
     if (st.kind != SolveStep::COUNT8) continue;
     for (uint32_t h = st.a; h < st.a + st.b && h < circ.H.rows(); h++) {
-      uint32_t w = 0, nw = 0;
+      uint32_t w = 0;
       int64_t cst = 0;
-      bool ok = true;
-      for (uint32_t t = circ.H.rowptr[h]; t < circ.H.rowptr[h + 1] && ok; t++) {
-        const Term& tm = circ.H.terms[t];
-        int64_t v;
-        if (!small_of(tm.coeff, &v)) { ok = false; break; }
-        if (tm.wire == 0) cst += v;
-        else if (v == 1) { w = tm.wire; nw++; }
-        else ok = false;
-      }
-      if (!ok || nw != 1 || cst < -32000 || cst > 32000 || slot_of[w] >= 0) continue;
+      if (!circuit_byte_ranged_lookup(circ, h, &w, &cst) || slot_of[w] >= 0) continue;   // msm_classes.hpp: the rule the range classes use
       slot_of[w] = (int32_t)wires.size();
       wires.push_back(w);
       lo.push_back((int32_t)-cst);

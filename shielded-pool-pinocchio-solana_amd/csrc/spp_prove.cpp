@@ -67,7 +67,7 @@ static void run_msm(spp_circuit* c, Workspace& w, const MsmSet<F>& s, MsmBuf<F>&
   int16_t* dig = ws_dig(w, (F*)nullptr);
   launch_msm_digits(st, s.rows, scal, dig, s.N, P, s.c);
   // the event pair receives the dispatch's own start/stop timestamps (what rocprofv3 reports as the kernel's duration)
-  launch_msm_accumulate<F>(st, s.table, dig, b.partial, s.N, P, s.c, pl, ev ? ev->first : nullptr, ev ? ev->second : nullptr);
+  launch_msm_accumulate<F>(st, s.table, s.blocks, dig, b.partial, s.N, P, s.c, pl, ev ? ev->first : nullptr, ev ? ev->second : nullptr);
   if (fold) launch_msm_reduce<F>(st, b.partial, b.out, P, pl, s.c, s.N == 0);
 }
 
@@ -78,7 +78,9 @@ static int prove_on_device(spp_circuit* c, Workspace& w, uint32_t P, const uint8
   const uint32_t n = c->n;
   w.msm_ev_used = 0;
   w.last_P = P;
-  const bool scaled_blind = P <= scaled_blind_max_batch(c->A.N, c->B1.N) && !c->sw.no_coop;
+  // (the two scaled sums walk the A and B1 tables with full-size scalars for every base: not over tables whose narrow rows only
+  // serve their wires' range classes -- such a circuit keeps the per-lane multiplication at every batch size)
+  const bool scaled_blind = P <= scaled_blind_max_batch(c->A.N, c->B1.N) && !c->sw.no_coop && !c->A.narrow && !c->B1.narrow;
   HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(uint32_t) * P, st));
   hipEventRecord(w.ev[0], st);
   // 1. inputs, solver phase 1, commitment, challenge, solver phase 2
