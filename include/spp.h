@@ -21,6 +21,10 @@
  *   spp_verify                `sunspot verify` noir_circuit/prove_linux.sh:86-87, audit_circuit/prove_audit.sh:98-99
  *   spp_verify_batch          the same for many proofs on the GPU
  *   spp_shamir_reconstruct / spp_rlwe_decrypt_batch   scripts/rlwe_decrypt.py:61-132, demo-frontend/app/lib/shamir.ts:97-169
+ *   spp_prove_audit_records   scripts/generate_audit.py:468-691 with the ciphertext.json of :590-606: the audit RECORD
+ *                             (proof, public witness, ciphertext) from the prover's raw secrets
+ *   spp_audit_open_batch      scripts/rlwe_decrypt.py:61-149 for a batch of such records, after `sunspot verify`
+ *                             (audit_circuit/prove_audit.sh:98-99) and with the two binding checks the script leaves out
  *   spp_msm_g1(_pippenger) / spp_ntt_fr   micro-benchmark entry points (BASELINE.json configs[4]); no reference equivalent
  *
  * Conventions: field elements cross the boundary as 32-byte big-endian canonical integers (the encoding
@@ -258,6 +262,23 @@ int spp_audit_inputs_batch_device(spp_ctx* ctx, const void* d_pk_a, const void* 
 int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk, const void* d_r,
                                         const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs, void* d_pws, void* d_status);
 
+/* The audit record, not just the proof.  spp_prove_audit_from_secrets_device plus the ciphertext each proof commits to: d_c0 count*64 u32,
+ * d_c1 count*1024 u32, coefficients in [0,q) -- the c0_sparse / c1 of ciphertext.json (generate_audit.py:590-606), the layout
+ * spp_rlwe_decrypt_batch and spp_audit_open_batch read.  Without it the proofs of the call above are records nobody can decrypt.
+ * The ciphertext is written by the RLWE kernel of the input pipeline, on the batch's own proving stream: complete after spp_sync(),
+ * also for a row the circuit refuses (status != 0).  Same argument checks, pipelining and workspace rotation, same proof and
+ * public-witness bytes as the call above; the ciphertext buffers, like the other outputs, must not be shared by calls in flight. */
+int spp_prove_audit_records_device(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk, const void* d_r,
+                                   const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs, void* d_pws, void* d_status,
+                                   void* d_c0, void* d_c1);
+/* host convenience (host buffers, rs NULL = OS randomness, status optional), chunked like spp_prove_withdraw_notes: at most 2 048
+ * records per chunk, two chunks in flight.  proofs, pws, status as spp_prove_batch (a refused record: status SPP_ERR_UNSAT, proof
+ * bytes zero, ciphertext still written); returns SPP_ERR_UNSAT if any record was refused.  Also refused with SPP_ERR_BAD_INPUT: a
+ * public-key coefficient >= q, count > 2^24. */
+int spp_prove_audit_records(spp_circuit* c, const uint32_t* pk_a, const uint32_t* pk_b, size_t count, const uint8_t* sk, const int8_t* r,
+                            const int8_t* e1, const int8_t* e2, const uint8_t* rs, uint8_t* proofs, uint8_t* pws, int32_t* status,
+                            uint32_t* c0, uint32_t* c1);
+
 /* Withdraw proofs from notes against the resident tree: the withdraw counterpart of the call above.  Replaces the per-recipient
  * loop of client/payroll-demo.ts:323-340 -- generateIdentityKeypair (client/merkle.ts:98-113), wa_commitment and nullifier
  * (payroll-demo.ts:264-271), mt.getRoot() / mt.getProof(index) (client/merkle.ts:165-176,198-221), generateProof -- with one
@@ -313,6 +334,25 @@ int spp_shamir_reconstruct(spp_ctx* ctx, uint32_t t, const uint32_t* xs, const u
 /* rlweDecrypt (shamir.ts:134-169 / rlwe_decrypt.py:106-132) for `count` ciphertexts: c0 count*64, c1 count*1024 in
  * [0,q); msg = count * 64 recovered byte slots (owner_x = slots 0..31 little-endian, owner_y = slots 32..63). */
 int spp_rlwe_decrypt_batch(spp_ctx* ctx, const uint32_t* sk_mod_q, size_t count, const uint32_t* c0, const uint32_t* c1, uint8_t* msg);
+
+/* Opening audit records in one pass: what an auditor replaying submit_audit logs asks of every record (proof, public witness,
+ * ciphertext) -- does the proof verify, is this the ciphertext the proof committed to, is the decrypted identity the one the
+ * withdrawal is bound to.  (scripts/rlwe_decrypt.py:135-149 only compares with an expected owner the PROVER wrote.)  One upload,
+ * k_verify, then one kernel over the records: range check, packing + ct_commitment sponge, decryption, identity checks, comparison with
+ * the two words of the public witness; one download.  Each bit is decided on its own: a record with a bad proof still has bits 2
+ * and 4 evaluated and its owner written.  The comparisons are bytewise against the canonical value computed here. */
+#define SPP_AUDIT_BAD_PROOF 1       /* the proof does not verify under vk: the decision of spp_verify / spp_verify_batch */
+#define SPP_AUDIT_BAD_CIPHERTEXT 2  /* a coefficient >= q, or Poseidon2 sponge(pack(c0) ++ pack(c1)) != the pw's ct_commitment */
+#define SPP_AUDIT_BAD_IDENTITY 4    /* decrypted owner_x or owner_y >= r, not on Grumpkin, or H(owner_x, owner_y) != the pw's wa_commitment */
+/* proofs count*388, pws count*76, c0 count*64 u32, c1 count*1024 u32 (host buffers); sk_mod_q: 1024 u32 in [0,q) from
+ * spp_shamir_reconstruct.  owners: count*64 B, owner_x | owner_y as 32 B big-endian each, the decrypted bytes as they are, always
+ * written (a coefficient >= q decrypts as its residue mod q).  flags[i] = 0: record i is proved, bound to this ciphertext, and
+ * decrypts to the identity wa_commitment commits to.
+ * vk NULL (vk_len 0): records already verified elsewhere (the chain did) -- bit 1 is never set, proofs may be NULL.
+ * Refused before any device work: NULL pointers, sk_mod_q[i] >= q, count > 2^24 (SPP_ERR_BAD_INPUT); a malformed vk or one whose
+ * public-input count is not 2 (SPP_ERR_FORMAT).  count == 0 is SPP_OK. */
+int spp_audit_open_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint32_t* sk_mod_q, size_t count, const uint8_t* proofs,
+                         const uint8_t* pws, const uint32_t* c0, const uint32_t* c1, uint8_t* owners, uint32_t* flags);
 
 /* ---- micro-benchmark / unit entry points ---- */
 /* data: n = 2^logn elements, 32 B big-endian each, natural order in and out */

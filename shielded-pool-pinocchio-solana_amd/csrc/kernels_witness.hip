@@ -11,10 +11,12 @@
 //   k_deposit_leaves      client/payroll-demo.ts:264-292 (keygen, calculateCommitment, mt.insert)
 //   k_deposit_roots       the same deposits' mt.getRoot() after each insert
 //   k_poseidon2_sponge    ct_helper/src/main.nr:15-34 (= scripts/generate_audit.py:355-374)
+//   k_audit_open          scripts/rlwe_decrypt.py:61-149 for a batch of (pw, ciphertext) records, with the binding checks it omits
 #include "kernels.hpp"
 #include "poseidon29.hpp"
 #include "lanes.hpp"
 #include "rlwe_ntt.hpp"
+#include "audit_open.hpp"
 
 namespace spp {
 
@@ -575,7 +577,7 @@ void launch_poseidon2_sponge(hipStream_t st, HashConsts hc, const uint8_t* in_be
 // ----------------------------------------------------------------------------------------------------
 // msg[i] = round(centered((c0 + sk*c1 mod (X^n+1, q))[i]) / Delta) mod 256 for the 64 message slots; one 64-lane block per
 // ciphertext, lane i owns slot i:  (sk*c1)[i] = sum_j SK2[(i - j) mod 2048] * c1[j],  SK2 = [sk, (q - sk) mod q].
-// Products are 28 x 28 bits: the 64-bit accumulator is folded mod q every 128 terms.
+// Products are 28 x 28 bits: the 64-bit accumulator is folded mod q every 128 terms (ao_decrypt_slot, audit_open.hpp).
 __global__ void __launch_bounds__(64) k_rlwe_decrypt(const uint32_t* __restrict__ sk_mod_q, const uint32_t* __restrict__ c0,
                                                      const uint32_t* __restrict__ c1, uint8_t* __restrict__ msg, uint32_t count) {
   __shared__ uint32_t SK2[2 * RL_N];
@@ -583,24 +585,11 @@ __global__ void __launch_bounds__(64) k_rlwe_decrypt(const uint32_t* __restrict_
   const uint32_t inst = blockIdx.x, t = threadIdx.x;
   if (inst >= count) return;
   for (int i = t; i < RL_N; i += 64) {
-    const uint32_t s = sk_mod_q[i];
-    SK2[i] = s;
-    SK2[RL_N + i] = s ? (uint32_t)RL_Q - s : 0u;
+    ao_sk2_entry(sk_mod_q[i], SK2[i], SK2[RL_N + i]);
     cs[i] = c1[(size_t)inst * RL_N + i];
   }
   __syncthreads();
-  unsigned long long acc = 0, total = 0;
-  for (int j = 0; j < RL_N; j++) {
-    acc += (unsigned long long)SK2[(t - j) & 2047] * cs[j];
-    if ((j & 127) == 127) { total += acc % (unsigned long long)RL_Q; acc = 0; }
-  }
-  const long long skc1 = (long long)(total % (unsigned long long)RL_Q);
-  long long noisy = ((long long)c0[(size_t)inst * RL_SLOTS + t] + skc1) % RL_Q;
-  if (noisy > RL_Q / 2) noisy -= RL_Q;                       // centered_mod (rlwe_decrypt.py:54-58)
-  long long k = noisy / RL_DELTA, rem = noisy % RL_DELTA;    // floor division
-  if (rem < 0) { rem += RL_DELTA; k -= 1; }
-  if (2 * rem > RL_DELTA || (2 * rem == RL_DELTA && (k & 1))) k += 1;   // Python round(): half to even
-  msg[(size_t)inst * RL_SLOTS + t] = (uint8_t)(((k % 256) + 256) % 256);
+  msg[(size_t)inst * RL_SLOTS + t] = ao_decrypt_slot(SK2, cs, c0[(size_t)inst * RL_SLOTS + t], t);   // audit_open.hpp, shared with k_audit_open
 }
 void launch_rlwe_decrypt(hipStream_t st, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, uint8_t* msg, uint32_t count) {
   if (count) hipLaunchKernelGGL(k_rlwe_decrypt, dim3(count), dim3(64), 0, st, sk_mod_q, c0, c1, msg, count);
@@ -630,6 +619,93 @@ __global__ void __launch_bounds__(256) k_shamir_combine(const Fr* __restrict__ l
 void launch_shamir_combine(hipStream_t st, const Fr* lambda, const uint8_t* ys_be, uint32_t t, uint32_t n, uint8_t* secret_be,
                            uint32_t* sk_mod_q) {
   if (n) hipLaunchKernelGGL(k_shamir_combine, dim3((n + 255) / 256), dim3(256), 0, st, lambda, ys_be, t, n, secret_be, sk_mod_q);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Opening audit records (scripts/rlwe_decrypt.py:61-149 plus the two checks it leaves out, see include/spp.h): one 64-lane wave
+// per 64 records, in two phases that each use the lanes the way their work is shaped.
+//   phase 1, the wave on one record at a time: its ciphertext (c0 64 + c1 1024 words, 4 352 B) goes into LDS with coalesced
+//     16-byte loads; every coefficient is checked against q (__any over the wave); lane t decrypts message slot t with the loop
+//     and rounding of k_rlwe_decrypt (audit_open.hpp) against the doubled secret key, which is built in LDS once per block and
+//     serves all 64 records; the byte goes to the owner record and to a 64 x 64-byte LDS tile.
+//   phase 2, one lane per record: the 157 packed fields (pack_values: 7 x 32 bits) are formed word by word from the record's
+//     coefficients -- read a second time, per lane at a 4 KB stride -- and absorbed three at a time into the Poseidon2 sponge, so the packed
+//     row never exists in memory; then the lane reads its record's two 256-bit integers from the tile: both < r, y^2 = x^3 - 17,
+//     H(x, y) by the t = 3 Poseidon; then the two hashes against the words of the public witness, bytewise (ao_decide), or-ed
+//     with the verdict of k_verify, which ran before on the same stream (proof_ok; nullptr: no verification asked for).
+// Why the sponge is not the lane-parallel one of lanes.hpp: 53 chained permutations per record are the bulk of the work, and a
+// wave that spends its 64 lanes on one record's permutation pays about 25 times the issue slots per record of a wave whose lanes
+// hold 64 records (launch_poseidon2_sponge draws the same line at 256 instances).  By the figure DESIGN.md gives for the wave
+// form of the sponge (2 048 instances = about 12 ms of a saturated chip) that would be about 0.2 s at 2^15 records (an estimate);
+// measured in this form (profiles/audit_open_kernel_stats.csv): 22.3 ms per launch at 2^15 records, against 20.0 + 0.45 + 0.43 ms
+// for k_poseidon2_sponge, k_rlwe_decrypt and k_poseidon_hash on the same records, and 207 ms for k_verify in front of it -- the
+// latency of one sponge chain either way, second read of the ciphertext included.  Small batches pay for the choice: a single
+// record is one wave of the chip.
+// LDS per block: 8 KB key + 4.25 KB ciphertext + 4.25 KB tile = 16.6 KB; a block is one wave and 2^15 records are 512 blocks on
+// 256 CUs, so neither LDS nor registers limit what is resident.
+// ----------------------------------------------------------------------------------------------------
+static constexpr uint32_t AO_TILE_STRIDE = 68;   // bytes per record in the message tile: 17 words, so the lanes of phase 2 spread over the banks
+__global__ void __launch_bounds__(64) k_audit_open(HashConsts hc, const uint32_t* __restrict__ sk_mod_q, const uint32_t* __restrict__ c0,
+                                                   const uint32_t* __restrict__ c1, const uint8_t* __restrict__ pws,
+                                                   const int32_t* __restrict__ proof_ok, uint8_t* __restrict__ owners,
+                                                   uint32_t* __restrict__ flags, uint32_t count) {
+  __shared__ uint32_t SK2[2 * AO_N];
+  __shared__ __attribute__((aligned(16))) uint32_t ct[AO_CT_WORDS];
+  __shared__ __attribute__((aligned(4))) uint8_t tile[64 * AO_TILE_STRIDE];
+  __shared__ uint8_t coeff_bad[64];
+  const uint32_t lane = threadIdx.x, first = blockIdx.x * 64;
+  if (first >= count) return;
+  const uint32_t nrec = count - first < 64 ? count - first : 64;
+  for (uint32_t i = lane; i < AO_N; i += 64) ao_sk2_entry(sk_mod_q[i], SK2[i], SK2[AO_N + i]);
+  // ---- phase 1 ----
+#pragma unroll 1
+  for (uint32_t k = 0; k < nrec; k++) {
+    const size_t inst = (size_t)first + k;
+    bool bad = false;
+    ct[lane] = ao_coeff(c0[inst * AO_SLOTS + lane], bad);
+    const uint4* src = reinterpret_cast<const uint4*>(c1 + inst * AO_N);   // rows of 4 KB: 16-byte aligned
+#pragma unroll
+    for (uint32_t j = 0; j < AO_N / 4 / 64; j++) {
+      const uint32_t i = lane + 64 * j;
+      uint4 v = src[i];
+      v.x = ao_coeff(v.x, bad); v.y = ao_coeff(v.y, bad); v.z = ao_coeff(v.z, bad); v.w = ao_coeff(v.w, bad);
+      reinterpret_cast<uint4*>(ct + AO_SLOTS)[i] = v;
+    }
+    const bool any_bad = __any(bad ? 1 : 0) != 0;
+    if (lane == 0) coeff_bad[k] = any_bad ? 1 : 0;
+    __syncthreads();
+    const uint8_t m = ao_decrypt_slot(SK2, ct + AO_SLOTS, ct[lane], lane);
+    tile[k * AO_TILE_STRIDE + lane] = m;
+    owners[inst * 64 + ao_owner_byte(lane)] = m;               // always written, whatever the decisions below
+    __syncthreads();                                            // ct is overwritten by the next record
+  }
+  if (lane >= nrec) return;
+  // ---- phase 2: ct_commitment, the rate-3 sponge over the packed fields (ct_helper/src/main.nr:15-34), 157 = 52 * 3 + 1 ----
+  const size_t inst = (size_t)first + lane;
+  const uint32_t *my0 = c0 + inst * AO_SLOTS, *my1 = c1 + inst * AO_N;
+  Fr s[4] = {Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
+#pragma unroll 1
+  for (uint32_t i = 0; i < AO_FIELDS / 3; i++) {
+    SPP_UNROLL for (uint32_t j = 0; j < 3; j++) s[j] = s[j] + ao_packed_field(my0, my1, 3 * i + j);
+    poseidon2_permute(s, hc.p2_rc, hc.p2_mu);
+  }
+  static_assert(AO_FIELDS % 3 == 1, "one field left for the last absorption");
+  s[0] = s[0] + ao_packed_field(my0, my1, AO_FIELDS - 1);
+  poseidon2_permute(s, hc.p2_rc, hc.p2_mu);
+  uint8_t ct_be[32], wa_be[32];
+  s[0].to_bytes_be(ct_be);
+  uint32_t x[8], y[8];
+  ao_owner_limbs(tile + lane * AO_TILE_STRIDE, x, y);
+  Fr fx, fy;
+  const bool point_ok = ao_owner_on_curve(x, y, &fx, &fy);
+  if (point_ok) poseidon_hash2(hc, fx, fy).to_bytes_be(wa_be);
+  uint32_t f = ao_decide(coeff_bad[lane] != 0, ct_be, point_ok, wa_be, pws + inst * 76);
+  if (proof_ok && !proof_ok[inst]) f |= AO_BAD_PROOF;
+  flags[inst] = f;
+}
+void launch_audit_open(hipStream_t st, HashConsts hc, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, const uint8_t* pws,
+                       const int32_t* proof_ok, uint8_t* owners, uint32_t* flags, uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_audit_open, dim3((count + 63) / 64), dim3(64), 0, st, hc, sk_mod_q, c0, c1, pws, proof_ok, owners, flags, count);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -1,0 +1,47 @@
+// libspp C ABI, auditor side of a batch of audit records: spp_audit_open_batch.  One upload of (proofs, public witnesses,
+// ciphertexts), k_verify as spp_verify_batch runs it, then k_audit_open (kernels_witness.hip, audit_open.hpp) on the same
+// stream, one download of owners and flags.  Replaces scripts/rlwe_decrypt.py:61-149 for many records and adds what that
+// script leaves to the reader: is this ciphertext the one the proof commits to, is the decrypted identity the one it commits to.
+#include "spp_internal.hpp"
+#include "verify_key_prep.hpp"
+
+extern "C" int spp_audit_open_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint32_t* sk_mod_q, size_t count,
+                                    const uint8_t* proofs, const uint8_t* pws, const uint32_t* c0, const uint32_t* c1, uint8_t* owners,
+                                    uint32_t* flags) {
+  if (!ctx || !sk_mod_q || (count && (!pws || !c0 || !c1 || !owners || !flags))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if ((vk == nullptr) != (vk_len == 0)) return fail(SPP_ERR_BAD_INPUT, "vk and vk_len must both be given or both be absent");
+  if (vk && count && !proofs) return fail(SPP_ERR_BAD_INPUT, "NULL argument: proofs (needed with a verifying key)");
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many records in one call (%zu; at most 2^24)", count);
+  for (int i = 0; i < 1024; i++)
+    if (sk_mod_q[i] >= 167772161u) return fail(SPP_ERR_BAD_INPUT, "secret key coefficient %d not in [0, q)", i);
+  VerifyKeyPrep key;
+  if (vk) {
+    if (int e = key.parse(vk, vk_len, 0)) return e;
+    if (key.nk != 4) return fail(SPP_ERR_FORMAT, "the verifying key has %u public inputs, an audit proof has 2 (wa_commitment, ct_commitment)", key.nk - 2);
+  }
+  if (count == 0) return SPP_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  DevBuf dsk, dproofs, dpws, d0, d1, dok, downers, dflags;
+  UP(dsk, sk_mod_q, 4096);
+  UP(dpws, pws, count * (size_t)SPP_AUDIT_PW_LEN);
+  UP(d0, c0, count * 64 * 4);
+  UP(d1, c1, count * 1024 * 4);
+  HIP_TRY(downers.alloc(count * 64));
+  HIP_TRY(dflags.alloc(count * sizeof(uint32_t)));
+  if (vk) {
+    if (int e = key.upload(st)) return e;
+    UP(dproofs, proofs, count * (size_t)SPP_PROOF_LEN);
+    HIP_TRY(dok.alloc(count * sizeof(int32_t)));
+    launch_verify(st, key.dev(), dproofs.as<uint8_t>(), dpws.as<uint8_t>(), SPP_AUDIT_PW_LEN, (uint32_t)count, dok.as<int32_t>());
+  }
+  launch_audit_open(st, ctx->hc, dsk.as<uint32_t>(), d0.as<uint32_t>(), d1.as<uint32_t>(), dpws.as<uint8_t>(), vk ? dok.as<int32_t>() : nullptr,
+                    downers.as<uint8_t>(), dflags.as<uint32_t>(), (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(owners, downers.p, count * 64, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(flags, dflags.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}

@@ -8,6 +8,7 @@
 //   spp_setup.cpp        circuit construction (host only) and the trusted setup on the GPU
 //   spp_witness_api.cpp  witness-input kernels, Merkle trees, auditor side
 //   spp_verify_api.cpp   verification and pairing checks
+//   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points
 #pragma once
 #include "../../include/spp.h"
@@ -207,7 +208,8 @@ int build_generator_table(hipStream_t st, const Affine<F>& g, uint32_t c, DevBuf
 // the audit input pipeline as stream-ordered work (spp_witness_api.cpp); used by spp_prove_audit_from_secrets_device
 size_t spp_audit_scratch_bytes(size_t count);
 int spp_audit_inputs_enqueue(spp_ctx* ctx, hipStream_t st, void* scratch, const uint32_t* d_pk_a, const uint32_t* d_pk_b, uint32_t count,
-                             const uint8_t* d_sk, const int8_t* d_r, const int8_t* d_e1, const int8_t* d_e2, uint8_t* d_rows);
+                             const uint8_t* d_sk, const int8_t* d_r, const int8_t* d_e1, const int8_t* d_e2, uint8_t* d_rows, uint32_t* d_c0_out,
+                             uint32_t* d_c1_out);
 // withdraw notes (spp_witness_api.cpp): SPP_ERR_BAD_INPUT unless every field of every note is canonical
 int spp_check_notes(size_t count, const uint8_t* notes);
 // lazily built per-context constants (spp_witness_api.cpp)

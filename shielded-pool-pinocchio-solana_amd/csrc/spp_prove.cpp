@@ -241,13 +241,27 @@ extern "C" int spp_prove_batch_device(spp_circuit* c, size_t count, const void* 
   if (!tail) return SPP_OK;
   return prove_on_device(c, c->ws[c->next_ws], tail, (const uint8_t*)d_inputs + body * c->in_stride, io.at(c, body));
 }
+// rs = NULL of the host entry points: 64 bytes of OS randomness per proof
+static int os_blinding(std::vector<uint8_t>& rnd, size_t count) {
+  rnd.resize(64 * count);
+  FILE* f = fopen("/dev/urandom", "rb");
+  if (!f || fread(rnd.data(), 1, rnd.size(), f) != rnd.size()) {
+    if (f) fclose(f);
+    return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+  }
+  fclose(f);
+  return SPP_OK;
+}
 // End to end: the audit proof from the prover's raw secrets.  The input pipeline of scripts/generate_audit.py:468-641 (keygen,
 // wa_commitment, RLWE encryption, quotients, packing, ct_commitment) is enqueued on the batch's own proving stream in front of the
 // solver, into the workspace's input rows: nothing returns to the host between the secrets and the proof bytes, and the
 // pipelining of consecutive calls is that of spp_prove_batch_device.
-extern "C" int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk,
-                                                   const void* d_r, const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs,
-                                                   void* d_pws, void* d_status) {
+// d_c0 / d_c1 (both or neither): the ciphertext every proof commits to, written by the RLWE kernel of the input pipeline -- on
+// the batch's own proving stream, in front of the solver, so a refused row has its ciphertext like any other.  *stream
+// (optional): the proving stream the batch went to.
+static int prove_audit_from_secrets(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk, const void* d_r,
+                                    const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs, void* d_pws, void* d_status,
+                                    void* d_c0, void* d_c1, hipStream_t* stream = nullptr) {
   if (!c || !d_pk_a || !d_pk_b || !d_sk || !d_r || !d_e1 || !d_e2 || !d_rs || !d_proofs || !d_pws || !d_status)
     return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   if (c->circ.id != SPP_CIRCUIT_AUDIT || c->circ.n_inputs() != 3360) return fail(SPP_ERR_BAD_INPUT, "not the audit circuit");
@@ -259,6 +273,7 @@ extern "C" int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count,
   Workspace* wp;
   if (int e = take_sized_workspace(c, count, false, &wp)) return e;
   Workspace& w = *wp;
+  if (stream) *stream = w.st;
   const size_t need = spp_audit_scratch_bytes(count);
   if (need > w.audit_scratch_cap) {
     HIP_TRY(hipStreamSynchronize(w.st));
@@ -269,10 +284,106 @@ extern "C" int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count,
     w.audit_scratch_cap = need;
   }
   if (int e = spp_audit_inputs_enqueue(c->ctx, w.st, w.audit_scratch, (const uint32_t*)d_pk_a, (const uint32_t*)d_pk_b, (uint32_t)count,
-                                       (const uint8_t*)d_sk, (const int8_t*)d_r, (const int8_t*)d_e1, (const int8_t*)d_e2, w.d_inputs))
+                                       (const uint8_t*)d_sk, (const int8_t*)d_r, (const int8_t*)d_e1, (const int8_t*)d_e2, w.d_inputs, (uint32_t*)d_c0,
+                                       (uint32_t*)d_c1))
     return e;
   // one piece, no cut into body and tail (batch_tail): the cut would change which kernels a 2 049-proof audit batch runs
   return prove_on_device(c, w, count, w.d_inputs, BatchIO{(const uint8_t*)d_rs, (uint8_t*)d_proofs, (uint8_t*)d_pws, (uint32_t*)d_status});
+}
+extern "C" int spp_prove_audit_from_secrets_device(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk,
+                                                   const void* d_r, const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs,
+                                                   void* d_pws, void* d_status) {
+  return prove_audit_from_secrets(c, count, d_pk_a, d_pk_b, d_sk, d_r, d_e1, d_e2, d_rs, d_proofs, d_pws, d_status, nullptr, nullptr);
+}
+// The same with the record's third part: the ciphertext (generate_audit.py:590-606 writes it next to the proof).
+extern "C" int spp_prove_audit_records_device(spp_circuit* c, size_t count, const void* d_pk_a, const void* d_pk_b, const void* d_sk,
+                                              const void* d_r, const void* d_e1, const void* d_e2, const void* d_rs, void* d_proofs, void* d_pws,
+                                              void* d_status, void* d_c0, void* d_c1) {
+  if (!d_c0 || !d_c1) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  return prove_audit_from_secrets(c, count, d_pk_a, d_pk_b, d_sk, d_r, d_e1, d_e2, d_rs, d_proofs, d_pws, d_status, d_c0, d_c1);
+}
+// Host form: chunks of at most 2 048 records take turns on two sets of device buffers, so the uploads of chunk k + 1 and the
+// input pipeline in front of its solver overlap the MSMs of chunk k; the results of chunk k are fetched once chunk k + 1 is
+// enqueued (as spp_prove_batch does).  status and the zeroing of refused proofs follow spp_prove_batch.
+extern "C" int spp_prove_audit_records(spp_circuit* c, const uint32_t* pk_a, const uint32_t* pk_b, size_t count, const uint8_t* sk,
+                                       const int8_t* r, const int8_t* e1, const int8_t* e2, const uint8_t* rs, uint8_t* proofs, uint8_t* pws,
+                                       int32_t* status, uint32_t* c0, uint32_t* c1) {
+  if (!c || !pk_a || !pk_b || !sk || !r || !e1 || !e2 || !proofs || !pws || !c0 || !c1) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (c->circ.id != SPP_CIRCUIT_AUDIT || c->circ.n_inputs() != 3360) return fail(SPP_ERR_BAD_INPUT, "not the audit circuit");
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many records in one call");
+  for (int i = 0; i < 1024; i++)
+    if (pk_a[i] >= 167772161u || pk_b[i] >= 167772161u) return fail(SPP_ERR_BAD_INPUT, "public key coefficient not in [0, q)");
+  std::vector<uint8_t> rnd;
+  if (!rs) {
+    if (int e = os_blinding(rnd, count)) return e;
+    rs = rnd.data();
+  }
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  const size_t chunk = std::min<size_t>(count, 2048), pwl = c->pw_stride;
+  struct CopyStream {   // the copies of this call, beside whatever else runs on the context; the proving streams are the library's
+    hipStream_t s = nullptr;
+    ~CopyStream() { if (s) hipStreamDestroy(s); }
+  } copy;
+  HIP_TRY(hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
+  hipStream_t st = copy.s;
+  struct Set {
+    DevBuf sk, r, e1, e2, rs, proofs, pws, status, c0, c1;
+    hipStream_t proving = nullptr;
+    size_t off = 0, n = 0;
+  } sets[2];
+  DevBuf da, db;
+  UP(da, pk_a, 4096);
+  UP(db, pk_b, 4096);
+  for (Set& s : sets) {
+    HIP_TRY(s.sk.alloc(chunk * 32)); HIP_TRY(s.r.alloc(chunk * 1024)); HIP_TRY(s.e1.alloc(chunk * 64)); HIP_TRY(s.e2.alloc(chunk * 1024));
+    HIP_TRY(s.rs.alloc(chunk * 64)); HIP_TRY(s.proofs.alloc(chunk * SPP_PROOF_LEN)); HIP_TRY(s.pws.alloc(chunk * pwl));
+    HIP_TRY(s.status.alloc(chunk * 4)); HIP_TRY(s.c0.alloc(chunk * 64 * 4)); HIP_TRY(s.c1.alloc(chunk * 1024 * 4));
+    if (count <= chunk) break;       // one chunk: one set
+  }
+  std::vector<uint32_t> stat(count);
+  auto fetch = [&](Set& s) -> int {
+    HIP_TRY(hipStreamSynchronize(s.proving));
+    HIP_TRY(hipMemcpyAsync(proofs + (size_t)SPP_PROOF_LEN * s.off, s.proofs.p, (size_t)SPP_PROOF_LEN * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pws + pwl * s.off, s.pws.p, pwl * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stat.data() + s.off, s.status.p, 4 * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c0 + 64 * s.off, s.c0.p, 64 * 4 * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c1 + 1024 * s.off, s.c1.p, 1024 * 4 * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s.n = 0;
+    return 0;
+  };
+  int k = 0;
+  for (size_t off = 0; off < count; off += chunk, k ^= 1) {
+    Set& s = sets[k];
+    if (s.n)
+      if (int e = fetch(s)) return e;
+    const size_t n = std::min(chunk, count - off);
+    HIP_TRY(hipMemcpyAsync(s.sk.p, sk + 32 * off, 32 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.r.p, r + 1024 * off, 1024 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.e1.p, e1 + 64 * off, 64 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.e2.p, e2 + 1024 * off, 1024 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.rs.p, rs + 64 * off, 64 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s.off = off;
+    s.n = n;
+    if (int e = prove_audit_from_secrets(c, n, da.p, db.p, s.sk.p, s.r.p, s.e1.p, s.e2.p, s.rs.p, s.proofs.p, s.pws.p, s.status.p, s.c0.p, s.c1.p,
+                                         &s.proving))
+      return e;
+  }
+  for (int j = 0; j < 2; j++) {      // the older chunk first
+    Set& s = sets[k ^ j];
+    if (s.n)
+      if (int e = fetch(s)) return e;
+  }
+  int rc = SPP_OK;
+  for (size_t i = 0; i < count; i++) {
+    const int32_t v = stat[i] ? SPP_ERR_UNSAT : SPP_OK;
+    if (status) status[i] = v;
+    if (v && rc == SPP_OK) rc = fail(SPP_ERR_UNSAT, "record %zu: inputs do not satisfy the circuit", i);
+    if (v) memset(proofs + (size_t)SPP_PROOF_LEN * i, 0, SPP_PROOF_LEN);
+  }
+  return rc;
 }
 // Withdraw proofs from notes against the resident tree (include/spp.h).  The rows are gathered on the TREE's stream (ctx->stream),
 // not on the proving stream: spp_merkle_tree_insert runs there and may reallocate the level arrays (mt_reserve), so an insert
@@ -427,13 +538,7 @@ extern "C" int spp_prove_batch(spp_circuit* c, size_t count, const uint8_t* inpu
   if (count == 0) return SPP_OK;
   std::vector<uint8_t> rnd;
   if (!rs) {
-    rnd.resize(64 * count);
-    FILE* f = fopen("/dev/urandom", "rb");
-    if (!f || fread(rnd.data(), 1, rnd.size(), f) != rnd.size()) {
-      if (f) fclose(f);
-      return fail(SPP_ERR_IO, "cannot read /dev/urandom");
-    }
-    fclose(f);
+    if (int e = os_blinding(rnd, count)) return e;
     rs = rnd.data();
   }
   std::vector<uint32_t> st(count);

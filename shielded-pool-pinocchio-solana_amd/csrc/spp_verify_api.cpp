@@ -1,6 +1,7 @@
 // libspp C ABI, verification: `sunspot verify` on the host (spp_verify), the batched GPU verifier (spp_verify_batch) and the
 // pairing-product checks that pin the pairing code to the reference's gnark-made verifying keys.
 #include "spp_internal.hpp"
+#include "verify_key_prep.hpp"
 
 // -----------------------------------------------------------------------------------------------------
 // verification (host): `sunspot verify <vk> <proof> <pw>`
@@ -68,43 +69,14 @@ extern "C" int spp_verify_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, 
   if (kernel_ms) *kernel_ms = 0;
   if (count == 0) return SPP_OK;
   if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "count too large");
-  auto be32 = [](const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; };
-  if (vk_len < 576 + 4) return fail(SPP_ERR_FORMAT, "verifying key too short");
-  const uint32_t nk = be32(vk + 576);
-  size_t off = 580;
-  if (nk < 2 || vk_len != off + (size_t)nk * 64 + 12 + 256) return fail(SPP_ERR_FORMAT, "verifying key has the wrong length");
-  if (pw_len != 12 + 32 * (size_t)(nk - 2)) return fail(SPP_ERR_FORMAT, "public witness length does not match the verifying key");
-  const G1Affine alpha1 = g1_from_raw(vk);
-  const G2Affine beta2 = g2_from_raw(vk + 128), gamma2 = g2_from_raw(vk + 256), delta2 = g2_from_raw(vk + 448);
-  std::vector<G1Affine> K(nk);
-  for (uint32_t i = 0; i < nk; i++) K[i] = g1_from_raw(vk + off + 64 * (size_t)i);
-  off += (size_t)nk * 64;
-  if (be32(vk + off) != 1 || be32(vk + off + 4) != 0 || be32(vk + off + 8) != 1) return fail(SPP_ERR_FORMAT, "unsupported commitment layout");
-  const G2Affine pedG = g2_from_raw(vk + off + 12), pedGS = g2_from_raw(vk + off + 12 + 128);
-  for (const G2Affine* q : {&beta2, &gamma2, &delta2, &pedG, &pedGS})
-    if (q->is_inf() || !g2_on_curve(*q)) return fail(SPP_ERR_FORMAT, "verifying key holds an invalid G2 point");
-  if (!pairing_fast_consts_consistent()) return fail(SPP_ERR_HIP, "internal: Frobenius constants are not two-term");
+  VerifyKeyPrep key;
+  if (int e = key.parse(vk, vk_len, pw_len)) return e;
 
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  // per-key preparation on the host: line tables of the four key-side G2 points, e(-alpha, beta), constants
-  VerifyKeyDev h;
-  h.pc = make_pairing_fast_consts();
-  h.e_alpha_beta = f12_from(miller_loop(alpha1.neg(), beta2));
-  h.twist_b = twist_b();
-  h.nk = nk;
-  DevBuf dtab[4], dK, dvk, dproofs, dpws, dok;
-  const G2Affine* qs[4] = {&gamma2, &delta2, &pedG, &pedGS};
-  std::vector<LineStep> tabs_host[4];   // stay alive until the stream has been synchronised
-  for (int k = 0; k < 4; k++) {
-    tabs_host[k] = build_line_table(*qs[k]);
-    UP(dtab[k], tabs_host[k].data(), tabs_host[k].size() * sizeof(LineStep));
-    h.tab[k] = dtab[k].as<LineStep>();
-  }
-  UP(dK, K.data(), K.size() * sizeof(G1Affine));
-  h.K = dK.as<G1Affine>();
-  UP(dvk, &h, sizeof h);
+  if (int e = key.upload(st)) return e;
+  DevBuf dproofs, dpws, dok;
   UP(dproofs, proofs, count * (size_t)SPP_PROOF_LEN);
   UP(dpws, pws, count * pw_len);
   HIP_TRY(dok.alloc(count * sizeof(int32_t)));
@@ -116,7 +88,7 @@ extern "C" int spp_verify_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, 
   HIP_TRY(hipEventCreate(&ev1.e));
   hipEvent_t e0 = ev0.e, e1 = ev1.e;
   hipEventRecord(e0, st);
-  launch_verify(st, dvk.as<VerifyKeyDev>(), dproofs.as<uint8_t>(), dpws.as<uint8_t>(), (uint32_t)pw_len, (uint32_t)count, dok.as<int32_t>());
+  launch_verify(st, key.dev(), dproofs.as<uint8_t>(), dpws.as<uint8_t>(), (uint32_t)pw_len, (uint32_t)count, dok.as<int32_t>());
   hipEventRecord(e1, st);
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());

@@ -477,9 +477,11 @@ size_t spp_audit_scratch_bytes(size_t count) {
 }
 // Enqueues the whole input pipeline of scripts/generate_audit.py:468-641 on `st` (no synchronisation): the rows are complete
 // for whatever is enqueued on `st` next.  scratch: spp_audit_scratch_bytes(count) bytes of device memory that stay untouched
-// until those kernels have run.
+// until those kernels have run.  d_c0_out / d_c1_out (optional, count * 64 / count * 1024 u32): the ciphertext c0 / c1 of every
+// instance (generate_audit.py:590-606), written by the RLWE kernel itself.
 int spp_audit_inputs_enqueue(spp_ctx* ctx, hipStream_t st, void* scratch, const uint32_t* d_pk_a, const uint32_t* d_pk_b, uint32_t count,
-                             const uint8_t* d_sk, const int8_t* d_r, const int8_t* d_e1, const int8_t* d_e2, uint8_t* d_rows) {
+                             const uint8_t* d_sk, const int8_t* d_r, const int8_t* d_e1, const int8_t* d_e2, uint8_t* d_rows, uint32_t* d_c0_out,
+                             uint32_t* d_c1_out) {
   ScratchPiece xy, msg, c0, c1, k0, k1, packed, ct, wa, pkhat;
   {
     size_t sizes[AUDIT_PIECES], off = 0;
@@ -493,6 +495,10 @@ int spp_audit_inputs_enqueue(spp_ctx* ctx, hipStream_t st, void* scratch, const 
   if (int e = spp_ensure_rlwe(ctx)) return e;
   RlweDev rd = ctx->rlwe;
   rd.pk = pkhat.as<RlwePkDev>();   // the transformed public key of THIS call (calls in flight on other streams may use other keys)
+  // the ciphertext is read by nothing after the RLWE kernel (the rows take the packed form): a caller that wants it gets it
+  // written in place of the scratch pieces, at no extra traffic
+  if (d_c0_out) c0.p = d_c0_out;
+  if (d_c1_out) c1.p = d_c1_out;
   launch_grumpkin_keygen(st, ctx->gk_table, d_sk, xy.as<uint8_t>(), count);                       // generate_audit.py:482
   launch_poseidon_hash(st, ctx->hc, xy.as<uint8_t>(), 2, wa.as<uint8_t>(), count);                 // wa_commitment
   launch_audit_msg(st, xy.as<uint8_t>(), msg.as<uint8_t>(), count);                                // :489-496
@@ -515,7 +521,7 @@ static int audit_inputs_on_device(spp_ctx* ctx, const uint32_t* d_pk_a, const ui
     HIP_TRY(hipMalloc(&ctx->audit_scratch, total));
     ctx->audit_scratch_cap = total;
   }
-  if (int e = spp_audit_inputs_enqueue(ctx, st, ctx->audit_scratch, d_pk_a, d_pk_b, count, d_sk, d_r, d_e1, d_e2, d_rows)) return e;
+  if (int e = spp_audit_inputs_enqueue(ctx, st, ctx->audit_scratch, d_pk_a, d_pk_b, count, d_sk, d_r, d_e1, d_e2, d_rows, nullptr, nullptr)) return e;
   HIP_TRY(hipStreamSynchronize(st));   // the rows are complete when the call returns (the caller hands them to a proving stream)
   HIP_TRY(hipGetLastError());
   return SPP_OK;

@@ -8,6 +8,10 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                                                                                                   #    skipped when the keys match the circuit)
     python -m spp.cli prove   target/<name>.sppc target/<name>.pk Prover.toml                    # -> <name>.proof, <name>.pw
     python -m spp.cli verify  target/<name>.vk target/<name>.proof target/<name>.pw              # exit 0 / 1
+    python -m spp.cli audit-open target/<name>.vk|- <name>.proof <name>.pw ciphertext.json --shares share_1.json share_2.json
+                              # the auditor's `python scripts/rlwe_decrypt.py`: reconstructs the key from the shares, verifies the
+                              # proof (`-`: already verified elsewhere), checks that the ciphertext is the one the proof commits
+                              # to and that it decrypts to the identity the proof commits to; exit 0 only if all three hold
     python -m spp.cli execute target/<name>.json Prover.toml [-o target/<name>.gz]               # `nargo execute`: ACIR witness stack
     python -m spp.cli prove   target/<name>.json target/<name>.gz target/<name>.sppc target/<name>.pk
                               # sunspot's own argument order (acir, witness, constraint system, proving key;
@@ -63,6 +67,36 @@ def input_vector(vals):
     return lib.SPP_CIRCUIT_AUDIT, [v % R for v in row]
 
 
+def _audit_open(a):
+    from . import witness
+    try:   # everything that can be wrong with the files is found before a device is opened
+        shares = [witness.load_share_json(p) for p in a.shares]
+        if len({s["x"] for s in shares}) != len(shares) or len(shares) < max(s["threshold"] for s in shares):
+            raise ValueError("need %d shares with distinct indices, got %d" % (max(s["threshold"] for s in shares), len(shares)))
+        c0, c1, claimed = witness.load_ciphertext_json(a.ciphertext)
+        vk = None if a.vk == "-" else open(a.vk, "rb").read()
+        proof, pw = open(a.proof, "rb").read(), open(a.pw, "rb").read()
+        if len(proof) != lib.PROOF_LEN or len(pw) != lib.AUDIT_PW_LEN:
+            raise ValueError("an audit record is a proof of %d bytes and a public witness of %d" % (lib.PROOF_LEN, lib.AUDIT_PW_LEN))
+    except (OSError, ValueError) as e:
+        print("spp audit-open: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        sk = witness.reconstruct_sk(ctx, shares)
+        owners, flags = ctx.audit_open(vk, sk, [proof], [pw], [c0], [c1])
+    finally:
+        ctx.close()
+    f = flags[0]
+    print("owner_x = 0x%064x\nowner_y = 0x%064x" % owners[0])
+    print("proof: %s" % ("not checked" if vk is None else "FAILED" if f & lib.SPP_AUDIT_BAD_PROOF else "verified"))
+    print("ciphertext: %s" % ("NOT the one the proof commits to" if f & lib.SPP_AUDIT_BAD_CIPHERTEXT else "bound to the proof (ct_commitment)"))
+    print("identity: %s" % ("NOT the one the proof commits to" if f & lib.SPP_AUDIT_BAD_IDENTITY else "bound to the proof (wa_commitment)"))
+    if claimed is not None and claimed != owners[0]:
+        print("note: the prover's expected_owner differs from the decrypted owner")
+    return 0 if f == 0 else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="spp")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -77,7 +111,13 @@ def main(argv=None):
                    help="blinding factors (parity runs only: the default draws fresh ones from the OS, as every real proof must)")
     x = sub.add_parser("execute"); x.add_argument("acir"); x.add_argument("toml"); x.add_argument("-o", "--out", default=None)
     v = sub.add_parser("verify"); v.add_argument("vk"); v.add_argument("proof"); v.add_argument("pw")
+    o = sub.add_parser("audit-open"); o.add_argument("vk", help="verifying key, or - for a record already verified elsewhere")
+    o.add_argument("proof"); o.add_argument("pw"); o.add_argument("ciphertext", help="ciphertext.json (scripts/generate_audit.py:590-606)")
+    o.add_argument("--shares", nargs="+", required=True, metavar="SHARE.json", help="threshold many share files (scripts/rlwe_keygen.py)")
+    o.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.cmd == "audit-open":
+        return _audit_open(a)
     if a.cmd == "compile" and a.circuit.endswith(".ccs"):
         from . import ccs
         c = ccs.load_ccs(a.circuit)

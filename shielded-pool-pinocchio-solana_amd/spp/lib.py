@@ -15,6 +15,11 @@ SPP_CIRCUIT_WITHDRAW_REFSHAPE = 3   # build only: withdraw padded to the referen
 PROOF_LEN = 388
 NOTE_LEN = 160                      # withdraw note: recipient | amount | secret_key | randomness | index
 DEPOSIT_LEN = 96                    # deposit: secret_key | amount | randomness
+AUDIT_PW_LEN = 76                   # audit public witness: header | wa_commitment | ct_commitment
+# spp_audit_open_batch: bits of flags[i] (include/spp.h)
+SPP_AUDIT_BAD_PROOF = 1
+SPP_AUDIT_BAD_CIPHERTEXT = 2
+SPP_AUDIT_BAD_IDENTITY = 4
 
 
 class SppError(RuntimeError):
@@ -99,6 +104,9 @@ def load_library():
     L.spp_audit_inputs_batch.argtypes = [vp, vp, vp, sz, cp, vp, vp, vp, vp]
     L.spp_audit_inputs_batch_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.spp_prove_audit_from_secrets_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.spp_prove_audit_records_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.spp_prove_audit_records.argtypes = [vp, vp, vp, sz, cp, vp, vp, vp, cp, vp, vp, vp, vp, vp]
+    L.spp_audit_open_batch.argtypes = [vp, cp, sz, vp, sz, cp, cp, vp, vp, vp, vp]
     L.spp_withdraw_rows_from_tree.argtypes = [vp, sz, cp, vp]
     L.spp_prove_withdraw_notes_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     L.spp_prove_withdraw_notes.argtypes = [vp, vp, sz, cp, cp, vp, vp, vp]

@@ -1,6 +1,7 @@
 """Thin object layer over the C ABI: Context (one GPU), CircuitHandle (R1CS + pk + tables in HBM)."""
 import ctypes
-from .lib import load_library, check, SppError, PROOF_LEN, SPP_ERR_UNSAT
+import numpy as np
+from .lib import load_library, check, SppError, PROOF_LEN, SPP_ERR_UNSAT, AUDIT_PW_LEN
 
 
 def build_circuit(circuit_id, out_path, aux=None):
@@ -116,6 +117,29 @@ class Context:
         res = [bool(ok[i]) for i in range(count)]
         return (res, ms.value) if want_ms else res
 
+    def audit_open(self, vk, sk_mod_q, proofs, pws, c0, c1):
+        """Opens audit records in one pass on the GPU (spp_audit_open_batch): verification, ciphertext binding, decryption,
+        identity binding.  vk: bytes, or None for records already verified elsewhere (proofs may then be None); sk_mod_q: 1024
+        ints (witness.reconstruct_sk); proofs / pws: lists of bytes (or one bytes object each); c0 [count, 64], c1 [count, 1024].
+        Returns (owners, flags): owners[i] = (owner_x, owner_y) as decrypted, flags[i] = SPP_AUDIT_* bits, 0 = all three hold."""
+        c0 = np.ascontiguousarray(c0, dtype=np.uint32).reshape(-1, 64)
+        count = c0.shape[0]
+        c1 = np.ascontiguousarray(c1, dtype=np.uint32).reshape(count, 1024)
+        sk = np.ascontiguousarray(sk_mod_q, dtype=np.uint32)
+        if sk.shape != (1024,):
+            raise ValueError("sk_mod_q must hold 1024 coefficients")
+        join = lambda v: None if v is None else (bytes(v) if isinstance(v, (bytes, bytearray)) else b"".join(v))
+        pb, wb = join(proofs), join(pws)
+        if wb is None or len(wb) != AUDIT_PW_LEN * count or (pb is not None and len(pb) != PROOF_LEN * count):
+            raise ValueError("audit_open: %d ciphertexts need %d public witnesses of %d bytes (and as many proofs of %d)"
+                             % (count, count, AUDIT_PW_LEN, PROOF_LEN))
+        owners = np.zeros((max(count, 1), 64), dtype=np.uint8)
+        flags = np.zeros(max(count, 1), dtype=np.uint32)
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        check(self.L.spp_audit_open_batch(self.h, vk, len(vk) if vk is not None else 0, p(sk), count, pb, wb, p(c0), p(c1), p(owners), p(flags)))
+        return ([(int.from_bytes(owners[i, :32].tobytes(), "big"), int.from_bytes(owners[i, 32:].tobytes(), "big")) for i in range(count)],
+                [int(f) for f in flags[:count]])
+
     def msm_g1_pippenger_bench(self, n, seed=5, scale=None, iters=1, small_permille=0):
         """Returns (result bytes, ms per MSM, ms of the bucket kernel). small_permille: share of byte-sized scalars."""
         out = ctypes.create_string_buffer(64)
@@ -224,6 +248,42 @@ class CircuitHandle:
         """Audit proofs from (secret_key, r, e1, e2) resident on the device (spp_prove_audit_from_secrets_device): the input pipeline of
         scripts/generate_audit.py:468-641 runs on the proving stream in front of the solver.  Raw device pointers (ints)."""
         check(self.L.spp_prove_audit_from_secrets_device(self.h, count, d_pk_a, d_pk_b, d_sk, d_r, d_e1, d_e2, d_rs, d_proofs, d_pws, d_status))
+
+    def prove_audit_records_device(self, count, d_pk_a, d_pk_b, d_sk, d_r, d_e1, d_e2, d_rs, d_proofs, d_pws, d_status, d_c0, d_c1):
+        """prove_audit_from_secrets_device plus the ciphertext each proof commits to (spp_prove_audit_records_device): d_c0
+        count*64 u32, d_c1 count*1024 u32, written on the batch's proving stream.  Raw device pointers (ints)."""
+        check(self.L.spp_prove_audit_records_device(self.h, count, d_pk_a, d_pk_b, d_sk, d_r, d_e1, d_e2, d_rs, d_proofs, d_pws, d_status,
+                                                    d_c0, d_c1))
+
+    def prove_audit_records(self, pk_a, pk_b, sks, r, e1, e2, rs=None):
+        """Audit records from the provers' secrets, host buffers (spp_prove_audit_records): sks list of ints, r / e2 [count, 1024]
+        and e1 [count, 64] int8, rs list of (r, s) ints or None (OS randomness).  Returns (proofs, pws, status, c0, c1): lists of
+        bytes, status[i] == 0 or SPP_ERR_UNSAT, c0 [count, 64] / c1 [count, 1024] uint32 -- the ciphertext.json of each proof
+        (spp.witness.ciphertext_json)."""
+        count = len(sks)
+        r = np.ascontiguousarray(r, dtype=np.int8).reshape(count, 1024)
+        e1 = np.ascontiguousarray(e1, dtype=np.int8).reshape(count, 64)
+        e2 = np.ascontiguousarray(e2, dtype=np.int8).reshape(count, 1024)
+        a = np.ascontiguousarray(pk_a, dtype=np.uint32)
+        b = np.ascontiguousarray(pk_b, dtype=np.uint32)
+        if a.shape != (1024,) or b.shape != (1024,):
+            raise ValueError("the public key is two polynomials of 1024 coefficients")
+        skb = b"".join(int(v).to_bytes(32, "big") for v in sks)
+        rsb = None
+        if rs is not None:
+            rsb = b"".join(int(x).to_bytes(32, "big") + int(y).to_bytes(32, "big") for x, y in rs)
+        proofs = ctypes.create_string_buffer(PROOF_LEN * max(count, 1))
+        pws = ctypes.create_string_buffer(self.pw_len * max(count, 1))
+        status = (ctypes.c_int32 * max(count, 1))()
+        c0 = np.zeros((count, 64), dtype=np.uint32)
+        c1 = np.zeros((count, 1024), dtype=np.uint32)
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        rc = self.L.spp_prove_audit_records(self.h, p(a), p(b), count, skb, p(r), p(e1), p(e2), rsb, ctypes.cast(proofs, ctypes.c_void_p),
+                                            ctypes.cast(pws, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p), p(c0), p(c1))
+        if rc != 0 and rc != SPP_ERR_UNSAT:
+            check(rc)
+        return ([proofs.raw[PROOF_LEN * i:PROOF_LEN * (i + 1)] for i in range(count)],
+                [pws.raw[self.pw_len * i:self.pw_len * (i + 1)] for i in range(count)], list(status)[:count], c0, c1)
 
     def prove_withdraw_notes(self, tree, notes, rs=None):
         """Withdraw proofs from notes (spp.witness.pack_withdraw_notes tuples) against the resident tree `tree`

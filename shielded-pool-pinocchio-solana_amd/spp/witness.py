@@ -9,6 +9,8 @@
     pack_deposits(...)       the three values a depositor supplies, for ShieldedPoolMerkleTree.deposit
     deposit_instruction_data shielded_pool_program/src/instructions/deposit.rs:21-37
     ct_commitment(...)       ct_helper/src/main.nr:15-34
+    ciphertext_json(...)     scripts/generate_audit.py:590-606 (keys/ciphertext.json, what the prover leaves for the auditor)
+    load_share_json(...)     scripts/rlwe_keygen.py:157-171 (keys/rlwe_sk_shares/share_<i>.json)
 All of them take and return Python ints / lists; field elements cross the C ABI as 32-byte big-endian.
 """
 import ctypes
@@ -274,3 +276,66 @@ def rlwe_decrypt(ctx, sk_mod_q, c0, c1):
     check(ctx.L.spp_rlwe_decrypt_batch(ctx.h, p(sk), count, p(c0), p(c1), p(msg)))
     owners = [(int.from_bytes(msg[i, :32].tobytes(), "little"), int.from_bytes(msg[i, 32:].tobytes(), "little")) for i in range(count)]
     return owners, msg
+
+
+# ---- the files the prover and the key holders leave for the auditor ----
+RLWE_Q = 167772161
+CIPHERTEXT_KEYS = ("c0_sparse", "c1", "c0_packed", "c1_packed", "pack_width", "pack_bits", "msg_slots", "q", "delta",
+                   "expected_owner_x", "expected_owner_y")
+
+
+def _pack7(values):
+    return [sum(int(c) << (32 * j) for j, c in enumerate(values[i:i + 7])) for i in range(0, len(values), 7)]
+
+
+def ciphertext_json(c0, c1, owner=None):
+    """The dict scripts/generate_audit.py:593-605 dumps as keys/ciphertext.json, for one ciphertext (c0: 64 and c1: 1024
+    coefficients in [0, q), e.g. a row of CircuitHandle.prove_audit_records).  owner: (owner_x, owner_y) the prover expects, or
+    None -- the two expected_owner_* keys are then null: an auditor checks the identity against wa_commitment (Context.audit_open),
+    not against what the prover claims."""
+    c0, c1 = [int(v) for v in c0], [int(v) for v in c1]
+    if len(c0) != MSG_SLOTS or len(c1) != RLWE_N or not all(0 <= v < RLWE_Q for v in c0 + c1):
+        raise ValueError("a ciphertext is 64 + 1024 coefficients in [0, q)")
+    return {"c0_sparse": c0, "c1": c1, "c0_packed": [hex(v) for v in _pack7(c0)], "c1_packed": [hex(v) for v in _pack7(c1)],
+            "pack_width": 7, "pack_bits": 32, "msg_slots": MSG_SLOTS, "q": RLWE_Q, "delta": RLWE_Q // 256,
+            "expected_owner_x": None if owner is None else hex(int(owner[0])),
+            "expected_owner_y": None if owner is None else hex(int(owner[1]))}
+
+
+def load_ciphertext_json(path):
+    """Reads a ciphertext.json (the reference's or ciphertext_json's): returns (c0, c1, owner) with owner = (x, y) or None.  Raises
+    ValueError when the file is not one: missing keys, other parameters than the circuit's, wrong lengths, packed fields that are
+    not the packing of the coefficients."""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    if not isinstance(d, dict) or set(CIPHERTEXT_KEYS) - set(d):
+        raise ValueError("%s: not a ciphertext.json (keys %s)" % (path, ", ".join(CIPHERTEXT_KEYS)))
+    if (d["pack_width"], d["pack_bits"], d["msg_slots"], d["q"], d["delta"]) != (7, 32, MSG_SLOTS, RLWE_Q, RLWE_Q // 256):
+        raise ValueError("%s: parameters differ from the audit circuit's" % path)
+    c0, c1 = [int(v) for v in d["c0_sparse"]], [int(v) for v in d["c1"]]
+    if len(c0) != MSG_SLOTS or len(c1) != RLWE_N or not all(0 <= v < 1 << 32 for v in c0 + c1):
+        raise ValueError("%s: a ciphertext is 64 + 1024 32-bit coefficients" % path)
+    if [int(v, 16) for v in d["c0_packed"]] != _pack7(c0) or [int(v, 16) for v in d["c1_packed"]] != _pack7(c1):
+        raise ValueError("%s: the packed fields are not the packing of the coefficients" % path)
+    ox, oy = d["expected_owner_x"], d["expected_owner_y"]
+    owner = None if ox is None or oy is None else (int(ox, 16), int(oy, 16))
+    return c0, c1, owner
+
+
+def load_share_json(path):
+    """Reads one Shamir share file of scripts/rlwe_keygen.py:157-171 ({"share_index", "threshold", "num_shares", "coefficients":
+    [{"x", "y": hex}] * 1024}) into the form reconstruct_sk takes: {"x", "y": [int] * 1024, "share_index", "threshold"}."""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    try:
+        co = d["coefficients"]
+        xs = {int(c["x"]) for c in co}
+        ys = [int(c["y"], 16) if isinstance(c["y"], str) else int(c["y"]) for c in co]
+        out = {"x": xs.pop(), "y": ys, "share_index": int(d["share_index"]), "threshold": int(d["threshold"])}
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError("%s: not a share file (%s)" % (path, e))
+    if xs or len(ys) != RLWE_N or not all(0 <= v < FR_MODULUS for v in ys) or out["x"] <= 0:
+        raise ValueError("%s: a share is 1024 field elements at one nonzero x" % path)
+    return out
