@@ -25,6 +25,12 @@
  *                             (proof, public witness, ciphertext) from the prover's raw secrets
  *   spp_audit_open_batch      scripts/rlwe_decrypt.py:61-149 for a batch of such records, after `sunspot verify`
  *                             (audit_circuit/prove_audit.sh:98-99) and with the two binding checks the script leaves out
+ *   spp_pool_*                the pool program's state and decisions, shielded_pool_program/src: ShieldedPoolState and its root ring
+ *                             (state.rs:6-46, instructions/initialize.rs:65-69), process_submit_audit
+ *                             (instructions/submit_audit.rs:41-87) and process_withdraw (instructions/withdraw.rs:94-175) for a
+ *                             batch of instructions in order -- what the relayer sends without any pre-check
+ *                             (demo-frontend/app/api/relay/withdraw/route.ts:224-276)
+ *   spp_pool_add_roots        state.add_root (state.rs:28-33) for the new_root of every deposit (instructions/deposit.rs:21-37)
  *   spp_msm_g1(_pippenger) / spp_ntt_fr   micro-benchmark entry points (BASELINE.json configs[4]); no reference equivalent
  *
  * Conventions: field elements cross the boundary as 32-byte big-endian canonical integers (the encoding
@@ -353,6 +359,68 @@ int spp_rlwe_decrypt_batch(spp_ctx* ctx, const uint32_t* sk_mod_q, size_t count,
  * public-input count is not 2 (SPP_ERR_FORMAT).  count == 0 is SPP_OK. */
 int spp_audit_open_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint32_t* sk_mod_q, size_t count, const uint8_t* proofs,
                          const uint8_t* pws, const uint32_t* c0, const uint32_t* c1, uint8_t* owners, uint32_t* flags);
+
+/* ---- the pool ledger: which of these proofs would the pool accept? ---- */
+/* A device-resident restatement of the state the pool program decides on (shielded_pool_program/src): ShieldedPoolState's root ring
+ * (state.rs:6-46; fresh = all zero, instructions/initialize.rs:65-69, so on a fresh pool an all-zero root passes check_root, as it
+ * does in the program) and the two sets of accounts whose existence the program tests -- spent nullifiers, the ["nullifier", n] PDAs,
+ * and audit records, the ["audit", wa_commitment] PDAs.  Keys are the 32 raw bytes of the public-witness word, compared bytewise:
+ * v and v + r are different keys, as they are different PDAs.  Each set is an open-addressing table in HBM with a power-of-two slot
+ * count >= 2 x capacity (capacity: keys per set, fixed at creation); the slot of a key is the low 64 bits of the key mixed with a
+ * per-pool 64-bit salt, from OS randomness unless env SPP_POOL_SALT (hex) is set.  Both verifying keys are prepared once and stay
+ * resident; the withdraw key must have 5 public inputs and the audit key 2 (else SPP_ERR_FORMAT).
+ *
+ * The two batch calls settle instructions 0..count-1 WITH THE DECISIONS THE PROGRAM MAKES PROCESSING THEM ONE AFTER ANOTHER on the
+ * state as it stood at the call: each instruction reports the first check that fails, in program order, and an instruction that
+ * succeeds creates its account for the ones after it -- inside the batch too.  Duplicates inside a batch are resolved in parallel
+ * on the device (csrc/pool_table.hpp has the argument); the results do not depend on scheduling.  "The proof verifies" is the
+ * decision of spp_verify / spp_verify_batch, the 12-byte witness header included.
+ * This is a pre-screen and a replay tool; it does not replace the on-chain program.  NOT modelled: the vault balance and the lamport
+ * transfers (withdraw.rs:199-228) -- `amounts` is returned so that a caller can model them -- and signer / writability / program-id
+ * checks on the accounts of a transaction (withdraw.rs:21-59, submit_audit.rs:24-39).
+ * All buffers are host memory, all calls synchronous and serialised with the other calls on the pool's spp_ctx.  The return value
+ * is an error only for refused calls and HIP failures, never because instructions were rejected.  Refused with SPP_ERR_BAD_INPUT
+ * before anything changes: NULL arguments (checked before the context is touched), count > 2^24, and a call that could overflow a
+ * set (size + count > capacity).  count == 0 is SPP_OK. */
+typedef struct spp_pool spp_pool;
+#define SPP_POOL_STATE_LEN 1072            /* size_of::<ShieldedPoolState>(), state.rs:6-17 */
+#define SPP_POOL_NULLIFIERS 0
+#define SPP_POOL_AUDIT_RECORDS 1
+#define SPP_POOL_OK 0                      /* the instruction succeeds; its account is created */
+#define SPP_POOL_AUDIT_EXISTS 1            /* submit_audit.rs:66-73: Ok, nothing verified, nothing written */
+#define SPP_POOL_NO_AUDIT_RECORD 2         /* withdraw.rs:94-125 */
+#define SPP_POOL_BAD_ROOT 3                /* withdraw.rs:131 */
+#define SPP_POOL_NULLIFIER_USED 4          /* withdraw.rs:137-147 */
+#define SPP_POOL_BAD_RECIPIENT 5           /* withdraw.rs:150-154 */
+#define SPP_POOL_BAD_PROOF 6               /* the verifier CPI fails: withdraw.rs:164-175, submit_audit.rs:82-87 */
+
+int  spp_pool_new(spp_ctx*, const uint8_t* withdraw_vk, size_t withdraw_vk_len, const uint8_t* audit_vk, size_t audit_vk_len,
+                  uint64_t capacity, spp_pool** out);
+void spp_pool_free(spp_pool*);
+/* state.add_root for `count` deposits in order: roots = count * 32 B, the `roots` output of spp_merkle_tree_deposit as it is */
+int  spp_pool_add_roots(spp_pool*, size_t count, const uint8_t* roots);
+/* the account bytes as bytemuck lays them out: "poolstat", current_root, roots[32], roots_index as u32 LE, 4 zero bytes */
+int  spp_pool_state(spp_pool*, uint8_t state[SPP_POOL_STATE_LEN]);
+/* counts[0] = spent nullifiers, counts[1] = audit records */
+int  spp_pool_counts(spp_pool*, uint64_t counts[2]);
+/* accounts known from elsewhere (bootstrapping from chain state): keys = count * 32 B into set `which`; duplicates, within the
+ * call or with the set, are ignored */
+int  spp_pool_import_keys(spp_pool*, int which, size_t count, const uint8_t* keys);
+/* present[i] = 1 if keys[i] is in set `which`, else 0 */
+int  spp_pool_contains(spp_pool*, int which, size_t count, const uint8_t* keys, uint8_t* present);
+/* process_submit_audit for `count` instructions: proofs = count * 388 B, pws = count * 76 B; key = the wa_commitment word.
+ * result[i]: a record with that key exists -- before the call, or made by an earlier instruction of this batch -- gives
+ * SPP_POOL_AUDIT_EXISTS whatever proof i is (the program returns Ok before the CPI); otherwise a valid proof gives SPP_POOL_OK and
+ * the record is created, an invalid one SPP_POOL_BAD_PROOF. */
+int  spp_pool_submit_audit_batch(spp_pool*, size_t count, const uint8_t* proofs, const uint8_t* pws, int32_t* result);
+/* process_withdraw for `count` instructions: proofs = count * 388 B, pws = count * 172 B (root, nullifier, recipient, amount,
+ * wa_commitment), recipients = count * 32 B account addresses.  result[i] = the first of: no audit record for wa_commitment
+ * (NO_AUDIT_RECORD), root neither current nor in the ring (BAD_ROOT), nullifier spent -- before the call, or by an earlier
+ * instruction of this batch that succeeded -- (NULLIFIER_USED), recipient word != 00 00 | address[0..30] (BAD_RECIPIENT), proof
+ * fails (BAD_PROOF); else SPP_POOL_OK and the nullifier is spent.  Neither the ring nor the audit set changes during the call.
+ * amounts (optional): amounts[i] = the u64 in bytes 24..31 of the amount word (withdraw.rs:157-161), written for every instruction. */
+int  spp_pool_withdraw_batch(spp_pool*, size_t count, const uint8_t* proofs, const uint8_t* pws, const uint8_t* recipients,
+                             int32_t* result, uint64_t* amounts);
 
 /* ---- micro-benchmark / unit entry points ---- */
 /* data: n = 2^logn elements, 32 B big-endian each, natural order in and out */

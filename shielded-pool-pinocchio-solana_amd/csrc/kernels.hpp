@@ -170,6 +170,25 @@ void launch_verify(hipStream_t st, const VerifyKeyDev* vk, const uint8_t* proofs
                    int32_t* ok);
 struct PairingCheckDev;
 void launch_pairing_check(hipStream_t st, const PairingCheckDev* a, int32_t* ok);
+// k_verify over a compacted list: ok[list[j]] for j < *n_list (a device word; at most max_count), the other entries of ok untouched
+void launch_verify_list(hipStream_t st, const VerifyKeyDev* vk, const uint8_t* proofs, const uint8_t* pws, uint32_t pw_len, uint32_t max_count,
+                        const uint32_t* list, const uint32_t* n_list, int32_t* ok);
+// ---- pool ledger (kernels_pool.hip); the structures and what a lane does live in pool_table.hpp ----
+struct PoolSet;
+struct PoolState;
+void launch_pool_screen_audit(hipStream_t st, const PoolSet& audits, uint64_t salt, const uint8_t* pws, uint32_t count, int32_t* prov, uint32_t* list,
+                              uint32_t* n_list);
+void launch_pool_screen_withdraw(hipStream_t st, const PoolState* state, const PoolSet& audits, const PoolSet& nullifiers, uint64_t salt,
+                                 const uint8_t* pws, const uint8_t* recipients, uint32_t count, int32_t* prov, uint64_t* amounts, uint32_t* list,
+                                 uint32_t* n_list);
+void launch_pool_screen_import(hipStream_t st, const PoolSet& set, uint64_t salt, const uint8_t* keys, uint32_t count, int32_t* prov);
+void launch_pool_contains(hipStream_t st, const PoolSet& set, uint64_t salt, const uint8_t* keys, uint32_t count, uint8_t* present);
+// claim + settle: slots = the resolve table (mask + 1 words, all POOL_NONE), key of instruction i = keys + i * stride;
+// proof_ok == nullptr: every pending instruction is a candidate; dup = the code of an instruction that meets an earlier winner
+void launch_pool_resolve(hipStream_t st, uint32_t* slots, uint32_t mask, uint64_t salt, const uint8_t* keys, uint32_t stride, uint32_t count,
+                         const int32_t* prov, const int32_t* proof_ok, int32_t dup, int32_t* result);
+void launch_pool_commit(hipStream_t st, const PoolSet& set, uint64_t salt, const uint8_t* keys, uint32_t stride, uint32_t count, const int32_t* result,
+                        uint32_t* set_count);
 // small: [sm_nslots][P] int16 scratch of the small rows (may be nullptr when the circuit has none)
 void launch_spmv_check(hipStream_t st, DevCircuit dc, const Fr* W, Fr* abc, uint32_t n, uint32_t P, uint32_t* status, int16_t* small = nullptr);
 

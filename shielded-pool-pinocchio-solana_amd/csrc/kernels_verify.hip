@@ -19,6 +19,19 @@ __global__ void __launch_bounds__(64) k_verify(const VerifyKeyDev* __restrict__ 
   ok[i] = verify_one(*vkp, proofs + (size_t)i * 388, pws + (size_t)i * pw_len) ? 1 : 0;
 }
 
+// k_verify over a compacted list (the pool ledger, kernels_pool.hip): lane j verifies proof list[j] for j < *n_list, a word the
+// screen kernel in front of it counted on the device, so the host launches for the largest possible list and never reads the
+// length back.  A wave with one live lane takes as long as a full one, so the waves past the end of the list -- whole waves,
+// gone at their first instruction -- are what a batch of mostly settled instructions saves.
+__global__ void __launch_bounds__(64) k_verify_list(const VerifyKeyDev* __restrict__ vkp, const uint8_t* __restrict__ proofs,
+                                                    const uint8_t* __restrict__ pws, uint32_t pw_len, const uint32_t* __restrict__ list,
+                                                    const uint32_t* __restrict__ n_list, int32_t* __restrict__ ok) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= *n_list) return;
+  const uint32_t i = list[j];
+  ok[i] = verify_one(*vkp, proofs + (size_t)i * 388, pws + (size_t)i * pw_len) ? 1 : 0;
+}
+
 // prod_k e(P_k, Q_k) == 1 for caller-supplied points, with exactly the device functions k_verify uses (pair 0 through the
 // projective-line path a proof's Bs takes, pairs 1.. through host-built line tables like the key-side points), preceded by
 // the curve and subgroup checks.  One lane; exists so that key material made by gnark (the reference's .vk files) can be
@@ -46,6 +59,12 @@ void launch_verify(hipStream_t st, const VerifyKeyDev* vk, const uint8_t* proofs
                    int32_t* ok) {
   if (count == 0) return;
   hipLaunchKernelGGL(k_verify, dim3((count + 63) / 64), dim3(64), 0, st, vk, proofs, pws, pw_len, count, ok);
+}
+
+void launch_verify_list(hipStream_t st, const VerifyKeyDev* vk, const uint8_t* proofs, const uint8_t* pws, uint32_t pw_len, uint32_t max_count,
+                        const uint32_t* list, const uint32_t* n_list, int32_t* ok) {
+  if (max_count == 0) return;
+  hipLaunchKernelGGL(k_verify_list, dim3((max_count + 63) / 64), dim3(64), 0, st, vk, proofs, pws, pw_len, list, n_list, ok);
 }
 
 }  // namespace spp

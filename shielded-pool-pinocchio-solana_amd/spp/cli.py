@@ -12,6 +12,11 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # the auditor's `python scripts/rlwe_decrypt.py`: reconstructs the key from the shares, verifies the
                               # proof (`-`: already verified elsewhere), checks that the ciphertext is the one the proof commits
                               # to and that it decrypts to the identity the proof commits to; exit 0 only if all three hold
+    python -m spp.cli pool-replay withdraw.vk audit.vk log.jsonl [--capacity N]
+                              # the pool program's decisions for a log of instructions, one JSON object per line, values in hex:
+                              #   {"deposit": {"root"}}  {"submit_audit": {"proof", "pw"}}  {"withdraw": {"proof", "pw", "recipient"}}
+                              # prints one result name per line (OK, AUDIT_EXISTS, NO_AUDIT_RECORD, BAD_ROOT, NULLIFIER_USED,
+                              # BAD_RECIPIENT, BAD_PROOF; a deposit only pushes its root and prints OK)
     python -m spp.cli execute target/<name>.json Prover.toml [-o target/<name>.gz]               # `nargo execute`: ACIR witness stack
     python -m spp.cli prove   target/<name>.json target/<name>.gz target/<name>.sppc target/<name>.pk
                               # sunspot's own argument order (acir, witness, constraint system, proving key;
@@ -97,6 +102,65 @@ def _audit_open(a):
     return 0 if f == 0 else 1
 
 
+_POOL_FIELDS = {"deposit": (("root", 32),), "submit_audit": (("proof", lib.PROOF_LEN), ("pw", lib.AUDIT_PW_LEN)),
+                "withdraw": (("proof", lib.PROOF_LEN), ("pw", lib.WITHDRAW_PW_LEN), ("recipient", 32))}
+
+
+def parse_pool_log(lines):
+    """[(kind, (bytes, ...))] from the lines of a pool-replay log; raises ValueError naming the line that is not an instruction"""
+    out = []
+    for no, line in enumerate(lines, 1):
+        if not line.strip():
+            continue
+        try:
+            d = json.loads(line)
+            (kind, body), = d.items()
+            vals = tuple(bytes.fromhex(body[name][2:] if body[name].lower().startswith("0x") else body[name]) for name, _ in _POOL_FIELDS[kind])
+        except (ValueError, KeyError, TypeError, AttributeError) as e:
+            raise ValueError("line %d: not a deposit / submit_audit / withdraw instruction (%s)" % (no, e))
+        for (name, size), v in zip(_POOL_FIELDS[kind], vals):
+            if len(v) != size:
+                raise ValueError("line %d: %s.%s must be %d bytes, got %d" % (no, kind, name, size, len(v)))
+        out.append((kind, vals))
+    return out
+
+
+def _pool_replay(a):
+    from . import witness
+    try:   # everything that can be wrong with the files is found before a device is opened
+        wvk, avk = open(a.withdraw_vk, "rb").read(), open(a.audit_vk, "rb").read()
+        log = parse_pool_log(open(a.log))
+    except (OSError, ValueError) as e:
+        print("spp pool-replay: %s" % e, file=sys.stderr)
+        return 2
+    capacity = a.capacity or max(1, sum(k == "submit_audit" for k, _ in log), sum(k == "withdraw" for k, _ in log))
+    ctx = Context(a.device)
+    try:
+        with witness.Pool(ctx, wvk, avk, capacity) as pool:
+            i = 0
+            while i < len(log):   # consecutive instructions of one kind are one batch: a batch is settled in order
+                j = i
+                while j < len(log) and log[j][0] == log[i][0]:
+                    j += 1
+                cols = list(zip(*(v for _, v in log[i:j])))
+                if log[i][0] == "deposit":
+                    pool.add_roots(cols[0])
+                    codes = [lib.SPP_POOL_OK] * (j - i)
+                elif log[i][0] == "submit_audit":
+                    codes = pool.submit_audit(cols[0], cols[1])
+                else:
+                    codes, _ = pool.withdraw(cols[0], cols[1], cols[2])
+                for c in codes:
+                    print(lib.POOL_RESULT_NAMES[c])
+                i = j
+    except lib.SppError as e:
+        print("spp pool-replay: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="spp")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -115,9 +179,14 @@ def main(argv=None):
     o.add_argument("proof"); o.add_argument("pw"); o.add_argument("ciphertext", help="ciphertext.json (scripts/generate_audit.py:590-606)")
     o.add_argument("--shares", nargs="+", required=True, metavar="SHARE.json", help="threshold many share files (scripts/rlwe_keygen.py)")
     o.add_argument("--device", type=int, default=0)
+    r = sub.add_parser("pool-replay"); r.add_argument("withdraw_vk"); r.add_argument("audit_vk"); r.add_argument("log", help="one instruction per line (JSON)")
+    r.add_argument("--capacity", type=int, default=0, help="keys per set (default: enough for the log)")
+    r.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.cmd == "audit-open":
         return _audit_open(a)
+    if a.cmd == "pool-replay":
+        return _pool_replay(a)
     if a.cmd == "compile" and a.circuit.endswith(".ccs"):
         from . import ccs
         c = ccs.load_ccs(a.circuit)

@@ -20,6 +20,19 @@ AUDIT_PW_LEN = 76                   # audit public witness: header | wa_commitme
 SPP_AUDIT_BAD_PROOF = 1
 SPP_AUDIT_BAD_CIPHERTEXT = 2
 SPP_AUDIT_BAD_IDENTITY = 4
+# the pool ledger, spp_pool_* (include/spp.h)
+WITHDRAW_PW_LEN = 172               # withdraw public witness: header | root | nullifier | recipient | amount | wa_commitment
+SPP_POOL_STATE_LEN = 1072           # size_of::<ShieldedPoolState>()
+SPP_POOL_NULLIFIERS = 0
+SPP_POOL_AUDIT_RECORDS = 1
+SPP_POOL_OK = 0
+SPP_POOL_AUDIT_EXISTS = 1
+SPP_POOL_NO_AUDIT_RECORD = 2
+SPP_POOL_BAD_ROOT = 3
+SPP_POOL_NULLIFIER_USED = 4
+SPP_POOL_BAD_RECIPIENT = 5
+SPP_POOL_BAD_PROOF = 6
+POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
 
 
 class SppError(RuntimeError):
@@ -107,6 +120,16 @@ def load_library():
     L.spp_prove_audit_records_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.spp_prove_audit_records.argtypes = [vp, vp, vp, sz, cp, vp, vp, vp, cp, vp, vp, vp, vp, vp]
     L.spp_audit_open_batch.argtypes = [vp, cp, sz, vp, sz, cp, cp, vp, vp, vp, vp]
+    L.spp_pool_new.argtypes = [vp, cp, sz, cp, sz, ctypes.c_uint64, ctypes.POINTER(vp)]
+    L.spp_pool_free.argtypes = [vp]
+    L.spp_pool_free.restype = None
+    L.spp_pool_add_roots.argtypes = [vp, sz, cp]
+    L.spp_pool_state.argtypes = [vp, vp]
+    L.spp_pool_counts.argtypes = [vp, vp]
+    L.spp_pool_import_keys.argtypes = [vp, i32, sz, cp]
+    L.spp_pool_contains.argtypes = [vp, i32, sz, cp, vp]
+    L.spp_pool_submit_audit_batch.argtypes = [vp, sz, cp, cp, vp]
+    L.spp_pool_withdraw_batch.argtypes = [vp, sz, cp, cp, cp, vp, vp]
     L.spp_withdraw_rows_from_tree.argtypes = [vp, sz, cp, vp]
     L.spp_prove_withdraw_notes_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     L.spp_prove_withdraw_notes.argtypes = [vp, vp, sz, cp, cp, vp, vp, vp]

@@ -3,6 +3,8 @@
     rlwe_witness(...)        scripts/generate_audit.py:507-584  /  demo-frontend/app/lib/rlwe.ts:157-247
     poseidon_hash2/4(...)    client/merkle.ts:22-38
     ShieldedPoolMerkleTree   client/merkle.ts:146-222
+    Pool                     shielded_pool_program/src/state.rs, instructions/submit_audit.rs, instructions/withdraw.rs: the
+                             pool program's state and its decisions for a batch of instructions (spp_pool_*)
     identity_public_key(...) client/merkle.ts:98-113
     pack_withdraw_notes(...) the five values a withdrawer supplies (noir_circuit/src/main.nr:38-51), for the rows / proofs
                              from notes against the resident tree (ShieldedPoolMerkleTree.withdraw_rows)
@@ -15,7 +17,8 @@ All of them take and return Python ints / lists; field elements cross the C ABI 
 """
 import ctypes
 import numpy as np
-from .lib import check, NOTE_LEN, DEPOSIT_LEN
+from .lib import (check, NOTE_LEN, DEPOSIT_LEN, PROOF_LEN, AUDIT_PW_LEN, WITHDRAW_PW_LEN, SPP_POOL_STATE_LEN,
+                  SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS)
 
 TREE_DEPTH = 16
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -208,6 +211,113 @@ class ShieldedPoolMerkleTree:
         rows = ctypes.create_string_buffer(32 * n_in * max(len(notes), 1))
         check(self.ctx.L.spp_withdraw_rows_from_tree(self.h, len(notes), buf, ctypes.cast(rows, ctypes.c_void_p)))
         return [_unbe(rows.raw[32 * n_in * i:], n_in) for i in range(len(notes))]
+
+
+def _joined(items, each, what):
+    """a list of byte strings (or one bytes object) as one buffer of len(items) * each bytes"""
+    buf = bytes(items) if isinstance(items, (bytes, bytearray)) else b"".join(bytes(x) for x in items)
+    if len(buf) % each:
+        raise ValueError("%s: %d bytes each" % (what, each))
+    return buf
+
+
+def _key_bytes(keys):
+    return b"".join(int(k).to_bytes(32, "big") if isinstance(k, int) else bytes(k) for k in keys)
+
+
+def recipient_word(address):
+    """The recipient public input the pool program expects for a 32-byte account address: 00 00 | address[0..30]
+    (shielded_pool_program/src/instructions/withdraw.rs:150-154), as an integer."""
+    address = bytes(address)
+    if len(address) != 32:
+        raise ValueError("an account address is 32 bytes")
+    return int.from_bytes(address[:30], "big")
+
+
+class Pool:
+    """The pool program's state on the device (spp_pool_*): ShieldedPoolState's root ring (state.rs:6-46) and the sets of spent
+    nullifiers and audit records, with the decisions process_submit_audit / process_withdraw make for a batch of instructions
+    taken in order.  A pre-screen for a relayer (which of these transactions would land?) and a replay tool for an auditor; the
+    vault balance and lamport transfers are not modelled -- withdraw() returns the amounts for that.
+    withdraw_vk / audit_vk: the two verifying keys (bytes); capacity: keys per set, fixed.  Keys (nullifiers, wa_commitments)
+    are ints or 32-byte strings; results are SPP_POOL_* codes (spp.lib.POOL_RESULT_NAMES)."""
+
+    def __init__(self, ctx, withdraw_vk, audit_vk, capacity):
+        self.ctx, self.capacity = ctx, int(capacity)
+        h = ctypes.c_void_p()
+        check(ctx.L.spp_pool_new(ctx.h, withdraw_vk, len(withdraw_vk), audit_vk, len(audit_vk), self.capacity, ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.spp_pool_free(self.h)
+            self.h = None
+
+    # the sets live in HBM: release them when the object goes away (context manager or garbage collection), not only on close()
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the library may already be gone
+            pass
+
+    def add_roots(self, roots):
+        """state.add_root for every deposit in order; roots: ints (ShieldedPoolMerkleTree.deposit's third result) or bytes"""
+        buf = _key_bytes(roots)
+        check(self.ctx.L.spp_pool_add_roots(self.h, len(buf) // 32, buf))
+
+    def state(self):
+        """the 1072 bytes of the ShieldedPoolState account"""
+        out = ctypes.create_string_buffer(SPP_POOL_STATE_LEN)
+        check(self.ctx.L.spp_pool_state(self.h, ctypes.cast(out, ctypes.c_void_p)))
+        return out.raw
+
+    def counts(self):
+        """(spent nullifiers, audit records)"""
+        c = (ctypes.c_uint64 * 2)()
+        check(self.ctx.L.spp_pool_counts(self.h, ctypes.cast(c, ctypes.c_void_p)))
+        return int(c[0]), int(c[1])
+
+    def import_keys(self, which, keys):
+        """accounts known from elsewhere; which: SPP_POOL_NULLIFIERS or SPP_POOL_AUDIT_RECORDS; duplicates are ignored"""
+        buf = _key_bytes(keys)
+        check(self.ctx.L.spp_pool_import_keys(self.h, int(which), len(buf) // 32, buf))
+
+    def contains(self, which, keys):
+        buf = _key_bytes(keys)
+        n = len(buf) // 32
+        out = ctypes.create_string_buffer(max(n, 1))
+        check(self.ctx.L.spp_pool_contains(self.h, int(which), n, buf, ctypes.cast(out, ctypes.c_void_p)))
+        return [bool(b) for b in out.raw[:n]]
+
+    def submit_audit(self, proofs, pws):
+        """process_submit_audit for the instructions in order: proofs / pws lists of bytes (388 / 76 each).  Returns the codes."""
+        pb, wb = _joined(proofs, PROOF_LEN, "proofs"), _joined(pws, AUDIT_PW_LEN, "audit public witnesses")
+        n = len(pb) // PROOF_LEN
+        if len(wb) != AUDIT_PW_LEN * n:
+            raise ValueError("submit_audit: %d proofs need %d public witnesses of %d bytes" % (n, n, AUDIT_PW_LEN))
+        res = (ctypes.c_int32 * max(n, 1))()
+        check(self.ctx.L.spp_pool_submit_audit_batch(self.h, n, pb, wb, ctypes.cast(res, ctypes.c_void_p)))
+        return list(res)[:n]
+
+    def withdraw(self, proofs, pws, recipients):
+        """process_withdraw for the instructions in order: proofs / pws lists of bytes (388 / 172 each), recipients the 32-byte
+        addresses of the recipient accounts.  Returns (codes, amounts)."""
+        pb, wb = _joined(proofs, PROOF_LEN, "proofs"), _joined(pws, WITHDRAW_PW_LEN, "withdraw public witnesses")
+        rb = _joined(recipients, 32, "recipient addresses")
+        n = len(pb) // PROOF_LEN
+        if len(wb) != WITHDRAW_PW_LEN * n or len(rb) != 32 * n:
+            raise ValueError("withdraw: %d proofs need %d public witnesses of %d bytes and %d addresses of 32" % (n, n, WITHDRAW_PW_LEN, n))
+        res = (ctypes.c_int32 * max(n, 1))()
+        amounts = (ctypes.c_uint64 * max(n, 1))()
+        check(self.ctx.L.spp_pool_withdraw_batch(self.h, n, pb, wb, rb, ctypes.cast(res, ctypes.c_void_p), ctypes.cast(amounts, ctypes.c_void_p)))
+        return list(res)[:n], [int(a) for a in amounts][:n]
 
 
 def merkle_build(ctx, leaves, queries, depth=TREE_DEPTH):
