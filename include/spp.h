@@ -31,6 +31,9 @@
  *                             batch of instructions in order -- what the relayer sends without any pre-check
  *                             (demo-frontend/app/api/relay/withdraw/route.ts:224-276)
  *   spp_pool_add_roots        state.add_root (state.rs:28-33) for the new_root of every deposit (instructions/deposit.rs:21-37)
+ *   spp_pool_settle_log       a log in which the three kinds alternate, as the chain's does (one audit and one withdraw transaction per
+ *                             withdrawal, route.ts:224-276, deposits in between), settled in one call: state.rs:28-46,
+ *                             instructions/deposit.rs:21-37, submit_audit.rs:41-87, withdraw.rs:94-175
  *   spp_msm_g1(_pippenger) / spp_ntt_fr   micro-benchmark entry points (BASELINE.json configs[4]); no reference equivalent
  *
  * Conventions: field elements cross the boundary as 32-byte big-endian canonical integers (the encoding
@@ -417,10 +420,34 @@ int  spp_pool_submit_audit_batch(spp_pool*, size_t count, const uint8_t* proofs,
  * wa_commitment), recipients = count * 32 B account addresses.  result[i] = the first of: no audit record for wa_commitment
  * (NO_AUDIT_RECORD), root neither current nor in the ring (BAD_ROOT), nullifier spent -- before the call, or by an earlier
  * instruction of this batch that succeeded -- (NULLIFIER_USED), recipient word != 00 00 | address[0..30] (BAD_RECIPIENT), proof
- * fails (BAD_PROOF); else SPP_POOL_OK and the nullifier is spent.  Neither the ring nor the audit set changes during the call.
+ * fails (BAD_PROOF); else SPP_POOL_OK and the nullifier is spent.  Neither the ring nor the audit set changes during the call
+ * (spp_pool_settle_log is the call for a log in which they do).
  * amounts (optional): amounts[i] = the u64 in bytes 24..31 of the amount word (withdraw.rs:157-161), written for every instruction. */
 int  spp_pool_withdraw_batch(spp_pool*, size_t count, const uint8_t* proofs, const uint8_t* pws, const uint8_t* recipients,
                              int32_t* result, uint64_t* amounts);
+/* A log of `count` instructions of all three kinds, in the order the chain processed them: kinds[i] is the kind of instruction i,
+ * and the k-th instruction of a kind takes row k of that kind's columns -- roots = n_deposits * 32 B as for spp_pool_add_roots
+ * (the new_root a deposit pushes, instructions/deposit.rs:21-37; add_root / check_root are state.rs:28-46), audit_proofs / audit_pws as for
+ * spp_pool_submit_audit_batch (submit_audit.rs:41-87), withdraw_proofs / withdraw_pws / recipients as for spp_pool_withdraw_batch
+ * (withdraw.rs:94-175).  result[i] = the SPP_POOL_* code the program gives instruction i processing instructions 0..count-1 one
+ * after another on the state as it stood at the call; a deposit gives SPP_POOL_OK.  A withdraw meets the audit records and the ring
+ * AS OF ITS POSITION: the records that were resident or that an earlier submit_audit of the log created -- a withdraw ahead of its
+ * own submit_audit gets NO_AUDIT_RECORD --, and check_root (state.rs:36-46) after exactly the deposits before it, so a root is
+ * known for the 32 pushes that follow it and the zero root of a fresh pool until the 32nd push, inside the log as across calls.
+ * amounts (optional): the u64 of the amount word for withdraws, 0 elsewhere.  After the call the ring, both sets, spp_pool_state and
+ * spp_pool_counts are as if the instructions had gone through the three calls above one at a time.  The number of kernel launches is
+ * fixed (two of the verifier), whatever the interleaving.
+ * Refused with SPP_ERR_BAD_INPUT before anything changes: NULL arguments (a column may be NULL only when its count is 0), a kinds
+ * byte above 2, per-kind counts that do not match kinds or do not sum to count, count > 2^24, audit records + n_audits > capacity,
+ * nullifiers + n_withdraws > capacity.  count == 0 is SPP_OK. */
+#define SPP_INSTR_DEPOSIT 0
+#define SPP_INSTR_SUBMIT_AUDIT 1
+#define SPP_INSTR_WITHDRAW 2
+int  spp_pool_settle_log(spp_pool*, size_t count, const uint8_t* kinds,
+                         size_t n_deposits, const uint8_t* roots,
+                         size_t n_audits, const uint8_t* audit_proofs, const uint8_t* audit_pws,
+                         size_t n_withdraws, const uint8_t* withdraw_proofs, const uint8_t* withdraw_pws, const uint8_t* recipients,
+                         int32_t* result, uint64_t* amounts);
 
 /* ---- micro-benchmark / unit entry points ---- */
 /* data: n = 2^logn elements, 32 B big-endian each, natural order in and out */

@@ -181,6 +181,14 @@ void launch_pool_screen_audit(hipStream_t st, const PoolSet& audits, uint64_t sa
 void launch_pool_screen_withdraw(hipStream_t st, const PoolState* state, const PoolSet& audits, const PoolSet& nullifiers, uint64_t salt,
                                  const uint8_t* pws, const uint8_t* recipients, uint32_t count, int32_t* prov, uint64_t* amounts, uint32_t* list,
                                  uint32_t* n_list);
+// a withdraw of a log: the ring and the audit records as of its position (PoolLogView, pool_table.hpp); count > 0
+struct PoolLogView;
+void launch_pool_screen_withdraw_log(hipStream_t st, const PoolLogView& view, const PoolSet& audits, const PoolSet& nullifiers, uint64_t salt,
+                                     const uint8_t* pws, const uint8_t* recipients, const uint32_t* deposits_before, const uint32_t* audits_before,
+                                     uint32_t count, int32_t* prov, uint64_t* amounts, uint32_t* list, uint32_t* n_list);
+// result[pos[i]] = codes[i] and, unless amounts_out is nullptr, amounts_out[pos[i]] = amounts[i]; count > 0
+void launch_pool_scatter(hipStream_t st, const uint32_t* pos, uint32_t count, const int32_t* codes, int32_t* result, const uint64_t* amounts,
+                         uint64_t* amounts_out);
 void launch_pool_screen_import(hipStream_t st, const PoolSet& set, uint64_t salt, const uint8_t* keys, uint32_t count, int32_t* prov);
 void launch_pool_contains(hipStream_t st, const PoolSet& set, uint64_t salt, const uint8_t* keys, uint32_t count, uint8_t* present);
 // claim + settle: slots = the resolve table (mask + 1 words, all POOL_NONE), key of instruction i = keys + i * stride;

@@ -9,6 +9,8 @@
 //   claim     candidates (everything passed, proof included) claim their key in the per-call resolve table: lowest index wins
 //   settle    every undecided instruction reads the winner of its key back and gets its final code
 //   commit    winners only: the key goes into the resident set, the set's count goes up
+// A log of all three kinds (spp_pool_settle_log) is the same steps for its submit_audits and then for its withdraws, with the
+// withdraw screen reading the audit resolve table and both commits after it, and a scatter of the codes to log order.
 // The resident sets are read in screen and written in commit only; the resolve table is written in claim and read in settle only:
 // every dependence crosses a kernel boundary on one stream.  32-bit atomicCAS / atomicMin / atomicAdd on global memory, plain
 // stores otherwise.
@@ -40,6 +42,33 @@ __global__ void __launch_bounds__(256) k_pool_screen_withdraw(const PoolState* _
   const int32_t c = pool_screen_withdraw(*state, audits, nullifiers, salt, pw, recipients + (size_t)i * 32);
   prov[i] = c;
   if (c == POOL_PENDING_PROOF) pool_list_push(list, n_list, i);
+}
+
+// A withdraw of a log (spp_pool_settle_log): lane r is the withdraw of rank r, which sees the ring after deposits_before[r] of the
+// batch's roots and the audit records of the submit_audits of rank < audits_before[r].  Runs after the audit claim, before any commit.
+__global__ void __launch_bounds__(256) k_pool_screen_withdraw_log(PoolLogView view, PoolSet audits, PoolSet nullifiers, uint64_t salt,
+                                                                  const uint8_t* __restrict__ pws, const uint8_t* __restrict__ recipients,
+                                                                  const uint32_t* __restrict__ deposits_before,
+                                                                  const uint32_t* __restrict__ audits_before, uint32_t count,
+                                                                  int32_t* __restrict__ prov, uint64_t* __restrict__ amounts,
+                                                                  uint32_t* __restrict__ list, uint32_t* n_list) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const uint8_t* pw = pws + (size_t)i * POOL_WITHDRAW_PW;
+  amounts[i] = pool_amount_u64(pw);
+  const int32_t c = pool_screen_withdraw_at(view, deposits_before[i], audits_before[i], audits, nullifiers, salt, pw, recipients + (size_t)i * 32);
+  prov[i] = c;
+  if (c == POOL_PENDING_PROOF) pool_list_push(list, n_list, i);
+}
+
+// the codes (and amounts, when asked for) of one kind, by rank, to their positions in the log
+__global__ void __launch_bounds__(256) k_pool_scatter(const uint32_t* __restrict__ pos, uint32_t count, const int32_t* __restrict__ codes,
+                                                      int32_t* __restrict__ result, const uint64_t* __restrict__ amounts,
+                                                      uint64_t* __restrict__ amounts_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  result[pos[i]] = codes[i];
+  if (amounts_out) amounts_out[pos[i]] = amounts[i];
 }
 
 // import_keys: a key that is resident is done (any final code but OK); the others are candidates without a proof to check
@@ -95,6 +124,16 @@ void launch_pool_screen_withdraw(hipStream_t st, const PoolState* state, const P
                                  uint32_t* n_list) {
   hipLaunchKernelGGL(k_pool_screen_withdraw, pool_grid(count), dim3(256), 0, st, state, audits, nullifiers, salt, pws, recipients, count, prov, amounts,
                      list, n_list);
+}
+void launch_pool_screen_withdraw_log(hipStream_t st, const PoolLogView& view, const PoolSet& audits, const PoolSet& nullifiers, uint64_t salt,
+                                     const uint8_t* pws, const uint8_t* recipients, const uint32_t* deposits_before, const uint32_t* audits_before,
+                                     uint32_t count, int32_t* prov, uint64_t* amounts, uint32_t* list, uint32_t* n_list) {
+  hipLaunchKernelGGL(k_pool_screen_withdraw_log, pool_grid(count), dim3(256), 0, st, view, audits, nullifiers, salt, pws, recipients, deposits_before,
+                     audits_before, count, prov, amounts, list, n_list);
+}
+void launch_pool_scatter(hipStream_t st, const uint32_t* pos, uint32_t count, const int32_t* codes, int32_t* result, const uint64_t* amounts,
+                         uint64_t* amounts_out) {
+  hipLaunchKernelGGL(k_pool_scatter, pool_grid(count), dim3(256), 0, st, pos, count, codes, result, amounts, amounts_out);
 }
 void launch_pool_screen_import(hipStream_t st, const PoolSet& set, uint64_t salt, const uint8_t* keys, uint32_t count, int32_t* prov) {
   hipLaunchKernelGGL(k_pool_screen_import, pool_grid(count), dim3(256), 0, st, set, salt, keys, count, prov);

@@ -23,6 +23,23 @@
 // equal -> atomicMin(slot, i), else probe on.  A slot only ever changes from EMPTY to an index and then to lower indices OF THE
 // SAME KEY, so the key a slot stands for is fixed by its first claim, no key bytes are written at all, and whatever order the
 // lanes arrive in the slot ends at the minimum: the result does not depend on scheduling.  A second launch reads the winner back.
+//
+// A log of all three kinds in one call (spp_pool_settle_log; state.rs:28-46, instructions/deposit.rs:21-37, submit_audit.rs:41-87,
+// withdraw.rs:94-175).  The dependences between kinds run one way: a deposit depends on nothing and pushes its root; a
+// submit_audit depends on the audit set and on earlier submit_audits only; a withdraw reads the audit set and the ring AS OF ITS
+// POSITION and the nullifier set, and nothing a withdraw does feeds back into a deposit or an audit.  So the audits are settled
+// first, by the rule above over their ranks (rank = index among the instructions of one kind), and two cross-kind rules let every
+// withdraw be screened on its own lane:
+//   audit record at a position   the record of wa_commitment exists for a withdraw with `a` audits before it iff the key is
+//                                resident or the audit resolve table's winner of that key has a rank < a: the winner is the lowest
+//                                candidate, candidates are the only instructions that create the record, and a key with a resident
+//                                record has no candidate at all.  The lookup is by a key of ANOTHER buffer (pool_resolve_find).
+//   ring at a position           the resident ring's 32 entries in push order, oldest first (pool_ring_entries), followed by the
+//                                batch's deposit roots: after the first d of them the ring holds entries d .. d+31 and
+//                                current_root is entry d+31, because add_root overwrites the oldest slot (pool_check_root_at).
+// With the audit-record and root checks position-exact and final, the withdraws are left coupled through their nullifiers only,
+// which is the rule above over withdraw ranks.  The audit COMMIT comes after the withdraw screen: were the records inserted first, a
+// withdraw that precedes its submit_audit in the log would find them.  The resident sets stay "read in screens, written in commits".
 #pragma once
 #include "bn254.hpp"
 
@@ -72,6 +89,23 @@ SPP_HD bool pool_check_root(const PoolState& s, const uint8_t* root) {   // stat
   if (pool_key_equal(s.current_root, root)) return true;
   for (uint32_t k = 0; k < POOL_ROOTS; k++)
     if (pool_key_equal(s.roots[k], root)) return true;
+  return false;
+}
+// The ring of a log.  entries: the 32 slots in the order add_root will overwrite them, oldest first (slots never written are zero
+// and come first, which is the zero root of a fresh pool), then -- appended by the caller -- the roots the batch's deposits push.
+SPP_HD void pool_ring_entries(const PoolState& s, uint8_t out[POOL_ROOTS * 32]) {
+  for (uint32_t k = 0; k < POOL_ROOTS; k++) {
+    const uint32_t slot = (s.roots_index + k) % POOL_ROOTS;
+    for (int i = 0; i < 32; i++) out[32 * k + i] = s.roots[slot][i];
+  }
+}
+// check_root (state.rs:36-46) on the state after `pushed` of the batch's roots: current_root is the newest entry, roots[] the 32
+// newest.  On a pool that has seen no push at all both are zero, as the account is.
+SPP_HD bool pool_check_root_at(const uint8_t* entries, uint32_t pushed, const uint8_t* root) {
+  const uint8_t* ring = entries + (size_t)pushed * 32;
+  if (pool_key_equal(ring + (POOL_ROOTS - 1) * 32, root)) return true;   // current_root
+  for (uint32_t k = 0; k < POOL_ROOTS; k++)
+    if (pool_key_equal(ring + k * 32, root)) return true;
   return false;
 }
 // the account bytes as bytemuck lays the struct out (state.rs:6-17)
@@ -168,6 +202,14 @@ SPP_HD uint32_t pool_resolve_winner(const uint32_t* slots, uint32_t mask, uint64
     if (cur == i || pool_key_equal(keys + (size_t)cur * stride, key)) return cur;
   }
 }
+// the same for a key that lies in another buffer (a withdraw's wa_commitment in the table its batch's submit_audits claimed)
+SPP_HD uint32_t pool_resolve_find(const uint32_t* slots, uint32_t mask, uint64_t salt, const uint8_t* keys, size_t stride, const uint8_t* key) {
+  for (uint32_t s = pool_slot(key, salt, mask);; s = (s + 1) & mask) {
+    const uint32_t cur = slots[s];
+    if (cur == POOL_NONE) return POOL_NONE;
+    if (pool_key_equal(keys + (size_t)cur * stride, key)) return cur;
+  }
+}
 // the final code of instruction i: prov from the screen, proof_ok from the verifier (read only for POOL_PENDING_PROOF), winner
 // from pool_resolve_winner, dup = what the program answers when the account exists (AUDIT_EXISTS / NULLIFIER_USED)
 SPP_HD bool pool_is_candidate(int32_t prov, bool proof_ok) { return prov == POOL_PENDING_PROOF && proof_ok; }
@@ -199,6 +241,56 @@ SPP_HD int32_t pool_screen_withdraw(const PoolState& st, const PoolSet& audits, 
   if (pool_set_contains(nullifiers, salt, pw + POOL_W_NULLIFIER)) return POOL_NULLIFIER_USED;
   if (!pool_recipient_matches(pw + POOL_W_RECIPIENT, address)) return pool_pending_refused(POOL_BAD_RECIPIENT);
   return POOL_PENDING_PROOF;
+}
+
+// ---- a log of all three kinds ----
+// What a withdraw of a log sees of the instructions before it: the ring entries (above), how many of the batch's deposits and
+// submit_audits precede it, and the resolve table the submit_audits claimed (keys: their wa_commitments, by audit rank).
+struct PoolLogView {
+  const uint8_t* ring;          // (32 + deposits) x 32 B
+  const uint32_t* audit_slots;  // the audit resolve table, after every claim
+  uint32_t audit_mask;
+  const uint8_t* audit_keys;    // key of audit rank r = audit_keys + r * audit_stride
+  size_t audit_stride;
+};
+// withdraw.rs:94-125 at a position
+SPP_HD bool pool_audit_record_at(const PoolLogView& v, const PoolSet& audits, uint64_t salt, uint32_t audits_before, const uint8_t* wa) {
+  if (pool_set_contains(audits, salt, wa)) return true;
+  return pool_resolve_find(v.audit_slots, v.audit_mask, salt, v.audit_keys, v.audit_stride, wa) < audits_before;   // POOL_NONE is above every rank
+}
+// withdraw.rs:94-154 at a position, the checks in program order; the provisional codes are pool_screen_withdraw's
+SPP_HD int32_t pool_screen_withdraw_at(const PoolLogView& v, uint32_t deposits_before, uint32_t audits_before, const PoolSet& audits,
+                                       const PoolSet& nullifiers, uint64_t salt, const uint8_t* pw, const uint8_t* address) {
+  if (!pool_audit_record_at(v, audits, salt, audits_before, pw + POOL_W_WA)) return POOL_NO_AUDIT_RECORD;
+  if (!pool_check_root_at(v.ring, deposits_before, pw + POOL_W_ROOT)) return POOL_BAD_ROOT;
+  if (pool_set_contains(nullifiers, salt, pw + POOL_W_NULLIFIER)) return POOL_NULLIFIER_USED;
+  if (!pool_recipient_matches(pw + POOL_W_RECIPIENT, address)) return pool_pending_refused(POOL_BAD_RECIPIENT);
+  return POOL_PENDING_PROOF;
+}
+
+// The index arrays of a log, on the host: the caller has to read the `count` kind bytes once anyway to validate them, and a running
+// count per kind in that pass is all a scan would compute, so no device scan is spent on one byte per instruction.
+//   n[k]                  instructions of kind k (0 deposit, 1 submit_audit, 2 withdraw)
+//   audit_pos[r]          position in the log of the submit_audit of rank r;  withdraw_pos[r] likewise
+//   deposits_before[r], audits_before[r]   of the withdraw of rank r
+// The arrays hold max_audits / max_withdraws entries (0 and NULL: a counting pass); ranks past them are counted, not written, so
+// a caller whose per-kind counts disagree with kinds finds out from n[] after the same pass.  false: a kind byte above 2.
+static constexpr uint8_t POOL_INSTR_DEPOSIT = 0, POOL_INSTR_SUBMIT_AUDIT = 1, POOL_INSTR_WITHDRAW = 2;
+inline bool pool_log_index(const uint8_t* kinds, size_t count, size_t n[3], size_t max_audits, size_t max_withdraws, uint32_t* audit_pos,
+                           uint32_t* withdraw_pos, uint32_t* deposits_before, uint32_t* audits_before) {
+  n[0] = n[1] = n[2] = 0;
+  for (size_t i = 0; i < count; i++) {
+    const uint8_t k = kinds[i];
+    if (k > POOL_INSTR_WITHDRAW) return false;
+    if (k == POOL_INSTR_SUBMIT_AUDIT && n[1] < max_audits) audit_pos[n[1]] = (uint32_t)i;
+    if (k == POOL_INSTR_WITHDRAW && n[2] < max_withdraws) {
+      withdraw_pos[n[2]] = (uint32_t)i;
+      deposits_before[n[2]] = (uint32_t)n[0];
+      audits_before[n[2]] = (uint32_t)n[1];
+    }
+    n[k]++;
+  }
+  return true;
 }
 
 }  // namespace spp

@@ -4,6 +4,8 @@
 // the program makes processing them one after another (instructions/submit_audit.rs, withdraw.rs).  What a lane does and why the
 // parallel resolution of duplicates equals the sequential one is in pool_table.hpp; the launches are in kernels_pool.hip.
 // One call = one upload, screen -> verify (compacted list) -> claim -> settle -> commit on ctx->stream, one download.
+// spp_pool_settle_log takes a log in which deposits, submit_audits and withdraws alternate (state.rs:28-46,
+// instructions/deposit.rs:21-37, submit_audit.rs:41-87, withdraw.rs:94-175) and settles it with a fixed number of launches.
 #include "spp_internal.hpp"
 #include "verify_key_prep.hpp"
 #include "pool_table.hpp"
@@ -24,7 +26,8 @@ static_assert(SPP_POOL_STATE_LEN == POOL_STATE_LEN && SPP_POOL_OK == POOL_OK && 
                   SPP_POOL_NO_AUDIT_RECORD == POOL_NO_AUDIT_RECORD && SPP_POOL_BAD_ROOT == POOL_BAD_ROOT &&
                   SPP_POOL_NULLIFIER_USED == POOL_NULLIFIER_USED && SPP_POOL_BAD_RECIPIENT == POOL_BAD_RECIPIENT &&
                   SPP_POOL_BAD_PROOF == POOL_BAD_PROOF && SPP_PROOF_LEN == POOL_PROOF && SPP_WITHDRAW_PW_LEN == POOL_WITHDRAW_PW &&
-                  SPP_AUDIT_PW_LEN == POOL_AUDIT_PW,
+                  SPP_AUDIT_PW_LEN == POOL_AUDIT_PW && SPP_INSTR_DEPOSIT == POOL_INSTR_DEPOSIT && SPP_INSTR_SUBMIT_AUDIT == POOL_INSTR_SUBMIT_AUDIT &&
+                  SPP_INSTR_WITHDRAW == POOL_INSTR_WITHDRAW,
               "include/spp.h and pool_table.hpp disagree");
 
 static constexpr size_t POOL_MAX_BATCH = (size_t)1 << 24;
@@ -279,6 +282,125 @@ extern "C" int spp_pool_withdraw_batch(spp_pool* p, size_t count, const uint8_t*
   if (int e = pool_fetch_counts(p, st, cnt)) return e;
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
+  p->counts[0] = cnt[0];
+  p->counts[1] = cnt[1];
+  return SPP_OK;
+}
+
+// A log of deposit / submit_audit / withdraw instructions in one call.  Order on the stream (pool_table.hpp has the argument):
+// audit screen -> verify -> audit claim + settle -> withdraw screen at each position (resident sets + the audit resolve table) ->
+// verify -> nullifier claim + settle -> both commits -> scatter to log order.  A kind without instructions launches nothing.
+extern "C" int spp_pool_settle_log(spp_pool* p, size_t count, const uint8_t* kinds, size_t n_deposits, const uint8_t* roots, size_t n_audits,
+                                   const uint8_t* audit_proofs, const uint8_t* audit_pws, size_t n_withdraws, const uint8_t* withdraw_proofs,
+                                   const uint8_t* withdraw_pws, const uint8_t* recipients, int32_t* result, uint64_t* amounts) {
+  if (!p || (count && (!kinds || !result)) || (n_deposits && !roots) || (n_audits && (!audit_proofs || !audit_pws)) ||
+      (n_withdraws && (!withdraw_proofs || !withdraw_pws || !recipients)))
+    return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count > POOL_MAX_BATCH) return fail(SPP_ERR_BAD_INPUT, "too many instructions in one call (%zu; at most 2^24)", count);
+  if (n_deposits > count || n_audits > count || n_withdraws > count || n_deposits + n_audits + n_withdraws != count)
+    return fail(SPP_ERR_BAD_INPUT, "%zu deposits, %zu submit_audits and %zu withdraws are not %zu instructions", n_deposits, n_audits, n_withdraws, count);
+  // the one pass over kinds: validation, and the index arrays in one block [audit_pos | withdraw_pos | deposits_before | audits_before]
+  std::vector<uint32_t> index(n_audits + 3 * n_withdraws);
+  uint32_t* ix = index.data();
+  size_t n[3];
+  if (!pool_log_index(kinds, count, n, n_audits, n_withdraws, ix, ix + n_audits, ix + n_audits + n_withdraws, ix + n_audits + 2 * n_withdraws))
+    return fail(SPP_ERR_BAD_INPUT, "kinds: SPP_INSTR_DEPOSIT, SPP_INSTR_SUBMIT_AUDIT or SPP_INSTR_WITHDRAW");
+  if (n[0] != n_deposits || n[1] != n_audits || n[2] != n_withdraws)
+    return fail(SPP_ERR_BAD_INPUT, "kinds holds %zu deposits, %zu submit_audits and %zu withdraws, the counts say %zu, %zu and %zu", n[0], n[1], n[2],
+                n_deposits, n_audits, n_withdraws);
+  if (count == 0) return SPP_OK;
+  spp_ctx* ctx = p->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int e = pool_room(p, SPP_POOL_AUDIT_RECORDS, n_audits)) return e;
+  if (int e = pool_room(p, SPP_POOL_NULLIFIERS, n_withdraws)) return e;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const uint32_t na = (uint32_t)n_audits, nw = (uint32_t)n_withdraws;
+  const PoolSet& audits = p->set[SPP_POOL_AUDIT_RECORDS];
+  const PoolSet& nullifiers = p->set[SPP_POOL_NULLIFIERS];
+
+  // the ring after the call, and (for the withdraws) the entries every position is a window of
+  PoolState next = p->state;
+  for (size_t i = 0; i < n_deposits; i++) pool_add_root(next, roots + 32 * i);
+  uint8_t resident[POOL_ROOTS * 32];
+  pool_ring_entries(p->state, resident);
+
+  DevBuf dindex, dall, dall_amounts, dring;
+  DevBuf aproofs, apws, aprov, alist, anlist, aok, aslots, aresult;
+  DevBuf wproofs, wpws, wrecip, wprov, wamounts, wlist, wnlist, wok, wslots, wresult;
+  uint32_t amask = 0, wmask = 0, cnt[2];
+  // upload
+  UP(dindex, index.data(), index.size() * sizeof(uint32_t));
+  UP(aproofs, audit_proofs, n_audits * (size_t)SPP_PROOF_LEN);
+  UP(apws, audit_pws, n_audits * (size_t)SPP_AUDIT_PW_LEN);
+  UP(wproofs, withdraw_proofs, n_withdraws * (size_t)SPP_PROOF_LEN);
+  UP(wpws, withdraw_pws, n_withdraws * (size_t)SPP_WITHDRAW_PW_LEN);
+  UP(wrecip, recipients, n_withdraws * 32);
+  if (nw) {
+    HIP_TRY(dring.alloc((POOL_ROOTS + n_deposits) * 32));
+    HIP_TRY(hipMemcpyAsync(dring.p, resident, sizeof resident, hipMemcpyHostToDevice, st));
+    if (n_deposits) HIP_TRY(hipMemcpyAsync(dring.as<uint8_t>() + sizeof resident, roots, n_deposits * 32, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(dall.alloc(count * sizeof(int32_t)));
+  HIP_TRY(hipMemsetAsync(dall.p, 0, count * sizeof(int32_t), st));   // SPP_POOL_OK: what a deposit gives
+  if (amounts) {
+    HIP_TRY(dall_amounts.alloc(count * sizeof(uint64_t)));
+    HIP_TRY(hipMemsetAsync(dall_amounts.p, 0, count * sizeof(uint64_t), st));
+  }
+  const uint32_t* audit_pos = dindex.as<uint32_t>();
+  const uint32_t* withdraw_pos = audit_pos + na;
+  const uint32_t* deposits_before = withdraw_pos + nw;
+  const uint32_t* audits_before = deposits_before + nw;
+  const uint8_t* akeys = apws.as<uint8_t>() + POOL_A_WA;
+  const uint8_t* wkeys = wpws.as<uint8_t>() + POOL_W_NULLIFIER;
+
+  // the submit_audits among themselves; the table stays for the withdraws (all empty when there is no submit_audit)
+  if (int e = pool_resolve_table(st, n_audits, aslots, &amask)) return e;
+  if (na) {
+    HIP_TRY(aprov.alloc(n_audits * sizeof(int32_t)));
+    HIP_TRY(aresult.alloc(n_audits * sizeof(int32_t)));
+    HIP_TRY(alist.alloc(n_audits * sizeof(uint32_t)));
+    HIP_TRY(anlist.alloc(sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(anlist.p, 0, sizeof(uint32_t), st));
+    launch_pool_screen_audit(st, audits, p->salt, apws.as<uint8_t>(), na, aprov.as<int32_t>(), alist.as<uint32_t>(), anlist.as<uint32_t>());
+    if (int e = pool_verify(p, st, 1, aproofs.as<uint8_t>(), apws.as<uint8_t>(), SPP_AUDIT_PW_LEN, na, alist.as<uint32_t>(), anlist.as<uint32_t>(), aok)) return e;
+    launch_pool_resolve(st, aslots.as<uint32_t>(), amask, p->salt, akeys, SPP_AUDIT_PW_LEN, na, aprov.as<int32_t>(), aok.as<int32_t>(), POOL_AUDIT_EXISTS,
+                        aresult.as<int32_t>());
+  }
+  // the withdraws, each against the ring and the audit records as of its position
+  if (nw) {
+    HIP_TRY(wprov.alloc(n_withdraws * sizeof(int32_t)));
+    HIP_TRY(wresult.alloc(n_withdraws * sizeof(int32_t)));
+    HIP_TRY(wamounts.alloc(n_withdraws * sizeof(uint64_t)));
+    HIP_TRY(wlist.alloc(n_withdraws * sizeof(uint32_t)));
+    HIP_TRY(wnlist.alloc(sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(wnlist.p, 0, sizeof(uint32_t), st));
+    if (int e = pool_resolve_table(st, n_withdraws, wslots, &wmask)) return e;
+    const PoolLogView view{dring.as<uint8_t>(), aslots.as<uint32_t>(), amask, akeys, SPP_AUDIT_PW_LEN};
+    launch_pool_screen_withdraw_log(st, view, audits, nullifiers, p->salt, wpws.as<uint8_t>(), wrecip.as<uint8_t>(), deposits_before, audits_before, nw,
+                                    wprov.as<int32_t>(), wamounts.as<uint64_t>(), wlist.as<uint32_t>(), wnlist.as<uint32_t>());
+    if (int e = pool_verify(p, st, 0, wproofs.as<uint8_t>(), wpws.as<uint8_t>(), SPP_WITHDRAW_PW_LEN, nw, wlist.as<uint32_t>(), wnlist.as<uint32_t>(), wok)) return e;
+    launch_pool_resolve(st, wslots.as<uint32_t>(), wmask, p->salt, wkeys, SPP_WITHDRAW_PW_LEN, nw, wprov.as<int32_t>(), wok.as<int32_t>(),
+                        POOL_NULLIFIER_USED, wresult.as<int32_t>());
+  }
+  // the commits, after the last screen; then log order
+  if (na) {
+    launch_pool_commit(st, audits, p->salt, akeys, SPP_AUDIT_PW_LEN, na, aresult.as<int32_t>(), p->d_counts + SPP_POOL_AUDIT_RECORDS);
+    launch_pool_scatter(st, audit_pos, na, aresult.as<int32_t>(), dall.as<int32_t>(), nullptr, nullptr);
+  }
+  if (nw) {
+    launch_pool_commit(st, nullifiers, p->salt, wkeys, SPP_WITHDRAW_PW_LEN, nw, wresult.as<int32_t>(), p->d_counts + SPP_POOL_NULLIFIERS);
+    launch_pool_scatter(st, withdraw_pos, nw, wresult.as<int32_t>(), dall.as<int32_t>(), wamounts.as<uint64_t>(),
+                        amounts ? dall_amounts.as<uint64_t>() : nullptr);
+  }
+  if (n_deposits) HIP_TRY(hipMemcpyAsync(p->d_state, &next, sizeof(PoolState), hipMemcpyHostToDevice, st));
+  // download
+  HIP_TRY(hipMemcpyAsync(result, dall.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (amounts) HIP_TRY(hipMemcpyAsync(amounts, dall_amounts.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (int e = pool_fetch_counts(p, st, cnt)) return e;
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  p->state = next;   // the host ring takes the batch's roots only now, after the stream has come through without an error
   p->counts[0] = cnt[0];
   p->counts[1] = cnt[1];
   return SPP_OK;

@@ -104,6 +104,7 @@ def _audit_open(a):
 
 _POOL_FIELDS = {"deposit": (("root", 32),), "submit_audit": (("proof", lib.PROOF_LEN), ("pw", lib.AUDIT_PW_LEN)),
                 "withdraw": (("proof", lib.PROOF_LEN), ("pw", lib.WITHDRAW_PW_LEN), ("recipient", 32))}
+_POOL_LOG_CHUNK = 1 << 24   # spp_pool_settle_log takes at most 2^24 instructions
 
 
 def parse_pool_log(lines):
@@ -137,22 +138,11 @@ def _pool_replay(a):
     ctx = Context(a.device)
     try:
         with witness.Pool(ctx, wvk, avk, capacity) as pool:
-            i = 0
-            while i < len(log):   # consecutive instructions of one kind are one batch: a batch is settled in order
-                j = i
-                while j < len(log) and log[j][0] == log[i][0]:
-                    j += 1
-                cols = list(zip(*(v for _, v in log[i:j])))
-                if log[i][0] == "deposit":
-                    pool.add_roots(cols[0])
-                    codes = [lib.SPP_POOL_OK] * (j - i)
-                elif log[i][0] == "submit_audit":
-                    codes = pool.submit_audit(cols[0], cols[1])
-                else:
-                    codes, _ = pool.withdraw(cols[0], cols[1], cols[2])
+            # the whole log in one call, whatever the interleaving of the kinds (consecutive chunks past 2^24 instructions)
+            for i in range(0, len(log), _POOL_LOG_CHUNK):
+                codes, _ = pool.settle_log([(kind,) + vals for kind, vals in log[i:i + _POOL_LOG_CHUNK]])
                 for c in codes:
                     print(lib.POOL_RESULT_NAMES[c])
-                i = j
     except lib.SppError as e:
         print("spp pool-replay: %s" % e, file=sys.stderr)
         return 2

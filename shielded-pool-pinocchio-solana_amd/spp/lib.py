@@ -32,6 +32,9 @@ SPP_POOL_BAD_ROOT = 3
 SPP_POOL_NULLIFIER_USED = 4
 SPP_POOL_BAD_RECIPIENT = 5
 SPP_POOL_BAD_PROOF = 6
+SPP_INSTR_DEPOSIT = 0               # kinds of spp_pool_settle_log
+SPP_INSTR_SUBMIT_AUDIT = 1
+SPP_INSTR_WITHDRAW = 2
 POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
 
 
@@ -130,6 +133,7 @@ def load_library():
     L.spp_pool_contains.argtypes = [vp, i32, sz, cp, vp]
     L.spp_pool_submit_audit_batch.argtypes = [vp, sz, cp, cp, vp]
     L.spp_pool_withdraw_batch.argtypes = [vp, sz, cp, cp, cp, vp, vp]
+    L.spp_pool_settle_log.argtypes = [vp, sz, cp, sz, cp, sz, cp, cp, sz, cp, cp, cp, vp, vp]
     L.spp_withdraw_rows_from_tree.argtypes = [vp, sz, cp, vp]
     L.spp_prove_withdraw_notes_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     L.spp_prove_withdraw_notes.argtypes = [vp, vp, sz, cp, cp, vp, vp, vp]

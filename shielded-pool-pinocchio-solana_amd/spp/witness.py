@@ -18,7 +18,7 @@ All of them take and return Python ints / lists; field elements cross the C ABI 
 import ctypes
 import numpy as np
 from .lib import (check, NOTE_LEN, DEPOSIT_LEN, PROOF_LEN, AUDIT_PW_LEN, WITHDRAW_PW_LEN, SPP_POOL_STATE_LEN,
-                  SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS)
+                  SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS, SPP_INSTR_DEPOSIT, SPP_INSTR_SUBMIT_AUDIT, SPP_INSTR_WITHDRAW)
 
 TREE_DEPTH = 16
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -317,6 +317,38 @@ class Pool:
         res = (ctypes.c_int32 * max(n, 1))()
         amounts = (ctypes.c_uint64 * max(n, 1))()
         check(self.ctx.L.spp_pool_withdraw_batch(self.h, n, pb, wb, rb, ctypes.cast(res, ctypes.c_void_p), ctypes.cast(amounts, ctypes.c_void_p)))
+        return list(res)[:n], [int(a) for a in amounts][:n]
+
+    _LOG_KINDS = {"deposit": (SPP_INSTR_DEPOSIT, 1), "submit_audit": (SPP_INSTR_SUBMIT_AUDIT, 2), "withdraw": (SPP_INSTR_WITHDRAW, 3)}
+
+    def settle_log(self, instructions):
+        """A log in which the kinds alternate, as the chain's does, in ONE call (spp_pool_settle_log): instructions is a sequence of
+        ("deposit", root), ("submit_audit", proof, pw) and ("withdraw", proof, pw, address) in the order the program processed
+        them; a withdraw meets the ring and the audit records as of its position.  Returns (codes, amounts) in log order; a deposit
+        gives SPP_POOL_OK, amounts are 0 except for withdraws."""
+        kinds, cols = bytearray(), ([], [], [], [], [], [])          # roots | audit proofs, pws | withdraw proofs, pws, addresses
+        for no, ins in enumerate(instructions):
+            kind, fields = self._LOG_KINDS.get(ins[0], (None, 0))
+            if kind is None or len(ins) != 1 + fields:
+                raise ValueError("instruction %d: (\"deposit\", root), (\"submit_audit\", proof, pw) or (\"withdraw\", proof, pw, address)" % no)
+            kinds.append(kind)
+            first = (0, 1, 3)[kind]
+            for k, v in enumerate(ins[1:]):
+                cols[first + k].append(v)
+        roots = _key_bytes(cols[0])
+        ap, aw = _joined(cols[1], PROOF_LEN, "proofs"), _joined(cols[2], AUDIT_PW_LEN, "audit public witnesses")
+        wp, ww = _joined(cols[3], PROOF_LEN, "proofs"), _joined(cols[4], WITHDRAW_PW_LEN, "withdraw public witnesses")
+        rb = _joined(cols[5], 32, "recipient addresses")
+        nd, na, nw = len(cols[0]), len(cols[1]), len(cols[3])
+        if len(roots) != 32 * nd or len(ap) != PROOF_LEN * na or len(aw) != AUDIT_PW_LEN * na or len(wp) != PROOF_LEN * nw or \
+                len(ww) != WITHDRAW_PW_LEN * nw or len(rb) != 32 * nw:
+            raise ValueError("settle_log: roots and addresses of 32 bytes, proofs of %d, public witnesses of %d (submit_audit) and %d (withdraw)"
+                             % (PROOF_LEN, AUDIT_PW_LEN, WITHDRAW_PW_LEN))
+        n = len(kinds)
+        res = (ctypes.c_int32 * max(n, 1))()
+        amounts = (ctypes.c_uint64 * max(n, 1))()
+        check(self.ctx.L.spp_pool_settle_log(self.h, n, bytes(kinds), nd, roots, na, ap, aw, nw, wp, ww, rb, ctypes.cast(res, ctypes.c_void_p),
+                                             ctypes.cast(amounts, ctypes.c_void_p)))
         return list(res)[:n], [int(a) for a in amounts][:n]
 
 
