@@ -456,6 +456,12 @@ int spp_ntt_fr(spp_ctx* ctx, uint8_t* data, uint32_t logn, int inverse);
 int spp_msm_g1(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, int window_bits, uint8_t out[64]);
 /* the same over G2: bases 128 B (gnark raw X.A1 | X.A0 | Y.A1 | Y.A0), out 128 B -- the table walk that produces a proof's Bs */
 int spp_msm_g2(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, int window_bits, uint8_t out[128]);
+/* The flat table walk of the proving sets (one table row per base, window passes put together by Horner) over caller-supplied bases:
+ * group 1 = G1 (64 B points), 2 = G2 (128 B); scalars = P rows of n (row p at scalars + 32 * n * p); out = P points.  n, P >= 1.
+ * redo_lanes (optional): lanes whose slice met an addition of a point to itself or to its negative and was summed again by the
+ * redo kernel (0 when all bases are distinct, up to coincidence). */
+int spp_msm_flat_unit(spp_ctx* ctx, int group, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t P, int window_bits, uint8_t* out,
+                      uint32_t* redo_lanes);
 
 /* General-base Pippenger (16-bit signed windows, bucket sort + accumulate + reduce) for large n; same conventions. */
 int spp_msm_g1_pippenger(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t out[64]);

@@ -258,7 +258,14 @@ struct XYZZ29 {
   }
 
   // this += (x2, +-y2); e = table entry (Fp words, not infinity)
-  SPP_HD void madd(const Affine<B>& e, bool negate) {
+  SPP_HD void madd(const Affine<B>& e, bool negate) { madd_any<false>(e, negate); }
+  // The same addition for a loop that keeps the same-x case out of its body (k_msm_flat): when the entry has the accumulator's x
+  // -- the doubling or the cancellation, which need e = +-(the accumulated point) -- nothing is added, the accumulator keeps every
+  // limb and the result is false; the caller sums that slice again with madd.  Every other case runs the statements of madd (one
+  // body, madd_any), so the lazy bounds and their certificates (tests/host/f29_bounds.py) are those of madd.
+  SPP_HD bool madd_distinct(const Affine<B>& e, bool negate) { return madd_any<true>(e, negate); }
+  template <bool DISTINCT>
+  SPP_HD bool madd_any(const Affine<B>& e, bool negate) {
     F x2 = F::from_words(e.x.l);                                         // limbs < 1, value < 2p
     F y2 = F::from_words(e.y.l);
     if (negate) y2 = F::template neg_lazy<Pm::SUBC_4P_1>(y2);            // limbs < 2 (2^30), value <= 4p
@@ -268,12 +275,13 @@ struct XYZZ29 {
       ZZ = F::template konst<Pm::K29_IN>();
       ZZZ = ZZ;
       inf = false;
-      return;
+      return true;
     }
     // statement order keeps few values alive at once (x2 dies first, then U2, P, PP, ...)
     const F U2 = x2 * ZZ;                                                // 1 x 1
     const F Pp = F::template sub_norm<Pm::SUBC_6P_1>(U2, X);             // normalised, < 7.1 p
     if (Pp.template is_zero_mod_p<7>()) {                                // same x: doubling or cancellation (rare)
+      if constexpr (DISTINCT) return false;
       const F S2 = y2 * ZZZ;
       const F Rr = F::template sub_norm<Pm::SUBC_2P_1>(S2, Y);
       if (Rr.template is_zero_mod_p<3>()) {
@@ -287,7 +295,7 @@ struct XYZZ29 {
       } else {
         inf = true;
       }
-      return;
+      return true;
     }
     const F PP = Pp.sqr();                                               // 1 x 1 -> < 1.3 p
     const F Q = X * PP;                                                  // < 1.05 p
@@ -301,6 +309,7 @@ struct XYZZ29 {
     const F T = F::template sub_lazy<Pm::SUBC_6P_1>(Q, X);               // limbs < 3, < 7.1 p
     const F Yn = F::template neg_lazy<Pm::SUBC_2P_1>(Y);                 // limbs < 2, <= 2p
     Y = F::mul2(Rr, T, Yn, PPP);                                         // 1x3 + 2x1 -> < 1.2 p
+    return true;
   }
 };
 
@@ -389,7 +398,11 @@ struct XYZZ29G2 {
   }
 
   // this += (x2, +-y2); e = table entry (Fq2 words, not infinity)
-  SPP_HD void madd(const Affine<Fq2>& e, bool negate) {
+  SPP_HD void madd(const Affine<Fq2>& e, bool negate) { madd_any<false>(e, negate); }
+  // as XYZZ29::madd_distinct: false and no limb changed when the entry has the accumulator's x
+  SPP_HD bool madd_distinct(const Affine<Fq2>& e, bool negate) { return madd_any<true>(e, negate); }
+  template <bool DISTINCT>
+  SPP_HD bool madd_any(const Affine<Fq2>& e, bool negate) {
     const E x2 = E::from_words(e.x);                                     // limbs < 1, value < 2p
     const E y2 = E::from_words(e.y);
     if (inf) {
@@ -408,7 +421,7 @@ struct XYZZ29G2 {
       }
       ZZZ = ZZ;
       inf = false;
-      return;
+      return true;
     }
     const E U2 = E::template mul<Pm::SUBC_4P_1>(x2, ZZ);                 // < 1.1 p
     const E Pp = E::template sub_norm<Pm::SUBC_6P_1>(U2, X);             // normalised, < 7.1 p
@@ -416,6 +429,7 @@ struct XYZZ29G2 {
     if (negate) S2 = E::template neg_lazy<Pm::SUBC_2P_1>(S2);            // limbs < 2, <= 2p
     const E Rr = E::template sub_norm<Pm::SUBC_2P_1>(S2, Y);             // normalised, < 4.1 p
     if (Pp.template is_zero_mod_p<7>()) {                                // same x: doubling or cancellation (rare)
+      if constexpr (DISTINCT) return false;
       if (Rr.template is_zero_mod_p<4>()) {
         XYZZ<Fq2> t = to_xyzz();
         t.dbl_inplace();
@@ -427,7 +441,7 @@ struct XYZZ29G2 {
       } else {
         inf = true;
       }
-      return;
+      return true;
     }
     const E PP = Pp.template sqr<Pm::SUBC_8P_1>();                       // < 2.3 p
     const E Q = E::template mul<Pm::SUBC_6P_1>(X, PP);                   // < 1.2 p
@@ -455,6 +469,7 @@ struct XYZZ29G2 {
     F::mac(c, nY1, PPP.c0);
     Y.c0 = y0;
     Y.c1 = F::reduce(c);
+    return true;
   }
 };
 

@@ -214,19 +214,25 @@ void launch_qap_product(hipStream_t st, Fr* abc, uint32_t n, uint32_t P);   // a
 // A base carries Wt table rows of 2^(c-1) affine multiples; row m = multiples of 2^(c*R*m) * Base, R = ceil(W / Wt) window passes
 // (W = ceil(254 / c) windows per scalar).  Wt = W: one row per window, no passes (the small-table latency layout).  Wt = 1: one row
 // per base and W passes whose sums are combined by Horner (the throughput layout: widest window for the bytes).
-// What tells the G1 walk from the G2 walk, in one place: k_msm_flat takes its launch bound and its loop form from here, and the
-// host passes waves_per_simd to msm_plan / msm_partial_cap as `occ`, so the planner counts the waves the launch bound allows.
+// What tells the G1 walk from the G2 walk, in one place: k_msm_flat and k_msm_flat_redo take their launch bound and the fast walk
+// its loop form from here, and the host passes occ(Wt) to msm_plan / msm_partial_cap, so the planner counts the waves the kernel it
+// plans for can have resident.  The flat walk keeps the same-x case of the mixed addition out of its loop (msm_table.hpp), which
+// is what its register counts rest on; k_msm_rows adds with the inline path and keeps the occupancy it had.
 template <class F>
 struct MsmWalk;
 template <>
 struct MsmWalk<Fq> {
-  static constexpr uint32_t waves_per_simd = 2;    // at most 256 VGPRs
-  static constexpr bool gather_ahead = false;      // the other resident wave hides a gather
+  static constexpr uint32_t waves_per_simd = 2;         // flat walk: at most 256 VGPRs (it takes 182)
+  static constexpr uint32_t rows_waves_per_simd = 2;    // k_msm_rows
+  static constexpr bool gather_ahead = false;           // the other resident wave hides a gather
+  static constexpr uint32_t occ(uint32_t Wt) { return Wt == 1 ? waves_per_simd : rows_waves_per_simd; }
 };
 template <>
 struct MsmWalk<Fq2> {
-  static constexpr uint32_t waves_per_simd = 1;    // up to 512 VGPRs
-  static constexpr bool gather_ahead = true;       // one-deep software pipeline of the table gathers (k_msm_flat)
+  static constexpr uint32_t waves_per_simd = 2;         // flat walk: at most 256 VGPRs, no AGPRs
+  static constexpr uint32_t rows_waves_per_simd = 1;    // k_msm_rows: up to 512 registers
+  static constexpr bool gather_ahead = false;           // as for G1
+  static constexpr uint32_t occ(uint32_t Wt) { return Wt == 1 ? waves_per_simd : rows_waves_per_simd; }
 };
 // builds rows [row0, row0 + nrows) (row = base * Wt + m; row0 a multiple of 64) of the table of N bases, E entries each;
 // tmp / tmp_pre: nrows * E elements each.  blocks = nullptr: the uniform layout, E = 2^(c-1) for every row; else the ragged layout
@@ -239,7 +245,7 @@ void launch_msm_digits(hipStream_t st, const uint32_t* rows, const Fr* scalars, 
 // lane g -> (pass, slice, proof); partial[R * Sg][P].  blocks: the block table of a flat set (pl.Wt == 1), required there
 template <class F>
 void launch_msm_accumulate(hipStream_t st, const Affine<F>* table, const MsmBlock* blocks, const int16_t* dig, XYZZ<F>* partial, uint32_t N, uint32_t P,
-                           uint32_t c, const MsmPlan& pl, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                           uint32_t c, const MsmPlan& pl, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, uint32_t* redo_count = nullptr);
 // out[p] = sum over slices and passes (empty: out[p] = infinity); folds in place: `partial` is scratch afterwards
 template <class F>
 void launch_msm_reduce(hipStream_t st, XYZZ<F>* partial, XYZZ<F>* out, uint32_t P, const MsmPlan& pl, uint32_t c, bool empty);

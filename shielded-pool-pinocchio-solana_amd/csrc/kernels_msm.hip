@@ -8,7 +8,7 @@ namespace spp {
 template void launch_build_table<Fq>(hipStream_t, const Affine<Fq>*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, Affine<Fq>*,
                                      XYZZ<Fq>*, Fq*, const MsmBlock*, uint32_t);
 template void launch_msm_accumulate<Fq>(hipStream_t, const Affine<Fq>*, const MsmBlock*, const int16_t*, XYZZ<Fq>*, uint32_t, uint32_t, uint32_t,
-                                        const MsmPlan&, hipEvent_t, hipEvent_t);
+                                        const MsmPlan&, hipEvent_t, hipEvent_t, uint32_t*);
 template void launch_msm_reduce_multi<Fq>(hipStream_t, MsmFoldSets<Fq>, uint32_t, uint32_t);
 template void launch_msm_reduce<Fq>(hipStream_t, XYZZ<Fq>*, XYZZ<Fq>*, uint32_t, const MsmPlan&, uint32_t, bool);
 template void launch_fixed_base_mul<Fq>(hipStream_t, const Affine<Fq>*, uint32_t, const Fr*, uint32_t, Affine<Fq>*);

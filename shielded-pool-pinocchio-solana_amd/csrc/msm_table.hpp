@@ -18,10 +18,11 @@
 // slices of the base range to fill 256 CUs; the slice sums of every (pass, proof) are folded pairwise.
 //
 // This header holds every kernel of the walk that is a template over the coordinate field F, with its launcher.  Two translation
-// units instantiate it: kernels_msm.hip for Fq (G1), built with the scheduler strategy max-ilp -- the G1 walk is 2 % faster for
-// it, 203 registers, two waves per SIMD -- and kernels_msm_g2.hip for Fq2 (G2) with the default scheduler: max-ilp makes
-// the 512-register G2 walk spill and 4 % slower.  What differs between the two walks is MsmWalk<F> (kernels.hpp); the host-side
-// planning is msm_plan.hpp.
+// units instantiate it: kernels_msm.hip for Fq (G1), built with the scheduler strategy max-ilp -- the G1 walk was 2 % faster for
+// it (measured when it took 203 registers; 182 now, two waves per SIMD) -- and kernels_msm_g2.hip for Fq2 (G2) with the default
+// scheduler: max-ilp made the G2 walk spill and 4 % slower when it ran one wave per SIMD, and the unit's flags have not been
+// touched since (201 registers, two waves per SIMD now).  What differs between the two walks is MsmWalk<F> (kernels.hpp); the
+// host-side planning is msm_plan.hpp.
 #pragma once
 #include <hip/hip_ext.h>
 #include "kernels.hpp"
@@ -165,6 +166,11 @@ struct MsmAcc<Fq> {
     if (words_all_zero(e.x) && words_all_zero(e.y)) return;   // table row of an infinity base (spp_msm_g1 callers)
     a.madd(e, sgn);
   }
+  // false: the entry has the accumulator's x, nothing was added (XYZZ29::madd_distinct)
+  __device__ __forceinline__ bool madd_distinct(const Affine<Fq>& e, bool sgn) {
+    if (words_all_zero(e.x) && words_all_zero(e.y)) return true;
+    return a.madd_distinct(e, sgn);
+  }
   __device__ __forceinline__ XYZZ<Fq> result() const { return a.to_xyzz(); }
 };
 
@@ -176,6 +182,10 @@ struct MsmAcc<Fq2> {
     if (words_all_zero(e.x.c0) && words_all_zero(e.x.c1) && words_all_zero(e.y.c0) && words_all_zero(e.y.c1)) return;
     a.madd(e, sgn);
   }
+  __device__ __forceinline__ bool madd_distinct(const Affine<Fq2>& e, bool sgn) {
+    if (words_all_zero(e.x.c0) && words_all_zero(e.x.c1) && words_all_zero(e.y.c0) && words_all_zero(e.y.c1)) return true;
+    return a.madd_distinct(e, sgn);
+  }
   __device__ __forceinline__ XYZZ<Fq2> result() const { return a.to_xyzz(); }
 };
 
@@ -183,26 +193,47 @@ struct MsmAcc<Fq2> {
 // throughput layout (Wt = 1): one table row per base, slice sl takes bases sl, sl + Sg, ... (neighbouring wires have similar
 // scalar sizes -- runs of bits, runs of hash states -- so a strided split gives every slice the same mix).  The digits of
 // four bases are fetched ahead of their additions (2 B each, packed into one register pair).
+//
+// The same-x case is not in the loop.  A mixed addition whose entry has the accumulator's x is a doubling or a cancellation: the
+// entry is +-(the sum so far), which a proving key produces by coincidence or with duplicate bases only.  Inline, that path
+// (to_xyzz, dbl_inplace, from_xyzz) never ran and still set the register budget of the whole loop: 203 VGPRs for G1, and for G2
+// 256 VGPRs + 242 AGPRs, one wave per SIMD.  The fast walk adds with madd_distinct (f29.hpp): a lane whose addition is refused
+// leaves the loop and stores the redo marker in place of its slice sum; k_msm_flat_redo, launched behind every fast walk, sums the
+// slices of marked lanes again with the complete addition and returns at once for every other lane.  Register counts and what
+// the two walks gained: profiles/walk_redo_resources.txt, DESIGN 8.1.
+//
+// Redo marker: the all-zero XYZZ<F>.  No slice sum is all zero: infinity is stored as (1, 1, 0, 0) with the non-zero words of
+// F::one() in X, and a finite sum has ZZ != 0 mod p, hence a non-zero word in ZZ (to_xyzz stores residues, zero words only for the
+// residue 0).  The marker test reads X and ZZ.
+//
 // One wave per workgroup (MSM_WALK_BLOCK): a 256-lane workgroup needs FOUR free wave slots of a CU at once, and with 2 slots per SIMD and waves of
 // unequal length (passes over sparse windows are shorter) a finished wave's slot waited for three more -- 1.79 resident waves per SIMD
-// on average where 2 fit.  (The second launch-bound, MsmWalk<F>::waves_per_simd, keeps the G1 walk within 256 registers = two waves per SIMD; the planner
+// on average where 2 fit.  (The second launch-bound, MsmWalk<F>::waves_per_simd, is the register budget of both kernels; the planner
 // reads the same figure.)
 template <class F>
-__global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_msm_flat(const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
-                                                  const int16_t* __restrict__ dig, XYZZ<F>* __restrict__ partial, uint32_t N, uint32_t P,
-                                                  uint32_t Pp, uint32_t R, uint32_t Sg) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t p = g % Pp, t = g / Pp;
-  if (t >= R * Sg || p >= P) return;
-  const uint32_t rho = t / Sg, sl = t % Sg;
-  const int16_t* __restrict__ dg = dig + ((size_t)rho * N) * Pp + p;
-  MsmAcc<F> acc;
-  acc.init();
-  if constexpr (MsmWalk<F>::gather_ahead) {
-    // G2: one wave per SIMD (512 registers), nothing else to run while a gather is in flight -- the counters of the first
-    // version showed 59 % VALU issue.  One-deep software pipeline: the entry of the next non-zero digit is requested BEFORE the
-    // pending addition is computed.  A last pass over the loop body (flush) retires the pending addition, so that the ~40 KB
-    // of a G2 mixed addition are instantiated once.
+__device__ __forceinline__ void msm_store_redo_marker(XYZZ<F>* out) {
+  static_assert(sizeof(XYZZ<F>) % 16 == 0, "stored as 16-byte words");
+  uint4* w = reinterpret_cast<uint4*>(out);
+  SPP_UNROLL for (uint32_t i = 0; i < sizeof(XYZZ<F>) / 16; i++) w[i] = make_uint4(0, 0, 0, 0);
+}
+template <class F>
+__device__ __forceinline__ bool msm_is_redo_marker(const XYZZ<F>* v) {
+  const uint32_t* x = reinterpret_cast<const uint32_t*>(&v->X);
+  const uint32_t* zz = reinterpret_cast<const uint32_t*>(&v->ZZ);
+  uint32_t o = 0;
+  SPP_UNROLL for (uint32_t i = 0; i < sizeof(F) / 4; i++) o |= x[i] | zz[i];
+  return o == 0;
+}
+// acc += the entries of slice sl in pass rho (dg = the digit rows of that pass for this lane's proof).  FAST: the additions are
+// madd_distinct, and the walk ends with false at the first one that is refused (acc is then no sum of anything); else the complete
+// madd, always true.
+template <class F, bool FAST>
+__device__ __forceinline__ bool msm_flat_walk(MsmAcc<F>& acc, const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
+                                              const int16_t* __restrict__ dg, uint32_t N, uint32_t Pp, uint32_t sl, uint32_t Sg) {
+  if constexpr (FAST && MsmWalk<F>::gather_ahead) {
+    // One-deep software pipeline: the entry of the next non-zero digit is requested BEFORE the pending addition is computed (for a
+    // walk whose SIMD has nothing else to run while a gather is in flight).  A last pass over the loop body (flush) retires the
+    // pending addition, so that the mixed addition is instantiated once.
     int d_next = 0;
     Affine<F> e_next;
     for (uint32_t i0 = sl;; i0 += 4 * Sg) {
@@ -223,11 +254,11 @@ __global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_
         const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
         MsmBlock blk{};
         if (d != 0) blk = blocks[i >> 6];
-        if (mag > blk.E) d = 0;   // see the G1 loop below
+        if (mag > blk.E) d = 0;   // see the loop below
         if (d != 0 || flush) {
           Affine<F> e;
           if (d != 0) e = table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)];
-          if (d_next != 0) acc.madd(e_next, d_next < 0);
+          if (d_next != 0 && !acc.madd_distinct(e_next, d_next < 0)) return false;
           d_next = d;
           if (d != 0) e_next = e;
         }
@@ -255,12 +286,53 @@ __global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_
           const uint32_t i = i0 + k * Sg;
           const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
           const MsmBlock blk = blocks[i >> 6];
-          if (mag <= blk.E) acc.madd(table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)], d < 0);
+          if (mag <= blk.E) {
+            const Affine<F> e = table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)];
+            if constexpr (FAST) {
+              if (!acc.madd_distinct(e, d < 0)) return false;
+            } else {
+              acc.madd(e, d < 0);
+            }
+          }
         }
       }
     }
   }
-  partial[(size_t)t * P + p] = acc.result();
+  return true;
+}
+template <class F>
+__global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_msm_flat(const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
+                                                  const int16_t* __restrict__ dig, XYZZ<F>* __restrict__ partial, uint32_t N, uint32_t P,
+                                                  uint32_t Pp, uint32_t R, uint32_t Sg) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t p = g % Pp, t = g / Pp;
+  if (t >= R * Sg || p >= P) return;
+  const uint32_t rho = t / Sg, sl = t % Sg;
+  MsmAcc<F> acc;
+  acc.init();
+  if (msm_flat_walk<F, true>(acc, table, blocks, dig + ((size_t)rho * N) * Pp + p, N, Pp, sl, Sg)) partial[(size_t)t * P + p] = acc.result();
+  else msm_store_redo_marker(partial + (size_t)t * P + p);
+}
+// Behind every k_msm_flat, same grid and arguments: a lane whose slice sum is the redo marker sums its slice again with the complete
+// addition (the loop without the gather pipeline); every other lane returns at once.  Bounded to the registers of the fast walk
+// it follows (it may use scratch: it is cold) -- with more it would wait for a whole SIMD to drain behind the MSM waves of the other
+// batch in flight.  When every lane is marked (one base repeated) this is the walk with the inline same-x path.  redo_count
+// (optional): the number of lanes that walked again.
+template <class F>
+__global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_msm_flat_redo(const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
+                                                  const int16_t* __restrict__ dig, XYZZ<F>* __restrict__ partial, uint32_t N, uint32_t P,
+                                                  uint32_t Pp, uint32_t R, uint32_t Sg, uint32_t* __restrict__ redo_count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t p = g % Pp, t = g / Pp;
+  if (t >= R * Sg || p >= P) return;
+  XYZZ<F>* out = partial + (size_t)t * P + p;
+  if (!msm_is_redo_marker(out)) return;
+  if (redo_count) atomicAdd(redo_count, 1u);
+  const uint32_t rho = t / Sg, sl = t % Sg;
+  MsmAcc<F> acc;
+  acc.init();
+  msm_flat_walk<F, false>(acc, table, blocks, dig + ((size_t)rho * N) * Pp + p, N, Pp, sl, Sg);
+  *out = acc.result();
 }
 
 // general layout (Wt rows per base; Q > 1: the rows of a base are shared by Q lanes, items = (base, chunk of Wq rows) in
@@ -304,18 +376,21 @@ __global__ void __launch_bounds__(256) k_msm_rows(const Affine<F>* __restrict__ 
 // ev_start / ev_stop (optional): receive the dispatch's own start and stop timestamps (hipExtLaunchKernelGGL), i.e. the
 // kernel's duration as a profiler reports it -- an event pair recorded around the launch would also count the time the
 // launch waits for kernels of the other proving stream.
+// The flat walk is two launches: the fast walk, which the event pair times, and the redo kernel behind it.  redo_count: see there.
 template <class F>
 void launch_msm_accumulate(hipStream_t st, const Affine<F>* table, const MsmBlock* blocks, const int16_t* dig, XYZZ<F>* partial, uint32_t N, uint32_t P,
-                           uint32_t c, const MsmPlan& pl, hipEvent_t ev_start, hipEvent_t ev_stop) {
+                           uint32_t c, const MsmPlan& pl, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t* redo_count) {
   if (N == 0 || P == 0) {
     if (ev_start) hipEventRecord(ev_start, st);
     if (ev_stop) hipEventRecord(ev_stop, st);
     return;
   }
   const uint64_t lanes = (uint64_t)pl.R * pl.Sg * pl.Pp;
-  if (pl.Wt == 1)
-    hipExtLaunchKernelGGL(k_msm_flat<F>, dim3((uint32_t)((lanes + MSM_WALK_BLOCK - 1) / MSM_WALK_BLOCK)), dim3(MSM_WALK_BLOCK), 0, st, ev_start, ev_stop, 0, table, blocks, dig, partial, N, P, pl.Pp, pl.R, pl.Sg);
-  else
+  if (pl.Wt == 1) {
+    const dim3 grid((uint32_t)((lanes + MSM_WALK_BLOCK - 1) / MSM_WALK_BLOCK));
+    hipExtLaunchKernelGGL(k_msm_flat<F>, grid, dim3(MSM_WALK_BLOCK), 0, st, ev_start, ev_stop, 0, table, blocks, dig, partial, N, P, pl.Pp, pl.R, pl.Sg);
+    hipLaunchKernelGGL(k_msm_flat_redo<F>, grid, dim3(MSM_WALK_BLOCK), 0, st, table, blocks, dig, partial, N, P, pl.Pp, pl.R, pl.Sg, redo_count);
+  } else
     hipExtLaunchKernelGGL(k_msm_rows<F>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, ev_start, ev_stop, 0, table, dig, partial, N, P, pl.Pp, c,
                           pl.Wt, pl.R, pl.W, pl.Sg, pl.Q, pl.Wq);
 }

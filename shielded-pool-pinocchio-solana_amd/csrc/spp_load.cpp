@@ -905,7 +905,7 @@ static int msm_fixed_unit(spp_ctx* ctx, const uint8_t* bases, const uint8_t* sca
   uint32_t* d_rows = nullptr;
   XYZZ<F> *partial = nullptr, *d_out = nullptr;
   DevBuf dig;
-  const MsmPlan pl = msm_plan((uint32_t)n, 1, cb, Wn, MsmWalk<F>::waves_per_simd, read_switches().msm);
+  const MsmPlan pl = msm_plan((uint32_t)n, 1, cb, Wn, MsmWalk<F>::occ(Wn), read_switches().msm);
   if (!e) e = own_upload(&tmpc, &d_sc, sc);
   if (!e) e = own_upload(&tmpc, &d_rows, rows);
   if (!e && hipMalloc((void**)&partial, sizeof(XYZZ<F>) * std::max<size_t>(pl.partial_elems(1), 1)) != hipSuccess) e = fail(SPP_ERR_HIP, "hipMalloc");
@@ -932,4 +932,70 @@ extern "C" int spp_msm_g1(spp_ctx* ctx, const uint8_t* bases, const uint8_t* sca
 // the same walk over G2 bases (128 B, gnark raw X.A1|X.A0|Y.A1|Y.A0): what Bs of a proof comes from (k_msm_fixed<Fq2>)
 extern "C" int spp_msm_g2(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, int window_bits, uint8_t out[128]) {
   return msm_fixed_unit<Fq2, 128>(ctx, bases, scalars, n, window_bits, out);
+}
+
+// The flat walk (one table row per base, the throughput layout of the proving sets) over caller-supplied bases: P scalar rows against
+// one table, launched as run_msm launches a flat set -- digits, the fast walk, the redo kernel, the folds, Horner.  The block list is
+// uniform (every block holds 2^(c-1) entries per row).  redo_lanes (optional): how many lanes the redo kernel walked again.
+template <class F, size_t PT_BYTES>
+static int msm_flat_unit(spp_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t P, int window_bits, uint8_t* out,
+                         uint32_t* redo_lanes) {
+  if (!ctx || !out || !bases || !scalars || n == 0 || P == 0) return fail(SPP_ERR_BAD_INPUT, "NULL or empty argument");
+  if (window_bits == 0) window_bits = 8;
+  if (window_bits < 4 || window_bits > 16) return fail(SPP_ERR_BAD_INPUT, "window_bits outside [4,16]");
+  if (n > (1u << 20) || P > (1u << 16)) return fail(SPP_ERR_BAD_INPUT, "too many bases or rows");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const uint32_t cb = (uint32_t)window_bits, N = (uint32_t)n, Pn = (uint32_t)P, E = 1u << (cb - 1);
+  if ((uint64_t)msm_table_elems(N, cb, 1) * PT_BYTES > ((uint64_t)64 << 30)) return fail(SPP_ERR_BAD_INPUT, "table would exceed 64 GiB; use a smaller window");
+  std::vector<Affine<F>> pts(n);
+  std::vector<Fr> sc(n * P);                 // [base][row]: what the digit kernel reads
+  std::vector<uint32_t> rows(n);
+  for (size_t i = 0; i < n; i++) {
+    pts[i] = point_from_raw<F>(bases + PT_BYTES * i);
+    rows[i] = (uint32_t)i;
+    for (size_t p = 0; p < P; p++) sc[i * P + p] = Fr::from_bytes_be(scalars + 32 * (p * n + i));
+  }
+  std::vector<MsmBlock> blocks(msm_table_rows(n, 1) / 64);
+  for (size_t b = 0; b < blocks.size(); b++) blocks[b] = {(uint64_t)b * E, E, 0};
+  spp_circuit tmpc;   // only used as an owner of device allocations
+  tmpc.ctx = ctx;
+  tmpc.c_bits = cb;
+  Affine<F>* table = nullptr;
+  int e = build_table_chunked<F>(&tmpc, pts, cb, 1, &table);
+  Fr* d_sc = nullptr;
+  uint32_t* d_rows = nullptr;
+  MsmBlock* d_blocks = nullptr;
+  const MsmPlan pl = msm_plan(N, Pn, cb, 1, MsmWalk<F>::occ(1), read_switches().msm);
+  DevBuf partial, d_out, dig, count;
+  if (!e) e = own_upload(&tmpc, &d_sc, sc);
+  if (!e) e = own_upload(&tmpc, &d_rows, rows);
+  if (!e) e = own_upload(&tmpc, &d_blocks, blocks);
+  if (!e && (partial.alloc(sizeof(XYZZ<F>) * pl.partial_elems(Pn)) != hipSuccess || d_out.alloc(sizeof(XYZZ<F>) * P) != hipSuccess ||
+             dig.alloc(sizeof(int16_t) * msm_digit_elems(N, Pn, cb)) != hipSuccess || count.alloc(sizeof(uint32_t)) != hipSuccess))
+    e = fail(SPP_ERR_HIP, "hipMalloc");
+  std::vector<XYZZ<F>> res(P);
+  uint32_t redone = 0;
+  if (!e) {
+    hipMemsetAsync(count.p, 0, sizeof(uint32_t), st);
+    launch_msm_digits(st, d_rows, d_sc, dig.as<int16_t>(), N, Pn, cb);
+    launch_msm_accumulate<F>(st, table, d_blocks, dig.as<int16_t>(), partial.as<XYZZ<F>>(), N, Pn, cb, pl, nullptr, nullptr, count.as<uint32_t>());
+    launch_msm_reduce<F>(st, partial.as<XYZZ<F>>(), d_out.as<XYZZ<F>>(), Pn, pl, cb, false);
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) e = fail(SPP_ERR_HIP, "msm kernels failed");
+    else if (hipMemcpy(res.data(), d_out.p, sizeof(XYZZ<F>) * P, hipMemcpyDeviceToHost) != hipSuccess ||
+             hipMemcpy(&redone, count.p, sizeof redone, hipMemcpyDeviceToHost) != hipSuccess)
+      e = fail(SPP_ERR_HIP, "copy back failed");
+  }
+  for (void* p : tmpc.owned) hipFree(p);
+  if (e) return e;
+  for (size_t p = 0; p < P; p++) point_to_raw(res[p].to_affine(), out + PT_BYTES * p);
+  if (redo_lanes) *redo_lanes = redone;
+  return SPP_OK;
+}
+extern "C" int spp_msm_flat_unit(spp_ctx* ctx, int group, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t P, int window_bits,
+                                 uint8_t* out, uint32_t* redo_lanes) {
+  if (group == 1) return msm_flat_unit<Fq, 64>(ctx, bases, n, scalars, P, window_bits, out, redo_lanes);
+  if (group == 2) return msm_flat_unit<Fq2, 128>(ctx, bases, n, scalars, P, window_bits, out, redo_lanes);
+  return fail(SPP_ERR_BAD_INPUT, "group is 1 or 2");
 }

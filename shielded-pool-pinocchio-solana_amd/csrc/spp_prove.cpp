@@ -11,7 +11,7 @@ static int ws_alloc(Workspace& w, T** p, size_t count) {
 }
 template <class F>
 static int ws_set(const spp_circuit* c, Workspace& w, const MsmSet<F>* s, MsmBuf<F>* b, size_t P) {
-  b->partial_cap = msm_partial_cap(s->N, P, s->c, s->Wt, MsmWalk<F>::waves_per_simd, c->sw.msm);
+  b->partial_cap = msm_partial_cap(s->N, P, s->c, s->Wt, MsmWalk<F>::occ(s->Wt), c->sw.msm);
   int e;
   if ((e = ws_alloc(w, &b->partial, b->partial_cap))) return e;
   return ws_alloc(w, &b->out, P);
@@ -58,7 +58,7 @@ static void run_msm(spp_circuit* c, Workspace& w, const MsmSet<F>& s, MsmBuf<F>&
                     std::pair<hipEvent_t, hipEvent_t>* ev_override = nullptr, bool fold = true, const Fr* scal_override = nullptr) {
   hipStream_t st = st_override ? st_override : w.st;
   const Fr* scal = scal_override ? scal_override : s.from_h ? w.abc : w.W;
-  MsmPlan pl = msm_plan(s.N, P, s.c, s.Wt, MsmWalk<F>::waves_per_simd, c->sw.msm);
+  MsmPlan pl = msm_plan(s.N, P, s.c, s.Wt, MsmWalk<F>::occ(s.Wt), c->sw.msm);
   pl.fit(P, b.partial_cap);   // never exceed the allocated partial buffer
   b.plan = pl;
   std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;

@@ -86,6 +86,19 @@ class Context:
         check(self.L.spp_msm_g2(self.h, bases_bytes, sc, len(scalars), int(window_bits), ctypes.cast(out, ctypes.c_void_p)))
         return out.raw
 
+    def msm_flat(self, group, bases_bytes, scalar_rows, window_bits=8):
+        """The flat table walk of the proving sets over caller-supplied bases (spp_msm_flat_unit): group 1 = G1, 2 = G2;
+        scalar_rows = P lists of n ints.  Returns (list of P points as raw bytes, lanes summed again by the redo kernel)."""
+        size = 64 if group == 1 else 128
+        n = len(scalar_rows[0])
+        assert all(len(r) == n for r in scalar_rows) and len(bases_bytes) == size * n
+        out = ctypes.create_string_buffer(size * len(scalar_rows))
+        sc = b"".join(int(s).to_bytes(32, "big") for r in scalar_rows for s in r)
+        redo = ctypes.c_uint32(0)
+        check(self.L.spp_msm_flat_unit(self.h, int(group), bases_bytes, n, sc, len(scalar_rows), int(window_bits),
+                                       ctypes.cast(out, ctypes.c_void_p), ctypes.byref(redo)))
+        return [out.raw[size * p:size * (p + 1)] for p in range(len(scalar_rows))], redo.value
+
     def msm_g1_pippenger(self, bases_bytes, scalars):
         out = ctypes.create_string_buffer(64)
         sc = b"".join(int(s).to_bytes(32, "big") for s in scalars)
