@@ -28,6 +28,18 @@ static constexpr uint32_t COEFF_ONE = 0x80000000u;
 static constexpr uint32_t COEFF_MINUS_ONE = 0x40000000u;
 static constexpr uint32_t COEFF_MASK = 0x3fffffffu;
 
+// Poseidon / Poseidon2 constants in HBM (Montgomery form): one upload per context (spp_ensure_ctx_consts), read by the solver
+// through DevCircuit::hc and by the stand-alone hash kernels
+struct HashConsts {
+  // the Poseidon round constants are canonical words (< p): poseidon29.hpp's value bounds rely on it
+  const Fr* pos3_rc;  const Fr* pos3_mds;   // t=3: 195 rc, 9 mds (row-major)
+  const Fr* pos5_rc;  const Fr* pos5_mds;   // t=5: 340 rc, 25 mds
+  const Fr* p2_rc;    const Fr* p2_mu;      // 88 rc, 4 mu
+  // Poseidon MDS matrices in the 9x29-bit form, scaled by 2^261 (f29.hpp): mont29(state word, entry) stays an x*2^256 word
+  const uint32_t* pos3_mds29;               // 9 x 9 limbs
+  const uint32_t* pos5_mds29;               // 25 x 9 limbs
+};
+
 struct DevCircuit {
   DevSparse A, B, C, H;
   const Fr* coeffs;
@@ -66,23 +78,8 @@ struct DevCircuit {
   const uint32_t* lg_rows;      // (matrix << 30) | constraint
   uint32_t lg_n;
   const uint8_t* row_long;      // the bits of the long rows alone (what k_spmv_check reads when the small-row path is off)
-  // hash constants (Montgomery)
-  const Fr* pos3_rc;  const Fr* pos3_mds;   // t=3: 195 rc, 9 mds (row-major)
-  const Fr* pos5_rc;  const Fr* pos5_mds;   // t=5: 340 rc, 25 mds
-  const Fr* p2_rc;    const Fr* p2_mu;      // 88 rc, 4 mu
+  HashConsts hc;                            // the context's hash constants
   const Fr* byte_mont;                      // Montgomery forms of 0..255
-  // Poseidon MDS matrices in the 9x29-bit form, scaled by 2^261 (f29.hpp): mont29(state word, entry) stays an x*2^256 word
-  const uint32_t* pos3_mds29;               // 9 x 9 limbs
-  const uint32_t* pos5_mds29;               // 25 x 9 limbs
-};
-
-// Poseidon / Poseidon2 constants in HBM (Montgomery form), shared by the solver and the stand-alone hash kernels
-struct HashConsts {
-  const Fr* pos3_rc;  const Fr* pos3_mds;   // rc words canonical (< p): poseidon29.hpp's value bounds rely on it
-  const Fr* pos5_rc;  const Fr* pos5_mds;
-  const Fr* p2_rc;    const Fr* p2_mu;
-  const uint32_t* pos3_mds29;               // MDS entries * 2^261 in 9 x 29-bit limbs (poseidon29.hpp)
-  const uint32_t* pos5_mds29;
 };
 
 // ---- stand-alone witness-input kernels (kernels_witness.hip) ----

@@ -11,7 +11,7 @@
 #include "kernels.hpp"
 #include "circuit.hpp"   // opcodes only
 #include "poseidon29.hpp"
-#include "lanes.hpp"
+#include "poseidon2.hpp"
 #include "gnark_hints.hpp"
 #include "sha256.hpp"
 
@@ -66,18 +66,13 @@ void launch_load_inputs(hipStream_t st, const uint8_t* d_inputs_be, const uint8_
 // ---------------------------------------------------------------------------------------------------
 // native permutations
 // ---------------------------------------------------------------------------------------------------
-// Poseidon and Poseidon2 S-boxes: x^2, x^3, x^4, x^5 (csrc/circuit.cpp sbox5)
-__device__ __forceinline__ Fr dev_sbox_emit(const Fr& x, Fr* __restrict__ W, uint32_t& out, uint32_t P, uint32_t p) {
-  Fr x2 = x.sqr();
-  Fr x3 = x2 * x;
-  Fr x4 = x2.sqr();
-  Fr x5 = x4 * x;
+// the four powers x^2, x^3, x^4, x^5 of an S-box input: wires out .. out + 3 (csrc/circuit.cpp sbox5)
+__device__ __forceinline__ void emit4(Fr* __restrict__ W, uint32_t out, uint32_t P, uint32_t p, const Fr& x2, const Fr& x3, const Fr& x4,
+                                      const Fr& x5) {
   W[(size_t)out * P + p] = x2;
   W[(size_t)(out + 1) * P + p] = x3;
   W[(size_t)(out + 2) * P + p] = x4;
   W[(size_t)(out + 3) * P + p] = x5;
-  out += 4;
-  return x5;
 }
 
 template <int T>
@@ -91,63 +86,13 @@ __device__ __noinline__ void dev_poseidon29(Fr (&st)[T], const Fr* __restrict__ 
   });
 }
 
-template <int T>
-__device__ __noinline__ void dev_poseidon(Fr (&s)[T], const Fr* __restrict__ rc, const Fr* __restrict__ mds, int rp, Fr* __restrict__ W,
-                                          uint32_t out, uint32_t P, uint32_t p) {
-  const int rf = 8;
-#pragma unroll 1
-  for (int r = 0; r < rf + rp; r++) {
-    SPP_UNROLL for (int i = 0; i < T; i++) s[i] = s[i] + rc[r * T + i];
-    const bool full = r < rf / 2 || r >= rf / 2 + rp;
-    if (full) {
-      SPP_UNROLL for (int i = 0; i < T; i++) s[i] = dev_sbox_emit(s[i], W, out, P, p);
-    } else {
-      s[0] = dev_sbox_emit(s[0], W, out, P, p);
-    }
-    Fr nx[T];
-    SPP_UNROLL for (int i = 0; i < T; i++) {
-      nx[i] = mds[i * T] * s[0];
-      SPP_UNROLL for (int j = 1; j < T; j++) nx[i] = nx[i] + mds[i * T + j] * s[j];
-    }
-    SPP_UNROLL for (int i = 0; i < T; i++) s[i] = nx[i];
-  }
-}
-
-__device__ __forceinline__ void dev_p2_external(Fr (&s)[4]) {
-  // rows (5,7,1,3),(4,6,1,1),(1,3,5,7),(1,1,4,6)
-  Fr t01 = s[0] + s[1], t23 = s[2] + s[3];
-  Fr d0 = s[0].dbl(), d1 = s[1].dbl(), d2 = s[2].dbl(), d3 = s[3].dbl();
-  Fr q0 = d0.dbl(), q1 = d1.dbl(), q2 = d2.dbl(), q3 = d3.dbl();
-  Fr n0 = q0 + s[0] + q1 + d1 + s[1] + s[2] + d3 + s[3];          // 5a+7b+c+3d
-  Fr n1 = q0 + q1 + d1 + t23;                                      // 4a+6b+c+d
-  Fr n2 = s[0] + d1 + s[1] + q2 + s[2] + q3 + d3 + s[3];          // a+3b+5c+7d
-  Fr n3 = t01 + q2 + q3 + d3;                                      // a+b+4c+6d
-  s[0] = n0; s[1] = n1; s[2] = n2; s[3] = n3;
-}
-
+// Poseidon2 (t = 4), one lane: poseidon2.hpp, p2_permute
 __device__ __noinline__ void dev_poseidon2(Fr (&s)[4], const Fr* __restrict__ rc, const Fr* __restrict__ mu, Fr* __restrict__ W,
                                            uint32_t out, uint32_t P, uint32_t p) {
-  dev_p2_external(s);
-  int k = 0;
-#pragma unroll 1
-  for (int r = 0; r < 4; r++) {
-    SPP_UNROLL for (int i = 0; i < 4; i++) s[i] = dev_sbox_emit(s[i] + rc[k + i], W, out, P, p);
-    k += 4;
-    dev_p2_external(s);
-  }
-#pragma unroll 1
-  for (int r = 0; r < 56; r++) {
-    s[0] = dev_sbox_emit(s[0] + rc[k], W, out, P, p);
-    k++;
-    Fr tot = s[0] + s[1] + s[2] + s[3];
-    SPP_UNROLL for (int i = 0; i < 4; i++) s[i] = mu[i] * s[i] + tot;
-  }
-#pragma unroll 1
-  for (int r = 0; r < 4; r++) {
-    SPP_UNROLL for (int i = 0; i < 4; i++) s[i] = dev_sbox_emit(s[i] + rc[k + i], W, out, P, p);
-    k += 4;
-    dev_p2_external(s);
-  }
+  p2_permute<true>(s, rc, mu, [&](const Fr& x2, const Fr& x3, const Fr& x4, const Fr& x5) {
+    emit4(W, out, P, p, x2, x3, x4, x5);
+    out += 4;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -461,11 +406,11 @@ __device__ __forceinline__ void solve_range(const DevCircuit& dc, Fr* __restrict
         if (t == 3) {
           Fr s[3];
           SPP_UNROLL for (int i = 0; i < 3; i++) s[i] = dev_row_dot(dc.H, dc.coeffs, h0 + i, 0, W, P, p);
-          dev_poseidon29<3>(s, dc.pos3_rc, dc.pos3_mds29, 57, W, out0, P, p);
+          dev_poseidon29<3>(s, dc.hc.pos3_rc, dc.hc.pos3_mds29, 57, W, out0, P, p);
         } else {
           Fr s[5];
           SPP_UNROLL for (int i = 0; i < 5; i++) s[i] = dev_row_dot(dc.H, dc.coeffs, h0 + i, 0, W, P, p);
-          dev_poseidon29<5>(s, dc.pos5_rc, dc.pos5_mds29, 60, W, out0, P, p);
+          dev_poseidon29<5>(s, dc.hc.pos5_rc, dc.hc.pos5_mds29, 60, W, out0, P, p);
         }
         break;
       }
@@ -474,7 +419,7 @@ __device__ __forceinline__ void solve_range(const DevCircuit& dc, Fr* __restrict
         pc += 3;
         Fr s[4];
         SPP_UNROLL for (int i = 0; i < 4; i++) s[i] = dev_row_dot(dc.H, dc.coeffs, h0 + i, 0, W, P, p);
-        dev_poseidon2(s, dc.p2_rc, dc.p2_mu, W, out0, P, p);
+        dev_poseidon2(s, dc.hc.p2_rc, dc.hc.p2_mu, W, out0, P, p);
         break;
       }
       case OP_MASK: {        // the commitment's random mask: fr.Hash(r || s, "spp-commit-mask1") of the proof's blinding factors (rows n_wires, n_wires + 1)
@@ -524,20 +469,13 @@ void launch_solve(hipStream_t st, DevCircuit dc, Fr* W, Fr* scratch, uint32_t pc
 //   COOP_POSEIDON2 different lanes -- three dependent multiplications per partial round instead of 13 (t = 3) / 8
 //   COOP_GRUMPKIN  the fixed-base ladder as a 64-lane prefix sum, one window per lane
 // The values written are the same field elements as the one-lane solver's (the words may be another representative < 2p).
-__device__ __forceinline__ void emit4(Fr* __restrict__ W, uint32_t out, uint32_t P, uint32_t p, const Fr& x2, const Fr& x3, const Fr& x4,
-                                      const Fr& x5) {
-  W[(size_t)out * P + p] = x2;
-  W[(size_t)(out + 1) * P + p] = x3;
-  W[(size_t)(out + 2) * P + p] = x4;
-  W[(size_t)(out + 3) * P + p] = x5;
-}
 
-// Poseidon2 (t = 4) in lane-parallel form: lanes.hpp, coop_p2_permute; the S-box powers go to the witness as they appear
+// Poseidon2 (t = 4) in lane-parallel form: poseidon2.hpp, coop_p2_permute; the S-box powers go to the witness as they appear
 __device__ __noinline__ void coop_poseidon2(const DevCircuit& dc, Fr* __restrict__ W, uint32_t h0, uint32_t out, uint32_t P, uint32_t p,
                                             uint32_t lane) {
   Fr s = Fr::zero();
   if (lane < 4) s = dev_row_dot(dc.H, dc.coeffs, h0 + lane, 0, W, P, p);
-  coop_p2_permute(dc.p2_rc, dc.p2_mu, s, lane, [&](uint32_t o, const Fr& x2, const Fr& x3, const Fr& x4, const Fr& x5) {
+  coop_p2_permute(dc.hc.p2_rc, dc.hc.p2_mu, s, lane, [&](uint32_t o, const Fr& x2, const Fr& x3, const Fr& x4, const Fr& x5) {
     emit4(W, out + o, P, p, x2, x3, x4, x5);
   });
 }
@@ -748,8 +686,8 @@ __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr
       }
       case COOP_POSEIDON: {
         const uint32_t t = pr[a + 1], h0 = pr[a + 2], out0 = pr[a + 3];
-        if (t == 3) coop_poseidon<3>(dc, dc.pos3_rc, dc.pos3_mds, 57, W, h0, out0, P, p, lane);
-        else coop_poseidon<5>(dc, dc.pos5_rc, dc.pos5_mds, 60, W, h0, out0, P, p, lane);
+        if (t == 3) coop_poseidon<3>(dc, dc.hc.pos3_rc, dc.hc.pos3_mds, 57, W, h0, out0, P, p, lane);
+        else coop_poseidon<5>(dc, dc.hc.pos5_rc, dc.hc.pos5_mds, 60, W, h0, out0, P, p, lane);
         break;
       }
       case COOP_POSEIDON2:

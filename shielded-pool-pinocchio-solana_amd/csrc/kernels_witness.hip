@@ -14,7 +14,7 @@
 //   k_audit_open          scripts/rlwe_decrypt.py:61-149 for a batch of (pw, ciphertext) records, with the binding checks it omits
 #include "kernels.hpp"
 #include "poseidon29.hpp"
-#include "lanes.hpp"
+#include "poseidon2.hpp"
 #include "rlwe_ntt.hpp"
 #include "audit_open.hpp"
 
@@ -229,10 +229,6 @@ __device__ __forceinline__ void store_be(uint8_t* p, const Fr& v) {
   uint8_t buf[32];
   v.to_bytes_be(buf);
   for (int i = 0; i < 32; i++) p[i] = buf[i];
-}
-__device__ __forceinline__ Fr sbox5(const Fr& x) {
-  Fr x2 = x.sqr();
-  return x2.sqr() * x;
 }
 // the permutation itself lives in poseidon29.hpp (9x29-bit form, lazy MDS rows); nothing is emitted here
 template <int T>
@@ -491,38 +487,9 @@ void launch_deposit_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t,
 // ----------------------------------------------------------------------------------------------------
 // Poseidon2 t=4 sponge (rate 3) over n field elements per instance; one lane per instance
 // ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void p2_external(Fr (&s)[4]) {
-  Fr t01 = s[0] + s[1], t23 = s[2] + s[3];
-  Fr d1 = s[1].dbl(), d3 = s[3].dbl();
-  Fr q0 = s[0].dbl().dbl(), q1 = d1.dbl(), q2 = s[2].dbl().dbl(), q3 = d3.dbl();
-  Fr n0 = q0 + s[0] + q1 + d1 + s[1] + s[2] + d3 + s[3];
-  Fr n1 = q0 + q1 + d1 + t23;
-  Fr n2 = s[0] + d1 + s[1] + q2 + s[2] + q3 + d3 + s[3];
-  Fr n3 = t01 + q2 + q3 + d3;
-  s[0] = n0; s[1] = n1; s[2] = n2; s[3] = n3;
-}
+// the permutation itself lives in poseidon2.hpp; nothing is emitted here
 __device__ __noinline__ void poseidon2_permute(Fr (&s)[4], const Fr* __restrict__ rc, const Fr* __restrict__ mu) {
-  p2_external(s);
-  int k = 0;
-#pragma unroll 1
-  for (int r = 0; r < 4; r++) {
-    SPP_UNROLL for (int i = 0; i < 4; i++) s[i] = sbox5(s[i] + rc[k + i]);
-    k += 4;
-    p2_external(s);
-  }
-#pragma unroll 1
-  for (int r = 0; r < 56; r++) {
-    s[0] = sbox5(s[0] + rc[k]);
-    k++;
-    Fr tot = s[0] + s[1] + s[2] + s[3];
-    SPP_UNROLL for (int i = 0; i < 4; i++) s[i] = mu[i] * s[i] + tot;
-  }
-#pragma unroll 1
-  for (int r = 0; r < 4; r++) {
-    SPP_UNROLL for (int i = 0; i < 4; i++) s[i] = sbox5(s[i] + rc[k + i]);
-    k += 4;
-    p2_external(s);
-  }
+  p2_permute<false>(s, rc, mu, Poseidon2NoEmit{});
 }
 __global__ void __launch_bounds__(64) k_poseidon2_sponge(HashConsts hc, const uint8_t* __restrict__ in_be, uint32_t n,
                                                          uint8_t* __restrict__ out_be, uint32_t count) {
@@ -544,7 +511,7 @@ __global__ void __launch_bounds__(64) k_poseidon2_sponge(HashConsts hc, const ui
   store_be(out_be + (size_t)g * 32, s[0]);
 }
 // Small counts (one audit proof through generateAuditProof, the tail of a batch): one WAVE per instance, the permutation in the
-// lane-parallel form the cooperative solver uses (lanes.hpp: three dependent products per round instead of eight) -- 53 chained
+// lane-parallel form the cooperative solver uses (poseidon2.hpp: three dependent products per round instead of eight) -- 53 chained
 // permutations are what a single instance waits for.  A wave spends 64 lanes' worth of issue slots on one instance, so large
 // counts keep one lane per instance: 2 048 instances are 32 waves there (latency-bound, hidden behind the proving streams) and
 // would be 2 048 waves x 53 permutations of chip time here.
@@ -553,16 +520,15 @@ __global__ void __launch_bounds__(64) k_poseidon2_sponge_coop(HashConsts hc, con
   const uint32_t g = blockIdx.x, lane = threadIdx.x;
   if (g >= count) return;
   const uint8_t* in = in_be + (size_t)g * n * 32;
-  auto no_emit = [](uint32_t, const Fr&, const Fr&, const Fr&, const Fr&) {};
   Fr s = Fr::zero();
   const uint32_t full = n / 3, rem = n - 3 * full;
 #pragma unroll 1
   for (uint32_t i = 0; i < full; i++) {
     if (lane < 3) s = s + load_be(in + (size_t)(3 * i + lane) * 32);
-    s = coop_p2_permute(hc.p2_rc, hc.p2_mu, s, lane, no_emit);
+    s = coop_p2_permute(hc.p2_rc, hc.p2_mu, s, lane, Poseidon2NoEmit{});
   }
   if (lane < rem) s = s + load_be(in + (size_t)(3 * full + lane) * 32);
-  s = coop_p2_permute(hc.p2_rc, hc.p2_mu, s, lane, no_emit);
+  s = coop_p2_permute(hc.p2_rc, hc.p2_mu, s, lane, Poseidon2NoEmit{});
   if (lane == 0) store_be(out_be + (size_t)g * 32, s);
 }
 void launch_poseidon2_sponge(hipStream_t st, HashConsts hc, const uint8_t* in_be, uint32_t n, uint8_t* out_be, uint32_t count) {
@@ -633,7 +599,7 @@ void launch_shamir_combine(hipStream_t st, const Fr* lambda, const uint8_t* ys_b
 //     row never exists in memory; then the lane reads its record's two 256-bit integers from the tile: both < r, y^2 = x^3 - 17,
 //     H(x, y) by the t = 3 Poseidon; then the two hashes against the words of the public witness, bytewise (ao_decide), or-ed
 //     with the verdict of k_verify, which ran before on the same stream (proof_ok; nullptr: no verification asked for).
-// Why the sponge is not the lane-parallel one of lanes.hpp: 53 chained permutations per record are the bulk of the work, and a
+// Why the sponge is not the lane-parallel one of poseidon2.hpp: 53 chained permutations per record are the bulk of the work, and a
 // wave that spends its 64 lanes on one record's permutation pays about 25 times the issue slots per record of a wave whose lanes
 // hold 64 records (launch_poseidon2_sponge draws the same line at 256 instances).  By the figure DESIGN.md gives for the wave
 // form of the sponge (2 048 instances = about 12 ms of a saturated chip) that would be about 0.2 s at 2^15 records (an estimate);

@@ -145,7 +145,7 @@ struct spp_ctx {
   hipStream_t pstream[SPP_NWS];   // proving: consecutive batches take the streams in turn, so the (latency-bound, few-wave)
                                   // witness solver of batch k+1 overlaps the MSMs of batch k; small batches use up to six
   std::mutex mu;
-  // lazily created constants of the stand-alone witness kernels
+  // lazily created constants: hc is read by the stand-alone witness kernels and by the solver of every circuit of the context
   bool consts_ready = false;
   HashConsts hc{};
   GkAffine* gk_table = nullptr;
@@ -213,8 +213,10 @@ int spp_audit_inputs_enqueue(spp_ctx* ctx, hipStream_t st, void* scratch, const 
                              uint32_t* d_c1_out);
 // withdraw notes (spp_witness_api.cpp): SPP_ERR_BAD_INPUT unless every field of every note is canonical
 int spp_check_notes(size_t count, const uint8_t* notes);
-// lazily built per-context constants (spp_witness_api.cpp)
-int spp_ensure_ctx_consts(spp_ctx* ctx);   // Poseidon / Poseidon2 constants, Grumpkin window table
+// lazily built per-context constants (spp_witness_api.cpp), called with ctx->mu held
+// Poseidon / Poseidon2 constants and the Grumpkin window table.  The ONE copy of the hash constants: a circuit's DevCircuit::hc
+// points into it (load_r1cs), so the buffers are in ctx->owned and live until the context goes, whatever circuits close first.
+int spp_ensure_ctx_consts(spp_ctx* ctx);
 int spp_ensure_rlwe(spp_ctx* ctx);         // NTT tables of the RLWE witness kernel
 // a new stream that really runs beside `ref` (spp_api.cpp)
 __attribute__((visibility("hidden"))) int pick_concurrent_stream(hipStream_t ref, hipStream_t* out);

@@ -375,45 +375,14 @@ static int load_r1cs(spp_circuit* c) {
   c->dc.n_public = circ.n_public;
   c->dc.n_inputs = circ.n_inputs();
   c->dc.challenge_wire = circ.challenge_wire;
-  {
-    auto flat = [](const PoseidonParams& pp) {
-      std::vector<Fr> m;
-      for (auto& row : pp.mds)
-        for (auto& v : row) m.push_back(v);
-      return m;
-    };
-    const PoseidonParams& p3 = poseidon_params(3);
-    const PoseidonParams& p5 = poseidon_params(5);
-    const Poseidon2Params& p2 = poseidon2_params();
-    Fr *a, *b, *cc, *d, *f, *g;
-    std::vector<Fr> mu(p2.mu, p2.mu + 4);
-    auto canon = [](std::vector<Fr> v) {   // words < p: dev_poseidon29's value bounds rely on it
-      for (auto& x : v) x = x.canonical();
-      return v;
-    };
-    if ((e = own_upload(c, &a, canon(p3.rc))) || (e = own_upload(c, &b, flat(p3))) || (e = own_upload(c, &cc, canon(p5.rc))) ||
-        (e = own_upload(c, &d, flat(p5))) || (e = own_upload(c, &f, p2.rc)) || (e = own_upload(c, &g, mu)))
-      return e;
-    std::vector<Fr> bytes(256);
-    for (int i = 0; i < 256; i++) bytes[i] = Fr::from_u64((uint64_t)i);
-    Fr* bm;
-    if ((e = own_upload(c, &bm, bytes))) return e;
-    c->dc.byte_mont = bm;
-    auto flat29 = [](const PoseidonParams& pp) {
-      std::vector<uint32_t> m;
-      for (auto& row : pp.mds)
-        for (auto& v : row) {
-          const F29<FrParams> x = F29<FrParams>::from_fp(v);     // v * 2^261, normalised, < 1.1 p
-          for (int k = 0; k < 9; k++) m.push_back(x.l[k]);
-        }
-      return m;
-    };
-    uint32_t *m3, *m5;
-    if ((e = own_upload(c, &m3, flat29(p3))) || (e = own_upload(c, &m5, flat29(p5)))) return e;
-    c->dc.pos3_mds29 = m3;
-    c->dc.pos5_mds29 = m5;
-    c->dc.pos3_rc = a; c->dc.pos3_mds = b; c->dc.pos5_rc = cc; c->dc.pos5_mds = d; c->dc.p2_rc = f; c->dc.p2_mu = g;
-  }
+  // the hash constants are the context's (one copy in HBM for every circuit and the stand-alone hash kernels)
+  if ((e = spp_ensure_ctx_consts(c->ctx))) return e;
+  c->dc.hc = c->ctx->hc;
+  std::vector<Fr> bytes(256);
+  for (int i = 0; i < 256; i++) bytes[i] = Fr::from_u64((uint64_t)i);
+  Fr* bm;
+  if ((e = own_upload(c, &bm, bytes))) return e;
+  c->dc.byte_mont = bm;
   return 0;
 }
 

@@ -17,7 +17,7 @@ int spp_ensure_ctx_consts(spp_ctx* ctx) {
   std::vector<Fr> mu(p2.mu, p2.mu + 4);
   Fr *a, *b, *c, *d, *f, *g;
   int e;
-  auto canon = [](std::vector<Fr> v) {
+  auto canon = [](std::vector<Fr> v) {   // words < p: poseidon_permute29's value bounds rely on it
     for (auto& x : v) x = x.canonical();
     return v;
   };
@@ -25,7 +25,7 @@ int spp_ensure_ctx_consts(spp_ctx* ctx) {
     std::vector<uint32_t> m;
     for (auto& row : pp.mds)
       for (auto& v : row) {
-        const F29<FrParams> x = F29<FrParams>::from_fp(v);
+        const F29<FrParams> x = F29<FrParams>::from_fp(v);     // v * 2^261, normalised, < 1.1 p
         for (int k = 0; k < 9; k++) m.push_back(x.l[k]);
       }
     return m;

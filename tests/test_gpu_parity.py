@@ -858,6 +858,51 @@ def test_poseidon2_sponge_kernel(ctx, rlwe_pk):
         assert witness.ct_commitments(ctx, [row]) == [H.poseidon2_sponge(row)]
 
 
+def test_poseidon2_sponge_one_lane_kernel(ctx):
+    """More than 256 rows leave the wave-per-row kernel for k_poseidon2_sponge, one lane per row: 257 rows (four full waves and
+    one lane) and 320 (five waves), at row lengths 1, 2 (the two ragged tails), 3 (the rate), 4 and 7 (full blocks and a tail)."""
+    from spp import witness
+    from oracle import hashes as H
+    from oracle.bn254 import R
+    rng = random.Random(31)
+    for n in (1, 2, 3, 4, 7):
+        rows = [[rng.randrange(R) for _ in range(n)] for _ in range(320)]
+        rows[0] = [0] * n
+        rows[256] = [R - 1] * n                                  # the lone lane of the fifth wave at 257 rows
+        want = [H.poseidon2_sponge(r) for r in rows]
+        assert witness.ct_commitments(ctx, rows[:257]) == want[:257], n
+        assert witness.ct_commitments(ctx, rows) == want, n
+
+
+def test_two_circuits_share_the_context_hash_constants(withdraw_artifacts, withdraw_kat):
+    """The Poseidon / Poseidon2 constants in HBM belong to the context and every circuit loaded on it reads them: closing one
+    circuit leaves its sibling and the context's own hash kernels with what they read."""
+    import spp
+    from spp import witness
+    from oracle import circuit as C, hashes as H
+    from oracle.bn254 import R
+    c = spp.Context(0)
+    try:
+        row, rs = C.withdraw_inputs(withdraw_kat), [(1000, 2000)]
+        h1 = c.load_circuit(withdraw_artifacts["sppc"], withdraw_artifacts["pk"], 6)
+        h2 = c.load_circuit(withdraw_artifacts["sppc"], withdraw_artifacts["pk"], 6)
+        try:
+            first = h1.prove_batch([row], rs)
+            assert first[2] == [0] and h2.prove_batch([row], rs) == first
+        finally:
+            h1.close()
+        try:
+            assert h2.prove_batch([row], rs) == first
+            f = lambda k: int(withdraw_kat[k], 16)
+            assert witness.poseidon_hash2(c, f("owner_x"), f("owner_y")) == f("wa_commitment")
+            short = [5, R - 1, 0, 77]
+            assert witness.ct_commitments(c, [short]) == [H.poseidon2_sponge(short)]
+        finally:
+            h2.close()
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------------------------------------- general Pippenger
 def test_pippenger_matches_oracle_and_is_linear(ctx):
     from oracle import bn254 as B, native
