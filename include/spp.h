@@ -195,6 +195,26 @@ int spp_verify(const uint8_t* vk, size_t vk_len, const uint8_t* proof, size_t pr
 /* debug / parity: full witness of proof 0 of the last batch, n_wires * 32 B big-endian */
 int spp_debug_witness(spp_circuit* c, uint8_t* out, size_t n_wires);
 
+/* debug / parity, TEST ONLY: the device compile of the arithmetic headers (csrc/bn254.hpp, csrc/f29.hpp) on RAW words.  Unlike every
+ * other entry point nothing is converted, reduced or moved to another domain on either side: `in` holds n cases of in_words
+ * little-endian uint32 limbs each, exactly the words the header function sees, and `out` receives out_words limbs per case,
+ * exactly what it returned.  One lane per case; the kernel loads, calls, stores -- all checking is the caller's
+ * (tests/test_gpu_arith.py against Python integers; tests/host/arith_raw_check.cpp is the g++ twin of the same dispatch).
+ * selector = field | operation: SPP_ARITH_FR or SPP_ARITH_FQ, plus one of the operation codes of csrc/arith_probe.hpp, which also
+ * fixes in_words / out_words per operation (Fp 8 words, F29 9 limbs, Fq2 / F29x2 two of them, c0 first; predicates one word).
+ * arg: the k of mul_small; for F29x2 mul / sqr which lifted constant negates a1 (2, 4, 6, 8 = SUBC_kP_1); otherwise ignored.
+ * Accumulator scripts (per case: step count <= 16, 16 step words `table index | negate << 8`, a table of 8 affine points as Fp
+ * words) run madd / madd_distinct from infinity and return the inf flag, to_xyzz().to_affine(), one bit per step for what
+ * madd_distinct returned, and the accumulator's own limbs.
+ * The probe does NOT check the preconditions the headers state (operands < 2p, limb bounds of the lazy forms, column sums
+ * < 2^64, table entries not infinity): out-of-range operands give the header's unspecified result, never a memory fault.
+ * SPP_ERR_BAD_INPUT: NULL pointers, n == 0 or n > 2^20, an unknown selector (or an Fq-only operation with SPP_ARITH_FR), an arg
+ * the operation does not know, in_words / out_words other than the operation's. */
+#define SPP_ARITH_FR 0x000u
+#define SPP_ARITH_FQ 0x100u
+int spp_debug_arith(spp_ctx* ctx, uint32_t selector, uint32_t arg, size_t n, const uint32_t* in, size_t in_words, uint32_t* out,
+                    size_t out_words);
+
 /* ---- witness-input generation (what the reference computes on the client before proving) ---- */
 /* RLWE encryption + quotient witnesses for `count` instances (scripts/generate_audit.py:507-554, rlwe.ts:157-247):
  * pk_a, pk_b: 1024 coefficients in [0,q); r, e2: count*1024 int8; e1: count*64 int8; msg: count*64 bytes.

@@ -184,7 +184,9 @@ struct Fp {
   }
   // Values the compiler can prove to be < 2^24 make it select v_mul_u32_u24 / v_mul_hi_u32_u24 and drop the
   // masking AND; on gfx950 (ROCm 7.2) the high half then came back wrong (tests/micro/device_arith_check.hip,
-  // dbg_mul.hip).  An empty asm hides the range so the product stays a v_mad_u64_u32.
+  // dbg_mul.hip).  An empty asm hides the range so the product stays a v_mad_u64_u32.  tests/test_gpu_arith.py is the
+  // collected check: the device compile of this header on raw edge words (top limb 0 / 1 / maximal, all-ones limbs, 2^k)
+  // against Python integers, through spp_debug_arith.
   static SPP_HD void hide24(uint32_t& v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(v));

@@ -58,7 +58,7 @@ struct F29 {
       w[k] = v;
     }
   }
-  // carry sweep: limbs 0..7 < 2^29 afterwards (input limbs < 2^32, value unchanged)
+  // carry sweep: limbs 0..7 < 2^29 afterwards, value unchanged (input limbs <= 2^32 - 8: a limb plus the carry from below, <= 7, fits its word)
   SPP_HD F29 norm() const {
     F29 r;
     uint32_t carry = 0;

@@ -276,6 +276,10 @@ uint32_t pippenger_windows();
 void launch_pippenger_g1(hipStream_t st, const G1Affine* bases, const Fr* scalars, uint32_t n, void* workspace, G1XYZZ** out_windows,
                          hipEvent_t ev0, hipEvent_t ev1);
 
+// ---- raw-word probe of the arithmetic headers (kernels_arith_probe.hip, arith_probe.hpp): spp_debug_arith, test only ----
+// in: n * in_words, out: n * out_words device words (arith_probe_shape); false = unknown selector or arg, nothing launched
+bool launch_arith_probe(hipStream_t st, uint32_t selector, uint32_t arg, const uint32_t* in, uint32_t* out, uint32_t n);
+
 // ---- commitment challenge, proof assembly ----
 void launch_challenge(hipStream_t st, const G1XYZZ* commit, Fr* W, uint32_t challenge_wire, uint32_t P, G1Affine* commit_affine,
                       uint32_t* status);

@@ -10,7 +10,7 @@
 //   spp_verify_api.cpp   verification and pairing checks
 //   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
-//   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points
+//   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points, the raw-word arithmetic probe (spp_debug_arith)
 #pragma once
 #include "../../include/spp.h"
 

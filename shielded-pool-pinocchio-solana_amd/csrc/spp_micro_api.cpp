@@ -1,6 +1,7 @@
 // libspp C ABI, unit / micro-benchmark entry points: Fr NTT, table-based G1 MSM, general-base Pippenger (BASELINE.json
 // configs[4]).  No reference equivalent: gnark's NTT / MSM are internal to `sunspot prove`.
 #include "spp_internal.hpp"
+#include "arith_probe.hpp"
 
 // -----------------------------------------------------------------------------------------------------
 // micro-benchmark / unit entry points
@@ -31,6 +32,32 @@ extern "C" int spp_ntt_fr(spp_ctx* ctx, uint8_t* data, uint32_t logn, int invers
     if (inverse) v = v * ninv;
     v.to_bytes_be(data + 32 * (size_t)bitrev(pos, logn));
   }
+  return SPP_OK;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// raw-word probe of bn254.hpp / f29.hpp on the device (test only): words in, words out, nothing converted on either side
+// -----------------------------------------------------------------------------------------------------
+extern "C" int spp_debug_arith(spp_ctx* ctx, uint32_t selector, uint32_t arg, size_t n, const uint32_t* in, size_t in_words, uint32_t* out,
+                               size_t out_words) {
+  if (!ctx || !in || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (n == 0 || n > ((size_t)1 << 20)) return fail(SPP_ERR_BAD_INPUT, "n must be in [1, 2^20]");
+  uint32_t iw = 0, ow = 0;
+  if (!arith_probe_shape(selector, &iw, &ow)) return fail(SPP_ERR_BAD_INPUT, "unknown selector 0x%x", selector);
+  if (!arith_probe_arg_ok(selector, arg)) return fail(SPP_ERR_BAD_INPUT, "selector 0x%x does not know arg %u", selector, arg);
+  if (in_words != iw || out_words != ow)
+    return fail(SPP_ERR_BAD_INPUT, "selector 0x%x takes %u words and returns %u per case", selector, iw, ow);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf d_in, d_out;
+  UP(d_in, in, n * iw * sizeof(uint32_t));
+  HIP_TRY(d_out.alloc(n * ow * sizeof(uint32_t)));
+  if (!launch_arith_probe(st, selector, arg, d_in.as<uint32_t>(), d_out.as<uint32_t>(), (uint32_t)n))
+    return fail(SPP_ERR_BAD_INPUT, "unknown selector 0x%x", selector);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(out, d_out.p, n * ow * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return SPP_OK;
 }
 

@@ -7,6 +7,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "libspp.so")
 _LIB = None
 
 SPP_OK = 0
+SPP_ERR_BAD_INPUT = -1
 SPP_ERR_UNSAT = -4
 SPP_CIRCUIT_WITHDRAW = 1
 SPP_CIRCUIT_AUDIT = 2
@@ -35,6 +36,8 @@ SPP_POOL_BAD_PROOF = 6
 SPP_INSTR_DEPOSIT = 0               # kinds of spp_pool_settle_log
 SPP_INSTR_SUBMIT_AUDIT = 1
 SPP_INSTR_WITHDRAW = 2
+SPP_ARITH_FR = 0x000                # spp_debug_arith: field bits of the selector (operation codes: csrc/arith_probe.hpp)
+SPP_ARITH_FQ = 0x100
 POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
 
 
@@ -100,6 +103,7 @@ def load_library():
     L.spp_pairing_check.argtypes = [vp, u32, cp, cp, ctypes.POINTER(i32)]
     L.spp_pairing_check_host.argtypes = [u32, cp, cp, ctypes.POINTER(i32)]
     L.spp_debug_witness.argtypes = [vp, vp, sz]
+    L.spp_debug_arith.argtypes = [vp, u32, u32, sz, vp, sz, vp, sz]
     L.spp_rlwe_witness_batch.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.spp_rlwe_witness_batch_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.spp_ctx_sync.argtypes = [vp]

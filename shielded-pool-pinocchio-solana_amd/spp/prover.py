@@ -71,7 +71,19 @@ class Context:
         assert 1 << logn == n
         buf = ctypes.create_string_buffer(b"".join(int(v).to_bytes(32, "big") for v in values), 32 * n)
         check(self.L.spp_ntt_fr(self.h, ctypes.cast(buf, ctypes.c_void_p), logn, 1 if inverse else 0))
-        return [int.from_bytes(buf.raw[32 * i:32 * i + 32], "big") for i in range(n)]
+        raw = buf.raw                                   # one copy: buf.raw per element is quadratic in n
+        return [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(n)]
+
+    def debug_arith(self, selector, rows, out_words, arg=0):
+        """Test only (spp_debug_arith): one function of csrc/bn254.hpp / f29.hpp on the device, on RAW uint32 limbs.  rows: n cases of
+        operand words (n x in_words, anything numpy turns into uint32) -> n x out_words uint32 array; nothing is converted,
+        reduced or checked on either side.  selector = SPP_ARITH_FR / SPP_ARITH_FQ | operation code of csrc/arith_probe.hpp."""
+        a = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert a.ndim == 2
+        out = np.empty((a.shape[0], int(out_words)), dtype=np.uint32)
+        check(self.L.spp_debug_arith(self.h, int(selector), int(arg), a.shape[0], a.ctypes.data_as(ctypes.c_void_p), a.shape[1],
+                                     out.ctypes.data_as(ctypes.c_void_p), out.shape[1]))
+        return out
 
     def msm_g1(self, bases_bytes, scalars, window_bits=8):
         n = len(scalars)

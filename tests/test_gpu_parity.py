@@ -38,6 +38,37 @@ def test_ntt_matches_oracle(ctx):
     assert ctx.ntt(ctx.ntt(vals, False), True) == vals
 
 
+def test_ntt_remaining_sizes_and_closed_forms(ctx):
+    """The sizes test_ntt_matches_oracle leaves out -- below one wave's worth, between the proving domains, 2^16 (the largest
+    two-pass size) and 2^17 (the smallest that takes three passes through launch_ntt, reachable through spp_ntt_fr) -- and, at
+    2^8 / 2^9, inputs whose transform is known in closed form."""
+    from oracle import native
+    import ctypes
+    from oracle.bn254 import R, FR_GENERATOR
+    rng = random.Random(6)
+    for logn in (2, 3, 5, 6, 7, 10, 11, 12, 16, 17):
+        n = 1 << logn
+        raw = rng.getrandbits(256 * n).to_bytes(32 * n, "big")
+        vals = [int.from_bytes(raw[32 * i:32 * i + 32], "big") % R for i in range(n)]
+        for inverse in (False, True):
+            got = ctx.ntt(vals, inverse)
+            buf = ctypes.create_string_buffer(b"".join(v.to_bytes(32, "big") for v in vals), 32 * n)
+            native.lib().orc_ntt(ctypes.cast(buf, ctypes.c_void_p), logn, 1 if inverse else 0)
+            out = buf.raw
+            exp = [int.from_bytes(out[32 * i:32 * i + 32], "big") for i in range(n)]
+            assert got == exp, (logn, inverse)
+    for logn in (8, 9):
+        n = 1 << logn
+        w, ninv = pow(FR_GENERATOR, (R - 1) // n, R), pow(n, -1, R)
+        for inverse in (False, True):
+            s = ninv if inverse else 1                                   # the inverse transform scales by 1/n
+            assert ctx.ntt([0] * n, inverse) == [0] * n, (logn, inverse)
+            assert ctx.ntt([R - 1] * n, inverse) == [(R - 1) * n * s % R] + [0] * (n - 1), (logn, inverse)        # a constant: only X[0]
+            assert ctx.ntt([1] + [0] * (n - 1), inverse) == [s] * n, (logn, inverse)                              # delta at 0: a constant
+            sign = 1 if inverse else -1                                  # delta at n-1: X[k] = w^(-k) forward, w^k / n inverse
+            assert ctx.ntt([0] * (n - 1) + [1], inverse) == [pow(w, (sign * k) % n, R) * s % R for k in range(n)], (logn, inverse)
+
+
 def test_msm_g1_matches_oracle(ctx):
     from oracle import bn254 as B, native
     import ctypes

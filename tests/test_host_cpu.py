@@ -53,7 +53,9 @@ def test_host_arithmetic_header_matches_oracle(tmp_path):
             lines.append("%s sub %s %s" % (name, h(a), h(b))); exp.append(h((a - b) % m))
             lines.append("%s neg %s" % (name, h(a))); exp.append(h((-a) % m))
         # inverses: the binary extended Euclid of Fp::inv() against Python, against a^(p-2), on the non-canonical word of the
-        # same element, and on the values that drive its shift counts to the extremes (1, 2^k, p-1, (p+-1)/2, tiny, 0)
+        # same element, and on the values 1, 2^k, p-1, (p+-1)/2, tiny, 0.  These pass through from_canonical, so the WORD inv()
+        # works on is a * 2^256 mod p and looks random: the words that drive its shift counts to the extremes (a zero low limb,
+        # a first difference that is a power of two) are sent raw by tests/test_arith_raw_host.py
         inv_cases = [rng.randrange(1, m) for _ in range(120)] + [1, 2, 3, m - 1, m - 2, (m - 1) // 2, (m + 1) // 2, 1 << 128, 1 << 253,
                                                                   (1 << 253) + 1, 0xffffffff, 1 << 32, (1 << 64) - 1, m >> 1, 5]
         for a in inv_cases:
