@@ -85,7 +85,10 @@ def verify(vk_bytes, proof_bytes, pw_bytes):
         pr = parse_proof(proof_bytes)
     except Exception:
         return False
-    pub = parse_public_witness(pw_bytes)
+    try:
+        pub = parse_public_witness(pw_bytes)   # a header that does not fit its body is a refusal, like a bad commitment count
+    except Exception:
+        return False
     if len(pub) + 2 != len(vk["K"]):
         return False
     # canonical encodings only: gnark's readers refuse a public word >= r or a coordinate >= q instead of reducing it

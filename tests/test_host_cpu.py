@@ -362,32 +362,10 @@ def test_verifiers_reject_bs_outside_the_subgroup(withdraw_artifacts, withdraw_k
     rc, proof, pw = p.prove(row, 3, 4)
     vk = open(withdraw_artifacts["vk"], "rb").read()
     assert rc == 0 and groth16.verify(vk, proof, pw) and spp.verify(vk, proof, pw)
-    # find a twist point with small x: y^2 = x^3 + b'  (square root in Fq2, p = 3 mod 4)
-    P = B.P
-
-    def fq_sqrt(v):
-        r = pow(v, (P + 1) // 4, P)
-        return r if r * r % P == v % P else None
-
-    def fq2_sqrt(a):
-        alpha = fq_sqrt((a[0] * a[0] + a[1] * a[1]) % P)
-        if alpha is None:
-            return None
-        for d in ((a[0] + alpha) * pow(2, -1, P) % P, (a[0] - alpha) * pow(2, -1, P) % P):
-            x0 = fq_sqrt(d)
-            if x0:
-                y = (x0, a[1] * pow(2 * x0, -1, P) % P)
-                if B.f2_mul(y, y) == (a[0] % P, a[1] % P):
-                    return y
-        return None
-    x = 1
-    pt = None
-    while pt is None:
-        x += 1
-        rhs = B.f2_add(B.f2_mul(B.f2_mul((x, 0), (x, 0)), (x, 0)), B.G2_B)
-        y = fq2_sqrt(rhs)
-        if y is not None:
-            pt = ((x, 0), y)
+    # the twist point with the smallest x: y^2 = x^3 + b'  (square root in Fq2; one copy, shared with the forged-proof cases)
+    from verify_vectors import fq2_sqrt, twist_point_outside_the_subgroup
+    pt = twist_point_outside_the_subgroup()
+    assert pt[0][1] == 0 and fq2_sqrt(B.f2_mul(pt[1], pt[1])) in (pt[1], B.f2_neg(pt[1]))
     assert B.g2_is_on_curve(pt) and groth16._g2_times_r(pt) is not None
     forged = proof[:64] + B.g2_to_bytes(pt) + proof[192:]
     assert not groth16.verify(vk, forged, pw)
