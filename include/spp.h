@@ -20,6 +20,7 @@
  *                             per deposit) into the same tree
  *   spp_verify                `sunspot verify` noir_circuit/prove_linux.sh:86-87, audit_circuit/prove_audit.sh:98-99
  *   spp_verify_batch          the same for many proofs on the GPU
+ *   spp_verify_batch_rlc      the same by random linear combination: key-side pairings once per group of proofs
  *   spp_shamir_reconstruct / spp_rlwe_decrypt_batch   scripts/rlwe_decrypt.py:61-132, demo-frontend/app/lib/shamir.ts:97-169
  *   spp_prove_audit_records   scripts/generate_audit.py:468-691 with the ciphertext.json of :590-606: the audit RECORD
  *                             (proof, public witness, ciphertext) from the prover's raw secrets
@@ -344,6 +345,28 @@ int spp_prove_withdraw_notes(spp_circuit* c, spp_merkle_tree* t, size_t count, c
  * duration of the verification kernel. */
 int spp_verify_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, size_t count, const uint8_t* proofs, const uint8_t* pws, size_t pw_len,
                      int32_t* ok, float* kernel_ms);
+
+/* The same verification by random linear combination (`sunspot verify` for many proofs against one key,
+ * noir_circuit/prove_linux.sh:86-87, audit_circuit/prove_audit.sh:98-99).  The proofs are cut into groups of `group`; each
+ * proof keeps its format, curve and subgroup checks and one Miller loop, and the pairings against the key and the final
+ * exponentiation are paid once per group, on one combined equation weighted by secret 128-bit scalars derived from seed32 and
+ * the proof's index.  A group whose equation fails is settled proof by proof by the verifier of spp_verify_batch.
+ *   - The decisions are those of spp_verify_batch, except with probability about 2^-127 per call.
+ *   - A seed the prover knows or can influence voids that guarantee: with the scalars known, invalid proofs whose errors cancel
+ *     in the combination can be built.
+ *   - A caller-supplied seed must therefore be drawn AFTER the batch is fixed, and never reused for a batch the prover saw it
+ *     used on.  seed32 = NULL takes 32 bytes from the operating system per call.
+ * group: a multiple of 64 in [64, 4096], 0 = the default (256).  stats (optional): groups, groups refused, proofs re-verified,
+ * proofs dropped (refused by the format, curve or subgroup checks).  kernel_ms (optional) covers all launches of the call.
+ * Other arguments and their checks as spp_verify_batch; the key may have at most 34 public inputs. */
+#define SPP_RLC_SERIAL_TAIL 1   /* one-lane rlc_final_serial instead of the cooperative tail (tests, probe) */
+#define SPP_RLC_NO_FALLBACK 2   /* ok[i] of a refused group's surviving proofs = 0, nothing re-verified     */
+int spp_verify_batch_rlc(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, size_t count,
+                         const uint8_t* proofs, const uint8_t* pws, size_t pw_len,
+                         const uint8_t* seed32 /* NULL: 32 bytes from the OS */, uint32_t group /* 0: default */,
+                         uint32_t flags, int32_t* ok,
+                         uint32_t stats[4] /* optional: groups, groups refused, proofs re-verified, proofs dropped */,
+                         float* kernel_ms);
 
 /* prod_k e(P_k, Q_k) == 1 for 1..4 caller-supplied pairs (G1 64 B, G2 128 B, gnark raw uncompressed), computed on the GPU
  * with the device pairing code of spp_verify_batch (curve + subgroup checks included; *ok = 0 when a point is invalid).

@@ -170,6 +170,16 @@ void launch_pairing_check(hipStream_t st, const PairingCheckDev* a, int32_t* ok)
 // k_verify over a compacted list: ok[list[j]] for j < *n_list (a device word; at most max_count), the other entries of ok untouched
 void launch_verify_list(hipStream_t st, const VerifyKeyDev* vk, const uint8_t* proofs, const uint8_t* pws, uint32_t pw_len, uint32_t max_count,
                         const uint32_t* list, const uint32_t* n_list, int32_t* ok);
+// ---- batch verification by random linear combination (kernels_verify_rlc.hip); the structures live in verify_rlc.hpp ----
+// one slice of a call: terms (one lane per proof), groups (one wave per `group` proofs), then k_verify_list over the proofs of the
+// refused groups unless SPP_RLC_NO_FALLBACK.  ws: rlc_elems(nk) * count elements; live, list: count words; *n_list = 0 on entry;
+// stats[1..3] are added to.  index0: the index of the slice's first proof in the call (the scalars are derived from it)
+struct RlcKeyDev;
+struct RlcSeed;
+struct W256;
+void launch_verify_rlc(hipStream_t st, const VerifyKeyDev* vk, const RlcKeyDev* rk, const uint8_t* proofs, const uint8_t* pws, uint32_t pw_len,
+                       uint32_t count, const RlcSeed& seed, uint32_t index0, uint32_t group, uint32_t flags, W256* ws, uint32_t* live,
+                       int32_t* ok, uint32_t* list, uint32_t* n_list, uint32_t* stats);
 // ---- pool ledger (kernels_pool.hip); the structures and what a lane does live in pool_table.hpp ----
 struct PoolSet;
 struct PoolState;

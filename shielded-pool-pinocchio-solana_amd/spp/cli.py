@@ -8,6 +8,9 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                                                                                                   #    skipped when the keys match the circuit)
     python -m spp.cli prove   target/<name>.sppc target/<name>.pk Prover.toml                    # -> <name>.proof, <name>.pw
     python -m spp.cli verify  target/<name>.vk target/<name>.proof target/<name>.pw              # exit 0 / 1
+    python -m spp.cli verify-batch target/<name>.vk <a>.proof <a>.pw [<b>.proof <b>.pw ...]      # `sunspot verify` in a loop, on the GPU
+                              # by random linear combination (spp_verify_batch_rlc, seed from the OS): one verdict per pair,
+                              # exit 0 iff all verify
     python -m spp.cli audit-open target/<name>.vk|- <name>.proof <name>.pw ciphertext.json --shares share_1.json share_2.json
                               # the auditor's `python scripts/rlwe_decrypt.py`: reconstructs the key from the shares, verifies the
                               # proof (`-`: already verified elsewhere), checks that the ciphertext is the one the proof commits
@@ -151,6 +154,31 @@ def _pool_replay(a):
     return 0
 
 
+def _verify_batch(a):
+    try:   # everything that can be wrong with the files is found before a device is opened
+        if not a.files or len(a.files) % 2:
+            raise ValueError("verify-batch takes <vk> and then pairs <proof> <pw>")
+        vk = open(a.vk, "rb").read()
+        proofs = [open(p, "rb").read() for p in a.files[0::2]]
+        pws = [open(p, "rb").read() for p in a.files[1::2]]
+        if any(len(p) != lib.PROOF_LEN for p in proofs) or len({len(w) for w in pws}) != 1:
+            raise ValueError("proofs must be %d bytes and the public witnesses of one length" % lib.PROOF_LEN)
+    except (OSError, ValueError) as e:
+        print("spp verify-batch: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        got = ctx.verify_batch_rlc(vk, proofs, pws, group=a.group)
+    except lib.SppError as e:
+        print("spp verify-batch: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    for path, ok in zip(a.files[0::2], got):
+        print("%s: verification %s" % (path, "succeeded" if ok else "FAILED"))
+    return 0 if all(got) else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="spp")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -165,6 +193,9 @@ def main(argv=None):
                    help="blinding factors (parity runs only: the default draws fresh ones from the OS, as every real proof must)")
     x = sub.add_parser("execute"); x.add_argument("acir"); x.add_argument("toml"); x.add_argument("-o", "--out", default=None)
     v = sub.add_parser("verify"); v.add_argument("vk"); v.add_argument("proof"); v.add_argument("pw")
+    vb = sub.add_parser("verify-batch"); vb.add_argument("vk"); vb.add_argument("files", nargs="+", metavar="PROOF PW")
+    vb.add_argument("--group", type=int, default=0, help="proofs per combined equation (a multiple of 64 in [64, 4096]; default 256)")
+    vb.add_argument("--device", type=int, default=0)
     o = sub.add_parser("audit-open"); o.add_argument("vk", help="verifying key, or - for a record already verified elsewhere")
     o.add_argument("proof"); o.add_argument("pw"); o.add_argument("ciphertext", help="ciphertext.json (scripts/generate_audit.py:590-606)")
     o.add_argument("--shares", nargs="+", required=True, metavar="SHARE.json", help="threshold many share files (scripts/rlwe_keygen.py)")
@@ -175,6 +206,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.cmd == "audit-open":
         return _audit_open(a)
+    if a.cmd == "verify-batch":
+        return _verify_batch(a)
     if a.cmd == "pool-replay":
         return _pool_replay(a)
     if a.cmd == "compile" and a.circuit.endswith(".ccs"):

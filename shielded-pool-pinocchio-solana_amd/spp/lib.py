@@ -18,6 +18,8 @@ NOTE_LEN = 160                      # withdraw note: recipient | amount | secret
 DEPOSIT_LEN = 96                    # deposit: secret_key | amount | randomness
 AUDIT_PW_LEN = 76                   # audit public witness: header | wa_commitment | ct_commitment
 # spp_audit_open_batch: bits of flags[i] (include/spp.h)
+SPP_RLC_SERIAL_TAIL = 1     # spp_verify_batch_rlc flags (include/spp.h)
+SPP_RLC_NO_FALLBACK = 2
 SPP_AUDIT_BAD_PROOF = 1
 SPP_AUDIT_BAD_CIPHERTEXT = 2
 SPP_AUDIT_BAD_IDENTITY = 4
@@ -100,6 +102,7 @@ def load_library():
     L.spp_prove_withdraw.argtypes = [vp, ctypes.POINTER(WithdrawInputs), cp, vp, vp]
     L.spp_verify.argtypes = [cp, sz, cp, sz, cp, sz, ctypes.POINTER(i32)]
     L.spp_verify_batch.argtypes = [vp, cp, sz, sz, cp, cp, sz, vp, ctypes.POINTER(ctypes.c_float)]
+    L.spp_verify_batch_rlc.argtypes = [vp, cp, sz, sz, cp, cp, sz, cp, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_float)]
     L.spp_pairing_check.argtypes = [vp, u32, cp, cp, ctypes.POINTER(i32)]
     L.spp_pairing_check_host.argtypes = [u32, cp, cp, ctypes.POINTER(i32)]
     L.spp_debug_witness.argtypes = [vp, vp, sz]

@@ -142,6 +142,28 @@ class Context:
         res = [bool(ok[i]) for i in range(count)]
         return (res, ms.value) if want_ms else res
 
+    def verify_batch_rlc(self, vk, proofs, pws, seed=None, group=0, flags=0, want_stats=False, want_ms=False):
+        """verify_batch by random linear combination (spp_verify_batch_rlc): the key-side pairings and the final exponentiation
+        once per group of `group` proofs (0: the default), a refused group settled proof by proof.  Same verdicts as verify_batch
+        except with probability ~2^-127 per call, PROVIDED the prover cannot know or influence `seed`: leave it None (32 bytes
+        from the OS per call) or draw it after the batch is fixed.  flags: lib.SPP_RLC_*.  Returns a list of booleans, then
+        (groups, groups refused, proofs re-verified, proofs dropped) when want_stats, then the kernel time in ms when want_ms."""
+        count = len(proofs)
+        assert count == len(pws)
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        pw_len = len(pws[0]) if count else 12
+        ok = (ctypes.c_int32 * max(count, 1))()
+        stats = (ctypes.c_uint32 * 4)()
+        ms = ctypes.c_float(0)
+        check(self.L.spp_verify_batch_rlc(self.h, vk, len(vk), count, b"".join(proofs), b"".join(pws), pw_len,
+                                          None if seed is None else bytes(seed), group, flags, ctypes.cast(ok, ctypes.c_void_p), stats,
+                                          ctypes.byref(ms)))
+        res = [bool(ok[i]) for i in range(count)]
+        if not (want_stats or want_ms):
+            return res
+        return (res,) + ((tuple(stats),) if want_stats else ()) + ((ms.value,) if want_ms else ())
+
     def audit_open(self, vk, sk_mod_q, proofs, pws, c0, c1):
         """Opens audit records in one pass on the GPU (spp_audit_open_batch): verification, ciphertext binding, decryption,
         identity binding.  vk: bytes, or None for records already verified elsewhere (proofs may then be None); sk_mod_q: 1024
