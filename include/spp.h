@@ -22,6 +22,8 @@
  *   spp_verify_batch          the same for many proofs on the GPU
  *   spp_verify_batch_rlc      the same by random linear combination: key-side pairings once per group of proofs
  *   spp_shamir_reconstruct / spp_rlwe_decrypt_batch   scripts/rlwe_decrypt.py:61-132, demo-frontend/app/lib/shamir.ts:97-169
+ *   spp_rlwe_sample_key / spp_rlwe_keygen_batch / spp_rlwe_key_check / spp_shamir_split
+ *                             scripts/rlwe_keygen.py:98-182 (the audit key pair and its files) and :51-65 (shamir_share_field)
  *   spp_prove_audit_records   scripts/generate_audit.py:468-691 with the ciphertext.json of :590-606: the audit RECORD
  *                             (proof, public witness, ciphertext) from the prover's raw secrets
  *   spp_audit_open_batch      scripts/rlwe_decrypt.py:61-149 for a batch of such records, after `sunspot verify`
@@ -386,6 +388,28 @@ int spp_shamir_reconstruct(spp_ctx* ctx, uint32_t t, const uint32_t* xs, const u
 /* rlweDecrypt (shamir.ts:134-169 / rlwe_decrypt.py:106-132) for `count` ciphertexts: c0 count*64, c1 count*1024 in
  * [0,q); msg = count * 64 recovered byte slots (owner_x = slots 0..31 little-endian, owner_y = slots 32..63). */
 int spp_rlwe_decrypt_batch(spp_ctx* ctx, const uint32_t* sk_mod_q, size_t count, const uint32_t* c0, const uint32_t* c1, uint8_t* msg);
+
+/* ---- auditor key generation (scripts/rlwe_keygen.py:98-182, shamir_share_field :51-65) ----
+ * The key pair the audit circuit embeds and spp_prove_audit_records encrypts to, and the t-of-m shares spp_shamir_reconstruct
+ * reads.  Polynomials have 1024 coefficients, q = 167772161; `count` keys are count * 1024 values, key after key.
+ * All four calls refuse with SPP_ERR_BAD_INPUT before any device work, naming the offending index in spp_last_error(): NULL
+ * pointers (checked before the context is touched), an a / pk_a / pk_b / sk_mod_q value >= q, a field element >= r, t == 0,
+ * t > 64, m < t, m > 255, an x equal to 0 or repeated, count > 2^16, n > 2^20.  count == 0 and n == 0 are SPP_OK.  Synchronous and
+ * serialised on the context.  Device buffers that held sk or sharing coefficients are zeroed before they are freed, host scratch
+ * that held them is wiped; the caller's own buffers are the caller's to wipe. */
+/* host-only, OS randomness, uniform by rejection: sk, e count*1024 in [-bound, bound] (bound in [1,127]), a count*1024 in [0,q) */
+int spp_rlwe_sample_key(size_t count, uint32_t bound, int8_t* sk, uint32_t* a, int8_t* e);
+/* b = e - a*sk mod (X^1024+1, q).  pk_b count*1024; sk_mod_q optional, count*1024 */
+int spp_rlwe_keygen_batch(spp_ctx* ctx, size_t count, const int8_t* sk, const uint32_t* a, const int8_t* e, uint32_t* pk_b,
+                          uint32_t* sk_mod_q);
+/* max_abs = count*2: { max |centred(b + a*sk)|, max |centred(sk)| }; the caller compares with its bound */
+int spp_rlwe_key_check(spp_ctx* ctx, size_t count, const uint32_t* pk_a, const uint32_t* pk_b, const uint32_t* sk_mod_q,
+                       uint32_t* max_abs);
+/* t-of-m sharing of n field elements.  xs: m distinct non-zero indices, NULL = 1..m.  secrets_be n*32 canonical.
+ * coeffs_be (t-1)*n*32, coefficient of x^k of value i at ((k-1)*n + i)*32, canonical; NULL = OS randomness (rejection below r).
+ * ys = m*n*32, share-major.  t == 1: every share equals the secret. */
+int spp_shamir_split(spp_ctx* ctx, uint32_t t, uint32_t m, const uint32_t* xs, size_t n, const uint8_t* secrets_be,
+                     const uint8_t* coeffs_be, uint8_t* ys);
 
 /* Opening audit records in one pass: what an auditor replaying submit_audit logs asks of every record (proof, public witness,
  * ciphertext) -- does the proof verify, is this the ciphertext the proof committed to, is the decrypted identity the one the

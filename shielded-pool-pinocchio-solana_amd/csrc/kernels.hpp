@@ -124,6 +124,14 @@ void launch_poseidon2_sponge(hipStream_t st, HashConsts hc, const uint8_t* in_be
 void launch_rlwe_decrypt(hipStream_t st, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, uint8_t* msg, uint32_t count);
 void launch_shamir_combine(hipStream_t st, const Fr* lambda, const uint8_t* ys_be, uint32_t t, uint32_t n, uint8_t* secret_be,
                            uint32_t* sk_mod_q);
+// auditor key generation (rlwe_keygen.hpp): one wave per key; b, sk_mod_q (optional) count * 1024; max_abs count * 2
+void launch_rlwe_keygen(hipStream_t st, const RlweDev& rd, const int8_t* sk, const uint32_t* a, const int8_t* e, uint32_t* b,
+                        uint32_t* sk_mod_q, uint32_t count);
+void launch_rlwe_key_noise(hipStream_t st, const RlweDev& rd, const uint32_t* a, const uint32_t* b, const uint32_t* sk_mod_q,
+                           uint32_t* max_abs, uint32_t count);
+// t-of-m sharing of n values: xs m share indices as Fr, coeffs_be (t - 1) * n * 32 B, ys_be m * n * 32 B share-major
+void launch_shamir_split(hipStream_t st, const Fr* xs, const uint8_t* secrets_be, const uint8_t* coeffs_be, uint32_t t, uint32_t m,
+                         uint32_t n, uint8_t* ys_be);
 // one wave per 64 audit records (audit_open.hpp): owners count * 64 B, flags[i] = SPP_AUDIT_* bits; proof_ok (optional): the verdicts
 // of launch_verify for the same records, enqueued before on `st`
 void launch_audit_open(hipStream_t st, HashConsts hc, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, const uint8_t* pws,

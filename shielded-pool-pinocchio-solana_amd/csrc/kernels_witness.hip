@@ -12,11 +12,14 @@
 //   k_deposit_roots       the same deposits' mt.getRoot() after each insert
 //   k_poseidon2_sponge    ct_helper/src/main.nr:15-34 (= scripts/generate_audit.py:355-374)
 //   k_audit_open          scripts/rlwe_decrypt.py:61-149 for a batch of (pw, ciphertext) records, with the binding checks it omits
+//   k_rlwe_keygen         scripts/rlwe_keygen.py:98-116 (the audit key pair), k_rlwe_key_noise: the check a key holder can make
+//   k_shamir_split        scripts/rlwe_keygen.py:51-65 (shamir_share_field), the inverse of k_shamir_combine
 #include "kernels.hpp"
 #include "poseidon29.hpp"
 #include "poseidon2.hpp"
 #include "rlwe_ntt.hpp"
 #include "audit_open.hpp"
+#include "rlwe_keygen.hpp"
 
 namespace spp {
 
@@ -585,6 +588,106 @@ __global__ void __launch_bounds__(256) k_shamir_combine(const Fr* __restrict__ l
 void launch_shamir_combine(hipStream_t st, const Fr* lambda, const uint8_t* ys_be, uint32_t t, uint32_t n, uint8_t* secret_be,
                            uint32_t* sk_mod_q) {
   if (n) hipLaunchKernelGGL(k_shamir_combine, dim3((n + 255) / 256), dim3(256), 0, st, lambda, ys_be, t, n, secret_be, sk_mod_q);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Auditor key generation (scripts/rlwe_keygen.py:98-182): the key pair, the check of a key, the Shamir sharing of the secret.
+// One wavefront per key, lane t owns the coefficients t + 64 j, field 0 of the tables only (rlwe_keygen.hpp has the per-lane
+// phases and the bound argument of the chain: twist, two forward transforms, product, inverse transform, untwist).
+// ----------------------------------------------------------------------------------------------------
+// A <- A * S mod (X^1024 + 1, q) at the lane's coefficients, in (-q, q); A in [0, q), S any int32 per coefficient
+__device__ __forceinline__ void rk_negacyclic(uint32_t lane, int32_t (&A)[16], int32_t (&S)[16], int32_t* lds, const RnTables& tb,
+                                              int32_t scale) {
+  const RnField& f = tb.f[0];
+  rk_twist(lane, A, tb.psi[0], f);
+  rk_twist(lane, S, tb.psi[0], f);
+  rn_ntt1<true>(lane, A, lds, f, tb.w[0][0], 0);
+  rn_ntt1<true>(lane, S, lds, f, tb.w[0][0], 0);
+  rk_pointwise(A, S, scale, f);
+  rn_ntt1<true>(lane, A, lds, f, tb.w[0][1], 1);
+  rk_twist(lane, A, tb.ipsi[0], f);
+}
+// b = e - a * sk mod (X^1024 + 1, q) in [0, q)   (rlwe_keygen.py:110-116); sk_mod_q (optional): sk mod q (:105)
+__global__ void __launch_bounds__(64) k_rlwe_keygen(RnTables tb, int32_t scale, const int8_t* __restrict__ sk_in, const uint32_t* __restrict__ a_in,
+                                                    const int8_t* __restrict__ e_in, uint32_t* __restrict__ b_out,
+                                                    uint32_t* __restrict__ sk_mod_q, uint32_t count) {
+  __shared__ int32_t lds[RN_LDS_WORDS];
+  const uint32_t inst = blockIdx.x, lane = threadIdx.x;
+  if (inst >= count) return;
+  const size_t base = (size_t)inst * RL_N;
+  int32_t A[16], S[16];
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    const uint32_t i = lane + 64 * j;
+    A[j] = (int32_t)a_in[base + i];
+    S[j] = sk_in[base + i];                  // signed, as it is
+    if (sk_mod_q) sk_mod_q[base + i] = (uint32_t)rn_canon(S[j], tb.f[0]);
+  }
+  rk_negacyclic(lane, A, S, lds, tb, scale);
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    const uint32_t i = lane + 64 * j;
+    b_out[base + i] = rk_public_b(A[j], e_in[base + i], tb.f[0]);
+  }
+}
+// max_abs[2 inst] = max_i |centred(b + a * sk mod q)_i|, max_abs[2 inst + 1] = max_i |centred(sk_i)|; sk_mod_q in [0, q)
+__global__ void __launch_bounds__(64) k_rlwe_key_noise(RnTables tb, int32_t scale, const uint32_t* __restrict__ a_in,
+                                                       const uint32_t* __restrict__ b_in, const uint32_t* __restrict__ sk_mod_q,
+                                                       uint32_t* __restrict__ max_abs, uint32_t count) {
+  __shared__ int32_t lds[RN_LDS_WORDS];
+  const uint32_t inst = blockIdx.x, lane = threadIdx.x;
+  if (inst >= count) return;
+  const size_t base = (size_t)inst * RL_N;
+  int32_t A[16], S[16];
+  uint32_t msk = 0, mnoise = 0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    const uint32_t i = lane + 64 * j;
+    A[j] = (int32_t)a_in[base + i];
+    S[j] = (int32_t)sk_mod_q[base + i];
+    msk = rk_max(msk, rk_abs_centred((uint32_t)S[j], tb.f[0]));
+  }
+  rk_negacyclic(lane, A, S, lds, tb, scale);
+#pragma unroll
+  for (int j = 0; j < 16; j++) mnoise = rk_max(mnoise, rk_noise(b_in[base + lane + 64 * j], A[j], tb.f[0]));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mnoise = rk_max(mnoise, (uint32_t)__shfl_xor((int)mnoise, o, 64));
+    msk = rk_max(msk, (uint32_t)__shfl_xor((int)msk, o, 64));
+  }
+  if (lane == 0) {
+    max_abs[2 * (size_t)inst] = mnoise;
+    max_abs[2 * (size_t)inst + 1] = msk;
+  }
+}
+void launch_rlwe_keygen(hipStream_t st, const RlweDev& rd, const int8_t* sk, const uint32_t* a, const int8_t* e, uint32_t* b,
+                        uint32_t* sk_mod_q, uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_rlwe_keygen, dim3(count), dim3(64), 0, st, rd.tb, rd.pk_scale[0], sk, a, e, b, sk_mod_q, count);
+}
+void launch_rlwe_key_noise(hipStream_t st, const RlweDev& rd, const uint32_t* a, const uint32_t* b, const uint32_t* sk_mod_q,
+                           uint32_t* max_abs, uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_rlwe_key_noise, dim3(count), dim3(64), 0, st, rd.tb, rd.pk_scale[0], a, b, sk_mod_q, max_abs, count);
+}
+
+// Shamir sharing (shamir_share_field, rlwe_keygen.py:51-65): y[j][i] = sum_k c_k[i] x_j^k over Fr by Horner, c_0 = secret[i],
+// c_k at coeffs_be[(k - 1) n + i].  One lane per (value i, share j), i fastest: the loads of a wave are consecutive values.
+// ys_be is share-major, what k_shamir_combine reads.
+__global__ void __launch_bounds__(256) k_shamir_split(const Fr* __restrict__ xs, const uint8_t* __restrict__ secrets_be,
+                                                      const uint8_t* __restrict__ coeffs_be, uint32_t t, uint32_t m, uint32_t n,
+                                                      uint8_t* __restrict__ ys_be) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;   // m n <= 255 * 2^20
+  if (g >= m * n) return;
+  const uint32_t j = g / n, i = g % n;
+  const Fr x = xs[j];
+  Fr acc = Fr::zero();
+  for (uint32_t k = t - 1; k >= 1; k--) acc = (acc + load_be(coeffs_be + ((size_t)(k - 1) * n + i) * 32)) * x;
+  acc = acc + load_be(secrets_be + (size_t)i * 32);
+  store_be(ys_be + ((size_t)j * n + i) * 32, acc);
+}
+void launch_shamir_split(hipStream_t st, const Fr* xs, const uint8_t* secrets_be, const uint8_t* coeffs_be, uint32_t t, uint32_t m,
+                         uint32_t n, uint8_t* ys_be) {
+  const uint32_t lanes = m * n;
+  if (lanes) hipLaunchKernelGGL(k_shamir_split, dim3((lanes + 255) / 256), dim3(256), 0, st, xs, secrets_be, coeffs_be, t, m, n, ys_be);
 }
 
 // ----------------------------------------------------------------------------------------------------

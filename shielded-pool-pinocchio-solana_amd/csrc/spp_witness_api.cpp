@@ -614,3 +614,192 @@ extern "C" int spp_rlwe_decrypt_batch(spp_ctx* ctx, const uint32_t* sk_mod_q, si
   HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
+
+// -----------------------------------------------------------------------------------------------------
+// auditor key generation (scripts/rlwe_keygen.py:98-182): sampling on the host, the key pair and its check on the device, the
+// Shamir sharing of the secret key (:51-65).  Everything that held the secret key or the sharing polynomials is wiped.
+// -----------------------------------------------------------------------------------------------------
+namespace {
+const uint32_t RLWE_Q = 167772161u;
+const size_t KEYGEN_MAX_KEYS = (size_t)1 << 16, SHAMIR_MAX_VALUES = (size_t)1 << 20;
+void wipe(void* p, size_t bytes) {
+  volatile uint8_t* v = (volatile uint8_t*)p;
+  for (size_t i = 0; i < bytes; i++) v[i] = 0;
+}
+// OS randomness in blocks; wiped when it goes
+struct OsRandom {
+  FILE* f = nullptr;
+  uint8_t buf[4096];
+  size_t pos = sizeof buf;
+  ~OsRandom() {
+    if (f) fclose(f);
+    wipe(buf, sizeof buf);
+  }
+  bool next(uint8_t* out, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+      if (pos == sizeof buf) {
+        if (!f) {
+          f = fopen("/dev/urandom", "rb");
+          if (f) setvbuf(f, nullptr, _IONBF, 0);   // no second copy of the bytes in a stdio buffer
+        }
+        if (!f || fread(buf, 1, sizeof buf, f) != sizeof buf) return false;
+        pos = 0;
+      }
+      out[i] = buf[pos++];
+    }
+    return true;
+  }
+};
+// device buffer of secrets: zeroed on its stream before DevBuf's destructor frees it, on every return path
+struct WipedDevBuf : DevBuf {
+  size_t bytes = 0;
+  hipStream_t st = nullptr;
+  ~WipedDevBuf() {
+    if (p && bytes) {
+      (void)hipMemsetAsync(p, 0, bytes, st);
+      (void)hipStreamSynchronize(st);
+    }
+  }
+};
+#define UP_SECRET(buf, src, nbytes) \
+  do {                              \
+    buf.bytes = (nbytes);           \
+    buf.st = st;                    \
+    UP(buf, src, nbytes);           \
+  } while (0)
+int check_below_q(const char* what, const uint32_t* v, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (v[i] >= RLWE_Q) return fail(SPP_ERR_BAD_INPUT, "%s[%zu] = %u is not in [0, q)", what, i, v[i]);
+  return SPP_OK;
+}
+}  // namespace
+
+extern "C" int spp_rlwe_sample_key(size_t count, uint32_t bound, int8_t* sk, uint32_t* a, int8_t* e) {
+  if (!sk || !a || !e) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (bound < 1 || bound > 127) return fail(SPP_ERR_BAD_INPUT, "bound %u is not in [1, 127]", bound);
+  if (count > KEYGEN_MAX_KEYS) return fail(SPP_ERR_BAD_INPUT, "count %zu: at most 2^16 keys in one call", count);
+  OsRandom rnd;
+  const uint32_t range = 2 * bound + 1, limit = 256 - 256 % range;   // bytes below `limit` are uniform mod range
+  const size_t n = count * 1024;
+  for (int8_t* dst : {sk, e})
+    for (size_t i = 0; i < n;) {
+      uint8_t v;
+      if (!rnd.next(&v, 1)) return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+      if (v < limit) dst[i++] = (int8_t)((int)(v % range) - (int)bound);
+    }
+  for (size_t i = 0; i < n;) {
+    uint8_t w[4];
+    if (!rnd.next(w, 4)) return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+    const uint32_t v = ((uint32_t)w[0] | (uint32_t)w[1] << 8 | (uint32_t)w[2] << 16 | (uint32_t)w[3] << 24) & 0x0fffffffu;   // q < 2^28
+    if (v < RLWE_Q) a[i++] = v;
+  }
+  return SPP_OK;
+}
+
+extern "C" int spp_rlwe_keygen_batch(spp_ctx* ctx, size_t count, const int8_t* sk, const uint32_t* a, const int8_t* e, uint32_t* pk_b,
+                                     uint32_t* sk_mod_q) {
+  if (!ctx || !sk || !a || !e || !pk_b) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count > KEYGEN_MAX_KEYS) return fail(SPP_ERR_BAD_INPUT, "count %zu: at most 2^16 keys in one call", count);
+  if (count == 0) return SPP_OK;
+  if (int rc = check_below_q("a", a, count * 1024)) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (int rc = spp_ensure_rlwe(ctx)) return rc;
+  const size_t n = count * 1024;
+  WipedDevBuf dsk, dskq;
+  DevBuf da, de, db;
+  UP_SECRET(dsk, sk, n);
+  UP(da, a, n * 4); UP(de, e, n);
+  HIP_TRY(db.alloc(n * 4));
+  if (sk_mod_q) {
+    dskq.bytes = n * 4; dskq.st = st;
+    HIP_TRY(dskq.alloc(n * 4));
+  }
+  launch_rlwe_keygen(st, ctx->rlwe, dsk.as<int8_t>(), da.as<uint32_t>(), de.as<int8_t>(), db.as<uint32_t>(),
+                     sk_mod_q ? dskq.as<uint32_t>() : nullptr, (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(pk_b, db.p, n * 4, hipMemcpyDeviceToHost, st));
+  if (sk_mod_q) HIP_TRY(hipMemcpyAsync(sk_mod_q, dskq.p, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" int spp_rlwe_key_check(spp_ctx* ctx, size_t count, const uint32_t* pk_a, const uint32_t* pk_b, const uint32_t* sk_mod_q,
+                                  uint32_t* max_abs) {
+  if (!ctx || !pk_a || !pk_b || !sk_mod_q || !max_abs) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count > KEYGEN_MAX_KEYS) return fail(SPP_ERR_BAD_INPUT, "count %zu: at most 2^16 keys in one call", count);
+  if (count == 0) return SPP_OK;
+  const size_t n = count * 1024;
+  if (int rc = check_below_q("pk_a", pk_a, n)) return rc;
+  if (int rc = check_below_q("pk_b", pk_b, n)) return rc;
+  if (int rc = check_below_q("sk_mod_q", sk_mod_q, n)) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (int rc = spp_ensure_rlwe(ctx)) return rc;
+  WipedDevBuf dsk;
+  DevBuf da, db, dm;
+  UP_SECRET(dsk, sk_mod_q, n * 4);
+  UP(da, pk_a, n * 4); UP(db, pk_b, n * 4);
+  HIP_TRY(dm.alloc(count * 8));
+  launch_rlwe_key_noise(st, ctx->rlwe, da.as<uint32_t>(), db.as<uint32_t>(), dsk.as<uint32_t>(), dm.as<uint32_t>(), (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(max_abs, dm.p, count * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" int spp_shamir_split(spp_ctx* ctx, uint32_t t, uint32_t m, const uint32_t* xs, size_t n, const uint8_t* secrets_be,
+                                const uint8_t* coeffs_be, uint8_t* ys) {
+  if (!ctx || !secrets_be || !ys) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (t == 0 || t > 64) return fail(SPP_ERR_BAD_INPUT, "threshold %u is not in [1, 64]", t);
+  if (m < t || m > 255) return fail(SPP_ERR_BAD_INPUT, "%u shares: need between the threshold %u and 255", m, t);
+  if (xs)
+    for (uint32_t j = 0; j < m; j++) {
+      if (xs[j] == 0) return fail(SPP_ERR_BAD_INPUT, "xs[%u] is 0: that share would be the secret", j);
+      for (uint32_t k = 0; k < j; k++)
+        if (xs[k] == xs[j]) return fail(SPP_ERR_BAD_INPUT, "xs[%u] repeats xs[%u] = %u", j, k, xs[j]);
+    }
+  if (n > SHAMIR_MAX_VALUES) return fail(SPP_ERR_BAD_INPUT, "n %zu: at most 2^20 values in one call", n);
+  if (n == 0) return SPP_OK;
+  for (size_t i = 0; i < n; i++)
+    if (!be_is_canonical<FrParams>(secrets_be + 32 * i)) return fail(SPP_ERR_BAD_INPUT, "secret %zu is not a canonical field element", i);
+  const size_t ncoef = (size_t)(t - 1) * n;
+  if (coeffs_be)
+    for (size_t i = 0; i < ncoef; i++)
+      if (!be_is_canonical<FrParams>(coeffs_be + 32 * i))
+        return fail(SPP_ERR_BAD_INPUT, "coefficient %zu (x^%zu of value %zu) is not a canonical field element", i, i / n + 1, i % n);
+  // the sharing polynomials from the OS when the caller brings none: 254 random bits, kept when below r (3 of 4 are)
+  struct WipedBytes {
+    std::vector<uint8_t> v;
+    ~WipedBytes() { wipe(v.data(), v.size()); }
+  } drawn;
+  if (!coeffs_be && ncoef) {
+    drawn.v.resize(ncoef * 32);
+    OsRandom rnd;
+    for (size_t i = 0; i < ncoef;) {
+      uint8_t* c = drawn.v.data() + 32 * i;
+      if (!rnd.next(c, 32)) return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+      c[0] &= 0x3f;
+      if (be_is_canonical<FrParams>(c)) i++;
+    }
+    coeffs_be = drawn.v.data();
+  }
+  std::vector<Fr> x(m);
+  for (uint32_t j = 0; j < m; j++) x[j] = Fr::from_u64(xs ? xs[j] : j + 1);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  WipedDevBuf ds, dc;
+  DevBuf dx, dy;
+  UP(dx, x.data(), sizeof(Fr) * m);
+  UP_SECRET(ds, secrets_be, n * 32);
+  UP_SECRET(dc, coeffs_be, ncoef * 32);
+  HIP_TRY(dy.alloc((size_t)m * n * 32));
+  launch_shamir_split(st, dx.as<Fr>(), ds.as<uint8_t>(), dc.as<uint8_t>(), t, m, (uint32_t)n, dy.as<uint8_t>());
+  HIP_TRY(hipMemcpyAsync(ys, dy.p, (size_t)m * n * 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}

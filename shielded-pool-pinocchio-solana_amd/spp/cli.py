@@ -15,6 +15,13 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # the auditor's `python scripts/rlwe_decrypt.py`: reconstructs the key from the shares, verifies the
                               # proof (`-`: already verified elsewhere), checks that the ciphertext is the one the proof commits
                               # to and that it decrypts to the identity the proof commits to; exit 0 only if all three hold
+    python -m spp.cli rlwe-keygen --out DIR [--threshold 2 --shares 3] [--reference-seed N]
+                              # `python scripts/rlwe_keygen.py`: DIR/rlwe_pk.json, DIR/rlwe_params.json and
+                              # DIR/rlwe_sk_shares/share_<i>.json, from the operating system's randomness; then checks its own
+                              # files on the GPU (reconstructs the key from the first `threshold` shares, both noise maxima)
+    python -m spp.cli rlwe-key-check rlwe_pk.json --shares share_1.json share_2.json [--params rlwe_params.json]
+                              # are these shares the secret of this public key?  prints max |b + a*sk| and max |sk| (centred),
+                              # exit 0 iff both are within the noise bound of rlwe_params.json (next to rlwe_pk.json; default 3)
     python -m spp.cli pool-replay withdraw.vk audit.vk log.jsonl [--capacity N]
                               # the pool program's decisions for a log of instructions, one JSON object per line, values in hex:
                               #   {"deposit": {"root"}}  {"submit_audit": {"proof", "pw"}}  {"withdraw": {"proof", "pw", "recipient"}}
@@ -103,6 +110,92 @@ def _audit_open(a):
     if claimed is not None and claimed != owners[0]:
         print("note: the prover's expected_owner differs from the decrypted owner")
     return 0 if f == 0 else 1
+
+
+def _load_shares(paths):
+    """the share files of a key, enough of them and at distinct indices, or ValueError"""
+    from . import witness
+    shares = [witness.load_share_json(p) for p in paths]
+    need = max(s["threshold"] for s in shares)
+    if len({s["x"] for s in shares}) != len(shares) or len(shares) < need:
+        raise ValueError("need %d shares with distinct indices, got %d" % (need, len(shares)))
+    return shares
+
+
+def _key_maxima(ctx, pk_a, pk_b, shares):
+    from . import witness
+    sk = witness.reconstruct_sk(ctx, shares)
+    return witness.rlwe_key_check(ctx, pk_a, pk_b, sk)[0]
+
+
+def _rlwe_keygen(a):
+    from . import witness
+    t, m = a.threshold, a.shares
+    if not (1 <= t <= 64 and t <= m <= 255):
+        print("spp rlwe-keygen: need 1 <= threshold <= 64 and threshold <= shares <= 255", file=sys.stderr)
+        return 2
+    shares_dir = os.path.join(a.out, "rlwe_sk_shares")
+    try:
+        os.makedirs(shares_dir, exist_ok=True)
+    except OSError as e:
+        print("spp rlwe-keygen: %s" % e, file=sys.stderr)
+        return 2
+    bound = witness.NOISE_BOUND
+    if a.reference_seed is not None:
+        sk, pk_a, e, coeffs = witness.reference_key_draws(a.reference_seed, t)
+    else:
+        sk, pk_a, e = (x[0] for x in witness.rlwe_sample_key(lib.load_library(), 1, bound))
+        coeffs = None                                     # drawn by the library, from the operating system
+    pk_path = os.path.join(a.out, "rlwe_pk.json")
+    share_paths = [os.path.join(shares_dir, "share_%d.json" % (j + 1)) for j in range(m)]
+    ctx = Context(a.device)
+    try:
+        pk_b, _ = witness.rlwe_keygen(ctx, sk, pk_a, e)
+        shares = witness.shamir_split(ctx, [int(v) % R for v in sk], t, m, coeffs=coeffs)
+        witness.write_rlwe_pk_json(pk_path, pk_a, pk_b[0])
+        witness.write_rlwe_params_json(os.path.join(a.out, "rlwe_params.json"), t, m, bound)
+        for j, (path, sh) in enumerate(zip(share_paths, shares)):
+            witness.write_share_json(path, j + 1, t, m, sh["x"], sh["y"])
+        # the files as a key holder will read them, not the arrays they were written from
+        noise, skmax = _key_maxima(ctx, *witness.load_rlwe_pk_json(pk_path), _load_shares(share_paths[:t]))
+    except (OSError, ValueError, lib.SppError) as e:
+        print("spp rlwe-keygen: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    if noise > bound or skmax > bound:
+        print("spp rlwe-keygen: the files in %s FAILED their check (max |b + a*sk| = %d, max |sk| = %d, bound %d): do not use them"
+              % (a.out, noise, skmax, bound), file=sys.stderr)
+        return 1
+    print("rlwe-keygen: %s, rlwe_params.json and %d shares (threshold %d) in %s" % (pk_path, m, t, shares_dir))
+    print("check: key reconstructed from shares 1..%d, max |b + a*sk| = %d, max |sk| = %d (bound %d)" % (t, noise, skmax, bound))
+    return 0
+
+
+def _rlwe_key_check(a):
+    from . import witness
+    try:   # everything that can be wrong with the files is found before a device is opened
+        pk_a, pk_b = witness.load_rlwe_pk_json(a.pk)
+        shares = _load_shares(a.shares)
+        bound = witness.NOISE_BOUND
+        params = a.params or os.path.join(os.path.dirname(os.path.abspath(a.pk)), "rlwe_params.json")
+        if a.params or os.path.exists(params):
+            bound = int(json.load(open(params))["noise_bound"])
+    except (OSError, ValueError, KeyError, TypeError) as e:
+        print("spp rlwe-key-check: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        noise, skmax = _key_maxima(ctx, pk_a, pk_b, shares)
+    except lib.SppError as e:
+        print("spp rlwe-key-check: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    print("max |b + a*sk| = %d\nmax |sk| = %d\nnoise bound = %d" % (noise, skmax, bound))
+    ok = noise <= bound and skmax <= bound
+    print("key: %s" % ("the shares hold the secret of this public key" if ok else "NOT a key pair within the bound"))
+    return 0 if ok else 1
 
 
 _POOL_FIELDS = {"deposit": (("root", 32),), "submit_audit": (("proof", lib.PROOF_LEN), ("pw", lib.AUDIT_PW_LEN)),
@@ -203,7 +296,21 @@ def main(argv=None):
     r = sub.add_parser("pool-replay"); r.add_argument("withdraw_vk"); r.add_argument("audit_vk"); r.add_argument("log", help="one instruction per line (JSON)")
     r.add_argument("--capacity", type=int, default=0, help="keys per set (default: enough for the log)")
     r.add_argument("--device", type=int, default=0)
+    k = sub.add_parser("rlwe-keygen"); k.add_argument("--out", required=True, metavar="DIR")
+    k.add_argument("--threshold", type=int, default=2); k.add_argument("--shares", type=int, default=3)
+    k.add_argument("--reference-seed", type=int, default=None, metavar="N",
+                   help="draw from random.Random(N) in the order of scripts/rlwe_keygen.py: for reproducing fixtures only, "
+                        "NEVER a key to use (the default is the operating system's randomness)")
+    k.add_argument("--device", type=int, default=0)
+    kc = sub.add_parser("rlwe-key-check"); kc.add_argument("pk", help="rlwe_pk.json")
+    kc.add_argument("--shares", nargs="+", required=True, metavar="SHARE.json", help="threshold many share files")
+    kc.add_argument("--params", default=None, help="rlwe_params.json (default: next to the public key; without one the bound is 3)")
+    kc.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.cmd == "rlwe-keygen":
+        return _rlwe_keygen(a)
+    if a.cmd == "rlwe-key-check":
+        return _rlwe_key_check(a)
     if a.cmd == "audit-open":
         return _audit_open(a)
     if a.cmd == "verify-batch":

@@ -146,6 +146,10 @@ def load_library():
     L.spp_prove_withdraw_notes.argtypes = [vp, vp, sz, cp, cp, vp, vp, vp]
     L.spp_shamir_reconstruct.argtypes = [vp, u32, vp, cp, sz, vp, vp]
     L.spp_rlwe_decrypt_batch.argtypes = [vp, vp, sz, vp, vp, vp]
+    L.spp_rlwe_sample_key.argtypes = [sz, u32, vp, vp, vp]
+    L.spp_rlwe_keygen_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.spp_rlwe_key_check.argtypes = [vp, sz, vp, vp, vp, vp]
+    L.spp_shamir_split.argtypes = [vp, u32, u32, vp, sz, cp, cp, vp]
     L.spp_ntt_fr.argtypes = [vp, vp, u32, i32]
     L.spp_msm_g1.argtypes = [vp, cp, cp, sz, i32, vp]
     L.spp_msm_g2.argtypes = [vp, cp, cp, sz, i32, vp]

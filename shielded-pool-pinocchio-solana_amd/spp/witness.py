@@ -13,6 +13,11 @@
     ct_commitment(...)       ct_helper/src/main.nr:15-34
     ciphertext_json(...)     scripts/generate_audit.py:590-606 (keys/ciphertext.json, what the prover leaves for the auditor)
     load_share_json(...)     scripts/rlwe_keygen.py:157-171 (keys/rlwe_sk_shares/share_<i>.json)
+    rlwe_sample_key / rlwe_keygen / rlwe_key_check / shamir_split
+                             scripts/rlwe_keygen.py:98-116 (the audit key pair) and :51-65 (shamir_share_field)
+    write_rlwe_pk_json / write_rlwe_params_json / write_share_json
+                             scripts/rlwe_keygen.py:124-127, 133-142, 161-169: the files `cli compile --rlwe-pk` and
+                             load_share_json read
 All of them take and return Python ints / lists; field elements cross the C ABI as 32-byte big-endian.
 """
 import ctypes
@@ -481,3 +486,126 @@ def load_share_json(path):
     if xs or len(ys) != RLWE_N or not all(0 <= v < FR_MODULUS for v in ys) or out["x"] <= 0:
         raise ValueError("%s: a share is 1024 field elements at one nonzero x" % path)
     return out
+
+
+# ---- auditor key generation: scripts/rlwe_keygen.py ----
+NOISE_BOUND = 3
+
+
+def rlwe_sample_key(L, count=1, bound=NOISE_BOUND):
+    """count fresh (sk, a, e) from the operating system's randomness (host only; L: the loaded library): int8 [count,1024] in
+    [-bound, bound], uint32 [count,1024] in [0, q), int8 [count,1024]."""
+    sk = np.zeros((count, RLWE_N), dtype=np.int8)
+    a = np.zeros((count, RLWE_N), dtype=np.uint32)
+    e = np.zeros((count, RLWE_N), dtype=np.int8)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    check(L.spp_rlwe_sample_key(count, bound, p(sk), p(a), p(e)))
+    return sk, a, e
+
+
+def rlwe_keygen(ctx, sk, a, e):
+    """Batch: sk, e signed [count,1024], a [count,1024] in [0, q).  Returns (b, sk_mod_q), uint32 [count,1024]:
+    b = e - a*sk mod (X^1024 + 1, q) (rlwe_keygen.py:110-116) and sk mod q, the form rlwe_decrypt takes."""
+    sk = np.ascontiguousarray(sk, dtype=np.int8).reshape(-1, RLWE_N)
+    count = sk.shape[0]
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(count, RLWE_N)
+    e = np.ascontiguousarray(e, dtype=np.int8).reshape(count, RLWE_N)
+    b = np.zeros((count, RLWE_N), dtype=np.uint32)
+    skq = np.zeros((count, RLWE_N), dtype=np.uint32)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    check(ctx.L.spp_rlwe_keygen_batch(ctx.h, count, p(sk), p(a), p(e), p(b), p(skq)))
+    return b, skq
+
+
+def rlwe_key_check(ctx, pk_a, pk_b, sk_mod_q):
+    """Batch: for every key (max |centred(b + a*sk mod q)|, max |centred(sk)|) as a list of int pairs; a key pair made with noise
+    bound B has both at most B."""
+    a = np.ascontiguousarray(pk_a, dtype=np.uint32).reshape(-1, RLWE_N)
+    count = a.shape[0]
+    b = np.ascontiguousarray(pk_b, dtype=np.uint32).reshape(count, RLWE_N)
+    sk = np.ascontiguousarray(sk_mod_q, dtype=np.uint32).reshape(count, RLWE_N)
+    out = np.zeros((count, 2), dtype=np.uint32)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    check(ctx.L.spp_rlwe_key_check(ctx.h, count, p(a), p(b), p(sk), p(out)))
+    return [(int(x), int(y)) for x, y in out]
+
+
+def shamir_split(ctx, secrets, threshold, num_shares, xs=None, coeffs=None):
+    """threshold-of-num_shares sharing of a list of field elements (shamir_share_field, rlwe_keygen.py:51-65, for all of them at
+    once).  xs: the share indices (default 1..num_shares); coeffs: coeffs[k-1][i] = coefficient of x^k of value i (default: drawn
+    from the operating system by the library).  Returns the shares as reconstruct_sk takes them: [{"x", "y": [int] * n}]."""
+    secrets = [int(v) for v in secrets]
+    n, t, m = len(secrets), int(threshold), int(num_shares)
+    if xs is not None and len(xs) != m:
+        raise ValueError("xs must name %d shares" % m)
+    if coeffs is not None and (len(coeffs) != t - 1 or any(len(row) != n for row in coeffs)):
+        raise ValueError("coeffs must be %d rows of %d field elements" % (t - 1, n))
+    cx = None if xs is None else (ctypes.c_uint32 * m)(*[int(x) for x in xs])
+    cc = None if coeffs is None else _be(v for row in coeffs for v in row)
+    out = ctypes.create_string_buffer(max(1, m * n * 32))
+    check(ctx.L.spp_shamir_split(ctx.h, t, m, None if cx is None else ctypes.cast(cx, ctypes.c_void_p), n, _be(secrets), cc,
+                                 ctypes.cast(out, ctypes.c_void_p)))
+    ys = _unbe(out.raw, m * n)
+    return [{"x": int(xs[j]) if xs is not None else j + 1, "y": ys[j * n:(j + 1) * n]} for j in range(m)]
+
+
+def write_rlwe_pk_json(path, a, b):
+    """rlwe_pk.json (rlwe_keygen.py:124-127): {"a", "b"}, coefficients as "0x%08x"."""
+    import json
+    a, b = [int(v) for v in a], [int(v) for v in b]
+    if len(a) != RLWE_N or len(b) != RLWE_N or not all(0 <= v < RLWE_Q for v in a + b):
+        raise ValueError("a public key is 1024 + 1024 coefficients in [0, q)")
+    with open(path, "w") as f:
+        json.dump({"a": ["0x%08x" % v for v in a], "b": ["0x%08x" % v for v in b]}, f)
+
+
+def write_rlwe_params_json(path, threshold, num_shares, noise_bound=NOISE_BOUND):
+    """rlwe_params.json (rlwe_keygen.py:133-142)."""
+    import json
+    with open(path, "w") as f:
+        json.dump({"N": RLWE_N, "q": RLWE_Q, "noise_bound": int(noise_bound), "plaintext_modulus": 256, "delta": RLWE_Q // 256,
+                   "threshold": int(threshold), "num_shares": int(num_shares), "field": "BN254"}, f, indent=2)
+
+
+def share_json(share_index, threshold, num_shares, x, ys):
+    """the dict of one share_<i>.json (rlwe_keygen.py:161-169); "y" is "0x%064x", zero is "0x0" (to_hex_bn254, :91-95)"""
+    ys = [int(v) for v in ys]
+    if not all(0 <= v < FR_MODULUS for v in ys) or int(x) <= 0:
+        raise ValueError("a share is field elements at one nonzero x")
+    return {"share_index": int(share_index), "threshold": int(threshold), "num_shares": int(num_shares),
+            "coefficients": [{"x": int(x), "y": "0x0" if v == 0 else "0x%064x" % v} for v in ys]}
+
+
+def write_share_json(path, share_index, threshold, num_shares, x, ys):
+    import json
+    with open(path, "w") as f:
+        json.dump(share_json(share_index, threshold, num_shares, x, ys), f)
+
+
+def load_rlwe_pk_json(path):
+    """(a, b) of an rlwe_pk.json, the reference's (hex strings) or the fixture's (integers); ValueError if it is not one"""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    try:
+        a, b = ([int(v, 16) if isinstance(v, str) else int(v) for v in d[k]] for k in ("a", "b"))
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError("%s: not an rlwe_pk.json (%s)" % (path, e))
+    if len(a) != RLWE_N or len(b) != RLWE_N or not all(0 <= v < RLWE_Q for v in a + b):
+        raise ValueError("%s: a public key is 1024 + 1024 coefficients in [0, q)" % path)
+    return a, b
+
+
+def reference_key_draws(seed, threshold=2, n=RLWE_N):
+    """(sk, a, e, coeffs) as scripts/rlwe_keygen.py draws them from random.Random(seed) (:99-111, :51-55): sk, a, e, then per key
+    coefficient its threshold - 1 sharing coefficients.  For reproducing fixtures only: a seeded key is no key."""
+    import random
+    rng = random.Random(seed)
+    sk = [rng.randint(-NOISE_BOUND, NOISE_BOUND) for _ in range(n)]
+    a = [rng.randint(0, RLWE_Q - 1) for _ in range(n)]
+    e = [rng.randint(-NOISE_BOUND, NOISE_BOUND) for _ in range(n)]
+    coeffs = [[0] * n for _ in range(threshold - 1)]
+    for i in range(n):
+        for k in range(threshold - 1):
+            coeffs[k][i] = rng.randint(0, FR_MODULUS - 1)
+    return sk, a, e, coeffs
