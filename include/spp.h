@@ -198,20 +198,26 @@ int spp_verify(const uint8_t* vk, size_t vk_len, const uint8_t* proof, size_t pr
 /* debug / parity: full witness of proof 0 of the last batch, n_wires * 32 B big-endian */
 int spp_debug_witness(spp_circuit* c, uint8_t* out, size_t n_wires);
 
-/* debug / parity, TEST ONLY: the device compile of the arithmetic headers (csrc/bn254.hpp, csrc/f29.hpp) on RAW words.  Unlike every
+/* debug / parity, TEST ONLY: the device compile of the arithmetic headers (csrc/bn254.hpp, csrc/f29.hpp, csrc/gnark_hints.hpp) on RAW words.  Unlike every
  * other entry point nothing is converted, reduced or moved to another domain on either side: `in` holds n cases of in_words
  * little-endian uint32 limbs each, exactly the words the header function sees, and `out` receives out_words limbs per case,
  * exactly what it returned.  One lane per case; the kernel loads, calls, stores -- all checking is the caller's
  * (tests/test_gpu_arith.py against Python integers; tests/host/arith_raw_check.cpp is the g++ twin of the same dispatch).
  * selector = field | operation: SPP_ARITH_FR or SPP_ARITH_FQ, plus one of the operation codes of csrc/arith_probe.hpp, which also
  * fixes in_words / out_words per operation (Fp 8 words, F29 9 limbs, Fq2 / F29x2 two of them, c0 first; predicates one word).
- * arg: the k of mul_small; for F29x2 mul / sqr which lifted constant negates a1 (2, 4, 6, 8 = SUBC_kP_1); otherwise ignored.
+ * arg: the k of mul_small; for F29x2 mul / sqr which lifted constant negates a1 (2, 4, 6, 8 = SUBC_kP_1); for BIGS_ADD_SMALL_MUL the
+ * multiplier m as a signed 16-bit value, |m| <= 64; otherwise ignored.
  * Accumulator scripts (per case: step count <= 16, 16 step words `table index | negate << 8`, a table of 8 affine points as Fp
  * words) run madd / madd_distinct from infinity and return the inf flag, to_xyzz().to_affine(), one bit per step for what
  * madd_distinct returned, and the accumulator's own limbs.
+ * Solver hints (codes >= 128, SPP_ARITH_FR only; word layouts in csrc/arith_probe.hpp): HINT_GLV_SPLIT (the 28 constant words of
+ * the solver's scalar-decomposition step, then the scalar -> found, s1, s2), HINT_EMUL_REDUCE (six limb values, q and q^-1 mod 2^256
+ * -> quotient, remainder, the six carries as raw 384-bit words and as canonical field elements), HINT_GRUMPKIN_MUL (scalar, gy ->
+ * finite, x, y), and the wide-integer primitives under them: BIGS_ADD / SUB / NEGATE / LT / SAR64 / LOW64_ZERO / ADD_SMALL_MUL on
+ * 12-word two's-complement operands, BIG_MUL_ACC_4X4_12 / 2X2_12 / 8X8_8 (accumulator, a, b -> accumulator).
  * The probe does NOT check the preconditions the headers state (operands < 2p, limb bounds of the lazy forms, column sums
  * < 2^64, table entries not infinity): out-of-range operands give the header's unspecified result, never a memory fault.
- * SPP_ERR_BAD_INPUT: NULL pointers, n == 0 or n > 2^20, an unknown selector (or an Fq-only operation with SPP_ARITH_FR), an arg
+ * SPP_ERR_BAD_INPUT: NULL pointers, n == 0 or n > 2^20, an unknown selector (or an Fq-only operation with SPP_ARITH_FR, an Fr-only one with SPP_ARITH_FQ), an arg
  * the operation does not know, in_words / out_words other than the operation's. */
 #define SPP_ARITH_FR 0x000u
 #define SPP_ARITH_FQ 0x100u

@@ -1,16 +1,27 @@
 // arith_probe.hpp -- the raw-word probe of the arithmetic headers (spp_debug_arith, include/spp.h): one case = load the operand
-// words as they are, call ONE function of bn254.hpp / f29.hpp, store what it returned.  No conversion, no reduction, no check: the
-// caller (tests/arith_vectors.py) chooses the word the code sees and judges the result against Python integers.
+// words as they are, call ONE function of bn254.hpp / f29.hpp / gnark_hints.hpp, store what it returned.  No conversion, no
+// reduction, no check: the caller (tests/arith_vectors.py) chooses the word the code sees and judges the result against Python
+// integers.
 // The same probe_case is what the gfx950 kernels (kernels_arith_probe.hip) and the g++ twin (tests/host/arith_raw_check.cpp) run,
 // so a difference between the two is a difference of the compilers, not of the harness.
 #pragma once
 #include "f29.hpp"
+#include "gnark_hints.hpp"
 
 namespace spp {
 
-// X(name, code, in_words, out_words, fq_only).  Fp operands are 8 words, F29 operands 9 limbs; Fq2 / F29x2 are c0 then c1.
+// X(name, code, in_words, out_words, fields): fields 0 = Fr and Fq, 1 = Fq only, 2 = Fr only.
+// Fp operands are 8 words, F29 operands 9 limbs; Fq2 / F29x2 are c0 then c1.
 // Scripts: in = [nsteps, 16 step words (table index | negate << 8), 8 table points (x, y as Fp words)];
 //          out = [inf, affine x, y as Fp words, bit s = what step s returned, the accumulator's limbs X, Y, ZZ, ZZZ (zero padded)].
+// Solver hints (gnark_hints.hpp, codes >= 128, Fr only):
+//   HINT_GLV_SPLIT     in = [the 28 constant words of OP_GLV (v1x, v1y, v2x, v2y as 4 magnitude words + sign word, det 8 words), s 4 words]
+//                      out = [found, s1 4 words, s2 4 words]
+//   HINT_EMUL_REDUCE   dev_emulated_reduce<6, 6>: in = [a_0 .. a_5 as 8 canonical words each, q 8 words, q^-1 mod 2^256 8 words]
+//                      out = [k 8 words, r 8 words, carries c_0 .. c_5 as raw Big384 (12 words each), then to_canonical(fr_from_bigs(c_i)) 8 words each]
+//   HINT_GRUMPKIN_MUL  in = [k 8 words, gy as Fr words]; out = [finite, x, y as Fr words (zero when not finite)]
+//   BIGS_*             Big384 operands are 12 words; LT / LOW64_ZERO return one word; ADD_SMALL_MUL: arg = m as a signed 16-bit value
+//   BIG_MUL_ACC_AxB_N  in = [accumulator N words, a A words, b B words]; out = the accumulator (N words) after big_mul_acc
 #define SPP_ARITH_OPS(X)                      \
   X(FP_MUL, 1, 16, 8, 0)                      \
   X(FP_SQR, 2, 8, 8, 0)                       \
@@ -54,7 +65,20 @@ namespace spp {
   X(SCRIPT_G1, 98, 145, 54, 1)                \
   X(SCRIPT_G2_29, 99, 273, 106, 1)            \
   X(SCRIPT_G2_29_DISTINCT, 100, 273, 106, 1)  \
-  X(SCRIPT_G2, 101, 273, 106, 1)
+  X(SCRIPT_G2, 101, 273, 106, 1)              \
+  X(HINT_GLV_SPLIT, 128, 32, 9, 2)            \
+  X(HINT_EMUL_REDUCE, 129, 64, 136, 2)        \
+  X(HINT_GRUMPKIN_MUL, 130, 16, 17, 2)        \
+  X(BIGS_ADD, 136, 24, 12, 2)                 \
+  X(BIGS_SUB, 137, 24, 12, 2)                 \
+  X(BIGS_NEGATE, 138, 12, 12, 2)              \
+  X(BIGS_LT, 139, 24, 1, 2)                   \
+  X(BIGS_SAR64, 140, 12, 12, 2)               \
+  X(BIGS_LOW64_ZERO, 141, 12, 1, 2)           \
+  X(BIGS_ADD_SMALL_MUL, 142, 24, 12, 2)       \
+  X(BIG_MUL_ACC_4X4_12, 144, 20, 12, 2)       \
+  X(BIG_MUL_ACC_2X2_12, 145, 16, 12, 2)       \
+  X(BIG_MUL_ACC_8X8_8, 146, 24, 8, 2)
 
 enum ArithOp : uint32_t {
 #define X(name, code, iw, ow, fq) ARITH_##name = code,
@@ -63,6 +87,8 @@ enum ArithOp : uint32_t {
 };
 static constexpr uint32_t ARITH_FIELD_FQ = 0x100u;   // SPP_ARITH_FQ; SPP_ARITH_FR = 0
 static constexpr uint32_t ARITH_SCRIPT_STEPS = 16, ARITH_SCRIPT_POINTS = 8;
+static constexpr int ARITH_FIELDS_BOTH = 0, ARITH_FIELDS_FQ = 1, ARITH_FIELDS_FR = 2;   // the last column of SPP_ARITH_OPS
+static constexpr int ARITH_SMALL_MUL_MAX = 64;   // the largest |m| BIGS_ADD_SMALL_MUL takes (add_small_mul adds |m| times)
 
 // words per case of an operation; false = no such operation for that field
 inline bool arith_probe_shape(uint32_t selector, uint32_t* in_words, uint32_t* out_words) {
@@ -71,7 +97,7 @@ inline bool arith_probe_shape(uint32_t selector, uint32_t* in_words, uint32_t* o
   switch (selector & 0xffu) {
 #define X(name, code, iw, ow, fq) \
   case code:                      \
-    if (fq && !is_fq) return false; \
+    if ((fq == ARITH_FIELDS_FQ && !is_fq) || (fq == ARITH_FIELDS_FR && is_fq)) return false; \
     *in_words = iw;               \
     *out_words = ow;              \
     return true;
@@ -80,12 +106,17 @@ inline bool arith_probe_shape(uint32_t selector, uint32_t* in_words, uint32_t* o
   }
   return false;
 }
-// the args an operation knows (mul_small: the k < 2^16 of its comment; F29x2: which SUBC_kP_1 negates a1)
+// the args an operation knows (mul_small: the k < 2^16 of its comment; F29x2: which SUBC_kP_1 negates a1; add_small_mul: m as a
+// signed 16-bit value, |m| <= 64)
 inline bool arith_probe_arg_ok(uint32_t selector, uint32_t arg) {
   switch (selector & 0xffu) {
     case ARITH_FP_MUL_SMALL: return arg < (1u << 16);
     case ARITH_F29X2_MUL:
     case ARITH_F29X2_SQR: return arg == 2 || arg == 4 || arg == 6 || arg == 8;
+    case ARITH_BIGS_ADD_SMALL_MUL: {
+      const int m = (int16_t)(uint16_t)arg;
+      return arg < (1u << 16) && m >= -ARITH_SMALL_MUL_MAX && m <= ARITH_SMALL_MUL_MAX;
+    }
   }
   return true;
 }
@@ -214,6 +245,61 @@ SPP_HD void f29x2_case(bool sqr, const uint32_t* in, uint32_t* out) {
     st_f29x2(out, F29x2::template mul<CA>(a, ld_f29x2(in + 18)));
   }
 }
+
+SPP_HD Big384 ld_big(const uint32_t* w) {
+  Big384 r;
+  for (int i = 0; i < 12; i++) r.w[i] = w[i];
+  return r;
+}
+SPP_HD void st_big(uint32_t* w, const Big384& a) {
+  for (int i = 0; i < 12; i++) w[i] = a.w[i];
+}
+// big_mul_acc on an accumulator of NW words: in = [accumulator, a (NA words), b (NB words)]
+template <int NW, int NA, int NB>
+SPP_HD void mul_acc_case(const uint32_t* in, uint32_t* out) {
+  uint32_t acc[NW], a[NA], b[NB];
+  for (int i = 0; i < NW; i++) acc[i] = in[i];
+  for (int i = 0; i < NA; i++) a[i] = in[NW + i];
+  for (int i = 0; i < NB; i++) b[i] = in[NW + NA + i];
+  big_mul_acc(acc, NW, a, NA, b, NB);
+  for (int i = 0; i < NW; i++) out[i] = acc[i];
+}
+SPP_HD void glv_case(const uint32_t* in, uint32_t* out) {
+  uint32_t kc[28], s[4], s1[4], s2[4];
+  for (int i = 0; i < 28; i++) kc[i] = in[i];
+  for (int i = 0; i < 4; i++) s[i] = in[28 + i];
+  out[0] = dev_glv_split(kc, s, s1, s2) ? 1u : 0u;
+  for (int i = 0; i < 4; i++) {
+    out[1 + i] = s1[i];
+    out[5 + i] = s2[i];
+  }
+}
+SPP_HD void emul_case(const uint32_t* in, uint32_t* out) {
+  uint32_t a[6][8], qc[16], kq[8], rem[8];
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 8; j++) a[i][j] = in[8 * i + j];
+  for (int i = 0; i < 16; i++) qc[i] = in[48 + i];
+  Big384 carry[6];
+  dev_emulated_reduce<6, 6>(a, qc, kq, rem, carry);
+  for (int i = 0; i < 8; i++) {
+    out[i] = kq[i];
+    out[8 + i] = rem[i];
+  }
+  for (int i = 0; i < 6; i++) {
+    st_big(out + 16 + 12 * i, carry[i]);
+    uint32_t c[8];
+    fr_from_bigs(carry[i]).to_canonical(c);
+    for (int j = 0; j < 8; j++) out[88 + 8 * i + j] = c[j];
+  }
+}
+SPP_HD void grumpkin_case(const uint32_t* in, uint32_t* out) {
+  uint32_t k[8];
+  for (int i = 0; i < 8; i++) k[i] = in[i];
+  Fr x = Fr::zero(), y = Fr::zero();   // what the solver stores when the result is the point at infinity
+  out[0] = dev_grumpkin_mul(k, ld_fp<FrParams>(in + 8), &x, &y) ? 1u : 0u;
+  st_fp(out + 1, x);
+  st_fp(out + 9, y);
+}
 }  // namespace arith_probe
 
 // One case of operation OP over the field Pm: `in` and `out` point at this case's words (arith_probe_shape).
@@ -282,6 +368,26 @@ SPP_HD void arith_probe_case(uint32_t arg, const uint32_t* in, uint32_t* out) {
   else if constexpr (OP == ARITH_SCRIPT_G2_29) script29<XYZZ29G2, G2Affine, false>(in, out);
   else if constexpr (OP == ARITH_SCRIPT_G2_29_DISTINCT) script29<XYZZ29G2, G2Affine, true>(in, out);
   else if constexpr (OP == ARITH_SCRIPT_G2) script_plain<G2XYZZ, G2Affine>(in, out);
+  else if constexpr (OP == ARITH_HINT_GLV_SPLIT) glv_case(in, out);
+  else if constexpr (OP == ARITH_HINT_EMUL_REDUCE) emul_case(in, out);
+  else if constexpr (OP == ARITH_HINT_GRUMPKIN_MUL) grumpkin_case(in, out);
+  else if constexpr (OP == ARITH_BIGS_ADD || OP == ARITH_BIGS_SUB || OP == ARITH_BIGS_ADD_SMALL_MUL) {
+    Big384 a = ld_big(in);
+    const Big384 b = ld_big(in + 12);
+    if constexpr (OP == ARITH_BIGS_ADD) a.add(b);
+    else if constexpr (OP == ARITH_BIGS_SUB) a.sub(b);
+    else a.add_small_mul(b, (int)(int16_t)(uint16_t)arg);
+    st_big(out, a);
+  } else if constexpr (OP == ARITH_BIGS_NEGATE || OP == ARITH_BIGS_SAR64) {
+    Big384 a = ld_big(in);
+    if constexpr (OP == ARITH_BIGS_NEGATE) a.negate();
+    else a.sar64();
+    st_big(out, a);
+  } else if constexpr (OP == ARITH_BIGS_LT) out[0] = ld_big(in).lt(ld_big(in + 12)) ? 1u : 0u;
+  else if constexpr (OP == ARITH_BIGS_LOW64_ZERO) out[0] = ld_big(in).low64_zero() ? 1u : 0u;
+  else if constexpr (OP == ARITH_BIG_MUL_ACC_4X4_12) mul_acc_case<12, 4, 4>(in, out);
+  else if constexpr (OP == ARITH_BIG_MUL_ACC_2X2_12) mul_acc_case<12, 2, 2>(in, out);
+  else if constexpr (OP == ARITH_BIG_MUL_ACC_8X8_8) mul_acc_case<8, 8, 8>(in, out);
 }
 
 }  // namespace spp

@@ -5,7 +5,8 @@
 //   the ACIR MultiScalarMul black box over the Grumpkin generator                                         [dev_grumpkin_mul]
 // Neither hint's source is in the reference tree (Sunspot / gnark are third-party): both restate spp/ccs.py
 // (glv_split, _emulated_mul_hint), which derives them from the rows of the .ccs that consume their outputs, and are checked
-// wire for wire against it (tests/test_acir_ccs.py).  One lane works on one proof; nothing here is on a throughput path (three
+// wire for wire against it (tests/test_acir_ccs.py) and, function by function on raw words with every branch named, against Python
+// integers (arith_probe.hpp, tests/arith_vectors.py groups bigs, hint_glv, hint_emul, hint_gk).  One lane works on one proof; nothing here is on a throughput path (three
 // calls per proof), so the code is plain loops over 32-bit words.
 #pragma once
 #include "bn254.hpp"
@@ -44,10 +45,16 @@ struct BigS {
       c >>= 32;
     }
   }
-  // this < o (signed)
+  // this < o (signed), through the sign of the difference.  Domain: |this|, |o| < 2^(32 NW - 2) (2^382 for Big384); then
+  // |this - o| < 2^(32 NW - 1) fits the word and its sign is the answer.  Outside it the difference can wrap and the result is
+  // the sign of the wrapped word (2^382 < -2^382 comes back true).  What dev_glv_split compares stays far inside:
+  //   num against 2 det: num = +-2 s |v| + det with s, |v| < 2^128 and det < 2^256, so |num| < 2^258, and the loops only move it
+  //     towards [0, 2 det), 2 det < 2^257;
+  //   x, y against 2^127: s - m1 v1 - m2 v2 with |m| <= 64 + 5 (the step cap plus the search radius), so below 2^128 + 138 * 2^128 < 2^136.
+  // tests/arith_vectors.py (group bigs) judges lt on that domain and on every pair whose difference fits, and only records the rest.
   SPP_HD bool lt(const BigS& o) const {
     BigS t = *this;
-    t.sub(o);          // no overflow for the magnitudes used here (top bits spare)
+    t.sub(o);
     return t.neg();
   }
   // this += m * o for a small signed m
@@ -71,7 +78,7 @@ struct BigS {
 typedef BigS<12> Big384;
 
 // unsigned na-word x nb-word product accumulated into out (nw words, truncating)
-SPP_HD inline void big_mul_acc(uint32_t* out, int nw, const uint32_t* a, int na, const uint32_t* b, int nb) {
+SPP_HD void big_mul_acc(uint32_t* out, int nw, const uint32_t* a, int na, const uint32_t* b, int nb) {
   for (int i = 0; i < na; i++) {
     uint64_t c = 0;
     for (int j = 0; j < nb && i + j < nw; j++) {
@@ -88,7 +95,7 @@ SPP_HD inline void big_mul_acc(uint32_t* out, int nw, const uint32_t* a, int na,
 }
 
 // a signed 128-bit constant (sign + 4 magnitude words) as Big384
-SPP_HD inline Big384 big_from_s128(const uint32_t mag[4], bool negative) {
+SPP_HD Big384 big_from_s128(const uint32_t mag[4], bool negative) {
   Big384 r;
   r.zero();
   for (int i = 0; i < 4; i++) r.w[i] = mag[i];
@@ -100,7 +107,7 @@ SPP_HD inline Big384 big_from_s128(const uint32_t mag[4], bool negative) {
 // kc: constants laid out by spp/ccs.py (to_sppc_solved): v1x, v1y, v2x, v2y as (4 magnitude words, 1 sign word) each, then det
 // (8 words, positive).  s: the scalar, < 2^128 (4 words).  The search order is that of spp/ccs.py glv_split, so the outputs are
 // the same pair.  Returns false when no pair is in range (the rows that consume the outputs then fail).
-SPP_HD inline bool dev_glv_split(const uint32_t* kc, const uint32_t s[4], uint32_t s1[4], uint32_t s2[4]) {
+SPP_HD bool dev_glv_split(const uint32_t* kc, const uint32_t s[4], uint32_t s1[4], uint32_t s2[4]) {
   Big384 v[4];
   for (int k = 0; k < 4; k++) v[k] = big_from_s128(kc + 5 * k, kc[5 * k + 4] != 0);
   Big384 det2;   // 2 * det
@@ -167,7 +174,7 @@ SPP_HD inline bool dev_glv_split(const uint32_t* kc, const uint32_t s[4], uint32
 // Outputs: k (4 x 64-bit limbs as 8 words), r (8 words), carries c_0 .. c_{nc-1} as signed Big384 (|c| < 2^200).
 // Restates spp/ccs.py _emulated_mul_hint for bits = 64, n = nq = 4.
 template <int NA, int NC>
-SPP_HD inline void dev_emulated_reduce(const uint32_t (*a)[8], const uint32_t* qc, uint32_t kq[8], uint32_t rem[8], Big384 (&carry)[NC]) {
+SPP_HD void dev_emulated_reduce(const uint32_t (*a)[8], const uint32_t* qc, uint32_t kq[8], uint32_t rem[8], Big384 (&carry)[NC]) {
   // remainder through Fq: Horner over the limbs with radix 2^64
   uint32_t rad[8] = {0, 0, 1, 0, 0, 0, 0, 0};
   const Fq radix = Fq::from_canonical(rad);
@@ -223,7 +230,7 @@ SPP_HD inline void dev_emulated_reduce(const uint32_t (*a)[8], const uint32_t* q
   }
 }
 // a signed Big384 (|v| < r) as a field element
-SPP_HD inline Fr fr_from_bigs(const Big384& v) {
+SPP_HD Fr fr_from_bigs(const Big384& v) {
   Big384 m = v;
   const bool n = m.neg();
   if (n) m.negate();
@@ -236,7 +243,7 @@ SPP_HD inline Fr fr_from_bigs(const Big384& v) {
 // ---- Grumpkin fixed-base multiplication (ACIR MultiScalarMul over the generator) -----------------------------------------------
 // y^2 = x^3 - 17 over Fr, G = (1, gy).  k = lo + 2^128 * hi as 8 canonical words.  Jacobian double-and-add from the top bit; returns
 // false for the point at infinity (k = 0 mod the group order).
-SPP_HD inline bool dev_grumpkin_mul(const uint32_t k[8], const Fr& gy, Fr* ox, Fr* oy) {
+SPP_HD bool dev_grumpkin_mul(const uint32_t k[8], const Fr& gy, Fr* ox, Fr* oy) {
   const Fr gx = Fr::one();
   Fr X = Fr::zero(), Y = Fr::zero(), Z = Fr::zero();
   bool inf = true;
@@ -264,7 +271,7 @@ SPP_HD inline bool dev_grumpkin_mul(const uint32_t k[8], const Fr& gy, Fr* ox, F
         const Fr U2 = gx * Z2, S2 = gy * Z2 * Z;
         const Fr H = U2 - X, Rr = S2 - Y;
         if (H.is_zero()) {
-          if (Rr.is_zero()) {   // acc == G: double G (cannot happen on the way to k >= 2, kept for completeness)
+          if (Rr.is_zero()) {   // acc == G: double.  Reached when the bits above this one are (order + 1) / 2, e.g. k = order + 2
             const Fr A = X.sqr(), B = Y.sqr(), C = B.sqr();
             const Fr t = (X + B).sqr() - A - C;
             const Fr D = t.dbl();

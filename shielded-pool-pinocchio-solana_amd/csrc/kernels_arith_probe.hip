@@ -12,13 +12,14 @@ __global__ __launch_bounds__(64) void k_arith_probe(const uint32_t* __restrict__
   arith_probe_case<OP, Pm>(arg, in + (size_t)i * IW, out + (size_t)i * OW);
 }
 
-template <uint32_t OP, uint32_t IW, uint32_t OW, bool FQ_ONLY>
+// FIELDS: the fields an operation exists for (ARITH_FIELDS_*); arith_probe_shape has refused the others
+template <uint32_t OP, uint32_t IW, uint32_t OW, int FIELDS>
 static void launch_one(hipStream_t st, bool is_fq, uint32_t arg, const uint32_t* in, uint32_t* out, uint32_t n) {
   const dim3 grid((n + 63u) / 64u), block(64);
   if (is_fq) {
-    k_arith_probe<OP, FqParams, IW, OW><<<grid, block, 0, st>>>(in, out, n, arg);
-  } else if constexpr (!FQ_ONLY) {
-    k_arith_probe<OP, FrParams, IW, OW><<<grid, block, 0, st>>>(in, out, n, arg);
+    if constexpr (FIELDS != ARITH_FIELDS_FR) k_arith_probe<OP, FqParams, IW, OW><<<grid, block, 0, st>>>(in, out, n, arg);
+  } else {
+    if constexpr (FIELDS != ARITH_FIELDS_FQ) k_arith_probe<OP, FrParams, IW, OW><<<grid, block, 0, st>>>(in, out, n, arg);
   }
 }
 
@@ -30,7 +31,7 @@ bool launch_arith_probe(hipStream_t st, uint32_t selector, uint32_t arg, const u
   switch (selector & 0xffu) {
 #define X(name, code, IW, OW, fq)                              \
   case code:                                                   \
-    launch_one<code, IW, OW, fq != 0>(st, is_fq, arg, in, out, n); \
+    launch_one<code, IW, OW, fq>(st, is_fq, arg, in, out, n);      \
     return true;
     SPP_ARITH_OPS(X)
 #undef X

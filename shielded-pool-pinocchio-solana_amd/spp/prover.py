@@ -75,7 +75,7 @@ class Context:
         return [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(n)]
 
     def debug_arith(self, selector, rows, out_words, arg=0):
-        """Test only (spp_debug_arith): one function of csrc/bn254.hpp / f29.hpp on the device, on RAW uint32 limbs.  rows: n cases of
+        """Test only (spp_debug_arith): one function of csrc/bn254.hpp / f29.hpp / gnark_hints.hpp on the device, on RAW uint32 limbs.  rows: n cases of
         operand words (n x in_words, anything numpy turns into uint32) -> n x out_words uint32 array; nothing is converted,
         reduced or checked on either side.  selector = SPP_ARITH_FR / SPP_ARITH_FQ | operation code of csrc/arith_probe.hpp."""
         a = np.ascontiguousarray(rows, dtype=np.uint32)

@@ -1,4 +1,5 @@
-"""Raw-word vectors for the arithmetic headers (csrc/bn254.hpp, csrc/f29.hpp) and the predicate every result must satisfy.
+"""Raw-word vectors for the arithmetic headers (csrc/bn254.hpp, csrc/f29.hpp, csrc/gnark_hints.hpp) and the predicate every result
+must satisfy.
 
 Plain Python: the references are Python integers only (oracle.bn254 supplies the curve sums of the accumulator scripts).  The
 operands are the WORDS the header functions see -- nothing is converted on the way in or out -- so the limb patterns that break a
@@ -6,12 +7,20 @@ carry chain, a shift count or a limb selection can be chosen: a fixed edge list 
 Every generated case is run and asserted; the generator asserts the preconditions the headers state (operand < 2p, limb bounds,
 column sums < 2^64) before anything is sent, so a bad vector fails as a vector and not as a wrong result.
 
+The groups of gnark_hints.hpp (bigs, hint_glv, hint_emul, hint_gk) also name the BRANCH each case takes -- search radius and ring
+position of the scalar decomposition, sign of its quotients, sign of a carry, the ladder's equal-point cases -- and verify_group
+returns the cases per class, so a test can demand that no class is empty.
+
 Two runners consume the same batches: tests/test_gpu_arith.py (spp_debug_arith, the gfx950 compile) and tests/test_arith_raw_host.py
 (tests/host/arith_raw_check.cpp, the g++ compile of the same dispatch header).
 """
+import functools
+import math
 import random
 
 from oracle import bn254 as B
+from oracle import hashes as H
+from spp import ccs
 
 FR, FQ = "fr", "fq"
 MOD = {FR: B.R, FQ: B.P}
@@ -21,7 +30,8 @@ R261 = 1 << 261                              # Montgomery radix of F29
 M29 = (1 << 29) - 1
 N_RANDOM = 2000                              # random cases per operation: the count tests/host/f29_check.cpp uses
 
-# name -> (code, in_words, out_words, fq_only): the X-macro list of csrc/arith_probe.hpp (test_arith_raw_host.py compares the two)
+# name -> (code, in_words, out_words, fields): the X-macro list of csrc/arith_probe.hpp (test_arith_raw_host.py compares the two);
+# fields 0 = Fr and Fq, 1 = Fq only, 2 = Fr only
 OPS = {
     "FP_MUL": (1, 16, 8, 0), "FP_SQR": (2, 8, 8, 0), "FP_ADD": (3, 16, 8, 0), "FP_SUB": (4, 16, 8, 0), "FP_NEG": (5, 8, 8, 0),
     "FP_DBL": (6, 8, 8, 0), "FP_MUL_SMALL": (7, 8, 8, 0), "FP_INV": (8, 8, 8, 0), "FP_INV_FERMAT": (9, 8, 8, 0),
@@ -36,6 +46,10 @@ OPS = {
     "F29X2_MUL": (64, 36, 18, 1), "F29X2_SQR": (65, 18, 18, 1),
     "SCRIPT_G1_29": (96, 145, 54, 1), "SCRIPT_G1_29_DISTINCT": (97, 145, 54, 1), "SCRIPT_G1": (98, 145, 54, 1),
     "SCRIPT_G2_29": (99, 273, 106, 1), "SCRIPT_G2_29_DISTINCT": (100, 273, 106, 1), "SCRIPT_G2": (101, 273, 106, 1),
+    "HINT_GLV_SPLIT": (128, 32, 9, 2), "HINT_EMUL_REDUCE": (129, 64, 136, 2), "HINT_GRUMPKIN_MUL": (130, 16, 17, 2),
+    "BIGS_ADD": (136, 24, 12, 2), "BIGS_SUB": (137, 24, 12, 2), "BIGS_NEGATE": (138, 12, 12, 2), "BIGS_LT": (139, 24, 1, 2),
+    "BIGS_SAR64": (140, 12, 12, 2), "BIGS_LOW64_ZERO": (141, 12, 1, 2), "BIGS_ADD_SMALL_MUL": (142, 24, 12, 2),
+    "BIG_MUL_ACC_4X4_12": (144, 20, 12, 2), "BIG_MUL_ACC_2X2_12": (145, 16, 12, 2), "BIG_MUL_ACC_8X8_8": (146, 24, 8, 2),
 }
 
 
@@ -72,12 +86,13 @@ def lifted(p, k, m):
 
 
 class Batch:
-    """n cases of one operation: rows of operand words, and check(i, row, out) -> None or a message"""
+    """n cases of one operation: rows of operand words, and check(i, row, out) -> None or a message; classes(row, out) -> the
+    names of the branch classes a case belongs to (the groups of gnark_hints.hpp)"""
 
-    def __init__(self, group, field, op, rows, check, arg=0):
-        code, iw, ow, fq_only = OPS[op]
-        assert field == FQ or not fq_only
-        self.group, self.field, self.op, self.arg, self.check = group, field, op, arg, check
+    def __init__(self, group, field, op, rows, check, arg=0, classes=None):
+        code, iw, ow, fields = OPS[op]
+        assert fields == 0 or field == (FQ if fields == 1 else FR)
+        self.group, self.field, self.op, self.arg, self.check, self.classes = group, field, op, arg, check, classes
         self.selector, self.in_words, self.out_words = FIELD_BITS[field] | code, iw, ow
         rows = [list(r) for r in rows]
         if len(rows) % 64 == 0:                       # the probe runs blocks of 64 lanes: keep a ragged last block
@@ -683,8 +698,504 @@ def check_distinct_limbs_unchanged(batch, out_rows):
             batch.name(), ci, " ".join("%08x" % x for x in a[2 + aw:]), " ".join("%08x" % x for x in b[2 + aw:]))
 
 
+# ---------------------------------------------------------------------------------------------------------------- BigS<12>, big_mul_acc
+M384 = 1 << 384
+
+
+def wordsn(v, n):
+    assert 0 <= v < 1 << (32 * n)
+    return [(v >> (32 * i)) & 0xffffffff for i in range(n)]
+
+
+def from_words(w):
+    return sum(int(x) << (32 * i) for i, x in enumerate(w))
+
+
+def big(v):
+    """a signed value as the 12 two's-complement words of Big384"""
+    assert -(1 << 383) <= v < 1 << 383
+    return wordsn(v % M384, 12)
+
+
+def signed384(u):
+    return u - M384 if u >> 383 else u
+
+
+def bigs_edge_values():
+    e = [0, 1, -1, 2, -2, (1 << 383) - 1, -(1 << 383), -(1 << 383) + 1, 1 << 382, (1 << 382) - 1, -(1 << 382), -(1 << 382) - 1, -(1 << 382) + 1]
+    for k in range(32, 384, 32):                          # every word boundary, from both sides and in both signs
+        e += [1 << k, -(1 << k), (1 << k) - 1, -(1 << k) - 1, -(1 << k) + 1]
+    e += [signed384(0xffffffff << (32 * i)) for i in range(12)]                       # one all-ones word
+    e += [signed384(int("ffffffff00000000" * 6, 16)), signed384(int("00000000ffffffff" * 6, 16))]
+    return list(dict.fromkeys(e))
+
+
+def _rand_signed(rng, maxbits=383):
+    return rng.choice((1, -1)) * rng.getrandbits(rng.randrange(maxbits + 1))
+
+
+LT_DOMAIN = 1 << 382      # the bound the header comment of BigS::lt states: |a|, |b| < 2^382
+
+
+def lt_class(a, b):
+    if not -(1 << 383) <= a - b < 1 << 383:
+        return "lt overflowing difference"
+    return "lt in the stated domain" if abs(a) < LT_DOMAIN and abs(b) < LT_DOMAIN else "lt beyond the domain, difference fits"
+
+
+def bigs_batches():
+    rng = random.Random(81)
+    e = bigs_edge_values()
+    singles = e + [_rand_signed(rng) for _ in range(N_RANDOM)]
+    singles += [-(rng.getrandbits(300) << 64) for _ in range(50)] + [rng.getrandbits(300) << 64 for _ in range(20)]   # low 64 bits zero
+    singles += [rng.choice((1, -1)) * (rng.getrandbits(200) << 32 | 1) << 32 for _ in range(20)]                      # w[0] = 0, w[1] != 0
+    singles += [rng.choice((1, -1)) * ((rng.getrandbits(200) << 64) | rng.getrandbits(32) | 1) for _ in range(20)]    # w[1] = 0, w[0] != 0
+    pairs = [(a, b) for a in e for b in e]
+    # differences just below and exactly 2^383, from both sides
+    h, t = 1 << 382, 1 << 383
+    pairs += [(h, -h), (h - 1, -h), (-h, h), (-h - 1, h), (0, -t), (-1, -t), (t - 1, -1), (t - 1, 0), (-t, 1), (-t, 0), (t - 1, -t), (-t, t - 1)]
+    pairs += [(_rand_signed(rng), _rand_signed(rng)) for _ in range(N_RANDOM)]
+    pairs += [(_rand_signed(rng, 260), _rand_signed(rng, 260)) for _ in range(N_RANDOM // 4)]       # the magnitudes of dev_glv_split
+    pairs += [(a, a + d) for a in (_rand_signed(rng, 381) for _ in range(100)) for d in (-1, 0, 1)]  # equal high words
+    srows = [big(a) for a in singles]
+    prows = [big(a) + big(b) for a, b in pairs]
+    sg = lambda w: signed384(from_words(w))
+    out = []
+
+    def exact(o, want):
+        return None if from_words(o) == want % M384 else "expected %x" % (want % M384)
+
+    def carries(x, y, sub):
+        """the carry (borrow) out of each of the 12 words of x + y (x - y) on the raw words"""
+        return [(((x % (1 << 32 * k)) - (y % (1 << 32 * k))) < 0) if sub else (((x % (1 << 32 * k)) + (y % (1 << 32 * k))) >> (32 * k))
+                for k in range(1, 13)]
+
+    def cls_addsub(name, sub):
+        def f(row, o):
+            c = carries(from_words(row[:12]), from_words(row[12:]), sub)
+            return [name, name + (" borrowing" if sub else " carrying") + " through all 12 words"] if all(c) else [name]
+        return f
+    out.append(Batch("bigs", FR, "BIGS_ADD", prows, lambda i, row, o: exact(o, sg(row[:12]) + sg(row[12:])), classes=cls_addsub("add", False)))
+    out.append(Batch("bigs", FR, "BIGS_SUB", prows, lambda i, row, o: exact(o, sg(row[:12]) - sg(row[12:])), classes=cls_addsub("sub", True)))
+
+    def cls_negate(row, o):
+        a = sg(row)
+        return ["negate", "negate of 0 (the carry runs through all 12 words)"] if a == 0 else ["negate", "negate of -2^383"] if a == -(1 << 383) else ["negate"]
+    out.append(Batch("bigs", FR, "BIGS_NEGATE", srows, lambda i, row, o: exact(o, -sg(row)), classes=cls_negate))
+
+    def chk_lt(i, row, o):
+        a, b = sg(row[:12]), sg(row[12:])
+        if o[0] not in (0, 1):
+            return "not a truth value"
+        if lt_class(a, b) == "lt overflowing difference":
+            return None                                  # outside the domain: the result is recorded (lt_overflow_record), not judged
+        return None if o[0] == (1 if a < b else 0) else "expected %d" % (a < b)
+    out.append(Batch("bigs", FR, "BIGS_LT", prows, chk_lt, classes=lambda row, o: [lt_class(sg(row[:12]), sg(row[12:]))]))
+
+    def cls_sar(row, o):
+        a = sg(row)
+        return ["sar64 non-negative"] if a >= 0 else ["sar64 negative, low 64 bits %s" % ("zero" if a % (1 << 64) == 0 else "non-zero")]
+    out.append(Batch("bigs", FR, "BIGS_SAR64", srows, lambda i, row, o: exact(o, sg(row) >> 64), classes=cls_sar))
+
+    def chk_low(i, row, o):
+        want = 1 if from_words(row) % (1 << 64) == 0 else 0
+        return None if o[0] == want else "expected %d" % want
+    out.append(Batch("bigs", FR, "BIGS_LOW64_ZERO", srows, chk_low,
+                     classes=lambda row, o: ["low64_zero %s" % ("true" if row[0] | row[1] == 0 else "one word zero" if 0 in row[:2] else "false")]))
+    core = [0, 1, -1, (1 << 383) - 1, -(1 << 383), 1 << 128, -(1 << 128) + 1, signed384(int("ffffffff00000000" * 6, 16))]
+    mrows = [big(a) + big(b) for a in e for b in core] + prows[len(e) ** 2:len(e) ** 2 + 12 + 300]
+    for m in (0, 1, -1, 2, -3, 5, -5, 37, 64, -64):
+        out.append(Batch("bigs", FR, "BIGS_ADD_SMALL_MUL", mrows, lambda i, row, o, m=m: exact(o, sg(row[:12]) + m * sg(row[12:])), arg=m & 0xffff,
+                         classes=lambda row, o, m=m: ["add_small_mul m %s 0" % ("<" if m < 0 else ">" if m else "=")]))
+    # big_mul_acc, the three shapes in use: [accumulator nw, a na, b nb] -> (accumulator + a * b) mod 2^(32 nw)
+    for op, nw, na, nb in (("BIG_MUL_ACC_4X4_12", 12, 4, 4), ("BIG_MUL_ACC_2X2_12", 12, 2, 2), ("BIG_MUL_ACC_8X8_8", 8, 8, 8)):
+        full, prod = 1 << (32 * nw), 1 << (32 * min(nw, na + nb))
+        accs = [0, 1, full - 1, full - prod, prod - 1, full - 2, (full - 1) ^ (prod - 1) ^ 0xffffffff, rng.getrandbits(32 * nw)]
+        ops = lambda n: [0, 1, (1 << (32 * n)) - 1, 1 << 31, 0xffffffff, 1 << (32 * (n - 1)), (1 << (32 * n)) - (1 << 32), rng.getrandbits(32 * n)]
+        rows = [(c, a, b) for c in accs for a in ops(na) for b in ops(nb)]
+        rows += [(rng.getrandbits(32 * nw), rng.getrandbits(32 * na), rng.getrandbits(32 * nb)) for _ in range(N_RANDOM // 2)]
+        rows += [(full - 1 - rng.getrandbits(rng.randrange(32 * nw)), rng.getrandbits(32 * na), rng.getrandbits(32 * nb)) for _ in range(N_RANDOM // 2)]
+        dec = lambda row, nw=nw, na=na: (from_words(row[:nw]), from_words(row[nw:nw + na]), from_words(row[nw + na:]))
+
+        def chk(i, row, o, full=full, dec=dec):
+            c, a, b = dec(row)
+            return None if from_words(o) == (c + a * b) % full else "expected %x" % ((c + a * b) % full)
+
+        def cls(row, o, op=op, full=full, prod=prod, dec=dec):
+            c, a, b = dec(row)
+            r = [op]
+            if c and a * b:
+                r.append(op + " into a non-zero accumulator")
+            if prod < full and (c % prod) + a * b >= prod:
+                r.append(op + " carry out of the last written word")
+            if c + a * b >= full:
+                r.append(op + " truncated at nw")
+            return r
+        out.append(Batch("bigs", FR, op, [wordsn(c, nw) + wordsn(a, na) + wordsn(b, nb) for c, a, b in rows], chk, classes=cls))
+    return out
+
+
+def lt_overflow_record(bs, outs):
+    """(operand words, result) of every BIGS_LT case whose difference overflows 384 bits: what two builds must agree on"""
+    b, o = next((b, o) for b, o in zip(bs, outs) if b.op == "BIGS_LT")
+    sg = lambda w: signed384(from_words(w))
+    return [(tuple(row), int(out[0])) for row, out in zip(b.rows, o) if lt_class(sg(row[:12]), sg(row[12:])) == "lt overflowing difference"]
+
+
+# ---------------------------------------------------------------------------------------------------------------- dev_glv_split
+GLV_STEP_CAP = 60         # |b| + 5 <= 60: inside the 64 steps the device spends on a quotient (beyond the cap its answer is undefined)
+
+
+def glv_split_basis(s, v1, v2, bits=ccs.GLV_BITS):
+    """ccs.glv_split with the basis (v1, v2) given, det > 0, and the same search order: (found, s1, s2, radius, (i1, i2), b1, b2)
+    where glv_split raises"""
+    det = v1[0] * v2[1] - v2[0] * v1[1]
+    assert det > 0
+    b1 = (2 * s * v2[1] + det) // (2 * det)
+    b2 = (-2 * s * v1[1] + det) // (2 * det)
+    for radius in range(0, 6):
+        for i1 in range(-radius, radius + 1):
+            for i2 in range(-radius, radius + 1):
+                if max(abs(i1), abs(i2)) != radius:
+                    continue
+                x = s - (b1 + i1) * v1[0] - (b2 + i2) * v2[0]
+                y = -(b1 + i1) * v1[1] - (b2 + i2) * v2[1]
+                if 0 <= x < 1 << bits and 0 <= y < 1 << bits:
+                    return 1, x, y, radius, (i1, i2), b1, b2
+    return 0, 0, 0, None, None, b1, b2
+
+
+def glv_words(v1, v2):
+    """the 28 constant words of OP_GLV (ccs._glv_constants) for a basis"""
+    det = v1[0] * v2[1] - v2[0] * v1[1]
+    assert 0 < det < 1 << 256 and all(abs(v) < 1 << 128 for v in v1 + v2)
+    w = []
+    for v in v1 + v2:
+        w += wordsn(abs(v), 4) + [1 if v < 0 else 0]
+    return w + wordsn(det, 8)
+
+
+def glv_basis_of(words):
+    v = [(-1 if words[5 * k + 4] else 1) * from_words(words[5 * k:5 * k + 4]) for k in range(4)]
+    return (v[0], v[1]), (v[2], v[3])
+
+
+def glv_skewed_bases(n, seed=83):
+    """bases of two long, nearly parallel vectors (their difference is the short one): Babai rounding then lands up to half a long
+    vector from the target and the search has to walk rings (r, -r): radius 2 .. 5 and scalars with no pair at all.  The lattice
+    is {(x, y): x = lam * y mod det} for the lam the basis itself fixes.  -> [(v1, v2, lam, q = det, largest scalar within the cap)]"""
+    rng = random.Random(seed)
+    out = []
+    while len(out) < n:
+        x, y = (rng.randrange(1 << 125, 1 << 127) * rng.choice((1, -1)) for _ in range(2))
+        d1, d2 = (rng.randrange(1 << 121, 1 << 126) * rng.choice((1, -1)) for _ in range(2))
+        u1, u2 = (x, y), (x + d1, y + d2)
+        det = u1[0] * u2[1] - u2[0] * u1[1]
+        if det < 0:
+            u1, u2, det = u2, u1, -det
+        if det == 0 or det >> 256 or max(abs(v) for v in u1 + u2) >> 128 or math.gcd(u1[1], det) != 1 or math.gcd(u2[1], det) != 1:
+            continue
+        smax = min(1 << 128, (GLV_STEP_CAP - 6) * det // max(abs(u1[1]), abs(u2[1])))       # |b| <= s |v_y| / det + 1
+        if smax < 1 << 120:
+            continue
+        lam = u1[0] * pow(u1[1], -1, det) % det
+        assert (u2[0] - lam * u2[1]) % det == 0
+        out.append((u1, u2, lam, det, smax))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def glv_cases():
+    """[(v1, v2, lam, q, scalar)]: (a) the container's constants, (b) other bases of the same lattice, (c) skewed bases and sublattices"""
+    rng = random.Random(82)
+    lam, q = ccs.GLV_LAMBDA, ccs.Q_BASE
+    v1, v2 = glv_basis_of(ccs._glv_constants())
+    assert v1[0] * v2[1] - v2[0] * v1[1] == q
+    fixed = [0, 1, 2, (1 << 64) - 1, (1 << 64) + 1, (1 << 127) - 1, 1 << 127, (1 << 127) + 1, (1 << 128) - 1, lam % (1 << 128)]
+    for n in (1, 2):                                     # b1 = floor((2 s v2y + det) / (2 det)) first reaches n at this scalar
+        sn = -(-(2 * n - 1) * q // (2 * v2[1]))
+        assert glv_split_basis(sn - 1, v1, v2)[5] == n - 1 and glv_split_basis(sn, v1, v2)[5] == n
+        fixed += [sn - 1, sn, sn + 1]
+    assert all(0 <= s < 1 << 128 for s in fixed)
+    cases = [(v1, v2, lam, q, s) for s in fixed + [rng.getrandbits(128) for _ in range(N_RANDOM)]]
+    add = lambda a, b, k=1: (a[0] + k * b[0], a[1] + k * b[1])
+    neg = lambda a: (-a[0], -a[1])
+    for u1, u2 in ((neg(v2), v1), (neg(v1), neg(v2)), (add(v1, v2), v2), (v2, neg(v1)), (add(v1, v2, 2), v2)):
+        assert u1[0] * u2[1] - u2[0] * u1[1] == q
+        cases += [(u1, u2, lam, q, s) for s in fixed + [rng.getrandbits(128) for _ in range(N_RANDOM // 4)]]
+    for u1, u2 in (((2 * v1[0], 2 * v1[1]), v2), (v1, (2 * v2[0], 2 * v2[1])), (add(v1, v2), add(v2, v1, -1))):   # index-2 sublattices
+        assert u1[0] * u2[1] - u2[0] * u1[1] == 2 * q
+        cases += [(u1, u2, lam, q, s) for s in fixed + [rng.getrandbits(128) for _ in range(100)]]
+    for u1, u2, l2, q2, smax in glv_skewed_bases(24):
+        cases += [(u1, u2, l2, q2, s) for s in [0, 1, smax - 1] + [rng.randrange(smax) for _ in range(120)]]
+    for u1, u2, _, _, s in cases:                         # every base keeps the true quotients inside the device's step cap
+        _, _, _, _, _, b1, b2 = glv_split_basis(s, u1, u2)
+        assert abs(b1) + 5 <= GLV_STEP_CAP and abs(b2) + 5 <= GLV_STEP_CAP and 0 <= s < 1 << 128
+    return cases
+
+
+def glv_batches():
+    cases = glv_cases()
+    lattice = {tuple(glv_words(u1, u2)): (lam, q) for u1, u2, lam, q, _ in cases}
+
+    def expect(row):
+        v1, v2 = glv_basis_of(row[:28])
+        return glv_split_basis(from_words(row[28:]), v1, v2)
+
+    def chk(i, row, o):
+        found, x, y = expect(row)[:3]
+        got = (o[0], from_words(o[1:5]), from_words(o[5:9]))
+        if got != (found, x, y):
+            return "expected found %d s1 %x s2 %x" % (found, x, y)
+        if found:
+            lam, q = lattice[tuple(row[:28])]
+            s = from_words(row[28:])
+            if not (0 <= got[1] < 1 << 127 and 0 <= got[2] < 1 << 127 and (got[1] - lam * got[2] - s) % q == 0):
+                return "s1 - lambda s2 = s (mod q) or the range 2^127 does not hold"
+        return None
+
+    def cls(row, o):
+        found, _, _, radius, pos, b1, b2 = expect(row)
+        r = ["not found" if not found else "radius >= 3" if radius >= 3 else "radius %d" % radius]
+        if found and radius:
+            r.append("ring position %s%s" % ("+0-"[(pos[0] < 0) + (pos[0] <= 0)], "+0-"[(pos[1] < 0) + (pos[1] <= 0)]))
+        return r + [n for n, c in (("b1 < 0", b1 < 0), ("b1 > 0", b1 > 0), ("b2 < 0", b2 < 0), ("b2 > 0", b2 > 0)) if c]
+    return [Batch("hint_glv", FR, "HINT_GLV_SPLIT", [glv_words(u1, u2) + wordsn(s, 4) for u1, u2, _, _, s in cases], chk, classes=cls)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- dev_emulated_reduce<6, 6>
+B64 = 1 << 64
+EMUL_CMAX = 1 << 58       # |c_i| of the random generator (see emul_cases)
+
+
+def limbs64(v, n):
+    assert 0 <= v < 1 << (64 * n)
+    return [(v >> (64 * i)) & (B64 - 1) for i in range(n)]
+
+
+def emul_limbs(k, r, c):
+    """a_0 .. a_5 of a(X) = k(X) p(X) + r(X) + (2^64 - X) c(X) for the free carries c_0 .. c_4 (c_5 = k_3 p_3 closes the identity:
+    a has no X^6); None when a limb leaves [0, r_BN254)"""
+    q = ccs.Q_BASE
+    assert 0 <= k < 1 << 256 and 0 <= r < q and len(c) == 5
+    kl, pl, rl = limbs64(k, 4), limbs64(q, 4), limbs64(r, 4) + [0, 0]
+    c = list(c) + [kl[3] * pl[3]]
+    a = []
+    for i in range(6):
+        a.append(sum(kl[x] * pl[i - x] for x in range(4) if 0 <= i - x < 4) + rl[i] + B64 * c[i] - (c[i - 1] if i else 0))
+    return a if all(0 <= v < MOD[FR] for v in a) else None
+
+
+def emul_reference(a):
+    """ccs._emulated_mul_hint on the limbs a (b = [1], 64-bit limbs, n = nq = 4, six carries) -> (k, r, signed carries); the carries
+    are recomputed as integers here and must be the field elements the hint returns"""
+    q = ccs.Q_BASE
+    ref = ccs._emulated_mul_hint([64, 4, 6, 4] + limbs64(q, 4) + list(a) + [1], 14)
+    k, r = sum(v << (64 * i) for i, v in enumerate(ref[:4])), sum(v << (64 * i) for i, v in enumerate(ref[4:8]))
+    kl, pl, rl = limbs64(k, 4), limbs64(q, 4), limbs64(r, 4) + [0, 0]
+    cs, c = [], 0
+    for i in range(6):
+        num = a[i] - sum(kl[x] * pl[i - x] for x in range(4) if 0 <= i - x < 4) - rl[i] + c
+        assert num % B64 == 0
+        c = num // B64
+        cs.append(c)
+    assert [v % MOD[FR] for v in cs] == ref[8:] and cs[5] == kl[3] * pl[3]
+    return k, r, cs
+
+
+@functools.lru_cache(maxsize=None)
+def emul_cases():
+    """(edge cases, random cases, keep rate of the random generator) as limb lists.
+
+    The random generator picks k < 2^256, r < q and carries |c_i| <= 2^58 and keeps a case when every limb is in [0, r_BN254): a limb
+    is a_i = sum k_x p_y + r_i + 2^64 c_i - c_(i-1) with sum k_x p_y around 2^126, so a negative carry of 2^58 (2^122 after the
+    shift) leaves the limb non-negative unless the k limbs under it are small.  Measured keep rate: 0.98 (asserted >= 0.9 below).
+    A second family draws the LIMBS at random (a_i < r_BN254, the value below 2^256 q so the quotient fits): every such row is in the
+    domain, and its carries run up to 2^190 in both signs, which the constructive family cannot reach."""
+    rng = random.Random(84)
+    q, p = ccs.Q_BASE, MOD[FR]
+    ones = (1 << 256) - 1
+    cm = EMUL_CMAX
+    kbig = ones - (1 << 70)                              # every limb of k large: the limbs stay positive under a carry of -2^58
+    edges = [emul_limbs(0, 0, [0] * 5)]                                                        # a = 0
+    edges += [emul_limbs(kk, rr, [0] * 5) for kk, rr in ((0, q - 1), (1, 0), (1, 1), (2, 0))]   # a(2^64) = q - 1, q, q + 1, 2 q
+    edges += [emul_limbs(kbig, 0, [5, -7, 11, -13, 17]), emul_limbs(kbig, q - 1, [5, -7, 11, -13, 17]), emul_limbs(ones, q - 1, [0] * 5)]
+    edges += [emul_limbs(ones, 12345, [1, 2, 3, 4, 5]), emul_limbs(0, q - 1, [1, 1, 1, 0, 0])]
+    for kk in (int("ffffffffffffffff0000000000000000" * 2, 16), int("0000000000000000ffffffffffffffff" * 2, 16)):   # all-ones limb next to a zero limb
+        edges += [emul_limbs(kk, rng.randrange(q), [0] * 5), emul_limbs(kk, rng.randrange(q), [3, -3, 3, -3, 3])]
+    edges += [emul_limbs(0, rng.randrange(q), [0] * 5), emul_limbs(rng.getrandbits(192), rng.randrange(q), [0] * 5)]   # all carries zero
+    for j in range(5):
+        for v in (-1, cm, -cm, 1):                       # a carry of -1, and +- the largest magnitude the generator uses, at every place
+            c = [0] * 5
+            c[j] = v
+            edges.append(emul_limbs(kbig, rng.randrange(q), c))
+    edges += [emul_limbs(kbig, rng.randrange(q), [cm] * 5), emul_limbs(kbig, rng.randrange(q), [-cm] * 5)]
+    edges.append(emul_limbs(kbig, rng.randrange(q), [-cm, cm, -cm, cm, -cm]))
+    k1 = rng.getrandbits(128)                            # upper limbs a_4 = a_5 = 0 under a non-zero k: c_4 = 0, c_3 = k_1 p_3
+    edges.append(emul_limbs(k1, rng.randrange(q), [0, 0, 0, (k1 >> 64) * (q >> 192), 0]))
+    edges.append(emul_limbs(rng.getrandbits(64), rng.randrange(q), [0] * 5))
+    assert all(a is not None for a in edges), "an edge case left the domain"                   # none may be dropped
+    assert edges[-2][4:] == [0, 0] and edges[-1][4:] == [0, 0] and all(edges[5][4:])
+    kept, tried = [], 0
+    while len(kept) < N_RANDOM:
+        tried += 1
+        a = emul_limbs(rng.getrandbits(256), rng.randrange(q), [rng.randrange(-cm, cm + 1) for _ in range(5)])
+        if a is not None:
+            kept.append(a)
+    rate = len(kept) / tried
+    assert rate >= 0.9, rate
+    free = []
+    while len(free) < N_RANDOM // 2:
+        a = [rng.randrange(p) for _ in range(5)] + [rng.getrandbits(rng.randrange(1, 190))]
+        if sum(v << (64 * i) for i, v in enumerate(a)) < q << 256:
+            free.append(a)
+    for top in ((q << 256) - 1, (q << 256) - q, (q << 256) - q - 1):                            # the largest quotient a row can have
+        lo, a5 = top % (1 << 320), top >> 320
+        free.append(limbs64(lo % (1 << 256), 4) + [lo >> 256, a5])
+    return edges, kept + free, rate
+
+
+def emul_batches():
+    edges, rand, _ = emul_cases()
+    q = ccs.Q_BASE
+    qc = words8(q) + words8(pow(q, -1, R256))
+    limbs = lambda row: [from_words8(row[8 * i:8 * i + 8]) for i in range(6)]
+
+    def chk(i, row, o):
+        k, r, cs = emul_reference(limbs(row))
+        if from_words8(o[:8]) != k:
+            return "quotient, expected %x" % k
+        if from_words8(o[8:16]) != r:
+            return "remainder, expected %x" % r
+        for j in range(6):
+            raw = signed384(from_words(o[16 + 12 * j:28 + 12 * j]))
+            if raw != cs[j]:
+                return "carry %d is %d, expected %d" % (j, raw, cs[j])
+            if from_words8(o[88 + 8 * j:96 + 8 * j]) != cs[j] % MOD[FR]:
+                return "carry %d as a field element, expected %x" % (j, cs[j] % MOD[FR])
+        d6 = -(from_words(o[6:8]) * (q >> 192))           # the X^6 coefficient of a - k p - r: the identity closes when carry_5 + d_6 = 0
+        if signed384(from_words(o[76:88])) + d6 != 0:
+            return "carry_5 + d_6 != 0"
+        return None
+
+    def cls(row, o):
+        a = limbs(row)
+        k, r, cs = emul_reference(a)
+        r_ = ["remainder zero" if r == 0 else "remainder q - 1" if r == q - 1 else "remainder other",
+              "upper limbs a_4, a_5 %s" % ("zero" if a[4] == 0 and a[5] == 0 else "non-zero" if a[4] and a[5] else "one zero")]
+        if k == (1 << 256) - 1:
+            r_.append("quotient maximal")
+        if not any(cs):
+            r_.append("all carries zero")
+        if any(c < 0 for c in cs):
+            r_.append("a carry negative")
+        if -1 in cs:
+            r_.append("a carry -1")
+        if any(abs(c) == EMUL_CMAX for c in cs[:5]):
+            r_.append("a carry at +-2^58")
+        if any(abs(c) >> 180 for c in cs):
+            r_.append("a carry beyond 2^180")
+        return r_
+    rows = [sum((words8(v) for v in a), []) + qc for a in edges + rand]
+    return [Batch("hint_emul", FR, "HINT_EMUL_REDUCE", rows, chk, classes=cls)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- dev_grumpkin_mul
+def gk_add(P, Q_):
+    """affine addition on y^2 = x^3 - 17 over Fr; None is the point at infinity"""
+    p = MOD[FR]
+    if P is None:
+        return Q_
+    if Q_ is None:
+        return P
+    if P[0] == Q_[0]:
+        if (P[1] + Q_[1]) % p == 0:
+            return None
+        l = 3 * P[0] * P[0] * pow(2 * P[1], -1, p) % p
+    else:
+        l = (Q_[1] - P[1]) * pow(Q_[0] - P[0], -1, p) % p
+    x = (l * l - P[0] - Q_[0]) % p
+    return x, (l * (P[0] - x) - P[1]) % p
+
+
+def gk_mul(k):
+    """k * G by double-and-add from the top bit, and the names of the ladder's special steps k passes through"""
+    G = (1, ccs.GRUMPKIN_GY)
+    acc, seen = None, set()
+    for bit in range(k.bit_length() - 1, -1, -1):
+        acc = gk_add(acc, acc)
+        if (k >> bit) & 1:
+            if acc is None and bit != k.bit_length() - 1:
+                seen.add("ladder restarts from infinity")
+            elif acc == G:
+                seen.add("ladder adds G to G (H = 0, Rr = 0)")
+            elif acc is not None and acc[0] == G[0]:
+                seen.add("ladder adds G to -G")
+            acc = gk_add(acc, G)
+    return acc, seen
+
+
+@functools.lru_cache(maxsize=None)
+def gk_cases():
+    """[(k, k * G or None, special steps)]"""
+    rng = random.Random(85)
+    o = ccs.Q_BASE
+    ks = [0, 1, 2, 3, 1 << 127, (1 << 128) - 1, 1 << 128, 1 << 255, (1 << 256) - 1, o - 1, o, o + 1, 2 * o, 2 * o + 1]
+    ks += [o + 2, 2 * o + 4, 2 * o + 5, 4 * o - 1]         # (o + 2) >> 1 = (o + 1) / 2: doubled it is G again, and the last bit adds G
+    ks += [rng.getrandbits(256) for _ in range(N_RANDOM // 10)]
+    ks += [rng.getrandbits(rng.randrange(1, 129)) + (rng.getrandbits(rng.randrange(0, 129)) << 128) for _ in range(N_RANDOM // 10)]   # (lo, hi)
+    assert all(0 <= k < 1 << 256 for k in ks)
+    assert gk_mul(o)[0] is None and gk_mul(1)[0] == (1, ccs.GRUMPKIN_GY)
+    for k in (2, 3, (1 << 128) - 1, ks[20] % MOD[FR], ks[-1] % MOD[FR]):
+        assert gk_mul(k)[0] == tuple(H.fixed_base_scalar_mul(k))
+    return [(k,) + gk_mul(k) for k in ks]
+
+
+def gk_batches():
+    cases = {k: (pt, seen) for k, pt, seen in gk_cases()}
+    p = MOD[FR]
+    rinv = pow(R256, -1, p)
+    gy = words8(ccs.GRUMPKIN_GY * R256 % p)
+
+    def chk(i, row, o):
+        k = from_words8(row[:8])
+        want = cases[k][0]
+        assert (want is None) == (k % ccs.Q_BASE == 0)
+        if o[0] != (0 if want is None else 1):
+            return "finite flag %d" % o[0]
+        x, y = from_words8(o[1:9]), from_words8(o[9:17])
+        if want is None:
+            return None if x == 0 and y == 0 else "the point at infinity must come back as zero words"
+        if not (x < 2 * p and y < 2 * p and (x * rinv % p, y * rinv % p) == want):
+            return "expected (%x, %x)" % want
+        return None
+
+    def cls(row, o):
+        k = from_words8(row[:8])
+        pt, seen = cases[k]
+        return ["finite" if pt is not None else "k = 0 mod the group order"] + sorted(seen)
+    return [Batch("hint_gk", FR, "HINT_GRUMPKIN_MUL", [words8(k) + gy for k, _, _ in gk_cases()], chk, classes=cls)]
+
+
 # ---------------------------------------------------------------------------------------------------------------- the groups
 GROUPS = ("fp", "inv", "fq2", "f29", "is_zero_mod_p", "f29x2", "scripts_g1", "scripts_g2")
+HINT_GROUPS = ("bigs", "hint_glv", "hint_emul", "hint_gk")       # csrc/gnark_hints.hpp: verify_group returns cases per branch class
+_MUL_ACC = ["BIG_MUL_ACC_%s%s" % (sh, c) for sh in ("4X4_12", "2X2_12", "8X8_8") for c in ("", " into a non-zero accumulator", " truncated at nw")]
+HINT_CLASSES = {                                                  # every class must hold at least one case
+    "bigs": _MUL_ACC + ["BIG_MUL_ACC_4X4_12 carry out of the last written word", "BIG_MUL_ACC_2X2_12 carry out of the last written word",
+                        "add", "add carrying through all 12 words", "sub", "sub borrowing through all 12 words", "negate", "negate of -2^383",
+                        "negate of 0 (the carry runs through all 12 words)", "add_small_mul m < 0", "add_small_mul m = 0", "add_small_mul m > 0",
+                        "low64_zero false", "low64_zero one word zero", "low64_zero true", "lt in the stated domain",
+                        "lt beyond the domain, difference fits", "lt overflowing difference", "sar64 non-negative",
+                        "sar64 negative, low 64 bits zero", "sar64 negative, low 64 bits non-zero"],
+    # ring positions: (sign of i1, sign of i2) of the pair the search returns at radius >= 1; (+, +) is not reached by any base here
+    "hint_glv": ["radius 0", "radius 1", "radius 2", "radius >= 3", "not found", "b1 < 0", "b1 > 0", "b2 < 0", "b2 > 0"] +
+                ["ring position " + p for p in ("+-", "+0", "-+", "--", "-0", "0+", "0-")],
+    "hint_emul": ["remainder zero", "remainder q - 1", "remainder other", "quotient maximal", "all carries zero", "a carry negative", "a carry -1",
+                  "a carry at +-2^58", "a carry beyond 2^180", "upper limbs a_4, a_5 zero", "upper limbs a_4, a_5 one zero",
+                  "upper limbs a_4, a_5 non-zero"],
+    "hint_gk": ["finite", "k = 0 mod the group order", "ladder adds G to G (H = 0, Rr = 0)", "ladder adds G to -G", "ladder restarts from infinity"],
+}
 
 
 def batches(group):
@@ -704,12 +1215,29 @@ def batches(group):
         return script_batches(False)
     if group == "scripts_g2":
         return script_batches(True)
+    if group == "bigs":
+        return bigs_batches()
+    if group == "hint_glv":
+        return glv_batches()
+    if group == "hint_emul":
+        return emul_batches()
+    if group == "hint_gk":
+        return gk_batches()
     raise KeyError(group)
 
 
 def verify_group(group, bs, outs):
-    """all predicates of a group on the results `outs[k]` (rows of words) of batch bs[k]; returns {batch name: cases}"""
+    """all predicates of a group on the results `outs[k]` (rows of words) of batch bs[k]; returns {batch name: cases}, for the
+    groups of gnark_hints.hpp {branch class: cases}"""
     counts = {}
+    if group in HINT_GROUPS:
+        counts = {c: 0 for c in HINT_CLASSES.get(group, ())}
+        for b, o in zip(bs, outs):
+            b.verify(o)
+            for row, out in zip(b.rows, o):
+                for c in b.classes(row, [int(x) for x in out]):
+                    counts[c] = counts.get(c, 0) + 1
+        return counts
     for b, o in zip(bs, outs):
         counts[b.name()] = b.verify(o)
         if getattr(b, "pair_of", None):

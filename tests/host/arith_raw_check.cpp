@@ -30,12 +30,12 @@ template <uint32_t OP, class Pm>
 static void run(uint32_t arg, uint32_t n, uint32_t iw, uint32_t ow, const uint32_t* in, uint32_t* out) {
   for (uint32_t i = 0; i < n; i++) arith_probe_case<OP, Pm>(arg, in + (size_t)i * iw, out + (size_t)i * ow);
 }
-template <uint32_t OP, bool FQ_ONLY>
+template <uint32_t OP, int FIELDS>
 static void run_field(bool is_fq, uint32_t arg, uint32_t n, uint32_t iw, uint32_t ow, const uint32_t* in, uint32_t* out) {
   if (is_fq) {
-    run<OP, FqParams>(arg, n, iw, ow, in, out);
-  } else if constexpr (!FQ_ONLY) {
-    run<OP, FrParams>(arg, n, iw, ow, in, out);
+    if constexpr (FIELDS != ARITH_FIELDS_FR) run<OP, FqParams>(arg, n, iw, ow, in, out);
+  } else {
+    if constexpr (FIELDS != ARITH_FIELDS_FQ) run<OP, FrParams>(arg, n, iw, ow, in, out);
   }
 }
 
@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
     switch (selector & 0xffu) {
 #define X(name, code, IW, OW, fq)                                             \
   case code:                                                                  \
-    run_field<code, fq != 0>(is_fq, arg, n, iw, ow, in.data(), out.data());   \
+    run_field<code, fq>(is_fq, arg, n, iw, ow, in.data(), out.data());        \
     break;
       SPP_ARITH_OPS(X)
 #undef X

@@ -300,13 +300,15 @@ def _reference_system(tmp):
     return c, s, sppc
 
 
-def _fresh_note_inputs(seed):
-    """withdraw inputs of a note that is not the reference KAT (client/merkle.ts semantics from oracle/hashes.py)"""
+def _fresh_note_inputs(seed, sk=None):
+    """withdraw inputs of a note that is not the reference KAT (client/merkle.ts semantics from oracle/hashes.py); sk: the note's
+    secret key instead of a random one below 2^128"""
     import random
     from oracle import hashes as H
     rng = random.Random(seed)
     tree = H.MerkleTree()
-    sk, amount, rnd = rng.randrange(1, 1 << 128), rng.randrange(1, 1 << 40), rng.randrange(1 << 250)
+    rsk, amount, rnd = rng.randrange(1, 1 << 128), rng.randrange(1, 1 << 40), rng.randrange(1 << 250)
+    sk = rsk if sk is None else sk
     for _ in range(3):
         tree.insert(rng.randrange(1 << 250))
     owner = H.fixed_base_scalar_mul(sk)
@@ -420,58 +422,115 @@ def test_solver_plan_of_the_reference_r1cs(program):
     assert len(defined) == kinds["row"]                       # one wire per defining row
 
 
+@pytest.fixture(scope="module")
+def solved_system(program, tmp_path_factory):
+    """the reference's constraint system with its solver on the device (spp/ccs.py to_sppc_solved), set up and loaded once for the
+    GPU tests below, next to the oracle's prover of the all-inputs container of the same system under the same seed"""
+    import types
+    import spp
+    from spp import ccs
+    from oracle import native
+    tmp = tmp_path_factory.mktemp("solved")
+    c, s, pure = _reference_system(tmp)
+    solved = str(tmp / "solved.sppc")
+    n, ss = ccs.to_sppc_solved(s, c, program, solved)
+    assert n == 12452
+    pk, vk, opk, ovk = (str(tmp / x) for x in ("s.pk", "s.vk", "o.pk", "o.vk"))
+    seed = b"\x0b" * 32
+    ctx = spp.Context(0)
+    try:
+        ctx.setup(solved, seed, pk, vk)
+        native.setup(pure, seed, opk, ovk)
+        h = ctx.load_circuit(solved, pk, 6)
+        try:
+            yield types.SimpleNamespace(c=c, s=s, ss=ss, ctx=ctx, h=h, vk=vk, ovk=ovk, orc=native.Prover(pure, opk))
+        finally:
+            h.close()
+    finally:
+        ctx.close()
+
+
 @pytest.mark.gpu
-def test_reference_r1cs_is_solved_and_proved_on_the_gpu_from_the_26_inputs(program, withdraw_kat, tmp_path):
+def test_reference_r1cs_is_solved_and_proved_on_the_gpu_from_the_26_inputs(program, withdraw_kat, solved_system):
     """the reference's own constraint system with its SOLVER on the device (spp/ccs.py to_sppc_solved): the
     container takes the 26 withdraw inputs of client/proof.helper.ts:34-50.  (1) every wire the device computes == gnark's
     solver loop restated in spp/ccs.py solve_partial (fed by this repository's ACIR executor) on the reference KAT and on fresh
     notes with keys on both sides of 2^127 (the scalar decomposition's non-trivial half); (2) same verifying key and byte-identical
     proofs as the ORACLE proving the all-inputs container of the same system from solve_partial's witness, same seed, blinding
     and mask; (3) a batch of 64 distinct notes verifies; bad inputs are refused in place."""
-    import spp
     from spp import ccs, acir
-    from oracle import circuit as C, native, groth16
-    c, s, pure = _reference_system(tmp_path)
-    solved = str(tmp_path / "solved.sppc")
-    n, ss = ccs.to_sppc_solved(s, c, program, solved)
-    assert n == 12452
-    pk, vk, opk, ovk = (str(tmp_path / x) for x in ("s.pk", "s.vk", "o.pk", "o.vk"))
-    seed = b"\x0b" * 32
-    ctx = spp.Context(0)
-    try:
-        ctx.setup(solved, seed, pk, vk)
-        native.setup(pure, seed, opk, ovk)
-        assert open(vk, "rb").read() == open(ovk, "rb").read()          # the same statement under the same toxic waste
-        orc = native.Prover(pure, opk)
-        h = ctx.load_circuit(solved, pk, 6)
-        try:
-            assert h.n_inputs == 26 and h.n_wires == s.n_wires + 1 and h.n_constraints == 12452
-            rows = [C.withdraw_inputs(withdraw_kat)] + [_fresh_note_inputs(k) for k in range(20, 25)]
-            assert any(r[5] >> 127 for r in rows) and any(not (r[5] >> 127) for r in rows)
-            for i, row in enumerate(rows):
-                r_, s_ = 1000003 * i + 17, (1 << 200) + 29 * i
-                proofs, pws, status = h.prove_batch([row], [(r_, s_)])
-                assert status == [0]
-                dev = h.debug_witness()
-                wa = acir.execute(program, row)
-                ref, st = ccs.solve_partial(s, c, row[:5], {"__witness_%d" % k: v for k, v in wa.items()}, challenge=dev[ss.challenge_wire],
-                                            randomizer=C.mask_value(r_, s_))
-                assert not st["rows_unsatisfied"] and not st["rows_skipped"] and not st["hints_skipped"]
-                assert [dev[ss.perm[g]] for g in range(s.n_wires)] == ref, i        # every wire
-                rc, proof, pw = orc.prove(ref[1:], r_, s_)
-                assert rc == 0 and proofs[0] == proof and pws[0] == pw, i           # same bytes as the oracle on the all-inputs system
-                assert groth16.verify(open(vk, "rb").read(), proofs[0], pws[0])
-            batch = [_fresh_note_inputs(100 + k) for k in range(64)]
-            bad = list(batch[7]); bad[3] += 1                                       # amount
-            batch[7] = bad
-            proofs, pws, status = h.prove_batch(batch, [(3 * k + 1, 5 * k + 2) for k in range(64)])
-            assert [k for k in range(64) if status[k] != 0] == [7]
-            good = [k for k in range(64) if k != 7]
-            assert all(ctx.verify_batch(open(vk, "rb").read(), [proofs[k] for k in good], [pws[k] for k in good]))
-        finally:
-            h.close()
-    finally:
-        ctx.close()
+    from oracle import circuit as C, groth16
+    S = solved_system
+    c, s, ss, ctx, h, vk, orc = S.c, S.s, S.ss, S.ctx, S.h, S.vk, S.orc
+    assert open(vk, "rb").read() == open(S.ovk, "rb").read()          # the same statement under the same toxic waste
+    assert h.n_inputs == 26 and h.n_wires == s.n_wires + 1 and h.n_constraints == 12452
+    rows = [C.withdraw_inputs(withdraw_kat)] + [_fresh_note_inputs(k) for k in range(20, 25)]
+    assert any(r[5] >> 127 for r in rows) and any(not (r[5] >> 127) for r in rows)
+    for i, row in enumerate(rows):
+        r_, s_ = 1000003 * i + 17, (1 << 200) + 29 * i
+        proofs, pws, status = h.prove_batch([row], [(r_, s_)])
+        assert status == [0]
+        dev = h.debug_witness()
+        wa = acir.execute(program, row)
+        ref, st = ccs.solve_partial(s, c, row[:5], {"__witness_%d" % k: v for k, v in wa.items()}, challenge=dev[ss.challenge_wire],
+                                    randomizer=C.mask_value(r_, s_))
+        assert not st["rows_unsatisfied"] and not st["rows_skipped"] and not st["hints_skipped"]
+        assert [dev[ss.perm[g]] for g in range(s.n_wires)] == ref, i        # every wire
+        rc, proof, pw = orc.prove(ref[1:], r_, s_)
+        assert rc == 0 and proofs[0] == proof and pws[0] == pw, i           # same bytes as the oracle on the all-inputs system
+        assert groth16.verify(open(vk, "rb").read(), proofs[0], pws[0])
+    batch = [_fresh_note_inputs(100 + k) for k in range(64)]
+    bad = list(batch[7]); bad[3] += 1                                       # amount
+    batch[7] = bad
+    proofs, pws, status = h.prove_batch(batch, [(3 * k + 1, 5 * k + 2) for k in range(64)])
+    assert [k for k in range(64) if status[k] != 0] == [7]
+    good = [k for k in range(64) if k != 7]
+    assert all(ctx.verify_batch(open(vk, "rb").read(), [proofs[k] for k in good], [pws[k] for k in good]))
+
+
+EDGE_KEYS = (1, 2, 3, 1 << 64, (1 << 127) - 1, 1 << 127, (1 << 128) - 1)   # and GLV_LAMBDA mod 2^128
+
+
+@pytest.mark.gpu
+def test_solver_hints_on_edge_keys_through_the_solver_kernel(program, solved_system):
+    """The hints of csrc/gnark_hints.hpp where the solver kernel calls them (k_solve, kernels_solve.hip: OP_GLV, OP_EMUL,
+    OP_GK_MUL), on notes whose secret key sits on an edge of the scalar decomposition: 1, 2, 3, 2^64, 2^127 - 1, 2^127, 2^128 - 1
+    and lambda mod 2^128.  Alone in a batch (one live lane in the wave) the status is 0 and every device wire equals solve_partial;
+    then the eight rows go first in a batch of 65 with 57 random notes (a full wave and a ragged one):
+    all statuses 0, each edge row's proof is the bytes of its batch-of-one proof under the same blinding, and all 65 verify.
+    Both batch sizes run k_solve: a container with the generic solver instructions switches the cooperative planner off at load
+    (spp_load.cpp), so k_solve_coop never meets these hints.  A key solve_partial refuses must be refused by the device in place."""
+    from spp import ccs, acir
+    from oracle import circuit as C, groth16
+    S = solved_system
+    c, s, ss, h = S.c, S.s, S.ss, S.h
+    vkb = open(S.vk, "rb").read()
+    keys = EDGE_KEYS + (ccs.GLV_LAMBDA % (1 << 128),)
+    rows = [_fresh_note_inputs(300 + i, sk=k) for i, k in enumerate(keys)]
+    assert [r[5] for r in rows] == list(keys)
+    rs = [(7919 * i + 3, (1 << 190) + 31 * i) for i in range(65)]
+    alone, accepted = [], []
+    for i, row in enumerate(rows):
+        wa = acir.execute(program, row)
+        secret = {"__witness_%d" % k: v for k, v in wa.items()}
+        proofs, pws, status = h.prove_batch([row], [rs[i]])
+        dev = h.debug_witness()
+        ref, st = ccs.solve_partial(s, c, row[:5], secret, challenge=dev[ss.challenge_wire], randomizer=C.mask_value(*rs[i]))
+        assert not st["rows_skipped"] and not st["hints_skipped"]
+        accepted.append(not st["rows_unsatisfied"])
+        alone.append(proofs[0])
+        if not accepted[-1]:
+            assert status[0] != 0 and proofs[0] == bytes(388), keys[i]
+            continue
+        assert status == [0], keys[i]
+        assert [dev[ss.perm[g]] for g in range(s.n_wires)] == ref, keys[i]         # every wire
+    assert accepted[-1] and groth16.verify(vkb, proofs[0], pws[0])                 # the oracle's verifier on the last one ...
+    batch = rows + [_fresh_note_inputs(400 + k) for k in range(57)]
+    proofs, pws, status = h.prove_batch(batch, rs)
+    assert [st == 0 for st in status] == accepted + [True] * 57
+    assert proofs[:8] == alone                                                     # ... and the device's on all, the same bytes
+    live = [k for k in range(65) if status[k] == 0]
+    assert all(S.ctx.verify_batch(vkb, [proofs[k] for k in live], [pws[k] for k in live]))
 
 
 def test_fixtures_equal_the_reference_files():
