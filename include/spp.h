@@ -28,6 +28,7 @@
  *                             (proof, public witness, ciphertext) from the prover's raw secrets
  *   spp_audit_open_batch      scripts/rlwe_decrypt.py:61-149 for a batch of such records, after `sunspot verify`
  *                             (audit_circuit/prove_audit.sh:98-99) and with the two binding checks the script leaves out
+ *   spp_audit_open_batch_rlc  the same, the proofs verified by random linear combination
  *   spp_pool_*                the pool program's state and decisions, shielded_pool_program/src: ShieldedPoolState and its root ring
  *                             (state.rs:6-46, instructions/initialize.rs:65-69), process_submit_audit
  *                             (instructions/submit_audit.rs:41-87) and process_withdraw (instructions/withdraw.rs:94-175) for a
@@ -435,6 +436,14 @@ int spp_shamir_split(spp_ctx* ctx, uint32_t t, uint32_t m, const uint32_t* xs, s
  * public-input count is not 2 (SPP_ERR_FORMAT).  count == 0 is SPP_OK. */
 int spp_audit_open_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint32_t* sk_mod_q, size_t count, const uint8_t* proofs,
                          const uint8_t* pws, const uint32_t* c0, const uint32_t* c1, uint8_t* owners, uint32_t* flags);
+/* The same with the random-linear-combination verifier of spp_verify_batch_rlc in front of the open kernel instead of k_verify: same
+ * argument checks, outputs and vk == NULL behaviour; bit 1 of flags[i] is the decision of spp_audit_open_batch except with probability
+ * about 2^-127 per call.  The seed is 32 bytes from the operating system, drawn per call; slices and workspace as in
+ * spp_verify_batch_rlc.  group: a multiple of 64 in [64, 4096], 0 = 256 (else SPP_ERR_BAD_INPUT).  stats (optional): groups, groups
+ * refused, proofs re-verified, proofs dropped; all zero without a key. */
+int spp_audit_open_batch_rlc(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint32_t* sk_mod_q, size_t count, const uint8_t* proofs,
+                             const uint8_t* pws, const uint32_t* c0, const uint32_t* c1, uint32_t group, uint8_t* owners, uint32_t* flags,
+                             uint32_t stats[4] /* optional */);
 
 /* ---- the pool ledger: which of these proofs would the pool accept? ---- */
 /* A device-resident restatement of the state the pool program decides on (shielded_pool_program/src): ShieldedPoolState's root ring
@@ -473,6 +482,29 @@ typedef struct spp_pool spp_pool;
 int  spp_pool_new(spp_ctx*, const uint8_t* withdraw_vk, size_t withdraw_vk_len, const uint8_t* audit_vk, size_t audit_vk_len,
                   uint64_t capacity, spp_pool** out);
 void spp_pool_free(spp_pool*);
+/* Which verifier the three settling calls below run over the proofs the screen leaves (opt-in; a fresh pool is in mode EACH).
+ * Mode RLC verifies the compacted list by random linear combination (spp_verify_batch_rlc above has the scheme): groups of `group`
+ * list entries, one combined equation each, a refused group settled by the per-proof kernel.
+ *   - The decisions -- codes, amounts, state, sets -- are those of mode EACH except with probability about 2^-127 per verifier launch.
+ *   - Only how ok[i] ("the proof of instruction i verifies") is computed changes; every kernel that reads ok[i] is the same, so the
+ *     ordering argument of csrc/pool_table.hpp is untouched.
+ *   - The weights of a proof are derived from the launch's seed and its instruction index, not from its place in the list, which
+ *     depends on scheduling.  The seed is 32 bytes from the operating system for EVERY verifier launch (spp_pool_settle_log makes
+ *     two and draws two: instruction ranks overlap between the two kinds).  There is no seed argument and no environment override:
+ *     a reused or known seed voids the guarantee (see spp_verify_batch_rlc).
+ *   - Launches of the verifier for count <= 2^18 instructions of a kind: three (terms, groups, fallback), whatever the list holds;
+ *     beyond that three per slice of 2^18 list entries.  The length of the list is never read back.
+ *   - With env SPP_POOL_COMPACT=0 mode RLC runs the dense verifier of spp_verify_batch_rlc over all instructions of the kind.
+ * The beta line table and -alpha1 of both keys are prepared when RLC is first selected and stay resident until spp_pool_free.
+ * group: a multiple of 64 in [64, 4096], 0 = 256.  Refused with SPP_ERR_BAD_INPUT, the pool unchanged: a NULL pool, an unknown mode,
+ * a bad group (in either mode). */
+#define SPP_POOL_VERIFY_EACH  0     /* k_verify_list / k_verify: one lane per proof, the default */
+#define SPP_POOL_VERIFY_RLC   1     /* random linear combination over the compacted list */
+int  spp_pool_set_verifier(spp_pool*, int mode, uint32_t group /* multiple of 64 in [64,4096], 0 = 256 */);
+/* The verifier's counters of the last settling call (submit_audit_batch, withdraw_batch, settle_log) that got as far as the device:
+ * stats[0..3] for the withdraw key, stats[4..7] for the audit key, each: groups, groups refused, proofs re-verified, proofs dropped
+ * (refused by the format, curve or subgroup checks).  All zero after a call in mode EACH. */
+int  spp_pool_verify_stats(spp_pool*, uint32_t stats[8]);
 /* state.add_root for `count` deposits in order: roots = count * 32 B, the `roots` output of spp_merkle_tree_deposit as it is */
 int  spp_pool_add_roots(spp_pool*, size_t count, const uint8_t* roots);
 /* the account bytes as bytemuck lays them out: "poolstat", current_root, roots[32], roots_index as u32 LE, 4 zero bytes */

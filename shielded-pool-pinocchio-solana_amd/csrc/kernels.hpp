@@ -188,6 +188,15 @@ struct W256;
 void launch_verify_rlc(hipStream_t st, const VerifyKeyDev* vk, const RlcKeyDev* rk, const uint8_t* proofs, const uint8_t* pws, uint32_t pw_len,
                        uint32_t count, const RlcSeed& seed, uint32_t index0, uint32_t group, uint32_t flags, W256* ws, uint32_t* live,
                        int32_t* ok, uint32_t* list, uint32_t* n_list, uint32_t* stats);
+// the same over a compacted list (verify_rlc_list.hpp): the proofs in_list[0 .. *n_in) of a batch, *n_in a device word <= max_count
+// that the host never reads; ok[in_list[j]] = 1 for the accepted ones, the other entries of ok untouched (the caller cleared them).
+// Slices of at most 2^18 list positions, each: *n_list = 0, terms, groups, k_verify_list over the proofs of the refused groups
+// (max_count <= 2^18: exactly these three launches).  ws: rlc_elems(nk) * min(max_count, rlc_slice_len(group)) elements; live, list
+// (the fallback list): as many words; stats[0..3] are added to (groups are counted on the device).  The scalars are derived from
+// the seed and the index in the batch, in_list[j], not from j.  max_count > 0
+void launch_verify_rlc_list(hipStream_t st, const VerifyKeyDev* vk, const RlcKeyDev* rk, const uint8_t* proofs, const uint8_t* pws, uint32_t pw_len,
+                            uint32_t max_count, const uint32_t* in_list, const uint32_t* n_in, const RlcSeed& seed, uint32_t group, W256* ws,
+                            uint32_t* live, int32_t* ok, uint32_t* list, uint32_t* n_list, uint32_t* stats);
 // ---- pool ledger (kernels_pool.hip); the structures and what a lane does live in pool_table.hpp ----
 struct PoolSet;
 struct PoolState;

@@ -4,6 +4,9 @@
 // the program makes processing them one after another (instructions/submit_audit.rs, withdraw.rs).  What a lane does and why the
 // parallel resolution of duplicates equals the sequential one is in pool_table.hpp; the launches are in kernels_pool.hip.
 // One call = one upload, screen -> verify (compacted list) -> claim -> settle -> commit on ctx->stream, one download.
+// Which verifier "verify" is, is the pool's mode (spp_pool_set_verifier): k_verify_list / k_verify per proof, the default, or the
+// random-linear-combination verifier over the same list (verify_rlc_list.hpp; kernels_verify_rlc.hip).  Only how ok[i] is computed
+// differs; screen, claim, settle and commit read ok[i] as before.
 // spp_pool_settle_log takes a log in which deposits, submit_audits and withdraws alternate (state.rs:28-46,
 // instructions/deposit.rs:21-37, submit_audit.rs:41-87, withdraw.rs:94-175) and settles it with a fixed number of launches.
 #include "spp_internal.hpp"
@@ -20,6 +23,15 @@ struct spp_pool {
   PoolSet set[2]{};                 // SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS: device pointers
   uint32_t* d_counts = nullptr;     // keys per set, advanced by the commit kernel
   uint64_t counts[2] = {0, 0};      // as downloaded at the end of the last call that could change them
+  // the verifier (spp_pool_set_verifier).  The beta pairs and the counters are made when RLC is first selected and stay resident
+  int verifier = SPP_POOL_VERIFY_EACH;
+  uint32_t group = RLC_DEFAULT_GROUP;
+  bool rlc_ready = false;
+  RlcKeyPrep rkey[2];               // beside key[]
+  DevBuf dvstats;                   // per key 5 words: groups, groups refused, proofs re-verified, proofs dropped | fallback-list length
+  uint32_t vraw[10] = {};           // their download, and the groups of a dense launch (SPP_POOL_COMPACT=0), which only the host knows
+  uint32_t dense_groups[2] = {0, 0};
+  uint32_t vstats[8] = {};          // spp_pool_verify_stats: the last settling call, [0..3] withdraw key, [4..7] audit key
 };
 
 static_assert(SPP_POOL_STATE_LEN == POOL_STATE_LEN && SPP_POOL_OK == POOL_OK && SPP_POOL_AUDIT_EXISTS == POOL_AUDIT_EXISTS &&
@@ -135,6 +147,16 @@ static int pool_fetch_counts(spp_pool* p, hipStream_t st, uint32_t host[2]) {
   HIP_TRY(hipMemcpyAsync(host, p->d_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   return SPP_OK;
 }
+// ... and the verifier's counters of a settling call (mode RLC), behind its last launch; pool_stats_end after the synchronise
+static int pool_fetch_stats(spp_pool* p, hipStream_t st) {
+  if (p->verifier == SPP_POOL_VERIFY_RLC) HIP_TRY(hipMemcpyAsync(p->vraw, p->dvstats.p, sizeof p->vraw, hipMemcpyDeviceToHost, st));
+  return SPP_OK;
+}
+static void pool_stats_end(spp_pool* p) {
+  for (int k = 0; k < 2; k++)
+    for (int j = 0; j < 4; j++)
+      p->vstats[4 * k + j] = p->verifier == SPP_POOL_VERIFY_RLC ? p->vraw[5 * k + j] + (j == 0 ? p->dense_groups[k] : 0) : 0;
+}
 static int pool_room(const spp_pool* p, int which, size_t count) {
   if (p->counts[which] + count > p->capacity)
     return fail(SPP_ERR_BAD_INPUT, "the %s set holds %llu of %llu keys: a call with %zu more could overflow it",
@@ -198,11 +220,67 @@ extern "C" int spp_pool_contains(spp_pool* p, int which, size_t count, const uin
   return SPP_OK;
 }
 
-// screen has run and left prov, the verify list and its length; verdicts by instruction index into ok (zeroed here)
+extern "C" int spp_pool_set_verifier(spp_pool* p, int mode, uint32_t group) {
+  if (!p) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (mode != SPP_POOL_VERIFY_EACH && mode != SPP_POOL_VERIFY_RLC) return fail(SPP_ERR_BAD_INPUT, "mode: SPP_POOL_VERIFY_EACH or SPP_POOL_VERIFY_RLC");
+  if (int e = rlc_group_arg(group)) return e;
+  spp_ctx* ctx = p->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode == SPP_POOL_VERIFY_RLC && !p->rlc_ready) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    RlcKeyPrep fresh[2];
+    DevBuf counters;
+    for (int k = 0; k < 2; k++)
+      if (int e = fresh[k].upload(st, p->key[k])) return e;
+    HIP_TRY(counters.alloc(sizeof p->vraw));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < 2; k++) {                                      // complete: only now the pool takes them
+      std::swap(p->rkey[k].dtab.p, fresh[k].dtab.p);
+      std::swap(p->rkey[k].drk.p, fresh[k].drk.p);
+    }
+    std::swap(p->dvstats.p, counters.p);
+    p->rlc_ready = true;
+  }
+  p->verifier = mode;
+  p->group = group;
+  return SPP_OK;
+}
+
+extern "C" int spp_pool_verify_stats(spp_pool* p, uint32_t stats[8]) {
+  if (!p || !stats) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  std::lock_guard<std::mutex> lk(p->ctx->mu);
+  memcpy(stats, p->vstats, sizeof p->vstats);
+  return SPP_OK;
+}
+
+// the counters of a settling call: cleared in front of its first verifier launch, downloaded behind its last
+static int pool_stats_begin(spp_pool* p, hipStream_t st) {
+  p->dense_groups[0] = p->dense_groups[1] = 0;
+  if (p->verifier == SPP_POOL_VERIFY_RLC) HIP_TRY(hipMemsetAsync(p->dvstats.p, 0, sizeof p->vraw, st));
+  return SPP_OK;
+}
+
+// screen has run and left prov, the verify list and its length; verdicts by instruction index into ok (zeroed here).
+// which_key: 0 withdraw, 1 audit.  Mode RLC: a seed of its own per launch, from the operating system
 static int pool_verify(spp_pool* p, hipStream_t st, int which_key, const uint8_t* dproofs, const uint8_t* dpws, uint32_t pw_len, uint32_t count,
-                       const uint32_t* dlist, const uint32_t* dnlist, DevBuf& dok) {
+                       const uint32_t* dlist, const uint32_t* dnlist, DevBuf& dok, RlcScratch& sc) {
   HIP_TRY(dok.alloc(count * sizeof(int32_t)));
   HIP_TRY(hipMemsetAsync(dok.p, 0, count * sizeof(int32_t), st));
+  if (p->verifier == SPP_POOL_VERIFY_RLC) {
+    RlcSeed seed;
+    if (int e = rlc_os_seed(seed)) return e;
+    if (int e = sc.alloc(p->key[which_key].nk, count, p->group)) return e;
+    uint32_t* cnt = p->dvstats.as<uint32_t>() + 5 * which_key;
+    if (p->compact) {
+      launch_verify_rlc_list(st, p->key[which_key].dev(), p->rkey[which_key].dev(), dproofs, dpws, pw_len, count, dlist, dnlist, seed, p->group,
+                             sc.ws.as<W256>(), sc.live.as<uint32_t>(), dok.as<int32_t>(), sc.list.as<uint32_t>(), cnt + 4, cnt);
+      return SPP_OK;
+    }
+    p->dense_groups[which_key] = rlc_dense_groups(count, p->group);
+    return rlc_verify_dense(st, p->key[which_key].dev(), p->rkey[which_key].dev(), dproofs, dpws, pw_len, count, seed, p->group, 0, sc,
+                            dok.as<int32_t>(), cnt, cnt + 4);
+  }
   if (p->compact)
     launch_verify_list(st, p->key[which_key].dev(), dproofs, dpws, pw_len, count, dlist, dnlist, dok.as<int32_t>());
   else
@@ -221,6 +299,7 @@ extern "C" int spp_pool_submit_audit_batch(spp_pool* p, size_t count, const uint
   hipStream_t st = ctx->stream;
   const uint32_t n = (uint32_t)count;
   DevBuf dproofs, dpws, dprov, dlist, dnlist, dok, dslots, dresult;
+  RlcScratch sc;
   uint32_t rmask = 0, cnt[2];
   UP(dproofs, proofs, count * (size_t)SPP_PROOF_LEN);
   UP(dpws, pws, count * (size_t)SPP_AUDIT_PW_LEN);
@@ -230,17 +309,20 @@ extern "C" int spp_pool_submit_audit_batch(spp_pool* p, size_t count, const uint
   HIP_TRY(dnlist.alloc(sizeof(uint32_t)));
   HIP_TRY(hipMemsetAsync(dnlist.p, 0, sizeof(uint32_t), st));
   if (int e = pool_resolve_table(st, count, dslots, &rmask)) return e;
+  if (int e = pool_stats_begin(p, st)) return e;
   const PoolSet& audits = p->set[SPP_POOL_AUDIT_RECORDS];
   const uint8_t* keys = dpws.as<uint8_t>() + POOL_A_WA;
   launch_pool_screen_audit(st, audits, p->salt, dpws.as<uint8_t>(), n, dprov.as<int32_t>(), dlist.as<uint32_t>(), dnlist.as<uint32_t>());
-  if (int e = pool_verify(p, st, 1, dproofs.as<uint8_t>(), dpws.as<uint8_t>(), SPP_AUDIT_PW_LEN, n, dlist.as<uint32_t>(), dnlist.as<uint32_t>(), dok)) return e;
+  if (int e = pool_verify(p, st, 1, dproofs.as<uint8_t>(), dpws.as<uint8_t>(), SPP_AUDIT_PW_LEN, n, dlist.as<uint32_t>(), dnlist.as<uint32_t>(), dok, sc)) return e;
   launch_pool_resolve(st, dslots.as<uint32_t>(), rmask, p->salt, keys, SPP_AUDIT_PW_LEN, n, dprov.as<int32_t>(), dok.as<int32_t>(), POOL_AUDIT_EXISTS,
                       dresult.as<int32_t>());
   launch_pool_commit(st, audits, p->salt, keys, SPP_AUDIT_PW_LEN, n, dresult.as<int32_t>(), p->d_counts + SPP_POOL_AUDIT_RECORDS);
   HIP_TRY(hipMemcpyAsync(result, dresult.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   if (int e = pool_fetch_counts(p, st, cnt)) return e;
+  if (int e = pool_fetch_stats(p, st)) return e;
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
+  pool_stats_end(p);
   p->counts[0] = cnt[0];
   p->counts[1] = cnt[1];
   return SPP_OK;
@@ -258,6 +340,7 @@ extern "C" int spp_pool_withdraw_batch(spp_pool* p, size_t count, const uint8_t*
   hipStream_t st = ctx->stream;
   const uint32_t n = (uint32_t)count;
   DevBuf dproofs, dpws, drecip, dprov, damounts, dlist, dnlist, dok, dslots, dresult;
+  RlcScratch sc;
   uint32_t rmask = 0, cnt[2];
   UP(dproofs, proofs, count * (size_t)SPP_PROOF_LEN);
   UP(dpws, pws, count * (size_t)SPP_WITHDRAW_PW_LEN);
@@ -269,19 +352,22 @@ extern "C" int spp_pool_withdraw_batch(spp_pool* p, size_t count, const uint8_t*
   HIP_TRY(dnlist.alloc(sizeof(uint32_t)));
   HIP_TRY(hipMemsetAsync(dnlist.p, 0, sizeof(uint32_t), st));
   if (int e = pool_resolve_table(st, count, dslots, &rmask)) return e;
+  if (int e = pool_stats_begin(p, st)) return e;
   const PoolSet& nullifiers = p->set[SPP_POOL_NULLIFIERS];
   const uint8_t* keys = dpws.as<uint8_t>() + POOL_W_NULLIFIER;
   launch_pool_screen_withdraw(st, p->d_state, p->set[SPP_POOL_AUDIT_RECORDS], nullifiers, p->salt, dpws.as<uint8_t>(), drecip.as<uint8_t>(), n,
                               dprov.as<int32_t>(), damounts.as<uint64_t>(), dlist.as<uint32_t>(), dnlist.as<uint32_t>());
-  if (int e = pool_verify(p, st, 0, dproofs.as<uint8_t>(), dpws.as<uint8_t>(), SPP_WITHDRAW_PW_LEN, n, dlist.as<uint32_t>(), dnlist.as<uint32_t>(), dok)) return e;
+  if (int e = pool_verify(p, st, 0, dproofs.as<uint8_t>(), dpws.as<uint8_t>(), SPP_WITHDRAW_PW_LEN, n, dlist.as<uint32_t>(), dnlist.as<uint32_t>(), dok, sc)) return e;
   launch_pool_resolve(st, dslots.as<uint32_t>(), rmask, p->salt, keys, SPP_WITHDRAW_PW_LEN, n, dprov.as<int32_t>(), dok.as<int32_t>(),
                       POOL_NULLIFIER_USED, dresult.as<int32_t>());
   launch_pool_commit(st, nullifiers, p->salt, keys, SPP_WITHDRAW_PW_LEN, n, dresult.as<int32_t>(), p->d_counts + SPP_POOL_NULLIFIERS);
   HIP_TRY(hipMemcpyAsync(result, dresult.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   if (amounts) HIP_TRY(hipMemcpyAsync(amounts, damounts.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (int e = pool_fetch_counts(p, st, cnt)) return e;
+  if (int e = pool_fetch_stats(p, st)) return e;
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
+  pool_stats_end(p);
   p->counts[0] = cnt[0];
   p->counts[1] = cnt[1];
   return SPP_OK;
@@ -328,6 +414,7 @@ extern "C" int spp_pool_settle_log(spp_pool* p, size_t count, const uint8_t* kin
   DevBuf dindex, dall, dall_amounts, dring;
   DevBuf aproofs, apws, aprov, alist, anlist, aok, aslots, aresult;
   DevBuf wproofs, wpws, wrecip, wprov, wamounts, wlist, wnlist, wok, wslots, wresult;
+  RlcScratch asc, wsc;
   uint32_t amask = 0, wmask = 0, cnt[2];
   // upload
   UP(dindex, index.data(), index.size() * sizeof(uint32_t));
@@ -356,6 +443,7 @@ extern "C" int spp_pool_settle_log(spp_pool* p, size_t count, const uint8_t* kin
 
   // the submit_audits among themselves; the table stays for the withdraws (all empty when there is no submit_audit)
   if (int e = pool_resolve_table(st, n_audits, aslots, &amask)) return e;
+  if (int e = pool_stats_begin(p, st)) return e;
   if (na) {
     HIP_TRY(aprov.alloc(n_audits * sizeof(int32_t)));
     HIP_TRY(aresult.alloc(n_audits * sizeof(int32_t)));
@@ -363,7 +451,7 @@ extern "C" int spp_pool_settle_log(spp_pool* p, size_t count, const uint8_t* kin
     HIP_TRY(anlist.alloc(sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(anlist.p, 0, sizeof(uint32_t), st));
     launch_pool_screen_audit(st, audits, p->salt, apws.as<uint8_t>(), na, aprov.as<int32_t>(), alist.as<uint32_t>(), anlist.as<uint32_t>());
-    if (int e = pool_verify(p, st, 1, aproofs.as<uint8_t>(), apws.as<uint8_t>(), SPP_AUDIT_PW_LEN, na, alist.as<uint32_t>(), anlist.as<uint32_t>(), aok)) return e;
+    if (int e = pool_verify(p, st, 1, aproofs.as<uint8_t>(), apws.as<uint8_t>(), SPP_AUDIT_PW_LEN, na, alist.as<uint32_t>(), anlist.as<uint32_t>(), aok, asc)) return e;
     launch_pool_resolve(st, aslots.as<uint32_t>(), amask, p->salt, akeys, SPP_AUDIT_PW_LEN, na, aprov.as<int32_t>(), aok.as<int32_t>(), POOL_AUDIT_EXISTS,
                         aresult.as<int32_t>());
   }
@@ -379,7 +467,7 @@ extern "C" int spp_pool_settle_log(spp_pool* p, size_t count, const uint8_t* kin
     const PoolLogView view{dring.as<uint8_t>(), aslots.as<uint32_t>(), amask, akeys, SPP_AUDIT_PW_LEN};
     launch_pool_screen_withdraw_log(st, view, audits, nullifiers, p->salt, wpws.as<uint8_t>(), wrecip.as<uint8_t>(), deposits_before, audits_before, nw,
                                     wprov.as<int32_t>(), wamounts.as<uint64_t>(), wlist.as<uint32_t>(), wnlist.as<uint32_t>());
-    if (int e = pool_verify(p, st, 0, wproofs.as<uint8_t>(), wpws.as<uint8_t>(), SPP_WITHDRAW_PW_LEN, nw, wlist.as<uint32_t>(), wnlist.as<uint32_t>(), wok)) return e;
+    if (int e = pool_verify(p, st, 0, wproofs.as<uint8_t>(), wpws.as<uint8_t>(), SPP_WITHDRAW_PW_LEN, nw, wlist.as<uint32_t>(), wnlist.as<uint32_t>(), wok, wsc)) return e;
     launch_pool_resolve(st, wslots.as<uint32_t>(), wmask, p->salt, wkeys, SPP_WITHDRAW_PW_LEN, nw, wprov.as<int32_t>(), wok.as<int32_t>(),
                         POOL_NULLIFIER_USED, wresult.as<int32_t>());
   }
@@ -398,8 +486,10 @@ extern "C" int spp_pool_settle_log(spp_pool* p, size_t count, const uint8_t* kin
   HIP_TRY(hipMemcpyAsync(result, dall.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   if (amounts) HIP_TRY(hipMemcpyAsync(amounts, dall_amounts.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (int e = pool_fetch_counts(p, st, cnt)) return e;
+  if (int e = pool_fetch_stats(p, st)) return e;
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
+  pool_stats_end(p);
   p->state = next;   // the host ring takes the batch's roots only now, after the stream has come through without an error
   p->counts[0] = cnt[0];
   p->counts[1] = cnt[1];

@@ -105,16 +105,13 @@ extern "C" int spp_verify_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, 
 // batched verification by random linear combination (verify_rlc.hpp): `sunspot verify` for many proofs against one key
 // (noir_circuit/prove_linux.sh:86-87); same decisions as spp_verify_batch except with probability ~2^-127 per call
 // -----------------------------------------------------------------------------------------------------
-static constexpr uint32_t RLC_DEFAULT_GROUP = 256;       // profiles/verify_rlc_probe.json: 64 / 256 / 1024 at 2^15 proofs = 59.3 / 61.2 / 74.6 ms
-static constexpr size_t RLC_SLICE = (size_t)1 << 18;     // proofs per slice at most: bounds the workspace (~1.1 KB per proof)
 extern "C" int spp_verify_batch_rlc(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, size_t count, const uint8_t* proofs, const uint8_t* pws,
                                     size_t pw_len, const uint8_t* seed32, uint32_t group, uint32_t flags, int32_t* ok, uint32_t stats[4],
                                     float* kernel_ms) {
   if (!ctx || !vk || !ok || (count && (!proofs || !pws))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   if (kernel_ms) *kernel_ms = 0;
   if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (group == 0) group = RLC_DEFAULT_GROUP;
-  if (group < 64 || group > 4096 || group % 64) return fail(SPP_ERR_BAD_INPUT, "group must be a multiple of 64 in [64, 4096]");
+  if (int e = rlc_group_arg(group)) return e;
   if (flags & ~(uint32_t)(SPP_RLC_SERIAL_TAIL | SPP_RLC_NO_FALLBACK)) return fail(SPP_ERR_BAD_INPUT, "unknown flag");
   if (count == 0) return SPP_OK;
   if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "count too large");
@@ -124,31 +121,22 @@ extern "C" int spp_verify_batch_rlc(spp_ctx* ctx, const uint8_t* vk, size_t vk_l
   RlcSeed seed;
   if (seed32) {
     memcpy(seed.b, seed32, 32);
-  } else {
-    FILE* f = fopen("/dev/urandom", "rb");
-    const bool got = f && fread(seed.b, 1, 32, f) == 32;
-    if (f) fclose(f);
-    if (!got) return fail(SPP_ERR_BAD_INPUT, "no randomness from the operating system");
+  } else if (int e = rlc_os_seed(seed)) {
+    return e;
   }
 
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   if (int e = key.upload(st)) return e;
-  // the beta pair: a fifth line table and -alpha1, beside VerifyKeyDev
-  const std::vector<LineStep> tab_beta = build_line_table(key.beta2);
-  DevBuf dtab_beta, drk;
-  UP(dtab_beta, tab_beta.data(), tab_beta.size() * sizeof(LineStep));
-  const RlcKeyDev rk{dtab_beta.as<LineStep>(), key.alpha1.neg()};
-  UP(drk, &rk, sizeof rk);
-  const size_t slice = RLC_SLICE / group * group, ws_n = std::min(count, slice);
-  DevBuf dproofs, dpws, dok, dws, dlive, dlist, dcnt;
+  RlcKeyPrep rkey;
+  if (int e = rkey.upload(st, key)) return e;
+  RlcScratch sc;
+  DevBuf dproofs, dpws, dok, dcnt;
   UP(dproofs, proofs, count * (size_t)SPP_PROOF_LEN);
   UP(dpws, pws, count * pw_len);
   HIP_TRY(dok.alloc(count * sizeof(int32_t)));
-  HIP_TRY(dws.alloc(ws_n * rlc_elems(key.nk) * sizeof(W256)));
-  HIP_TRY(dlive.alloc(ws_n * sizeof(uint32_t)));
-  HIP_TRY(dlist.alloc(ws_n * sizeof(uint32_t)));
+  if (int e = sc.alloc(key.nk, count, group)) return e;
   HIP_TRY(dcnt.alloc(5 * sizeof(uint32_t)));              // stats[4], then the length of the fallback list
   HIP_TRY(hipMemsetAsync(dcnt.p, 0, 5 * sizeof(uint32_t), st));
   struct Ev {   // destroyed on every return path
@@ -158,13 +146,9 @@ extern "C" int spp_verify_batch_rlc(spp_ctx* ctx, const uint8_t* vk, size_t vk_l
   HIP_TRY(hipEventCreate(&ev0.e));
   HIP_TRY(hipEventCreate(&ev1.e));
   hipEventRecord(ev0.e, st);
-  for (size_t at = 0; at < count; at += slice) {
-    const uint32_t n = (uint32_t)std::min(slice, count - at);
-    if (at) HIP_TRY(hipMemsetAsync(dcnt.as<uint32_t>() + 4, 0, sizeof(uint32_t), st));
-    launch_verify_rlc(st, key.dev(), drk.as<RlcKeyDev>(), dproofs.as<uint8_t>() + at * SPP_PROOF_LEN, dpws.as<uint8_t>() + at * pw_len,
-                      (uint32_t)pw_len, n, seed, (uint32_t)at, group, flags, dws.as<W256>(), dlive.as<uint32_t>(), dok.as<int32_t>() + at,
-                      dlist.as<uint32_t>(), dcnt.as<uint32_t>() + 4, dcnt.as<uint32_t>());
-  }
+  if (int e = rlc_verify_dense(st, key.dev(), rkey.dev(), dproofs.as<uint8_t>(), dpws.as<uint8_t>(), pw_len, count, seed, group, flags, sc,
+                               dok.as<int32_t>(), dcnt.as<uint32_t>(), dcnt.as<uint32_t>() + 4))
+    return e;
   hipEventRecord(ev1.e, st);
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
@@ -174,7 +158,7 @@ extern "C" int spp_verify_batch_rlc(spp_ctx* ctx, const uint8_t* vk, size_t vk_l
   HIP_TRY(hipMemcpy(ok, dok.p, count * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (stats) {
     HIP_TRY(hipMemcpy(stats, dcnt.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (size_t at = 0; at < count; at += slice) stats[0] += (uint32_t)((std::min(slice, count - at) + group - 1) / group);
+    stats[0] += rlc_dense_groups(count, group);
   }
   return SPP_OK;
 }

@@ -22,11 +22,12 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
     python -m spp.cli rlwe-key-check rlwe_pk.json --shares share_1.json share_2.json [--params rlwe_params.json]
                               # are these shares the secret of this public key?  prints max |b + a*sk| and max |sk| (centred),
                               # exit 0 iff both are within the noise bound of rlwe_params.json (next to rlwe_pk.json; default 3)
-    python -m spp.cli pool-replay withdraw.vk audit.vk log.jsonl [--capacity N]
+    python -m spp.cli pool-replay withdraw.vk audit.vk log.jsonl [--capacity N] [--verifier each|rlc [--group N]]
                               # the pool program's decisions for a log of instructions, one JSON object per line, values in hex:
                               #   {"deposit": {"root"}}  {"submit_audit": {"proof", "pw"}}  {"withdraw": {"proof", "pw", "recipient"}}
                               # prints one result name per line (OK, AUDIT_EXISTS, NO_AUDIT_RECORD, BAD_ROOT, NULLIFIER_USED,
-                              # BAD_RECIPIENT, BAD_PROOF; a deposit only pushes its root and prints OK)
+                              # BAD_RECIPIENT, BAD_PROOF; a deposit only pushes its root and prints OK).  --verifier rlc checks
+                              # the proofs by random linear combination (spp_pool_set_verifier): the same lines
     python -m spp.cli execute target/<name>.json Prover.toml [-o target/<name>.gz]               # `nargo execute`: ACIR witness stack
     python -m spp.cli prove   target/<name>.json target/<name>.gz target/<name>.sppc target/<name>.pk
                               # sunspot's own argument order (acir, witness, constraint system, proving key;
@@ -233,7 +234,7 @@ def _pool_replay(a):
     capacity = a.capacity or max(1, sum(k == "submit_audit" for k, _ in log), sum(k == "withdraw" for k, _ in log))
     ctx = Context(a.device)
     try:
-        with witness.Pool(ctx, wvk, avk, capacity) as pool:
+        with witness.Pool(ctx, wvk, avk, capacity, verifier=a.verifier, group=a.group) as pool:
             # the whole log in one call, whatever the interleaving of the kinds (consecutive chunks past 2^24 instructions)
             for i in range(0, len(log), _POOL_LOG_CHUNK):
                 codes, _ = pool.settle_log([(kind,) + vals for kind, vals in log[i:i + _POOL_LOG_CHUNK]])
@@ -295,6 +296,8 @@ def main(argv=None):
     o.add_argument("--device", type=int, default=0)
     r = sub.add_parser("pool-replay"); r.add_argument("withdraw_vk"); r.add_argument("audit_vk"); r.add_argument("log", help="one instruction per line (JSON)")
     r.add_argument("--capacity", type=int, default=0, help="keys per set (default: enough for the log)")
+    r.add_argument("--verifier", choices=("each", "rlc"), default="each", help="each: one lane per proof (default); rlc: random linear combination")
+    r.add_argument("--group", type=int, default=0, help="with --verifier rlc: proofs per combined equation (a multiple of 64 in [64, 4096]; default 256)")
     r.add_argument("--device", type=int, default=0)
     k = sub.add_parser("rlwe-keygen"); k.add_argument("--out", required=True, metavar="DIR")
     k.add_argument("--threshold", type=int, default=2); k.add_argument("--shares", type=int, default=3)

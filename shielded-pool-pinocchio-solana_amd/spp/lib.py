@@ -35,6 +35,8 @@ SPP_POOL_BAD_ROOT = 3
 SPP_POOL_NULLIFIER_USED = 4
 SPP_POOL_BAD_RECIPIENT = 5
 SPP_POOL_BAD_PROOF = 6
+SPP_POOL_VERIFY_EACH = 0            # spp_pool_set_verifier: one lane per proof (the default)
+SPP_POOL_VERIFY_RLC = 1             # ... by random linear combination over the compacted list
 SPP_INSTR_DEPOSIT = 0               # kinds of spp_pool_settle_log
 SPP_INSTR_SUBMIT_AUDIT = 1
 SPP_INSTR_WITHDRAW = 2
@@ -130,6 +132,9 @@ def load_library():
     L.spp_prove_audit_records_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.spp_prove_audit_records.argtypes = [vp, vp, vp, sz, cp, vp, vp, vp, cp, vp, vp, vp, vp, vp]
     L.spp_audit_open_batch.argtypes = [vp, cp, sz, vp, sz, cp, cp, vp, vp, vp, vp]
+    L.spp_audit_open_batch_rlc.argtypes = [vp, cp, sz, vp, sz, cp, cp, vp, vp, u32, vp, vp, ctypes.POINTER(u32)]
+    L.spp_pool_set_verifier.argtypes = [vp, i32, u32]
+    L.spp_pool_verify_stats.argtypes = [vp, ctypes.POINTER(u32)]
     L.spp_pool_new.argtypes = [vp, cp, sz, cp, sz, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.spp_pool_free.argtypes = [vp]
     L.spp_pool_free.restype = None

@@ -164,9 +164,11 @@ class Context:
             return res
         return (res,) + ((tuple(stats),) if want_stats else ()) + ((ms.value,) if want_ms else ())
 
-    def audit_open(self, vk, sk_mod_q, proofs, pws, c0, c1):
+    def audit_open(self, vk, sk_mod_q, proofs, pws, c0, c1, rlc=False, group=0, want_stats=False):
         """Opens audit records in one pass on the GPU (spp_audit_open_batch): verification, ciphertext binding, decryption,
-        identity binding.  vk: bytes, or None for records already verified elsewhere (proofs may then be None); sk_mod_q: 1024
+        identity binding.  rlc: verify by random linear combination (spp_audit_open_batch_rlc; groups of `group`, 0 = 256, a fresh
+        seed from the OS) -- the same flags except with probability ~2^-127 per call; want_stats (with rlc): a third result,
+        (groups, groups refused, proofs re-verified, proofs dropped).  vk: bytes, or None for records already verified elsewhere (proofs may then be None); sk_mod_q: 1024
         ints (witness.reconstruct_sk); proofs / pws: lists of bytes (or one bytes object each); c0 [count, 64], c1 [count, 1024].
         Returns (owners, flags): owners[i] = (owner_x, owner_y) as decrypted, flags[i] = SPP_AUDIT_* bits, 0 = all three hold."""
         c0 = np.ascontiguousarray(c0, dtype=np.uint32).reshape(-1, 64)
@@ -183,9 +185,17 @@ class Context:
         owners = np.zeros((max(count, 1), 64), dtype=np.uint8)
         flags = np.zeros(max(count, 1), dtype=np.uint32)
         p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
-        check(self.L.spp_audit_open_batch(self.h, vk, len(vk) if vk is not None else 0, p(sk), count, pb, wb, p(c0), p(c1), p(owners), p(flags)))
-        return ([(int.from_bytes(owners[i, :32].tobytes(), "big"), int.from_bytes(owners[i, 32:].tobytes(), "big")) for i in range(count)],
-                [int(f) for f in flags[:count]])
+        stats = (ctypes.c_uint32 * 4)()
+        if rlc:
+            check(self.L.spp_audit_open_batch_rlc(self.h, vk, len(vk) if vk is not None else 0, p(sk), count, pb, wb, p(c0), p(c1), int(group),
+                                                  p(owners), p(flags), stats))
+        else:
+            if group or want_stats:
+                raise ValueError("audit_open: group and want_stats go with rlc=True")
+            check(self.L.spp_audit_open_batch(self.h, vk, len(vk) if vk is not None else 0, p(sk), count, pb, wb, p(c0), p(c1), p(owners), p(flags)))
+        res = ([(int.from_bytes(owners[i, :32].tobytes(), "big"), int.from_bytes(owners[i, 32:].tobytes(), "big")) for i in range(count)],
+               [int(f) for f in flags[:count]])
+        return res + (tuple(int(v) for v in stats),) if want_stats else res
 
     def msm_g1_pippenger_bench(self, n, seed=5, scale=None, iters=1, small_permille=0):
         """Returns (result bytes, ms per MSM, ms of the bucket kernel). small_permille: share of byte-sized scalars."""

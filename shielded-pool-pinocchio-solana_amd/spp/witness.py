@@ -23,7 +23,8 @@ All of them take and return Python ints / lists; field elements cross the C ABI 
 import ctypes
 import numpy as np
 from .lib import (check, NOTE_LEN, DEPOSIT_LEN, PROOF_LEN, AUDIT_PW_LEN, WITHDRAW_PW_LEN, SPP_POOL_STATE_LEN,
-                  SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS, SPP_INSTR_DEPOSIT, SPP_INSTR_SUBMIT_AUDIT, SPP_INSTR_WITHDRAW)
+                  SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS, SPP_INSTR_DEPOSIT, SPP_INSTR_SUBMIT_AUDIT, SPP_INSTR_WITHDRAW,
+                  SPP_POOL_VERIFY_EACH, SPP_POOL_VERIFY_RLC)
 
 TREE_DEPTH = 16
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -245,13 +246,38 @@ class Pool:
     taken in order.  A pre-screen for a relayer (which of these transactions would land?) and a replay tool for an auditor; the
     vault balance and lamport transfers are not modelled -- withdraw() returns the amounts for that.
     withdraw_vk / audit_vk: the two verifying keys (bytes); capacity: keys per set, fixed.  Keys (nullifiers, wa_commitments)
-    are ints or 32-byte strings; results are SPP_POOL_* codes (spp.lib.POOL_RESULT_NAMES)."""
+    are ints or 32-byte strings; results are SPP_POOL_* codes (spp.lib.POOL_RESULT_NAMES).
+    verifier: "each" (one lane per proof, the default) or "rlc" (random linear combination over the proofs the screen leaves, in
+    groups of `group`, 0 = 256; spp_pool_set_verifier): the same decisions except with probability about 2^-127 per launch."""
 
-    def __init__(self, ctx, withdraw_vk, audit_vk, capacity):
+    _VERIFIERS = {"each": SPP_POOL_VERIFY_EACH, "rlc": SPP_POOL_VERIFY_RLC}
+
+    def __init__(self, ctx, withdraw_vk, audit_vk, capacity, verifier="each", group=0):
+        if verifier not in self._VERIFIERS:
+            raise ValueError("verifier: \"each\" or \"rlc\"")
         self.ctx, self.capacity = ctx, int(capacity)
         h = ctypes.c_void_p()
         check(ctx.L.spp_pool_new(ctx.h, withdraw_vk, len(withdraw_vk), audit_vk, len(audit_vk), self.capacity, ctypes.byref(h)))
         self.h = h
+        if verifier != "each" or group:
+            try:
+                self.set_verifier(verifier, group)
+            except Exception:
+                self.close()
+                raise
+
+    def set_verifier(self, verifier, group=0):
+        """the verifier of the settling calls from now on: "each" or "rlc"; group: a multiple of 64 in [64, 4096], 0 = 256"""
+        if verifier not in self._VERIFIERS:
+            raise ValueError("verifier: \"each\" or \"rlc\"")
+        check(self.ctx.L.spp_pool_set_verifier(self.h, self._VERIFIERS[verifier], int(group)))
+
+    def verify_stats(self):
+        """(withdraw4, audit4) of the last settling call: (groups, groups refused, proofs re-verified, proofs dropped) of the
+        verifier under each key; all zero after a call with the "each" verifier"""
+        s = (ctypes.c_uint32 * 8)()
+        check(self.ctx.L.spp_pool_verify_stats(self.h, s))
+        return tuple(int(v) for v in s[:4]), tuple(int(v) for v in s[4:])
 
     def close(self):
         if getattr(self, "h", None):
