@@ -19,10 +19,12 @@
 //
 // This header holds every kernel of the walk that is a template over the coordinate field F, with its launcher.  Two translation
 // units instantiate it: kernels_msm.hip for Fq (G1), built with the scheduler strategy max-ilp -- the G1 walk was 2 % faster for
-// it (measured when it took 203 registers; 182 now, two waves per SIMD) -- and kernels_msm_g2.hip for Fq2 (G2) with the default
-// scheduler: max-ilp made the G2 walk spill and 4 % slower when it ran one wave per SIMD, and the unit's flags have not been
-// touched since (201 registers, two waves per SIMD now).  What differs between the two walks is MsmWalk<F> (kernels.hpp); the
-// host-side planning is msm_plan.hpp.
+// it (measured when it took 203 registers); its additions are written with product-scanning Montgomery products (F29_SCAN_SERIAL,
+// f29.hpp), whose serial chains that scheduler interleaves: 144 registers, three waves per SIMD -- and kernels_msm_g2.hip for Fq2
+// (G2) with the default scheduler: max-ilp made the G2 walk spill and 4 % slower when it ran one wave per SIMD; with the column
+// products it keeps (201 registers, two waves per SIMD) a headline run with the unit under max-ilp and scanning products measured
+// the same as without (profiles/README.md), so the unit's flags stay.  What differs between the two walks is MsmWalk<F>
+// (kernels.hpp); the host-side planning is msm_plan.hpp.
 #pragma once
 #include <hip/hip_ext.h>
 #include "kernels.hpp"
@@ -156,12 +158,14 @@ __device__ __forceinline__ bool words_all_zero(const Fq& v) {
   return o == 0;
 }
 // accumulator used by the table walk: G1 and G2 run on the unsaturated 9x29-bit form (f29.hpp)
-template <class F>
+// FORM (F29Form, f29.hpp): how the products of an addition are written -- MsmWalk<F>::product_form in the fast flat walk, the
+// column form everywhere else
+template <class F, int FORM = F29_COLUMNS>
 struct MsmAcc;
-template <>
-struct MsmAcc<Fq> {
-  XYZZ29<FqParams> a;
-  __device__ __forceinline__ void init() { a = XYZZ29<FqParams>::infinity(); }
+template <int FORM>
+struct MsmAcc<Fq, FORM> {
+  XYZZ29<FqParams, FORM> a;
+  __device__ __forceinline__ void init() { a = XYZZ29<FqParams, FORM>::infinity(); }
   __device__ __forceinline__ void madd(const Affine<Fq>& e, bool sgn) {
     if (words_all_zero(e.x) && words_all_zero(e.y)) return;   // table row of an infinity base (spp_msm_g1 callers)
     a.madd(e, sgn);
@@ -174,10 +178,10 @@ struct MsmAcc<Fq> {
   __device__ __forceinline__ XYZZ<Fq> result() const { return a.to_xyzz(); }
 };
 
-template <>
-struct MsmAcc<Fq2> {
-  XYZZ29G2 a;
-  __device__ __forceinline__ void init() { a = XYZZ29G2::infinity(); }
+template <int FORM>
+struct MsmAcc<Fq2, FORM> {
+  XYZZ29G2F<FORM> a;
+  __device__ __forceinline__ void init() { a = XYZZ29G2F<FORM>::infinity(); }
   __device__ __forceinline__ void madd(const Affine<Fq2>& e, bool sgn) {
     if (words_all_zero(e.x.c0) && words_all_zero(e.x.c1) && words_all_zero(e.y.c0) && words_all_zero(e.y.c1)) return;
     a.madd(e, sgn);
@@ -208,7 +212,7 @@ struct MsmAcc<Fq2> {
 //
 // One wave per workgroup (MSM_WALK_BLOCK): a 256-lane workgroup needs FOUR free wave slots of a CU at once, and with 2 slots per SIMD and waves of
 // unequal length (passes over sparse windows are shorter) a finished wave's slot waited for three more -- 1.79 resident waves per SIMD
-// on average where 2 fit.  (The second launch-bound, MsmWalk<F>::waves_per_simd, is the register budget of both kernels; the planner
+// on average where 2 fit (measured when the G1 walk was bounded to two waves).  (The second launch-bound, MsmWalk<F>::waves_per_simd, is the register budget of both kernels; the planner
 // reads the same figure.)
 template <class F>
 __device__ __forceinline__ void msm_store_redo_marker(XYZZ<F>* out) {
@@ -227,8 +231,8 @@ __device__ __forceinline__ bool msm_is_redo_marker(const XYZZ<F>* v) {
 // acc += the entries of slice sl in pass rho (dg = the digit rows of that pass for this lane's proof).  FAST: the additions are
 // madd_distinct, and the walk ends with false at the first one that is refused (acc is then no sum of anything); else the complete
 // madd, always true.
-template <class F, bool FAST>
-__device__ __forceinline__ bool msm_flat_walk(MsmAcc<F>& acc, const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
+template <class F, bool FAST, int FORM>
+__device__ __forceinline__ bool msm_flat_walk(MsmAcc<F, FORM>& acc, const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
                                               const int16_t* __restrict__ dg, uint32_t N, uint32_t Pp, uint32_t sl, uint32_t Sg) {
   if constexpr (FAST && MsmWalk<F>::gather_ahead) {
     // One-deep software pipeline: the entry of the next non-zero digit is requested BEFORE the pending addition is computed (for a
@@ -308,7 +312,7 @@ __global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_
   const uint32_t p = g % Pp, t = g / Pp;
   if (t >= R * Sg || p >= P) return;
   const uint32_t rho = t / Sg, sl = t % Sg;
-  MsmAcc<F> acc;
+  MsmAcc<F, MsmWalk<F>::product_form> acc;
   acc.init();
   if (msm_flat_walk<F, true>(acc, table, blocks, dig + ((size_t)rho * N) * Pp + p, N, Pp, sl, Sg)) partial[(size_t)t * P + p] = acc.result();
   else msm_store_redo_marker(partial + (size_t)t * P + p);
