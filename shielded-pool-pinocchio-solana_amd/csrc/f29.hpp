@@ -14,20 +14,14 @@
 //     bounds A, B of the two operands -- every call site below states its bounds; tests/test_host_cpu.py re-derives
 //     them by interval arithmetic (tests/host/f29_bounds.py) and tests/host/field_check.cpp checks the arithmetic
 //     against Fp on random and extremal inputs;
-//   * a product is written in one of the forms of F29Form below.  The column form (clear / mac / reduce) is the reference and what
-//     every user gets by default; the G1 table walk (msm_table.hpp) takes the product-scanning form, one running sum per product
+//   * a product is written in one of the two forms of F29Form below.  The column form (clear / mac / reduce) is the reference and
+//     what every user gets by default; the G1 table walk (msm_table.hpp) takes the product-scanning form, one running sum per product
 //     whose carry is the addend of the next column's first multiply-add: 144 64-bit carry adds fewer per mixed addition and 38
 //     registers fewer (k_msm_flat<Fq>: 182 -> 144 VGPRs, three waves per SIMD; profiles/f29_scan_accounting.txt).
 // Reference behaviour served: the G1/G2 multi-scalar multiplications and NTTs of `sunspot prove`
 // (noir_circuit/prove_linux.sh:83, scripts/generate_audit.py:680); the algorithm restated by oracle/c/groth16.c.
 #pragma once
 #include "bn254.hpp"
-
-#if defined(__HIPCC__)
-#define SPP_HD_COLD __host__ __device__ __attribute__((noinline))
-#else
-#define SPP_HD_COLD __attribute__((noinline))
-#endif
 
 // A register the optimiser cannot see through (device builds; nothing on the host): what keeps a running column sum in the order it
 // is written -- without it the compiler reassociates a product-scanning product back into separate column sums with carry adds.
@@ -39,15 +33,14 @@
 
 namespace spp {
 
-// How a Montgomery product is written (all forms give the same limbs; tests/host/f29_scan_check.cpp):
-//   COLUMNS     : clear / mac / reduce -- 18 column sums, every reduction step adds its carry into the next column (a 64-bit shift and
-//                 a 64-bit add per column).  The reference form, and the form of every user that has not been measured with another.
-//   SCAN_CARRY  : product scanning, one running sum per product; the carry out of a column is opaque, the terms of a column are not
-//                 (the compiler may still sum them apart and add the carry in).
-//   SCAN_SERIAL : as SCAN_CARRY with every accumulate opaque: one chain of multiply-adds per product, no carry add at all.
-//   SCAN_PAIRS  : SCAN_SERIAL, and the accumulators (XYZZ29, XYZZ29G2F) hand their independent products to the compiler two at a time,
-//                 term by term in turns, so that two dependent multiply-adds have an independent one between them.
-enum F29Form : int { F29_COLUMNS = 0, F29_SCAN_CARRY = 1, F29_SCAN_SERIAL = 2, F29_SCAN_PAIRS = 3 };
+// How a Montgomery product is written (both forms give the same limbs; tests/host/f29_scan_check.cpp):
+//   COLUMNS : clear / mac / reduce -- 18 column sums, every reduction step adds its carry into the next column (a 64-bit shift and a
+//             64-bit add per column).  The reference form, and the form of every user that has not been measured with another.
+//   SCAN    : product scanning, one running sum per product with every accumulate opaque: one chain of multiply-adds per product, no
+//             carry add at all.
+// The forms that lost (only the carry opaque; two products in lockstep) are at commit f5e9f1a, with their numbers in
+// profiles/f29_madd_chain.txt.
+enum F29Form : int { F29_COLUMNS = 0, F29_SCAN = 1 };
 
 template <class Pm>
 struct F29 {
@@ -150,16 +143,15 @@ struct F29 {
   // One running 64-bit sum per product: column k takes its a_i * b_(k-i), then its m_i * p_(k-i), then (k < 9) m_k and m_k * p_0;
   // shifted down 29 bits it is the carry into column k + 1 -- the addend of that column's first multiply-add, where reduce() spends a
   // shift and an add.  Every column total is the integer reduce() reaches in c[k], so the limbs are the same and the bound on a
-  // column (partial sums of unsigned terms never exceed the total) is the one tests/host/f29_bounds.py certifies.
-  // SERIAL: every accumulate is opaque (SCAN_SERIAL / SCAN_PAIRS), else only the carry (SCAN_CARRY).
-  template <bool SERIAL>
+  // column (partial sums of unsigned terms never exceed the total) is the one tests/host/f29_bounds.py certifies.  Every accumulate
+  // is opaque.
   struct Scan {
     uint64_t acc = 0;
     uint32_t m[9];
     F29 r;
     SPP_HD void fma(uint32_t x, uint32_t y) {
       acc += (uint64_t)x * y;
-      if constexpr (SERIAL) SPP_OPAQUE(acc);
+      SPP_OPAQUE(acc);
     }
     SPP_HD void ab(int k, int i, const F29& a, const F29& b) {
       const int j = k - i;
@@ -187,9 +179,9 @@ struct F29 {
     }
   };
   // sum of NP products, one reduction (limb bounds as for mac + reduce: 9 * sum A_t * B_t + 9 * 2^58 < 2^64)
-  template <bool SERIAL, int NP>
+  template <int NP>
   static SPP_HD F29 dot_scan(const F29* const (&a)[NP], const F29* const (&b)[NP]) {
-    Scan<SERIAL> s;
+    Scan s;
     SPP_UNROLL for (int k = 0; k < 17; k++) {
       SPP_UNROLL for (int t = 0; t < NP; t++) {
         SPP_UNROLL for (int i = 0; i < 9; i++) s.ab(k, i, *a[t], *b[t]);
@@ -199,11 +191,10 @@ struct F29 {
     }
     return s.r;
   }
-  template <bool SERIAL>
   SPP_HD F29 sqr_scan() const {
     uint32_t d[9];
     SPP_UNROLL for (int i = 0; i < 9; i++) d[i] = l[i] << 1;
-    Scan<SERIAL> s;
+    Scan s;
     SPP_UNROLL for (int k = 0; k < 17; k++) {
       SPP_UNROLL for (int i = 0; i < 9; i++) s.sq(k, i, *this, d);
       SPP_UNROLL for (int i = 0; i < 9; i++) s.mp(k, i);
@@ -211,91 +202,29 @@ struct F29 {
     }
     return s.r;
   }
-  // Two independent sums of products in lockstep: their terms alternate in the text, so the two serial chains fill each other's
-  // issue gaps whatever the scheduler does.  The results are written last (r0 / r1 may be operands).
-  template <int NP0, int NP1>
-  static SPP_HD void dot_scan_pair(F29& r0, const F29* const (&a0)[NP0], const F29* const (&b0)[NP0], F29& r1, const F29* const (&a1)[NP1],
-                                   const F29* const (&b1)[NP1]) {
-    Scan<true> s0, s1;
-    SPP_UNROLL for (int k = 0; k < 17; k++) {
-      SPP_UNROLL for (int t = 0; t < (NP0 > NP1 ? NP0 : NP1); t++) {
-        SPP_UNROLL for (int i = 0; i < 9; i++) {
-          if (t < NP0) s0.ab(k, i, *a0[t < NP0 ? t : 0], *b0[t < NP0 ? t : 0]);
-          if (t < NP1) s1.ab(k, i, *a1[t < NP1 ? t : 0], *b1[t < NP1 ? t : 0]);
-        }
-      }
-      SPP_UNROLL for (int i = 0; i < 9; i++) {
-        s0.mp(k, i);
-        s1.mp(k, i);
-      }
-      s0.end(k);
-      s1.end(k);
-    }
-    r0 = s0.r;
-    r1 = s1.r;
-  }
-  static SPP_HD void sqr_scan_pair(F29& r0, const F29& a0, F29& r1, const F29& a1) {
-    uint32_t d0[9], d1[9];
-    SPP_UNROLL for (int i = 0; i < 9; i++) {
-      d0[i] = a0.l[i] << 1;
-      d1[i] = a1.l[i] << 1;
-    }
-    Scan<true> s0, s1;
-    SPP_UNROLL for (int k = 0; k < 17; k++) {
-      SPP_UNROLL for (int i = 0; i < 9; i++) {
-        s0.sq(k, i, a0, d0);
-        s1.sq(k, i, a1, d1);
-      }
-      SPP_UNROLL for (int i = 0; i < 9; i++) {
-        s0.mp(k, i);
-        s1.mp(k, i);
-      }
-      s0.end(k);
-      s1.end(k);
-    }
-    r0 = s0.r;
-    r1 = s1.r;
-  }
-  static SPP_HD void mul_scan_pair(F29& r0, const F29& a0, const F29& b0, F29& r1, const F29& a1, const F29& b1) {
-    const F29* const x0[1] = {&a0};
-    const F29* const y0[1] = {&b0};
-    const F29* const x1[1] = {&a1};
-    const F29* const y1[1] = {&b1};
-    dot_scan_pair<1, 1>(r0, x0, y0, r1, x1, y1);
-  }
-  // the products by form (F29Form): what the accumulators below call
-  template <int FORM>
-  static SPP_HD F29 mul_as(const F29& a, const F29& b) {
-    if constexpr (FORM == F29_COLUMNS) return a * b;
-    else {
-      const F29* const x[1] = {&a};
-      const F29* const y[1] = {&b};
-      return dot_scan<(FORM >= F29_SCAN_SERIAL), 1>(x, y);
-    }
+  // the products by form (F29Form): what the accumulators below call.  dot_as and sqr_as are the only places that branch on the form.
+  // sum of NP products, one reduction
+  template <int FORM, int NP>
+  static SPP_HD F29 dot_as(const F29* const (&a)[NP], const F29* const (&b)[NP]) {
+    if constexpr (FORM == F29_COLUMNS) {
+      uint64_t c[18];
+      clear(c);
+      SPP_UNROLL for (int t = 0; t < NP; t++) mac(c, *a[t], *b[t]);
+      return reduce(c);
+    } else return dot_scan<NP>(a, b);
   }
   template <int FORM>
   SPP_HD F29 sqr_as() const {
     if constexpr (FORM == F29_COLUMNS) return sqr();
-    else return sqr_scan<(FORM >= F29_SCAN_SERIAL)>();
+    else return sqr_scan();
+  }
+  template <int FORM>
+  static SPP_HD F29 mul_as(const F29& a, const F29& b) {
+    return dot_as<FORM, 1>({&a}, {&b});
   }
   template <int FORM>
   static SPP_HD F29 mul2_as(const F29& a, const F29& b, const F29& cc, const F29& d) {
-    if constexpr (FORM == F29_COLUMNS) return mul2(a, b, cc, d);
-    else {
-      const F29* const x[2] = {&a, &cc};
-      const F29* const y[2] = {&b, &d};
-      return dot_scan<(FORM >= F29_SCAN_SERIAL), 2>(x, y);
-    }
-  }
-  // a0*b0 + a1*b1 + a2*b2 + a3*b3 with one reduction (the Y components of XYZZ29G2F::madd_any)
-  template <int FORM>
-  static SPP_HD F29 mul4_as(const F29* const (&a)[4], const F29* const (&b)[4]) {
-    if constexpr (FORM == F29_COLUMNS) {
-      uint64_t c[18];
-      clear(c);
-      SPP_UNROLL for (int t = 0; t < 4; t++) mac(c, *a[t], *b[t]);
-      return reduce(c);
-    } else return dot_scan<(FORM >= F29_SCAN_SERIAL), 4>(a, b);
+    return dot_as<FORM, 2>({&a, &cc}, {&b, &d});
   }
 
   // ---- additive operations (C = lifted multiple of p; see gen_consts.py `lifted`) ---------------------
@@ -449,33 +378,6 @@ struct XYZZ29 {
       inf = false;
       return true;
     }
-    if constexpr (FORM == F29_SCAN_PAIRS) {
-      // the statements of the other forms, with the independent products taken two at a time: (U2, S2), (PP, R2), (Q, PPP),
-      // (ZZZ * PPP, Y); ZZ * PP goes alone
-      F U2, S2;
-      F::mul_scan_pair(U2, x2, ZZ, S2, y2, ZZZ);                          // 1 x 1, 2 x 1
-      const F Pp = F::template sub_norm<Pm::SUBC_6P_1>(U2, X);
-      const F Rr = F::template sub_norm<Pm::SUBC_2P_1>(S2, Y);
-      if (Pp.template is_zero_mod_p<7>()) {
-        if constexpr (DISTINCT) return false;
-        same_x(Rr);
-        return true;
-      }
-      F PP, R2;
-      F::sqr_scan_pair(PP, Pp, R2, Rr);
-      F Q, PPP;
-      F::mul_scan_pair(Q, X, PP, PPP, Pp, PP);
-      ZZ = F::template mul_as<FORM>(ZZ, PP);
-      X = F::template sub3_norm<Pm::SUBC_4P_3>(R2, PPP, Q);
-      const F T = F::template sub_lazy<Pm::SUBC_6P_1>(Q, X);
-      const F Yn = F::template neg_lazy<Pm::SUBC_2P_1>(Y);
-      const F* const za[1] = {&ZZZ};
-      const F* const zb[1] = {&PPP};
-      const F* const ya[2] = {&Rr, &Yn};
-      const F* const yb[2] = {&T, &PPP};
-      F::template dot_scan_pair<1, 2>(ZZZ, za, zb, Y, ya, yb);            // 1 x 1; 1x3 + 2x1
-      return true;
-    }
     // statement order keeps few values alive at once (x2 dies first, then U2, P, PP, ...)
     const F U2 = F::template mul_as<FORM>(x2, ZZ);                       // 1 x 1
     const F Pp = F::template sub_norm<Pm::SUBC_6P_1>(U2, X);             // normalised, < 7.1 p
@@ -533,15 +435,7 @@ struct F29x2 {
   template <F::ConstFn CA, int FORM = F29_COLUMNS>
   static SPP_HD F29x2 mul(const F29x2& a, const F29x2& b) {
     const F na1 = F::template neg_lazy<CA>(a.c1);
-    if constexpr (FORM == F29_SCAN_PAIRS) {
-      const F* const xa[2] = {&a.c0, &na1};
-      const F* const xb[2] = {&b.c0, &b.c1};
-      const F* const ya[2] = {&a.c0, &a.c1};
-      const F* const yb[2] = {&b.c1, &b.c0};
-      F29x2 r;
-      F::template dot_scan_pair<2, 2>(r.c0, xa, xb, r.c1, ya, yb);
-      return r;
-    } else return {F::template mul2_as<FORM>(a.c0, b.c0, na1, b.c1), F::template mul2_as<FORM>(a.c0, b.c1, a.c1, b.c0)};
+    return {F::template mul2_as<FORM>(a.c0, b.c0, na1, b.c1), F::template mul2_as<FORM>(a.c0, b.c1, a.c1, b.c0)};
   }
   // by a real constant (components scale independently)
   SPP_HD F29x2 mul_real(const F& k) const { return {c0 * k, c1 * k}; }
@@ -551,11 +445,7 @@ struct F29x2 {
     const F s = add_lazy(c0, c1);
     const F d = F::template sub_lazy<CA>(c0, c1);
     const F t = add_lazy(c0, c0);
-    if constexpr (FORM == F29_SCAN_PAIRS) {
-      F29x2 r;
-      F::mul_scan_pair(r.c0, s, d, r.c1, t, c1);
-      return r;
-    } else return {F::template mul_as<FORM>(s, d), F::template mul_as<FORM>(t, c1)};
+    return {F::template mul_as<FORM>(s, d), F::template mul_as<FORM>(t, c1)};
   }
   template <F::ConstFn C>
   static SPP_HD F29x2 sub_norm(const F29x2& a, const F29x2& b) {
@@ -580,8 +470,8 @@ struct F29x2 {
 
 // G2 accumulator: same formulas and domains as XYZZ29 (X, Y in the R' domain, ZZ/ZZZ scaled by R'^2/R).
 // Value bounds per component: X < 5.6 p, Y < 1.5 p, ZZ/ZZZ < 1.3 p (certificate: check_madd_g2).
-// FORM (F29Form): as for XYZZ29.  XYZZ29G2 is the column form, which is also what the G2 walk runs: at two waves per SIMD no
-// scanning form was faster on the chain of additions (profiles/f29_madd_chain.txt), and F29_SCAN_PAIRS spills there.
+// FORM (F29Form): as for XYZZ29.  XYZZ29G2 is the column form, which is also what the G2 walk runs: at two waves per SIMD the
+// scanning form was not faster on the chain of additions (profiles/f29_madd_chain.txt).
 template <int FORM>
 struct XYZZ29G2F {
   using E = F29x2;
@@ -676,13 +566,9 @@ struct XYZZ29G2F {
     const F* const b0[4] = {&T.c0, &T.c1, &PPP.c0, &PPP.c1};
     const F* const a1[4] = {&Rr.c0, &Rr.c1, &nY0, &nY1};
     const F* const b1[4] = {&T.c1, &T.c0, &PPP.c1, &PPP.c0};
-    if constexpr (FORM == F29_SCAN_PAIRS) {
-      F::template dot_scan_pair<4, 4>(Y.c0, a0, b0, Y.c1, a1, b1);
-    } else {
-      const F y0 = F::template mul4_as<FORM>(a0, b0);
-      Y.c1 = F::template mul4_as<FORM>(a1, b1);
-      Y.c0 = y0;
-    }
+    const F y0 = F::template dot_as<FORM, 4>(a0, b0);
+    Y.c1 = F::template dot_as<FORM, 4>(a1, b1);
+    Y.c0 = y0;
     return true;
   }
 };

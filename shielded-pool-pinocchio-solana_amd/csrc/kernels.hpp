@@ -240,7 +240,7 @@ void launch_qap_product(hipStream_t st, Fr* abc, uint32_t n, uint32_t P);   // a
 // (W = ceil(254 / c) windows per scalar).  Wt = W: one row per window, no passes (the small-table latency layout).  Wt = 1: one row
 // per base and W passes whose sums are combined by Horner (the throughput layout: widest window for the bytes).
 // What tells the G1 walk from the G2 walk, in one place: k_msm_flat and k_msm_flat_redo take their launch bound and the fast walk
-// its loop form from here, and the host passes occ(Wt) to msm_plan / msm_partial_cap, so the planner counts the waves the kernel it
+// its product form from here, and the host passes occ(Wt) to msm_plan / msm_partial_cap, so the planner counts the waves the kernel it
 // plans for can have resident.  The flat walk keeps the same-x case of the mixed addition out of its loop (msm_table.hpp), which
 // is what its register counts rest on; k_msm_rows adds with the inline path and keeps the occupancy it had.  product_form: how the
 // fast walk writes the nine Montgomery products of an addition (F29Form, f29.hpp), chosen by tests/micro/f29_madd_chain.hip and the
@@ -251,16 +251,14 @@ template <>
 struct MsmWalk<Fq> {
   static constexpr uint32_t waves_per_simd = 3;         // flat walk: at most 168 VGPRs (it takes 144; the redo kernel 168 and 128 B of scratch)
   static constexpr uint32_t rows_waves_per_simd = 2;    // k_msm_rows
-  static constexpr bool gather_ahead = false;           // the other resident wave hides a gather
-  static constexpr int product_form = F29_SCAN_SERIAL;  // F29Form of the fast flat walk's additions (the redo kernel and k_msm_rows: F29_COLUMNS)
+  static constexpr int product_form = F29_SCAN;         // F29Form of the fast flat walk's additions (the redo kernel and k_msm_rows: F29_COLUMNS)
   static constexpr uint32_t occ(uint32_t Wt) { return Wt == 1 ? waves_per_simd : rows_waves_per_simd; }
 };
 template <>
 struct MsmWalk<Fq2> {
   static constexpr uint32_t waves_per_simd = 2;         // flat walk: at most 256 VGPRs, no AGPRs
   static constexpr uint32_t rows_waves_per_simd = 1;    // k_msm_rows: up to 512 registers
-  static constexpr bool gather_ahead = false;           // as for G1
-  static constexpr int product_form = F29_COLUMNS;      // G2: no scanning form beat the column form at two waves (profiles/f29_madd_chain.txt)
+  static constexpr int product_form = F29_COLUMNS;      // G2: the scanning form did not beat the column form at two waves (profiles/f29_madd_chain.txt)
   static constexpr uint32_t occ(uint32_t Wt) { return Wt == 1 ? waves_per_simd : rows_waves_per_simd; }
 };
 // builds rows [row0, row0 + nrows) (row = base * Wt + m; row0 a multiple of 64) of the table of N bases, E entries each;

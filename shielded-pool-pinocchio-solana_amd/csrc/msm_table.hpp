@@ -19,7 +19,7 @@
 //
 // This header holds every kernel of the walk that is a template over the coordinate field F, with its launcher.  Two translation
 // units instantiate it: kernels_msm.hip for Fq (G1), built with the scheduler strategy max-ilp -- the G1 walk was 2 % faster for
-// it (measured when it took 203 registers); its additions are written with product-scanning Montgomery products (F29_SCAN_SERIAL,
+// it (measured when it took 203 registers); its additions are written with product-scanning Montgomery products (F29_SCAN,
 // f29.hpp), whose serial chains that scheduler interleaves: 144 registers, three waves per SIMD -- and kernels_msm_g2.hip for Fq2
 // (G2) with the default scheduler: max-ilp made the G2 walk spill and 4 % slower when it ran one wave per SIMD; with the column
 // products it keeps (201 registers, two waves per SIMD) a headline run with the unit under max-ilp and scanning products measured
@@ -210,10 +210,10 @@ struct MsmAcc<Fq2, FORM> {
 // F::one() in X, and a finite sum has ZZ != 0 mod p, hence a non-zero word in ZZ (to_xyzz stores residues, zero words only for the
 // residue 0).  The marker test reads X and ZZ.
 //
-// One wave per workgroup (MSM_WALK_BLOCK): a 256-lane workgroup needs FOUR free wave slots of a CU at once, and with 2 slots per SIMD and waves of
-// unequal length (passes over sparse windows are shorter) a finished wave's slot waited for three more -- 1.79 resident waves per SIMD
-// on average where 2 fit (measured when the G1 walk was bounded to two waves).  (The second launch-bound, MsmWalk<F>::waves_per_simd, is the register budget of both kernels; the planner
-// reads the same figure.)
+// One wave per workgroup (MSM_WALK_BLOCK): a 256-lane workgroup needs FOUR free wave slots of a CU at once, and with 2 slots per SIMD
+// and waves of unequal length (passes over sparse windows are shorter) a finished wave's slot waited for three more -- 1.79 resident
+// waves per SIMD on average where 2 fit (measured when the G1 walk was bounded to two waves).
+// The second launch bound, MsmWalk<F>::waves_per_simd, is the register budget of both kernels; the planner reads the same figure.
 template <class F>
 __device__ __forceinline__ void msm_store_redo_marker(XYZZ<F>* out) {
   static_assert(sizeof(XYZZ<F>) % 16 == 0, "stored as 16-byte words");
@@ -234,69 +234,32 @@ __device__ __forceinline__ bool msm_is_redo_marker(const XYZZ<F>* v) {
 template <class F, bool FAST, int FORM>
 __device__ __forceinline__ bool msm_flat_walk(MsmAcc<F, FORM>& acc, const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
                                               const int16_t* __restrict__ dg, uint32_t N, uint32_t Pp, uint32_t sl, uint32_t Sg) {
-  if constexpr (FAST && MsmWalk<F>::gather_ahead) {
-    // One-deep software pipeline: the entry of the next non-zero digit is requested BEFORE the pending addition is computed (for a
-    // walk whose SIMD has nothing else to run while a gather is in flight).  A last pass over the loop body (flush) retires the
-    // pending addition, so that the mixed addition is instantiated once.
-    int d_next = 0;
-    Affine<F> e_next;
-    for (uint32_t i0 = sl;; i0 += 4 * Sg) {
-      const bool last = i0 >= N;
-      uint64_t pack = 0;
-      if (!last) {
-        SPP_UNROLL for (uint32_t k = 0; k < 4; k++) {
-          const uint32_t i = i0 + k * Sg;
-          const uint32_t d = i < N ? (uint32_t)(uint16_t)dg[(size_t)i * Pp] : 0u;
-          pack |= (uint64_t)d << (16 * k);
-        }
-      }
+  for (uint32_t i0 = sl; i0 < N; i0 += 4 * Sg) {
+    uint64_t pack = 0;
+    SPP_UNROLL for (uint32_t k = 0; k < 4; k++) {
+      const uint32_t i = i0 + k * Sg;
+      const uint32_t d = i < N ? (uint32_t)(uint16_t)dg[(size_t)i * Pp] : 0u;
+      pack |= (uint64_t)d << (16 * k);
+    }
+    if (pack == 0) continue;
 #pragma unroll 1
-      for (uint32_t k = 0; k < 4; k++) {
-        int d = (int)(int16_t)(uint16_t)(pack >> (16 * k));
-        const bool flush = last && k == 0;
+    for (uint32_t k = 0; k < 4; k++) {
+      const int d = (int)(int16_t)(uint16_t)(pack >> (16 * k));
+      if (d != 0) {
+        // The block of base i: where its rows start and how many entries they hold (the base index is the same for the whole
+        // wave once a wave holds one slice, so this is one 16-byte line for all lanes).  A digit above the block's entry count
+        // is skipped: the range class of a narrow block's wires (msm_classes.hpp) makes it impossible for a row that satisfies
+        // its lookup constraints, and a row that does not is refused through its status word whatever is summed here -- the
+        // compare keeps the gather inside the table.
         const uint32_t i = i0 + k * Sg;
         const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-        MsmBlock blk{};
-        if (d != 0) blk = blocks[i >> 6];
-        if (mag > blk.E) d = 0;   // see the loop below
-        if (d != 0 || flush) {
-          Affine<F> e;
-          if (d != 0) e = table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)];
-          if (d_next != 0 && !acc.madd_distinct(e_next, d_next < 0)) return false;
-          d_next = d;
-          if (d != 0) e_next = e;
-        }
-      }
-      if (last) break;
-    }
-  } else {
-    for (uint32_t i0 = sl; i0 < N; i0 += 4 * Sg) {
-      uint64_t pack = 0;
-      SPP_UNROLL for (uint32_t k = 0; k < 4; k++) {
-        const uint32_t i = i0 + k * Sg;
-        const uint32_t d = i < N ? (uint32_t)(uint16_t)dg[(size_t)i * Pp] : 0u;
-        pack |= (uint64_t)d << (16 * k);
-      }
-      if (pack == 0) continue;
-#pragma unroll 1
-      for (uint32_t k = 0; k < 4; k++) {
-        const int d = (int)(int16_t)(uint16_t)(pack >> (16 * k));
-        if (d != 0) {
-          // The block of base i: where its rows start and how many entries they hold (the base index is the same for the whole
-          // wave once a wave holds one slice, so this is one 16-byte line for all lanes).  A digit above the block's entry count
-          // is skipped: the range class of a narrow block's wires (msm_classes.hpp) makes it impossible for a row that satisfies
-          // its lookup constraints, and a row that does not is refused through its status word whatever is summed here -- the
-          // compare keeps the gather inside the table.
-          const uint32_t i = i0 + k * Sg;
-          const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-          const MsmBlock blk = blocks[i >> 6];
-          if (mag <= blk.E) {
-            const Affine<F> e = table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)];
-            if constexpr (FAST) {
-              if (!acc.madd_distinct(e, d < 0)) return false;
-            } else {
-              acc.madd(e, d < 0);
-            }
+        const MsmBlock blk = blocks[i >> 6];
+        if (mag <= blk.E) {
+          const Affine<F> e = table[((size_t)blk.off + (mag - 1)) * 64 + (i & 63)];
+          if constexpr (FAST) {
+            if (!acc.madd_distinct(e, d < 0)) return false;
+          } else {
+            acc.madd(e, d < 0);
           }
         }
       }
@@ -318,10 +281,10 @@ __global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_
   else msm_store_redo_marker(partial + (size_t)t * P + p);
 }
 // Behind every k_msm_flat, same grid and arguments: a lane whose slice sum is the redo marker sums its slice again with the complete
-// addition (the loop without the gather pipeline); every other lane returns at once.  Bounded to the registers of the fast walk
-// it follows (it may use scratch: it is cold) -- with more it would wait for a whole SIMD to drain behind the MSM waves of the other
-// batch in flight.  When every lane is marked (one base repeated) this is the walk with the inline same-x path.  redo_count
-// (optional): the number of lanes that walked again.
+// addition; every other lane returns at once.  Bounded to the registers of the fast walk it follows (it may use scratch: it is
+// cold) -- with more it would wait for a whole SIMD to drain behind the MSM waves of the other batch in flight.  When every lane is
+// marked (one base repeated) this is the walk with the inline same-x path.  redo_count (optional): the number of lanes that walked
+// again.
 template <class F>
 __global__ void __launch_bounds__(MSM_WALK_BLOCK, MsmWalk<F>::waves_per_simd) k_msm_flat_redo(const Affine<F>* __restrict__ table, const MsmBlock* __restrict__ blocks,
                                                   const int16_t* __restrict__ dig, XYZZ<F>* __restrict__ partial, uint32_t N, uint32_t P,

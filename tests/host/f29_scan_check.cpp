@@ -1,10 +1,9 @@
 // Test-only host build of csrc/f29.hpp: the product-scanning Montgomery products against clear / mac / mac_sqr / reduce, limb for
 // limb, and the one-multiplication filter of is_zero_mod_p against the comparison it replaced.
-//   - dot_scan<SERIAL, NP> for NP = 1, 2, 4, sqr_scan, the lockstep pairs (dot_scan_pair, sqr_scan_pair, mul_scan_pair) and the
-//     *_as<FORM> entry points, for both parameter sets (Fr, Fq): random limbs under the limb bounds the call sites state, and every
-//     limb AT its bound -- 1 x 1 (operator*), 2 x 1 (y2 * ZZZ), 1x3 + 2x1 (the Y of XYZZ29), 1x1 + 2x1 (F29x2::mul), 2 x 3 and 2 x 1
+//   - dot_scan<NP> for NP = 1, 2, 4, sqr_scan and the *_as<FORM> entry points (mul_as, mul2_as, dot_as<., 4>, sqr_as) in both
+//     forms, for both parameter sets (Fr, Fq): random limbs under the limb bounds the call sites state, and every limb AT its bound -- 1 x 1 (operator*), 2 x 1 (y2 * ZZZ), 1x3 + 2x1 (the Y of XYZZ29), 1x1 + 2x1 (F29x2::mul), 2 x 3 and 2 x 1
 //     (F29x2::sqr), 1x1 + 2x1 + 2x1 + 1x1 (the Y components of XYZZ29G2F), squares of limbs < 1 and < 2 (units of 2^29);
-//   - XYZZ29<Pm, FORM> and XYZZ29G2F<FORM>, FORM = 1, 2, 3: chains of madd_distinct / madd leave the limbs of FORM = 0;
+//   - XYZZ29<Pm, FORM> and XYZZ29G2F<FORM>, FORM = 1 (F29_SCAN): chains of madd_distinct / madd leave the limbs of FORM = 0;
 //   - is_zero_mod_p<KMAX>, KMAX = 3, 4, 7: 0, p, .., (KMAX + 2) p, each with its low limb, a middle limb and the top limb moved by
 //     one either way, and random values.
 // Prints "OK <n checks>" or "FAIL ...".
@@ -39,62 +38,33 @@ template <class Pm> static F29<Pm> limbs(uint32_t bound, int mode) {
 
 template <class Pm, int NP> static void dot_case(const uint32_t (&ba)[NP], const uint32_t (&bb)[NP], int mode, const char* what) {
   using F = F29<Pm>;
-  F a[NP], b[NP], a2[NP], b2[NP];
-  const F *pa[NP], *pb[NP], *pa2[NP], *pb2[NP];
+  F a[NP], b[NP];
+  const F *pa[NP], *pb[NP];
   for (int t = 0; t < NP; t++) {
     a[t] = limbs<Pm>(ba[t], mode);
     b[t] = limbs<Pm>(bb[t], mode);
-    a2[t] = limbs<Pm>(bb[t], mode == 1 ? 1 : 0);
-    b2[t] = limbs<Pm>(ba[t], mode == 1 ? 1 : 0);
-    pa[t] = &a[t]; pb[t] = &b[t]; pa2[t] = &a2[t]; pb2[t] = &b2[t];
+    pa[t] = &a[t]; pb[t] = &b[t];
   }
   uint64_t c[18];
   F::clear(c);
   for (int t = 0; t < NP; t++) F::mac(c, a[t], b[t]);
   const F ref = F::reduce(c);
-  F::clear(c);
-  for (int t = 0; t < NP; t++) F::mac(c, a2[t], b2[t]);
-  const F ref2 = F::reduce(c);
   typedef const F* const (&Ptrs)[NP];
-  Ptrs ra = reinterpret_cast<Ptrs>(pa), rb = reinterpret_cast<Ptrs>(pb), ra2 = reinterpret_cast<Ptrs>(pa2), rb2 = reinterpret_cast<Ptrs>(pb2);
-  CHECK(same(F::template dot_scan<false, NP>(ra, rb), ref), "%s: dot_scan<false, %d>", what, NP);
-  CHECK(same(F::template dot_scan<true, NP>(ra, rb), ref), "%s: dot_scan<true, %d>", what, NP);
-  F r0, r1;
-  F::template dot_scan_pair<NP, NP>(r0, ra, rb, r1, ra2, rb2);
-  CHECK(same(r0, ref) && same(r1, ref2), "%s: dot_scan_pair<%d, %d>", what, NP, NP);
-  // unequal lengths: the first product of the second sum alone beside the whole first sum, and the other way round
-  const F* const one_a[1] = {pa2[0]};
-  const F* const one_b[1] = {pb2[0]};
-  F::clear(c);
-  F::mac(c, a2[0], b2[0]);
-  const F ref1 = F::reduce(c);
-  F::template dot_scan_pair<NP, 1>(r0, ra, rb, r1, one_a, one_b);
-  CHECK(same(r0, ref) && same(r1, ref1), "%s: dot_scan_pair<%d, 1>", what, NP);
-  F::template dot_scan_pair<1, NP>(r1, one_a, one_b, r0, ra, rb);
-  CHECK(same(r0, ref) && same(r1, ref1), "%s: dot_scan_pair<1, %d>", what, NP);
+  Ptrs ra = reinterpret_cast<Ptrs>(pa), rb = reinterpret_cast<Ptrs>(pb);
+  CHECK(same(F::template dot_scan<NP>(ra, rb), ref), "%s: dot_scan<%d>", what, NP);
+  CHECK(same(F::template dot_as<0, NP>(ra, rb), ref) && same(F::template dot_as<1, NP>(ra, rb), ref), "%s: dot_as<., %d>", what, NP);
   if constexpr (NP == 1) {
     CHECK(same(a[0] * b[0], ref), "%s: operator*", what);
-    CHECK(same(F::template mul_as<0>(a[0], b[0]), ref) && same(F::template mul_as<1>(a[0], b[0]), ref) && same(F::template mul_as<2>(a[0], b[0]), ref) &&
-              same(F::template mul_as<3>(a[0], b[0]), ref), "%s: mul_as", what);
-    F::mul_scan_pair(r0, a[0], b[0], r1, a2[0], b2[0]);
-    CHECK(same(r0, ref) && same(r1, ref2), "%s: mul_scan_pair", what);
-    F x = a[0];                               // a result may be an operand
-    F::mul_scan_pair(x, x, b[0], r1, x, b[0]);
-    CHECK(same(x, ref) && same(r1, ref), "%s: mul_scan_pair in place", what);
+    CHECK(same(F::template mul_as<0>(a[0], b[0]), ref) && same(F::template mul_as<1>(a[0], b[0]), ref), "%s: mul_as", what);
   }
   if constexpr (NP == 2) {
     CHECK(same(F::mul2(a[0], b[0], a[1], b[1]), ref), "%s: mul2", what);
-    CHECK(same(F::template mul2_as<0>(a[0], b[0], a[1], b[1]), ref) && same(F::template mul2_as<1>(a[0], b[0], a[1], b[1]), ref) &&
-              same(F::template mul2_as<2>(a[0], b[0], a[1], b[1]), ref) && same(F::template mul2_as<3>(a[0], b[0], a[1], b[1]), ref), "%s: mul2_as", what);
-  }
-  if constexpr (NP == 4) {
-    CHECK(same(F::template mul4_as<0>(ra, rb), ref) && same(F::template mul4_as<1>(ra, rb), ref) && same(F::template mul4_as<2>(ra, rb), ref) &&
-              same(F::template mul4_as<3>(ra, rb), ref), "%s: mul4_as", what);
+    CHECK(same(F::template mul2_as<0>(a[0], b[0], a[1], b[1]), ref) && same(F::template mul2_as<1>(a[0], b[0], a[1], b[1]), ref), "%s: mul2_as", what);
   }
 }
 template <class Pm> static void sqr_case(uint32_t bound, int mode) {
   using F = F29<Pm>;
-  const F a = limbs<Pm>(bound, mode), b = limbs<Pm>(bound, mode == 1 ? 1 : 0);
+  const F a = limbs<Pm>(bound, mode);
   uint64_t c[18];
   F::clear(c);
   F::mac_sqr(c, a);
@@ -102,12 +72,9 @@ template <class Pm> static void sqr_case(uint32_t bound, int mode) {
   F::clear(c);
   F::mac(c, a, a);
   CHECK(same(F::reduce(c), ref), "mac_sqr against mac");
-  CHECK(same(a.template sqr_scan<false>(), ref) && same(a.template sqr_scan<true>(), ref), "sqr_scan, bound %u", bound);
-  CHECK(same(a.template sqr_as<0>(), ref) && same(a.template sqr_as<1>(), ref) && same(a.template sqr_as<2>(), ref) && same(a.template sqr_as<3>(), ref),
-        "sqr_as, bound %u", bound);
-  F r0, r1;
-  F::sqr_scan_pair(r0, a, r1, b);
-  CHECK(same(r0, ref) && same(r1, b.sqr()), "sqr_scan_pair, bound %u", bound);
+  CHECK(same(a.sqr_scan(), ref), "sqr_scan, bound %u", bound);
+  CHECK(same(a.sqr(), ref), "sqr, bound %u", bound);
+  CHECK(same(a.template sqr_as<0>(), ref) && same(a.template sqr_as<1>(), ref), "sqr_as, bound %u", bound);
 }
 template <class Pm> static void products(const char* name) {
   static const uint32_t b1[1] = {1}, b2[1] = {2}, b3[1] = {3};
@@ -149,18 +116,16 @@ template <class Pm> static void g1_chains(const char* name) {
   for (int trial = 0; trial < 20; trial++) {
     XYZZ29<Pm, 0> a0 = XYZZ29<Pm, 0>::infinity();
     XYZZ29<Pm, 1> a1 = XYZZ29<Pm, 1>::infinity();
-    XYZZ29<Pm, 2> a2 = XYZZ29<Pm, 2>::infinity();
-    XYZZ29<Pm, 3> a3 = XYZZ29<Pm, 3>::infinity();
     for (int s = 0; s < 30; s++) {
       const Affine<Fw> e{words_below_p<Fw>(), words_below_p<Fw>()};
       const bool neg = rnd32() & 1, distinct = rnd32() & 1;
       if (distinct) {
-        const bool d0 = a0.madd_distinct(e, neg), d1 = a1.madd_distinct(e, neg), d2 = a2.madd_distinct(e, neg), d3 = a3.madd_distinct(e, neg);
-        CHECK(d0 && d1 && d2 && d3, "%s: madd_distinct refused a random entry", name);
+        const bool d0 = a0.madd_distinct(e, neg), d1 = a1.madd_distinct(e, neg);
+        CHECK(d0 && d1, "%s: madd_distinct refused a random entry", name);
       } else {
-        a0.madd(e, neg); a1.madd(e, neg); a2.madd(e, neg); a3.madd(e, neg);
+        a0.madd(e, neg); a1.madd(e, neg);
       }
-      CHECK(same_g1(a0, a1) && same_g1(a0, a2) && same_g1(a0, a3), "%s: accumulator limbs differ between forms at step %d", name, s);
+      CHECK(same_g1(a0, a1), "%s: accumulator limbs differ between forms at step %d", name, s);
     }
   }
 }
@@ -168,18 +133,16 @@ static void g2_chains() {
   for (int trial = 0; trial < 20; trial++) {
     XYZZ29G2F<0> a0 = XYZZ29G2F<0>::infinity();
     XYZZ29G2F<1> a1 = XYZZ29G2F<1>::infinity();
-    XYZZ29G2F<2> a2 = XYZZ29G2F<2>::infinity();
-    XYZZ29G2F<3> a3 = XYZZ29G2F<3>::infinity();
     for (int s = 0; s < 30; s++) {
       const Affine<Fq2> e{{words_below_p<Fq>(), words_below_p<Fq>()}, {words_below_p<Fq>(), words_below_p<Fq>()}};
       const bool neg = rnd32() & 1, distinct = rnd32() & 1;
       if (distinct) {
-        const bool d0 = a0.madd_distinct(e, neg), d1 = a1.madd_distinct(e, neg), d2 = a2.madd_distinct(e, neg), d3 = a3.madd_distinct(e, neg);
-        CHECK(d0 && d1 && d2 && d3, "g2: madd_distinct refused a random entry");
+        const bool d0 = a0.madd_distinct(e, neg), d1 = a1.madd_distinct(e, neg);
+        CHECK(d0 && d1, "g2: madd_distinct refused a random entry");
       } else {
-        a0.madd(e, neg); a1.madd(e, neg); a2.madd(e, neg); a3.madd(e, neg);
+        a0.madd(e, neg); a1.madd(e, neg);
       }
-      CHECK(same_g2(a0, a1) && same_g2(a0, a2) && same_g2(a0, a3), "g2: accumulator limbs differ between forms at step %d", s);
+      CHECK(same_g2(a0, a1), "g2: accumulator limbs differ between forms at step %d", s);
     }
   }
 }
