@@ -38,6 +38,12 @@
  *   spp_pool_settle_log       a log in which the three kinds alternate, as the chain's does (one audit and one withdraw transaction per
  *                             withdrawal, route.ts:224-276, deposits in between), settled in one call: state.rs:28-46,
  *                             instructions/deposit.rs:21-37, submit_audit.rs:41-87, withdraw.rs:94-175
+ *   spp_merkle_tree_find      from a leaf value back to its position(s) in the resident tree: MerkleTreeState.leaves.indexOf, the
+ *                             leafIndex of a DepositRecord (demo-frontend/app/lib/storage.ts:9-26,45-50)
+ *   spp_wallet_sync           the DepositRecord of every deposit of a wallet -- commitment, leafIndex, nullifier, waCommitment, status
+ *                             "pending" | "withdrawn" (storage.ts:9-26), what exportData / importDeposits carry between browsers
+ *                             (storage.ts:233-260) -- recomputed from the three secrets per note, the resident tree and the pool's
+ *                             accounts: the nullifier PDAs and the audit records process_withdraw tests (withdraw.rs:94-147)
  *   spp_msm_g1(_pippenger) / spp_ntt_fr   micro-benchmark entry points (BASELINE.json configs[4]); no reference equivalent
  *
  * Conventions: field elements cross the boundary as 32-byte big-endian canonical integers (the encoding
@@ -553,6 +559,49 @@ int  spp_pool_settle_log(spp_pool*, size_t count, const uint8_t* kinds,
                          size_t n_audits, const uint8_t* audit_proofs, const uint8_t* audit_pws,
                          size_t n_withdraws, const uint8_t* withdraw_proofs, const uint8_t* withdraw_pws, const uint8_t* recipients,
                          int32_t* result, uint64_t* amounts);
+
+/* ---- wallet sync: find a wallet's notes in the resident tree and say which are spent ---- */
+/* A withdraw note needs its leaf index, and an index otherwise has one source: *first_index of the spp_merkle_tree_deposit call that
+ * made the leaf, in the same process.  The reference keeps the state per deposit in the browser (DepositRecord and MerkleTreeState,
+ * demo-frontend/app/lib/storage.ts:9-26,45-50, carried along by exportData / importDeposits :233-260); all of it derives from the
+ * three secrets of a note, the leaf list and the pool's accounts, so here it is recomputed: deposit (or insert the chain's leaves),
+ * sync, prove from the returned notes, settle, sync again.
+ * Both calls use a leaf index on the tree (csrc/leaf_index.hpp has the layout and the argument why the answers do not depend on
+ * scheduling): an open-addressing table of 32-bit leaf indices in HBM, built lazily by these two calls only and extended by the
+ * leaves that came since (one insert launch, then the query in a later launch), its slot function salted per tree from OS
+ * randomness unless env SPP_TREE_INDEX_SALT (hex) is set when the index is first built.  spp_merkle_tree_insert, _deposit, _root,
+ * _proofs and the notes path neither read nor change it; spp_merkle_tree_free releases it.  A value that sits at k leaves costs its
+ * queries k table entries to look at, and spp_wallet_sync one nullifier hash per occurrence it examines; k is not capped.
+ * Both calls are synchronous, hold the context lock for their whole length and run on the context's stream, so they are ordered with
+ * inserts, deposits and the pool's commits.  Refused with SPP_ERR_BAD_INPUT before any device work, tree, index and pool unchanged,
+ * the offender named in spp_last_error(): NULL t / leaves / indices / deposits / flags with count > 0 (checked before the context
+ * is touched), a value >= r, count > 2^24, a tree of more than 2^30 leaves; count == 0 is SPP_OK. */
+/* position of leaf values: indices[i] = the lowest leaf index >= from[i] (from NULL = 0) whose leaf equals leaves[i], UINT64_MAX if
+ * none; matches[i] (optional) = how many leaves equal it in the whole tree.  leaves count*32 B canonical big-endian. */
+int spp_merkle_tree_find(spp_merkle_tree* t, size_t count, const uint8_t* leaves, const uint64_t* from, uint64_t* indices, uint32_t* matches);
+
+/* For secret i (secret_key | amount | randomness, the key used as given, as spp_merkle_tree_deposit does): owner = secret_key * G,
+ * commitment = H(owner_x, owner_y, amount, randomness), wa_commitment = H(owner_x, owner_y), the occurrences of the commitment among
+ * the leaves, and nullifier = H(secret_key, index) of the occurrence that is reported:
+ *   - with a pool, the lowest index whose nullifier is not in the pool's nullifier set (withdraw.rs:137-147 would pass); if every
+ *     occurrence is spent, the lowest index, with SPP_WALLET_SPENT.  Anyone can deposit a copy of a commitment and the owner can
+ *     withdraw each copy under its own nullifier, so "first unspent" is the answer that leads to a payable proof;
+ *     spp_merkle_tree_find with `from` enumerates the rest;
+ *   - without a pool, the lowest index; SPENT and AUDITED are never set.
+ * A commitment that is no leaf: indices[i] = UINT64_MAX, no IN_TREE, nullifier word zero; AUDITED is still evaluated.  Nullifier and
+ * audit keys are compared bytewise with the canonical encoding computed here, which is what this library's prover writes into the
+ * public witness.  notes[i] is the note spp_prove_withdraw_notes takes (recipient | amount | secret_key | randomness | index); for an
+ * absent commitment its index word is 2^depth, canonical and out of range: a row the circuit refuses in place (status != 0).
+ * Also refused (as above): notes without recipients, secret_key == 0, amount >= 2^64, a recipient word >= r, a pool of another
+ * spp_ctx than the tree's. */
+#define SPP_WALLET_RECORD_LEN 160   /* commitment | nullifier | wa_commitment | owner_x | owner_y, 5 x 32 B big-endian */
+#define SPP_WALLET_IN_TREE  1       /* the commitment is a leaf */
+#define SPP_WALLET_SPENT    2       /* H(secret_key, index) is in the pool's nullifier set      (status "withdrawn") */
+#define SPP_WALLET_AUDITED  4       /* the pool holds the audit record of wa_commitment         (withdraw.rs:94-125 would pass) */
+#define SPP_WALLET_REPEATED 8       /* the commitment sits at more than one leaf */
+int spp_wallet_sync(spp_merkle_tree* t, spp_pool* pool /* optional */, size_t count, const uint8_t* deposits /* count * SPP_DEPOSIT_LEN */,
+                    const uint8_t* recipients /* optional: count * 32 B recipient words */, uint64_t* indices, uint32_t* flags,
+                    uint8_t* records /* optional */, uint8_t* notes /* optional, needs recipients: count * SPP_NOTE_LEN */);
 
 /* ---- micro-benchmark / unit entry points ---- */
 /* data: n = 2^logn elements, 32 B big-endian each, natural order in and out */

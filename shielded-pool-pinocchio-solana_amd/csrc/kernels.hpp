@@ -121,6 +121,18 @@ void launch_withdraw_rows(hipStream_t st, const GkAffine* table, HashConsts hc, 
 void launch_deposit_leaves(hipStream_t st, const GkAffine* table, HashConsts hc, const uint8_t* deposits, Fr* leaves, uint32_t count);
 void launch_deposit_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first, uint32_t count, uint8_t* roots_be,
                           uint8_t* commitments_be);
+// the leaf index of a resident tree and the wallet sync over it (leaf_index.hpp has the structures and what a lane does).  An insert
+// launch and a query launch never coincide: insert first, query in a later launch on the same stream.
+struct LeafIndex;
+struct PoolSet;
+void launch_leaf_index_insert(hipStream_t st, const LeafIndex& ix, const Fr* leaves, uint32_t first, uint32_t n);
+void launch_leaf_find(hipStream_t st, const LeafIndex& ix, const Fr* leaves, const uint8_t* keys_be, const uint64_t* from, uint64_t* indices,
+                      uint32_t* matches, uint32_t count);
+// identity + locate: records count * 160 B (always), notes optional (then recipients count * 32 B); sets: the pool's
+// { nullifiers, audit records } with its salt, or nullptr
+void launch_wallet_sync(hipStream_t st, const GkAffine* table, HashConsts hc, const LeafIndex& ix, const MerkleTreeDev* t, const PoolSet* sets,
+                        uint64_t pool_salt, const uint8_t* deposits, const uint8_t* recipients, uint8_t* records, uint64_t* indices,
+                        uint32_t* flags, uint8_t* notes, uint32_t count);
 void launch_poseidon2_sponge(hipStream_t st, HashConsts hc, const uint8_t* in_be, uint32_t n, uint8_t* out_be, uint32_t count);
 void launch_rlwe_decrypt(hipStream_t st, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, uint8_t* msg, uint32_t count);
 void launch_shamir_combine(hipStream_t st, const Fr* lambda, const uint8_t* ys_be, uint32_t t, uint32_t n, uint8_t* secret_be,

@@ -10,6 +10,9 @@
 //   k_withdraw_rows       client/payroll-demo.ts:323-340 (keygen, wa_commitment, nullifier, getRoot, getProof -> one withdraw row)
 //   k_deposit_leaves      client/payroll-demo.ts:264-292 (keygen, calculateCommitment, mt.insert)
 //   k_deposit_roots       the same deposits' mt.getRoot() after each insert
+//   k_leaf_index_insert / k_leaf_find / k_wallet_identity / k_wallet_locate
+//                         demo-frontend/app/lib/storage.ts:9-26,45-50 (leafIndex, nullifier, waCommitment, status of a DepositRecord
+//                         from the secrets, the leaf list and the pool's accounts; the leaf index is leaf_index.hpp)
 //   k_poseidon2_sponge    ct_helper/src/main.nr:15-34 (= scripts/generate_audit.py:355-374)
 //   k_audit_open          scripts/rlwe_decrypt.py:61-149 for a batch of (pw, ciphertext) records, with the binding checks it omits
 //   k_rlwe_keygen         scripts/rlwe_keygen.py:98-116 (the audit key pair), k_rlwe_key_noise: the check a key holder can make
@@ -20,6 +23,7 @@
 #include "rlwe_ntt.hpp"
 #include "audit_open.hpp"
 #include "rlwe_keygen.hpp"
+#include "leaf_index.hpp"
 
 namespace spp {
 
@@ -485,6 +489,121 @@ void launch_deposit_leaves(hipStream_t st, const GkAffine* table, HashConsts hc,
 void launch_deposit_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first, uint32_t count, uint8_t* roots_be,
                           uint8_t* commitments_be) {
   if (count) hipLaunchKernelGGL(k_deposit_roots, dim3((count + 63) / 64), dim3(64), 0, st, hc, t, first, count, roots_be, commitments_be);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Wallet sync (demo-frontend/app/lib/storage.ts:9-26,45-50: the DepositRecord a wallet keeps per deposit, rebuilt from its three
+// secrets, the tree and the pool's accounts).  What a lane does with the leaf index and why the answers do not depend on
+// scheduling is in leaf_index.hpp; the pool's sets are only READ here (pool_set_contains), which pool_table.hpp allows a launch
+// that inserts nothing.
+//   k_leaf_index_insert   leaves [first, first + n) each claim a slot; never in one launch with a query
+//   k_leaf_find           one lane per queried value: lowest index >= from, number of occurrences
+//   k_wallet_identity     one lane per secret: owner = sk * G, commitment = H4(owner, amount, randomness), wa_commitment = H2(owner)
+//   k_wallet_locate       one lane per secret: the occurrences of the commitment, nullifier = H2(secret_key, index) of each one
+//                         examined, the pool's two sets, the note
+// Two kernels, so that the Grumpkin ladder and the t = 5 permutation are not live beside the probe loop and its t = 3
+// permutation.  The permutations are inlined as in k_withdraw_rows (one call site each; the loop over the occurrences is kept
+// rolled for that).  record = commitment | nullifier | wa_commitment | owner_x | owner_y (5 x 32 B big-endian).
+// ----------------------------------------------------------------------------------------------------
+static constexpr uint32_t WALLET_RECORD_BYTES = 160;
+static constexpr uint32_t WALLET_IN_TREE = 1, WALLET_SPENT = 2, WALLET_AUDITED = 4, WALLET_REPEATED = 8;   // include/spp.h, SPP_WALLET_*
+__global__ void __launch_bounds__(256) k_leaf_index_insert(LeafIndex ix, const Fr* __restrict__ leaves, uint32_t first, uint32_t n) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < n) leaf_index_insert(ix, leaves, first + g);
+}
+__global__ void __launch_bounds__(256) k_leaf_find(LeafIndex ix, const Fr* __restrict__ leaves, const uint8_t* __restrict__ keys_be,
+                                                   const uint64_t* __restrict__ from, uint64_t* __restrict__ indices,
+                                                   uint32_t* __restrict__ matches, uint32_t count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  uint32_t m = 0;
+  const uint32_t i = leaf_index_lowest(ix, leaves, load_be(keys_be + (size_t)g * 32), from ? from[g] : 0, &m);
+  indices[g] = i == LEAF_NONE ? ~(uint64_t)0 : i;
+  if (matches) matches[g] = m;
+}
+__global__ void __launch_bounds__(64) k_wallet_identity(const GkAffine* __restrict__ table, HashConsts hc, const uint8_t* __restrict__ deposits,
+                                                        uint8_t* __restrict__ records, uint32_t count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const uint8_t* d = deposits + (size_t)g * DEPOSIT_BYTES;
+  uint8_t* o = records + (size_t)g * WALLET_RECORD_BYTES;
+  const GkAffine pk = grumpkin_mul_g(table, load_be(d));             // merkle.ts:98-113 (the key as given, as k_deposit_leaves)
+  store_be(o + 96, pk.x);
+  store_be(o + 128, pk.y);
+  {
+    Fr s[5] = {Fr::zero(), pk.x, pk.y, load_be(d + 32), load_be(d + 64)};
+    poseidon_permute29<5, false>(s, hc.pos5_rc, hc.pos5_mds29, 60, PoseidonNoEmit{});
+    store_be(o, s[0]);                                               // commitment (merkle.ts:126-133, main.nr:69-70)
+  }
+  Fr s[3] = {Fr::zero(), pk.x, pk.y};
+  poseidon_permute29<3, false>(s, hc.pos3_rc, hc.pos3_mds29, 57, PoseidonNoEmit{});
+  store_be(o + 64, s[0]);                                            // wa_commitment (main.nr:64-67)
+}
+// the table covers every leaf of the tree at the call (the insert launch ran before).  has_pool == false: the sets are not read.
+__global__ void __launch_bounds__(64) k_wallet_locate(LeafIndex ix, HashConsts hc, const MerkleTreeDev* __restrict__ t, bool has_pool,
+                                                      PoolSet nullifiers, PoolSet audits, uint64_t pool_salt,
+                                                      const uint8_t* __restrict__ deposits, const uint8_t* __restrict__ recipients,
+                                                      uint8_t* __restrict__ records, uint64_t* __restrict__ indices,
+                                                      uint32_t* __restrict__ flags, uint8_t* __restrict__ notes, uint32_t count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const uint8_t* d = deposits + (size_t)g * DEPOSIT_BYTES;
+  uint8_t* o = records + (size_t)g * WALLET_RECORD_BYTES;
+  const Fr* leaves = t->level[0];
+  const Fr key = load_be(o), sk = load_be(d);
+  uint8_t nf[32];
+  for (int i = 0; i < 32; i++) nf[i] = 0;
+  uint32_t f = 0, idx = LEAF_NONE, matches = 0;
+  if (leaf_index_lowest(ix, leaves, key, 0, &matches) != LEAF_NONE) {
+    f = WALLET_IN_TREE | (matches > 1 ? WALLET_REPEATED : 0);
+    // pass 0: the lowest occurrence whose nullifier is unspent; pass 1, when every one is spent: the lowest.  Without a pool
+    // pass 0 takes the lowest.  nf is left holding the nullifier of the occurrence that was taken.
+    bool any = !has_pool;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; pass++) {
+      idx = leaf_index_first(ix, leaves, key, 0, [&](uint32_t i) {
+        Fr s[3] = {Fr::zero(), sk, Fr::from_u64(i)};
+        poseidon_permute29<3, false>(s, hc.pos3_rc, hc.pos3_mds29, 57, PoseidonNoEmit{});   // main.nr:72-74
+        s[0].to_bytes_be(nf);
+        return any || !pool_set_contains(nullifiers, pool_salt, nf);
+      });
+      if (idx != LEAF_NONE) break;
+      any = true;
+    }
+    if (has_pool && any) f |= WALLET_SPENT;
+  }
+  if (has_pool && pool_set_contains(audits, pool_salt, o + 64)) f |= WALLET_AUDITED;
+  for (int i = 0; i < 32; i++) o[32 + i] = nf[i];
+  indices[g] = idx == LEAF_NONE ? ~(uint64_t)0 : idx;
+  flags[g] = f;
+  if (notes) {
+    uint8_t* nt = notes + (size_t)g * NOTE_BYTES;
+    copy32(nt, recipients + (size_t)g * 32);
+    copy32(nt + 32, d + 32);                                         // amount
+    copy32(nt + 64, d);                                              // secret_key
+    copy32(nt + 96, d + 64);                                         // randomness
+    // an absent note carries 2^depth: canonical and out of range, a row k_withdraw_rows builds from defaults and the circuit refuses
+    const uint64_t word = idx == LEAF_NONE ? (uint64_t)1 << t->depth : idx;
+    for (int i = 0; i < 24; i++) nt[128 + i] = 0;
+    for (int i = 0; i < 8; i++) nt[152 + i] = (uint8_t)(word >> (8 * (7 - i)));
+  }
+}
+void launch_leaf_index_insert(hipStream_t st, const LeafIndex& ix, const Fr* leaves, uint32_t first, uint32_t n) {
+  if (n) hipLaunchKernelGGL(k_leaf_index_insert, dim3((n + 255) / 256), dim3(256), 0, st, ix, leaves, first, n);
+}
+void launch_leaf_find(hipStream_t st, const LeafIndex& ix, const Fr* leaves, const uint8_t* keys_be, const uint64_t* from, uint64_t* indices,
+                      uint32_t* matches, uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_leaf_find, dim3((count + 255) / 256), dim3(256), 0, st, ix, leaves, keys_be, from, indices, matches, count);
+}
+void launch_wallet_sync(hipStream_t st, const GkAffine* table, HashConsts hc, const LeafIndex& ix, const MerkleTreeDev* t, const PoolSet* sets,
+                        uint64_t pool_salt, const uint8_t* deposits, const uint8_t* recipients, uint8_t* records, uint64_t* indices,
+                        uint32_t* flags, uint8_t* notes, uint32_t count) {
+  if (count == 0) return;
+  const dim3 grid((count + 63) / 64);
+  hipLaunchKernelGGL(k_wallet_identity, grid, dim3(64), 0, st, table, hc, deposits, records, count);
+  const PoolSet none{nullptr, nullptr, 0};
+  hipLaunchKernelGGL(k_wallet_locate, grid, dim3(64), 0, st, ix, hc, t, sets != nullptr, sets ? sets[0] : none, sets ? sets[1] : none, pool_salt,
+                     deposits, recipients, records, indices, flags, notes, count);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 //                        the experiment switches of the proving path from the environment (read_switches)
 //   spp_prove.cpp        workspaces, the proving pipeline and its batch entry points, timing queries
 //   spp_setup.cpp        circuit construction (host only) and the trusted setup on the GPU
-//   spp_witness_api.cpp  witness-input kernels, Merkle trees, auditor side
+//   spp_witness_api.cpp  witness-input kernels, Merkle trees and their leaf index (wallet sync), auditor side
 //   spp_verify_api.cpp   verification and pairing checks
 //   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
@@ -165,7 +165,18 @@ struct spp_merkle_tree {
   MerkleTreeDev host{};                        // host mirror of the device descriptor
   MerkleTreeDev* dev = nullptr;
   Fr* d_dflt = nullptr;                        // depth + 1 default hashes
+  // the leaf index (leaf_index.hpp), built lazily by spp_merkle_tree_find / spp_wallet_sync and by nothing else: it covers leaves
+  // [0, indexed) in index_slots slots; the salt is drawn when it is first built
+  uint32_t* d_index = nullptr;
+  uint32_t index_slots = 0;
+  uint64_t indexed = 0, index_salt = 0;
+  bool index_salted = false;
 };
+// the pool's two resident sets (SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS) and their salt, for a launch that only reads them
+// (spp_pool_api.cpp).  Returns the pool's context; sets (two entries) and salt are written when sets is not NULL, which needs that
+// context locked
+struct spp_pool;
+spp_ctx* spp_pool_view(spp_pool* p, PoolSet* sets, uint64_t* salt);
 template <class T>
 inline int ctx_upload(spp_ctx* ctx, T** dst, const std::vector<T>& src) {
   HIP_TRY(dev_upload(dst, src));

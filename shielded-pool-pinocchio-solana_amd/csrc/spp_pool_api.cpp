@@ -220,6 +220,16 @@ extern "C" int spp_pool_contains(spp_pool* p, int which, size_t count, const uin
   return SPP_OK;
 }
 
+// for spp_wallet_sync (spp_witness_api.cpp), whose locate kernel reads both sets and writes neither
+spp_ctx* spp_pool_view(spp_pool* p, PoolSet* sets, uint64_t* salt) {
+  if (sets) {
+    sets[0] = p->set[SPP_POOL_NULLIFIERS];
+    sets[1] = p->set[SPP_POOL_AUDIT_RECORDS];
+    *salt = p->salt;
+  }
+  return p->ctx;
+}
+
 extern "C" int spp_pool_set_verifier(spp_pool* p, int mode, uint32_t group) {
   if (!p) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   if (mode != SPP_POOL_VERIFY_EACH && mode != SPP_POOL_VERIFY_RLC) return fail(SPP_ERR_BAD_INPUT, "mode: SPP_POOL_VERIFY_EACH or SPP_POOL_VERIFY_RLC");

@@ -2,6 +2,7 @@
 // + quotient witnesses, Poseidon / Merkle / Grumpkin, the ct_commitment sponge, whole audit input rows) and the auditor side
 // (Shamir reconstruction, BFV decryption), batched on the GPU.
 #include "spp_internal.hpp"
+#include "leaf_index.hpp"
 
 int spp_ensure_ctx_consts(spp_ctx* ctx) {
   if (ctx->consts_ready) return 0;
@@ -289,6 +290,7 @@ extern "C" void spp_merkle_tree_free(spp_merkle_tree* t) {
   for (uint32_t l = 0; l <= 32; l++) if (t->host.level[l]) hipFree(t->host.level[l]);
   if (t->dev) hipFree(t->dev);
   if (t->d_dflt) hipFree(t->d_dflt);
+  if (t->d_index) hipFree(t->d_index);
   delete t;
 }
 extern "C" uint64_t spp_merkle_tree_size(const spp_merkle_tree* t) { return t ? t->n_leaves : 0; }
@@ -416,6 +418,134 @@ extern "C" int spp_withdraw_rows_from_tree(spp_merkle_tree* t, size_t count, con
   HIP_TRY(dr.alloc(count * row_bytes));
   launch_withdraw_rows(st, ctx->gk_table, ctx->hc, t->dev, dn.as<uint8_t>(), dr.as<uint8_t>(), (uint32_t)count);
   HIP_TRY(hipMemcpyAsync(rows, dr.p, count * row_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// Wallet sync: from leaf values and from secrets back to positions (demo-frontend/app/lib/storage.ts:9-26,45-50,233-260: the
+// DepositRecord / MerkleTreeState a wallet keeps, rebuilt instead of carried along).  The leaf index and its ordering argument are
+// leaf_index.hpp; insert, deposit, root, proofs and the notes path never touch it.
+// -----------------------------------------------------------------------------------------------------
+static_assert(SPP_WALLET_RECORD_LEN == 160 && SPP_WALLET_IN_TREE == 1 && SPP_WALLET_SPENT == 2 && SPP_WALLET_AUDITED == 4 &&
+                  SPP_WALLET_REPEATED == 8, "include/spp.h and kernels_witness.hip disagree");
+static int mt_index_salt(uint64_t* salt) {
+  if (const char* env = getenv("SPP_TREE_INDEX_SALT")) {
+    char* end = nullptr;
+    *salt = strtoull(env, &end, 16);
+    if (end == env || *end) return fail(SPP_ERR_BAD_INPUT, "SPP_TREE_INDEX_SALT is not a hexadecimal number");
+    return SPP_OK;
+  }
+  FILE* f = fopen("/dev/urandom", "rb");
+  if (!f || fread(salt, 1, sizeof *salt, f) != sizeof *salt) {
+    if (f) fclose(f);
+    return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+  }
+  fclose(f);
+  return SPP_OK;
+}
+// Brings the index up to the tree (ctx->mu held, device set): leaves [indexed, n_leaves) are inserted in ONE launch on the context's
+// stream; the caller's query is a later launch.  A table that would pass half full is allocated again at the larger size and every
+// leaf reinserted.
+static int mt_index_sync(spp_merkle_tree* t, LeafIndex* ix) {
+  if (t->n_leaves > LEAF_INDEX_MAX_LEAVES)
+    return fail(SPP_ERR_BAD_INPUT, "the tree has %llu leaves: the leaf index covers at most 2^30", (unsigned long long)t->n_leaves);
+  if (!t->index_salted) {
+    if (int e = mt_index_salt(&t->index_salt)) return e;
+    t->index_salted = true;
+  }
+  hipStream_t st = t->ctx->stream;
+  const uint32_t want = leaf_index_slots(t->n_leaves);
+  if (!t->d_index || want > t->index_slots) {
+    if (t->d_index) {
+      HIP_TRY(hipStreamSynchronize(st));
+      hipFree(t->d_index);
+      t->d_index = nullptr;
+    }
+    t->index_slots = 0;
+    t->indexed = 0;
+    HIP_TRY(hipMalloc((void**)&t->d_index, (size_t)want * sizeof(uint32_t)));
+    t->index_slots = want;
+    HIP_TRY(hipMemsetAsync(t->d_index, 0xFF, (size_t)want * sizeof(uint32_t), st));
+  }
+  *ix = LeafIndex{t->d_index, t->index_slots - 1, t->index_salt};
+  launch_leaf_index_insert(st, *ix, t->host.level[0], (uint32_t)t->indexed, (uint32_t)(t->n_leaves - t->indexed));
+  t->indexed = t->n_leaves;
+  return SPP_OK;
+}
+
+extern "C" int spp_merkle_tree_find(spp_merkle_tree* t, size_t count, const uint8_t* leaves, const uint64_t* from, uint64_t* indices,
+                                    uint32_t* matches) {
+  if (!t || (count && (!leaves || !indices))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many leaf values in one call (%zu; at most 2^24)", count);
+  for (size_t i = 0; i < count; i++)
+    if (!be_is_canonical<FrParams>(leaves + 32 * i)) return fail(SPP_ERR_BAD_INPUT, "leaf value %zu is not a canonical field element", i);
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  LeafIndex ix;
+  if (int e = mt_index_sync(t, &ix)) return e;
+  DevBuf dk, df, di, dm;
+  UP(dk, leaves, count * 32);
+  if (from) UP(df, from, count * sizeof(uint64_t));
+  HIP_TRY(di.alloc(count * sizeof(uint64_t)));
+  if (matches) HIP_TRY(dm.alloc(count * sizeof(uint32_t)));
+  launch_leaf_find(st, ix, t->host.level[0], dk.as<uint8_t>(), from ? df.as<uint64_t>() : nullptr, di.as<uint64_t>(),
+                   matches ? dm.as<uint32_t>() : nullptr, (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(indices, di.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (matches) HIP_TRY(hipMemcpyAsync(matches, dm.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" int spp_wallet_sync(spp_merkle_tree* t, spp_pool* pool, size_t count, const uint8_t* deposits, const uint8_t* recipients,
+                               uint64_t* indices, uint32_t* flags, uint8_t* records, uint8_t* notes) {
+  static const char* const field_name[3] = {"secret_key", "amount", "randomness"};
+  if (!t || (count && (!deposits || !indices || !flags))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (notes && !recipients) return fail(SPP_ERR_BAD_INPUT, "notes are built from recipients: recipients is NULL");
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many secrets in one call (%zu; at most 2^24)", count);
+  for (size_t i = 0; i < count; i++) {
+    const uint8_t* d = deposits + SPP_DEPOSIT_LEN * i;
+    for (int f = 0; f < 3; f++)
+      if (!be_is_canonical<FrParams>(d + 32 * f))
+        return fail(SPP_ERR_BAD_INPUT, "secret %zu: %s is not a canonical field element", i, field_name[f]);
+    bool sk_zero = true, amount_u64 = true;
+    for (int b = 0; b < 32; b++) sk_zero &= d[b] == 0;
+    for (int b = 0; b < 24; b++) amount_u64 &= d[32 + b] == 0;
+    if (sk_zero) return fail(SPP_ERR_BAD_INPUT, "secret %zu: secret_key is 0", i);
+    if (!amount_u64) return fail(SPP_ERR_BAD_INPUT, "secret %zu: amount does not fit 64 bits", i);
+    if (recipients && !be_is_canonical<FrParams>(recipients + 32 * i))
+      return fail(SPP_ERR_BAD_INPUT, "secret %zu: recipient is not a canonical field element", i);
+  }
+  spp_ctx* ctx = t->ctx;
+  if (pool && spp_pool_view(pool, nullptr, nullptr) != ctx) return fail(SPP_ERR_BAD_INPUT, "the pool belongs to another spp_ctx than the tree");
+  if (count == 0) return SPP_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  PoolSet sets[2];
+  uint64_t pool_salt = 0;
+  if (pool) spp_pool_view(pool, sets, &pool_salt);
+  LeafIndex ix;
+  if (int e = mt_index_sync(t, &ix)) return e;
+  DevBuf dd, dr, drec, di, df, dn;
+  UP(dd, deposits, count * SPP_DEPOSIT_LEN);
+  if (notes) UP(dr, recipients, count * 32);
+  HIP_TRY(drec.alloc(count * SPP_WALLET_RECORD_LEN));
+  HIP_TRY(di.alloc(count * sizeof(uint64_t)));
+  HIP_TRY(df.alloc(count * sizeof(uint32_t)));
+  if (notes) HIP_TRY(dn.alloc(count * SPP_NOTE_LEN));
+  launch_wallet_sync(st, ctx->gk_table, ctx->hc, ix, t->dev, pool ? sets : nullptr, pool_salt, dd.as<uint8_t>(), notes ? dr.as<uint8_t>() : nullptr,
+                     drec.as<uint8_t>(), di.as<uint64_t>(), df.as<uint32_t>(), notes ? dn.as<uint8_t>() : nullptr, (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(indices, di.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(flags, df.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (records) HIP_TRY(hipMemcpyAsync(records, drec.p, count * SPP_WALLET_RECORD_LEN, hipMemcpyDeviceToHost, st));
+  if (notes) HIP_TRY(hipMemcpyAsync(notes, dn.p, count * SPP_NOTE_LEN, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   return SPP_OK;

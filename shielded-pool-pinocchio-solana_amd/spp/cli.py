@@ -28,6 +28,14 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # prints one result name per line (OK, AUDIT_EXISTS, NO_AUDIT_RECORD, BAD_ROOT, NULLIFIER_USED,
                               # BAD_RECIPIENT, BAD_PROOF; a deposit only pushes its root and prints OK).  --verifier rlc checks
                               # the proofs by random linear combination (spp_pool_set_verifier): the same lines
+    python -m spp.cli wallet-sync secrets.json leaves.txt [--spent nullifiers.txt] [--audited wa.txt] [--vk withdraw.vk audit.vk] [--recipient HEX]
+                              # a wallet's DepositRecords (demo-frontend/app/lib/storage.ts:9-26) from its secrets -- a JSON list of
+                              # {"secretKey", "amount", "randomness"} -- and the chain's leaves, one hex leaf per line in chain order
+                              # (MerkleTreeState.leaves, :45-50).  --spent / --audited: the nullifier and wa_commitment accounts the
+                              # pool holds, one hex key per line (they go through spp_pool_import_keys and need --vk).  Prints one
+                              # JSON object per secret: commitment, leafIndex, root, nullifier, waCommitment, siblings, publicKeyX/Y,
+                              # status ("pending" | "withdrawn"; "absent" with leafIndex null when the commitment is no leaf), audited
+                              # (null without --vk) and occurrences -- the form importDeposits (:233-260) reads
     python -m spp.cli execute target/<name>.json Prover.toml [-o target/<name>.gz]               # `nargo execute`: ACIR witness stack
     python -m spp.cli prove   target/<name>.json target/<name>.gz target/<name>.sppc target/<name>.pk
                               # sunspot's own argument order (acir, witness, constraint system, proving key;
@@ -248,6 +256,95 @@ def _pool_replay(a):
     return 0
 
 
+def _hex_lines(path, what):
+    """the 32-byte values of a file with one hex value per line (0x optional, blank lines skipped); ValueError names the line"""
+    out = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            tok = line.strip()
+            if not tok:
+                continue
+            try:
+                v = int(tok, 16)
+            except ValueError:
+                raise ValueError("%s line %d: not a hexadecimal %s" % (path, no, what))
+            if not 0 <= v < 1 << 256:
+                raise ValueError("%s line %d: a %s is 32 bytes" % (path, no, what))
+            out.append(v)
+    return out
+
+
+def parse_wallet_secrets(text):
+    """[(secret_key, amount, randomness)] from the text of a secrets.json; ValueError names the secret the library would refuse"""
+    try:
+        items = json.loads(text)
+        secrets = [tuple(_num(str(d[k])) for k in ("secretKey", "amount", "randomness")) for d in items]
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError("not a list of {secretKey, amount, randomness} (%s)" % e)
+    for k, (sk, amount, rnd) in enumerate(secrets):
+        if not (0 < sk < R and 0 <= rnd < R):
+            raise ValueError("secret %d: secretKey must be in [1, r) and randomness in [0, r)" % k)
+        if not 0 <= amount < 1 << 64:
+            raise ValueError("secret %d: amount does not fit 64 bits" % k)
+    return secrets
+
+
+def _wallet_sync(a):
+    from . import witness
+    try:   # everything that can be wrong with the arguments and the files is found before a device is opened
+        secrets = parse_wallet_secrets(open(a.secrets).read())
+        leaves = _hex_lines(a.leaves, "leaf")
+        if any(v >= R for v in leaves):
+            raise ValueError("%s: leaf %d is not a canonical field element" % (a.leaves, next(i for i, v in enumerate(leaves) if v >= R)))
+        if not 1 <= a.depth <= 32 or len(leaves) > 1 << a.depth:
+            raise ValueError("%d leaves do not fit a tree of depth %d (1..32)" % (len(leaves), a.depth))
+        if (a.spent or a.audited) and not a.vk:
+            raise ValueError("--spent / --audited describe a pool: they need --vk withdraw.vk audit.vk")
+        spent = _hex_lines(a.spent, "nullifier") if a.spent else []
+        audited = _hex_lines(a.audited, "wa_commitment") if a.audited else []
+        wvk, avk = (open(p, "rb").read() for p in a.vk) if a.vk else (None, None)
+        recipient = None if a.recipient is None else int(a.recipient, 16)
+        if recipient is not None and not 0 <= recipient < R:
+            raise ValueError("--recipient is not a canonical field element")
+    except (OSError, ValueError) as e:
+        print("spp wallet-sync: %s" % e, file=sys.stderr)
+        return 2
+    hx = lambda v: "0x%064x" % v
+    ctx = Context(a.device)
+    try:
+        with witness.ShieldedPoolMerkleTree(ctx, a.depth) as tree:
+            tree.insert_many(leaves)
+            pool = witness.Pool(ctx, wvk, avk, max(1, len(spent), len(audited))) if a.vk else None
+            try:
+                if pool:
+                    pool.import_keys(lib.SPP_POOL_NULLIFIERS, spent)
+                    pool.import_keys(lib.SPP_POOL_AUDIT_RECORDS, audited)
+                records = tree.sync(secrets, pool)
+            finally:
+                if pool:
+                    pool.close()
+            root = tree.getRoot()
+            _, occurrences = tree.find([r[2] for r in records])
+            found = [r[0] for r in records if r[0] is not None]
+            siblings = dict(zip(found, tree.getProofs(found)))
+    except lib.SppError as e:
+        print("spp wallet-sync: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    for (sk, amount, rnd), (index, flags, com, nf, wa, owner), occ in zip(secrets, records, occurrences):
+        rec = {"id": hx(com), "secretKey": hx(sk), "publicKeyX": hx(owner[0]), "publicKeyY": hx(owner[1]), "amount": str(amount),
+               "randomness": hx(rnd), "commitment": hx(com), "leafIndex": index, "root": hx(root) if index is not None else None,
+               "nullifier": hx(nf) if index is not None else None, "waCommitment": hx(wa),
+               "siblings": [hx(v) for v in siblings[index]] if index is not None else [],
+               "status": "absent" if index is None else "withdrawn" if flags & lib.SPP_WALLET_SPENT else "pending",
+               "audited": bool(flags & lib.SPP_WALLET_AUDITED) if a.vk else None, "occurrences": occ}
+        if recipient is not None:
+            rec["recipient"] = hx(recipient)
+        print(json.dumps(rec))
+    return 0
+
+
 def _verify_batch(a):
     try:   # everything that can be wrong with the files is found before a device is opened
         if not a.files or len(a.files) % 2:
@@ -299,6 +396,13 @@ def main(argv=None):
     r.add_argument("--verifier", choices=("each", "rlc"), default="each", help="each: one lane per proof (default); rlc: random linear combination")
     r.add_argument("--group", type=int, default=0, help="with --verifier rlc: proofs per combined equation (a multiple of 64 in [64, 4096]; default 256)")
     r.add_argument("--device", type=int, default=0)
+    w = sub.add_parser("wallet-sync"); w.add_argument("secrets", help="JSON list of {secretKey, amount, randomness}")
+    w.add_argument("leaves", help="one hex leaf per line, in chain order")
+    w.add_argument("--spent", default=None, metavar="NULLIFIERS.txt", help="spent nullifiers, one hex key per line (needs --vk)")
+    w.add_argument("--audited", default=None, metavar="WA.txt", help="wa_commitments with an audit record, one hex key per line (needs --vk)")
+    w.add_argument("--vk", nargs=2, default=None, metavar=("WITHDRAW.vk", "AUDIT.vk"))
+    w.add_argument("--recipient", default=None, metavar="HEX", help="recipient word copied into every record")
+    w.add_argument("--depth", type=int, default=16); w.add_argument("--device", type=int, default=0)
     k = sub.add_parser("rlwe-keygen"); k.add_argument("--out", required=True, metavar="DIR")
     k.add_argument("--threshold", type=int, default=2); k.add_argument("--shares", type=int, default=3)
     k.add_argument("--reference-seed", type=int, default=None, metavar="N",
@@ -320,6 +424,8 @@ def main(argv=None):
         return _verify_batch(a)
     if a.cmd == "pool-replay":
         return _pool_replay(a)
+    if a.cmd == "wallet-sync":
+        return _wallet_sync(a)
     if a.cmd == "compile" and a.circuit.endswith(".ccs"):
         from . import ccs
         c = ccs.load_ccs(a.circuit)

@@ -40,6 +40,12 @@ SPP_POOL_VERIFY_RLC = 1             # ... by random linear combination over the 
 SPP_INSTR_DEPOSIT = 0               # kinds of spp_pool_settle_log
 SPP_INSTR_SUBMIT_AUDIT = 1
 SPP_INSTR_WITHDRAW = 2
+# wallet sync, spp_wallet_sync (include/spp.h): record = commitment | nullifier | wa_commitment | owner_x | owner_y
+SPP_WALLET_RECORD_LEN = 160
+SPP_WALLET_IN_TREE = 1              # the commitment is a leaf
+SPP_WALLET_SPENT = 2                # its nullifier is in the pool's nullifier set (status "withdrawn")
+SPP_WALLET_AUDITED = 4              # the pool holds the audit record of wa_commitment
+SPP_WALLET_REPEATED = 8             # the commitment sits at more than one leaf
 SPP_ARITH_FR = 0x000                # spp_debug_arith: field bits of the selector (operation codes: csrc/arith_probe.hpp)
 SPP_ARITH_FQ = 0x100
 POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
@@ -124,6 +130,8 @@ def load_library():
     L.spp_merkle_tree_root.argtypes = [vp, vp]
     L.spp_merkle_tree_proofs.argtypes = [vp, sz, vp, vp]
     L.spp_merkle_tree_deposit.argtypes = [vp, sz, cp, ctypes.POINTER(ctypes.c_uint64), vp, vp]
+    L.spp_merkle_tree_find.argtypes = [vp, sz, cp, vp, vp, vp]
+    L.spp_wallet_sync.argtypes = [vp, vp, sz, cp, cp, vp, vp, vp, vp]
     L.spp_grumpkin_keygen_batch.argtypes = [vp, sz, cp, vp]
     L.spp_poseidon2_sponge_batch.argtypes = [vp, sz, u32, cp, vp]
     L.spp_audit_inputs_batch.argtypes = [vp, vp, vp, sz, cp, vp, vp, vp, vp]

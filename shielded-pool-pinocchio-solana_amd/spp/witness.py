@@ -9,6 +9,9 @@
     pack_withdraw_notes(...) the five values a withdrawer supplies (noir_circuit/src/main.nr:38-51), for the rows / proofs
                              from notes against the resident tree (ShieldedPoolMerkleTree.withdraw_rows)
     pack_deposits(...)       the three values a depositor supplies, for ShieldedPoolMerkleTree.deposit
+    ShieldedPoolMerkleTree.find / .sync
+                             demo-frontend/app/lib/storage.ts:9-26,45-50,233-260: the leafIndex, nullifier, waCommitment and
+                             status a wallet keeps per deposit, recomputed from its secrets, the tree and the pool's accounts
     deposit_instruction_data shielded_pool_program/src/instructions/deposit.rs:21-37
     ct_commitment(...)       ct_helper/src/main.nr:15-34
     ciphertext_json(...)     scripts/generate_audit.py:590-606 (keys/ciphertext.json, what the prover leaves for the auditor)
@@ -24,12 +27,13 @@ import ctypes
 import numpy as np
 from .lib import (check, NOTE_LEN, DEPOSIT_LEN, PROOF_LEN, AUDIT_PW_LEN, WITHDRAW_PW_LEN, SPP_POOL_STATE_LEN,
                   SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS, SPP_INSTR_DEPOSIT, SPP_INSTR_SUBMIT_AUDIT, SPP_INSTR_WITHDRAW,
-                  SPP_POOL_VERIFY_EACH, SPP_POOL_VERIFY_RLC)
+                  SPP_POOL_VERIFY_EACH, SPP_POOL_VERIFY_RLC, SPP_WALLET_RECORD_LEN)
 
 TREE_DEPTH = 16
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 NOTE_FIELDS = ("recipient", "amount", "secret_key", "randomness", "index")
 DEPOSIT_FIELDS = ("secret_key", "amount", "randomness")
+WALLET_ABSENT = (1 << 64) - 1       # spp_merkle_tree_find / spp_wallet_sync: no such leaf (UINT64_MAX)
 RLWE_N, MSG_SLOTS = 1024, 64
 
 
@@ -217,6 +221,49 @@ class ShieldedPoolMerkleTree:
         rows = ctypes.create_string_buffer(32 * n_in * max(len(notes), 1))
         check(self.ctx.L.spp_withdraw_rows_from_tree(self.h, len(notes), buf, ctypes.cast(rows, ctypes.c_void_p)))
         return [_unbe(rows.raw[32 * n_in * i:], n_in) for i in range(len(notes))]
+
+    def find(self, leaves, start=None):
+        """From leaf values back to positions (spp_merkle_tree_find; MerkleTreeState.leaves.indexOf, demo-frontend/app/lib/
+        storage.ts:45-50).  leaves: ints; start: per value the index to search from (None = 0 for all).  Returns (indices,
+        matches): the lowest leaf index >= start[i] holding leaves[i] or None, and how many leaves hold it in the whole tree.
+        A value at several leaves is enumerated by calling again with start = index + 1."""
+        n = len(leaves)
+        if start is not None and len(start) != n:
+            raise ValueError("start must name one index per leaf value")
+        frm = None if start is None else (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in start])
+        idx = (ctypes.c_uint64 * max(n, 1))()
+        matches = (ctypes.c_uint32 * max(n, 1))()
+        check(self.ctx.L.spp_merkle_tree_find(self.h, n, _be(leaves), None if frm is None else ctypes.cast(frm, ctypes.c_void_p),
+                                              ctypes.cast(idx, ctypes.c_void_p), ctypes.cast(matches, ctypes.c_void_p)))
+        return [None if v == WALLET_ABSENT else int(v) for v in idx[:n]], [int(m) for m in matches[:n]]
+
+    def sync(self, deposits, pool=None, recipients=None):
+        """The DepositRecord of every secret (demo-frontend/app/lib/storage.ts:9-26) recomputed on the device (spp_wallet_sync).
+        deposits: (secret_key, amount, randomness) tuples as for deposit(); pool: a Pool of the same Context, whose nullifier and
+        audit-record sets decide SPP_WALLET_SPENT / SPP_WALLET_AUDITED; recipients: one recipient word per secret.
+        Returns per secret (index or None, flags, commitment, nullifier, wa_commitment, (owner_x, owner_y)): with a pool the
+        lowest occurrence whose nullifier is unspent (the lowest one, flagged SPENT, when all are), without one the lowest.
+        With recipients returns (records, notes), notes being (recipient, amount, secret_key, randomness, index) tuples ready for
+        CircuitHandle.prove_withdraw_notes; a secret whose commitment is no leaf gets index 2^depth, which the circuit refuses."""
+        n = len(deposits)
+        if recipients is not None and len(recipients) != n:
+            raise ValueError("recipients must name one recipient word per secret")
+        buf = pack_deposits(deposits)
+        rcp = None if recipients is None else _be(recipients)
+        idx = (ctypes.c_uint64 * max(n, 1))()
+        flags = (ctypes.c_uint32 * max(n, 1))()
+        rec = ctypes.create_string_buffer(SPP_WALLET_RECORD_LEN * max(n, 1))
+        notes = None if recipients is None else ctypes.create_string_buffer(NOTE_LEN * max(n, 1))
+        check(self.ctx.L.spp_wallet_sync(self.h, None if pool is None else pool.h, n, buf, rcp, ctypes.cast(idx, ctypes.c_void_p),
+                                         ctypes.cast(flags, ctypes.c_void_p), ctypes.cast(rec, ctypes.c_void_p),
+                                         None if notes is None else ctypes.cast(notes, ctypes.c_void_p)))
+        out = []
+        for i in range(n):
+            com, nf, wa, ox, oy = _unbe(rec.raw[SPP_WALLET_RECORD_LEN * i:], 5)
+            out.append((None if idx[i] == WALLET_ABSENT else int(idx[i]), int(flags[i]), com, nf, wa, (ox, oy)))
+        if notes is None:
+            return out
+        return out, [tuple(_unbe(notes.raw[NOTE_LEN * i:], 5)) for i in range(n)]
 
 
 def _joined(items, each, what):
