@@ -44,6 +44,13 @@
  *                             "pending" | "withdrawn" (storage.ts:9-26), what exportData / importDeposits carry between browsers
  *                             (storage.ts:233-260) -- recomputed from the three secrets per note, the resident tree and the pool's
  *                             accounts: the nullifier PDAs and the audit records process_withdraw tests (withdraw.rs:94-147)
+ *   spp_merkle_tree_root_at / _proofs_at / _prefix_roots, spp_withdraw_rows_from_tree_at, spp_prove_withdraw_notes_at(_device)
+ *                             getRoot / getProof / the withdraw row and proof for the tree of the first `size` leaves: the root a
+ *                             deposit computed locally and pushed (client/payroll-demo.ts:285-292), which the program takes as sent
+ *                             (shielded_pool_program/src/instructions/deposit.rs:31-36, :73) -- the resident tree is usually ahead
+ *   spp_merkle_tree_find_roots / spp_pool_root_sizes
+ *                             from a root word back to the size it belongs to, and which size this pool accepts a proof against:
+ *                             isRootValid / getRootAge / isRootNearExpiry (demo-frontend/app/lib/on-chain.ts:93-125,202-235)
  *   spp_msm_g1(_pippenger) / spp_ntt_fr   micro-benchmark entry points (BASELINE.json configs[4]); no reference equivalent
  *
  * Conventions: field elements cross the boundary as 32-byte big-endian canonical integers (the encoding
@@ -602,6 +609,57 @@ int spp_merkle_tree_find(spp_merkle_tree* t, size_t count, const uint8_t* leaves
 int spp_wallet_sync(spp_merkle_tree* t, spp_pool* pool /* optional */, size_t count, const uint8_t* deposits /* count * SPP_DEPOSIT_LEN */,
                     const uint8_t* recipients /* optional: count * 32 B recipient words */, uint64_t* indices, uint32_t* flags,
                     uint8_t* records /* optional */, uint8_t* notes /* optional, needs recipients: count * SPP_NOTE_LEN */);
+
+/* ---- the resident tree as of an earlier size: roots, paths and withdraw proofs the chain still accepts ---- */
+/* The pool program never checks the root a deposit pushes: instructions/deposit.rs:31-36 reads the commitment and ignores it, :73
+ * calls state.add_root on the 32 bytes the client sent, and the client computes them from its own copy of the leaves
+ * (client/payroll-demo.ts:285-292).  Two depositors on one base, a lagging indexer or a forged root all leave the chain's
+ * current root short of the chain's leaves, and a prover service that has inserted deposits not confirmed yet is ahead of it in any
+ * case; a proof against the tree as it stands is then SPP_POOL_BAD_ROOT.  The reference's wallet asks "is my root still among the 33
+ * the program accepts" (demo-frontend/app/lib/on-chain.ts:93-125,202-235: isRootValid, getRootAge, isRootNearExpiry).  An append-only
+ * tree holds every earlier version of itself -- one node per level differs from what is stored, csrc/merkle_prefix.hpp has the
+ * argument -- so these calls answer for the tree of the first `size` leaves (what a fresh tree holds after leaves 0..size-1, default
+ * hashes elsewhere, client/merkle.ts:150-156) without building it.
+ *   size: any value in [0, spp_merkle_tree_size], or SPP_TREE_SIZE_NOW, with which every _at call returns exactly what the call it
+ *   is named after returns.  A larger value is SPP_ERR_BAD_INPUT, both numbers in spp_last_error().
+ * An as-of result does not depend on leaves inserted before or after the call, as long as size <= the tree's size at the call: it is
+ * made of values that were final when leaf size-1 arrived.  Per call one single-lane launch computes the `depth` hashes of that
+ * size's frontier on the tree's stream; the launch that reads it follows on the same stream.
+ * The prefix roots R[0..size] are kept in a per-tree device array, extended by the sizes that came since and never recomputed, and
+ * a second index of the kind spp_merkle_tree_find uses (csrc/leaf_index.hpp; same fence: insert launch first, query in a later
+ * launch; same per-tree salt, env SPP_TREE_INDEX_SALT) goes from a root back to its sizes.  Both are built only by
+ * spp_merkle_tree_prefix_roots (the array), spp_merkle_tree_find_roots and spp_pool_root_sizes; insert, deposit, root, proofs, the
+ * notes path, find and wallet_sync neither read nor build them; spp_merkle_tree_free releases them.
+ * All calls are synchronous except spp_prove_withdraw_notes_at_device, serialised on the tree's spp_ctx; NULL arguments are refused
+ * before the context is touched; count == 0 (n == 0) is SPP_OK. */
+#define SPP_TREE_SIZE_NOW UINT64_MAX      /* the tree's size at the call */
+#define SPP_TREE_NO_SIZE  UINT64_MAX      /* in outputs: no prefix of this tree has that root */
+/* getRoot (client/merkle.ts:165-176) of the first `size` leaves */
+int spp_merkle_tree_root_at(spp_merkle_tree* t, uint64_t size, uint8_t root[32]);
+/* getProof (client/merkle.ts:198-221) in that tree; indices and siblings_out as spp_merkle_tree_proofs (any index below 2^depth) */
+int spp_merkle_tree_proofs_at(spp_merkle_tree* t, uint64_t size, size_t n, const uint64_t* indices, uint8_t* siblings_out);
+/* roots = count * 32 B: the roots of sizes first_size .. first_size+count-1, the last of which must be <= the tree's size.  roots[k]
+ * for first_size = 1 is what spp_merkle_tree_deposit reported for leaf k (client/payroll-demo.ts:285-292) */
+int spp_merkle_tree_prefix_roots(spp_merkle_tree* t, uint64_t first_size, size_t count, uint8_t* roots);   /* sizes first_size .. first_size+count-1 */
+/* sizes[i] = the lowest size in [0, tree size] whose root equals roots[i] (count * 32 B) bytewise in canonical big-endian form, or
+ * SPP_TREE_NO_SIZE; matches[i] = how many sizes have that root -- more than 1 only where zero-valued leaves were appended, the default
+ * leaf being 0 (client/merkle.ts:150-156).  A word >= r is not an error: the chain's roots are arbitrary bytes, it matches nothing.
+ * Refused: count > 2^24, a tree of more than 2^30 leaves. */
+int spp_merkle_tree_find_roots(spp_merkle_tree* t, size_t count, const uint8_t* roots, uint64_t* sizes, uint32_t* matches /* optional */);
+/* spp_withdraw_rows_from_tree (client/payroll-demo.ts:323-340) against the first `size` leaves: root = that size's root, siblings the prefix tree's.  A note whose
+ * index is >= size is not a leaf of it: a row the circuit refuses in place (status != 0).  Every other argument check as there */
+int spp_withdraw_rows_from_tree_at(spp_merkle_tree* t, uint64_t size, size_t count, const uint8_t* notes, uint8_t* rows);
+/* spp_prove_withdraw_notes_device / spp_prove_withdraw_notes with such rows, so that check_root (state.rs:36-46) finds the proof's
+ * root among the 33 the program holds (what isRootValid asks, demo-frontend/app/lib/on-chain.ts:93-125): argument checks, pipelining, workspaces and the body and
+ * tail split are theirs; the frontier launch and the rows launch go on the tree's stream, in order */
+int spp_prove_withdraw_notes_at_device(spp_circuit* c, spp_merkle_tree* t, uint64_t size, size_t count, const void* d_notes, const void* d_rs, void* d_proofs, void* d_pws, void* d_status);
+int spp_prove_withdraw_notes_at(spp_circuit* c, spp_merkle_tree* t, uint64_t size, size_t count, const uint8_t* notes, const uint8_t* rs, uint8_t* proofs, uint8_t* pws, int32_t* status);
+/* Which size can I prove against so that this pool accepts it?  sizes[0] is spp_merkle_tree_find_roots' answer for current_root and
+ * sizes[1+k] for roots[k] of spp_pool_state (state.rs:6-46: what check_root compares with); *best = the largest size found, or
+ * SPP_TREE_NO_SIZE when none of the 33 words is a prefix root of this tree -- a fresh pool's zero words never are.  Reads the pool,
+ * changes neither object's visible state.  Refused: NULL pool / t / sizes, a pool and a tree of different spp_ctx, a tree of more
+ * than 2^30 leaves. */
+int spp_pool_root_sizes(spp_pool* pool, spp_merkle_tree* t, uint64_t sizes[33], uint64_t* best /* optional */);
 
 /* ---- micro-benchmark / unit entry points ---- */
 /* data: n = 2^logn elements, 32 B big-endian each, natural order in and out */

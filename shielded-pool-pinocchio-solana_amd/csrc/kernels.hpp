@@ -121,6 +121,16 @@ void launch_withdraw_rows(hipStream_t st, const GkAffine* table, HashConsts hc, 
 void launch_deposit_leaves(hipStream_t st, const GkAffine* table, HashConsts hc, const uint8_t* deposits, Fr* leaves, uint32_t count);
 void launch_deposit_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first, uint32_t count, uint8_t* roots_be,
                           uint8_t* commitments_be);
+// The resident tree as of an earlier size (merkle_prefix.hpp has the rule).  size <= t->count[0], checked by the caller.
+//   launch_merkle_frontier   one lane: frontier[0..depth] of `size`; the as-of launches below read it in a LATER launch on the stream
+//   launch_merkle_gather_at / launch_withdraw_rows_at   launch_merkle_gather / launch_withdraw_rows with the three-case selection
+//   launch_prefix_roots      roots[k] = root of size first_size + k, k < count, one lane each (not big-endian: Fr as the levels hold it)
+void launch_merkle_frontier(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t size, Fr* frontier);
+void launch_merkle_gather_at(hipStream_t st, const MerkleTreeDev* t, uint32_t depth, uint64_t size, const Fr* frontier, const uint64_t* indices,
+                             uint32_t nq, uint8_t* out_be);
+void launch_withdraw_rows_at(hipStream_t st, const GkAffine* table, HashConsts hc, const MerkleTreeDev* t, uint64_t size, const Fr* frontier,
+                             const uint8_t* notes, uint8_t* rows, uint32_t count);
+void launch_prefix_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first_size, uint32_t count, Fr* roots);
 // the leaf index of a resident tree and the wallet sync over it (leaf_index.hpp has the structures and what a lane does).  An insert
 // launch and a query launch never coincide: insert first, query in a later launch on the same stream.
 struct LeafIndex;

@@ -13,6 +13,9 @@
 //   k_leaf_index_insert / k_leaf_find / k_wallet_identity / k_wallet_locate
 //                         demo-frontend/app/lib/storage.ts:9-26,45-50 (leafIndex, nullifier, waCommitment, status of a DepositRecord
 //                         from the secrets, the leaf list and the pool's accounts; the leaf index is leaf_index.hpp)
+//   k_merkle_frontier / k_prefix_roots / k_merkle_gather_at / k_withdraw_rows_at
+//                         the same getRoot / getProof / withdraw row for the tree of the first n leaves (merkle_prefix.hpp): the root
+//                         a deposit pushed (instructions/deposit.rs:31-36,73), which demo-frontend/app/lib/on-chain.ts:93-125 looks for
 //   k_poseidon2_sponge    ct_helper/src/main.nr:15-34 (= scripts/generate_audit.py:355-374)
 //   k_audit_open          scripts/rlwe_decrypt.py:61-149 for a batch of (pw, ciphertext) records, with the binding checks it omits
 //   k_rlwe_keygen         scripts/rlwe_keygen.py:98-116 (the audit key pair), k_rlwe_key_noise: the check a key holder can make
@@ -24,6 +27,7 @@
 #include "audit_open.hpp"
 #include "rlwe_keygen.hpp"
 #include "leaf_index.hpp"
+#include "merkle_prefix.hpp"
 
 namespace spp {
 
@@ -331,6 +335,47 @@ __global__ void __launch_bounds__(64) k_merkle_gather(const MerkleTreeDev* __res
   const Fr v = sib < t->count[l] ? t->level[l][sib] : t->dflt[l];
   store_be(out_be + ((size_t)q * depth + l) * 32, v);
 }
+// ---- the tree as of an earlier size (merkle_prefix.hpp: default / frontier / stored; one frontier node per level) ----
+__device__ __forceinline__ Fr poseidon_hash2_inline(const HashConsts& hc, const Fr& a, const Fr& b) {
+  Fr s[3] = {Fr::zero(), a, b};
+  poseidon_permute29<3, false>(s, hc.pos3_rc, hc.pos3_mds29, 57, PoseidonNoEmit{});
+  return s[0];
+}
+// F[0..depth] of the prefix tree of `size` leaves: depth dependent permutations on one lane, once per as-of call, so that the
+// per-note and per-sibling kernels below only select
+__global__ void __launch_bounds__(64) k_merkle_frontier(HashConsts hc, const MerkleTreeDev* __restrict__ t, uint64_t size, Fr* __restrict__ F) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  prefix_walk(size, t->depth, [&](uint32_t l) { return (const Fr*)t->level[l]; }, t->dflt,
+              [&](const Fr& a, const Fr& b) { return poseidon_hash2_inline(hc, a, b); }, F);
+}
+// R[first_size + g]: the same walk per lane, nothing kept but the root (k_deposit_roots' loop for leaf n-1, R[0] = dflt[depth])
+__global__ void __launch_bounds__(64) k_prefix_roots(HashConsts hc, const MerkleTreeDev* __restrict__ t, uint64_t first_size, uint32_t count,
+                                                     Fr* __restrict__ roots) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  roots[g] = prefix_walk(first_size + g, t->depth, [&](uint32_t l) { return (const Fr*)t->level[l]; }, t->dflt,
+                         [&](const Fr& a, const Fr& b) { return poseidon_hash2_inline(hc, a, b); }, (Fr*)nullptr);
+}
+// k_merkle_gather against the prefix tree of `size` leaves; F from k_merkle_frontier, an earlier launch
+__global__ void __launch_bounds__(64) k_merkle_gather_at(const MerkleTreeDev* __restrict__ t, uint64_t size, const Fr* __restrict__ F,
+                                                         const uint64_t* __restrict__ indices, uint32_t nq, uint8_t* __restrict__ out_be) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t depth = t->depth;
+  if (g >= nq * depth) return;
+  const uint32_t q = g / depth, l = g % depth;
+  store_be(out_be + ((size_t)q * depth + l) * 32, prefix_node(size, l, (indices[q] >> l) ^ 1, (const Fr*)t->level[l], t->dflt, F));
+}
+void launch_merkle_frontier(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t size, Fr* frontier) {
+  hipLaunchKernelGGL(k_merkle_frontier, dim3(1), dim3(64), 0, st, hc, t, size, frontier);
+}
+void launch_prefix_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first_size, uint32_t count, Fr* roots) {
+  if (count) hipLaunchKernelGGL(k_prefix_roots, dim3((count + 63) / 64), dim3(64), 0, st, hc, t, first_size, count, roots);
+}
+void launch_merkle_gather_at(hipStream_t st, const MerkleTreeDev* t, uint32_t depth, uint64_t size, const Fr* frontier, const uint64_t* indices,
+                             uint32_t nq, uint8_t* out_be) {
+  const uint32_t n = nq * depth;
+  if (n) hipLaunchKernelGGL(k_merkle_gather_at, dim3((n + 63) / 64), dim3(64), 0, st, t, size, frontier, indices, nq, out_be);
+}
 void launch_merkle_defaults(hipStream_t st, HashConsts hc, Fr* out, uint32_t depth) {
   hipLaunchKernelGGL(k_merkle_defaults, dim3(1), dim3(64), 0, st, hc, out, depth);
 }
@@ -401,8 +446,14 @@ static constexpr uint32_t NOTE_BYTES = 160;
 __device__ __forceinline__ void copy32(uint8_t* __restrict__ o, const uint8_t* __restrict__ p) {
   for (int i = 0; i < 32; i++) o[i] = p[i];
 }
-__global__ void __launch_bounds__(64) k_withdraw_rows(const GkAffine* __restrict__ table, HashConsts hc, const MerkleTreeDev* __restrict__ t,
-                                                      const uint8_t* __restrict__ notes, uint8_t* __restrict__ rows, uint32_t count) {
+// One body, two entries.  ASOF = false is k_withdraw_rows as it always was (size and F unused); ASOF = true takes root and siblings
+// from the prefix tree of `size` leaves: the root is F[depth], a sibling one of merkle_prefix.hpp's three cases.  The frontier is
+// k_merkle_frontier's, an earlier launch: no second permutation call site and no per-lane walk here (see the VGPR note below).
+// The pointers carry no __restrict__ here, the entries' parameters do: with it repeated on the inlined body k_withdraw_rows comes
+// out with another register allocation; as written its instructions are the former ones but for one commutative operand order.
+template <bool ASOF>
+__device__ __forceinline__ void withdraw_rows_body(const GkAffine* table, const HashConsts& hc, const MerkleTreeDev* t, uint64_t size, const Fr* F,
+                                                   const uint8_t* notes, uint8_t* rows, uint32_t count) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= count) return;
   const uint32_t depth = t->depth;
@@ -432,16 +483,36 @@ __global__ void __launch_bounds__(64) k_withdraw_rows(const GkAffine* __restrict
   for (int i = 0; i < 24; i++) in_range &= nt[128 + i] == 0;
   for (int i = 24; i < 32; i++) idx = (idx << 8) | nt[128 + i];
   in_range &= (idx >> depth) == 0;
-  // root at call time (spp_merkle_tree_root), siblings as k_merkle_gather
-  store_be(o, t->count[depth] ? t->level[depth][0] : t->dflt[depth]);
-  for (uint32_t l = 0; l < depth; l++) {
-    const uint64_t sib = (idx >> l) ^ 1;
-    store_be(o + (10 + l) * 32, in_range && sib < t->count[l] ? t->level[l][sib] : t->dflt[l]);
+  if constexpr (ASOF) {
+    // the prefix tree's root and siblings (spp_merkle_tree_root_at / _proofs_at), as k_merkle_gather_at
+    store_be(o, F[depth]);
+    for (uint32_t l = 0; l < depth; l++)
+      store_be(o + (10 + l) * 32, in_range ? prefix_node(size, l, (idx >> l) ^ 1, (const Fr*)t->level[l], t->dflt, F) : t->dflt[l]);
+  } else {
+    // root at call time (spp_merkle_tree_root), siblings as k_merkle_gather
+    store_be(o, t->count[depth] ? t->level[depth][0] : t->dflt[depth]);
+    for (uint32_t l = 0; l < depth; l++) {
+      const uint64_t sib = (idx >> l) ^ 1;
+      store_be(o + (10 + l) * 32, in_range && sib < t->count[l] ? t->level[l][sib] : t->dflt[l]);
+    }
   }
+}
+__global__ void __launch_bounds__(64) k_withdraw_rows(const GkAffine* __restrict__ table, HashConsts hc, const MerkleTreeDev* __restrict__ t,
+                                                      const uint8_t* __restrict__ notes, uint8_t* __restrict__ rows, uint32_t count) {
+  withdraw_rows_body<false>(table, hc, t, 0, nullptr, notes, rows, count);
+}
+__global__ void __launch_bounds__(64) k_withdraw_rows_at(const GkAffine* __restrict__ table, HashConsts hc, const MerkleTreeDev* __restrict__ t,
+                                                         uint64_t size, const Fr* __restrict__ F, const uint8_t* __restrict__ notes,
+                                                         uint8_t* __restrict__ rows, uint32_t count) {
+  withdraw_rows_body<true>(table, hc, t, size, F, notes, rows, count);
 }
 void launch_withdraw_rows(hipStream_t st, const GkAffine* table, HashConsts hc, const MerkleTreeDev* t, const uint8_t* notes, uint8_t* rows,
                           uint32_t count) {
   if (count) hipLaunchKernelGGL(k_withdraw_rows, dim3((count + 63) / 64), dim3(64), 0, st, table, hc, t, notes, rows, count);
+}
+void launch_withdraw_rows_at(hipStream_t st, const GkAffine* table, HashConsts hc, const MerkleTreeDev* t, uint64_t size, const Fr* frontier,
+                             const uint8_t* notes, uint8_t* rows, uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_withdraw_rows_at, dim3((count + 63) / 64), dim3(64), 0, st, table, hc, t, size, frontier, notes, rows, count);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 //                        the experiment switches of the proving path from the environment (read_switches)
 //   spp_prove.cpp        workspaces, the proving pipeline and its batch entry points, timing queries
 //   spp_setup.cpp        circuit construction (host only) and the trusted setup on the GPU
-//   spp_witness_api.cpp  witness-input kernels, Merkle trees and their leaf index (wallet sync), auditor side
+//   spp_witness_api.cpp  witness-input kernels, Merkle trees, their leaf index (wallet sync) and earlier sizes (merkle_prefix.hpp), auditor side
 //   spp_verify_api.cpp   verification and pairing checks
 //   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
@@ -171,12 +171,26 @@ struct spp_merkle_tree {
   uint32_t index_slots = 0;
   uint64_t indexed = 0, index_salt = 0;
   bool index_salted = false;
+  // the tree as of an earlier size (merkle_prefix.hpp), all lazily made by the _at calls, spp_merkle_tree_prefix_roots / _find_roots
+  // and spp_pool_root_sizes and by nothing else:
+  Fr* d_frontier = nullptr;                    // 33 words: F[0..depth] of the as-of call last enqueued on the context's stream
+  Fr* d_roots = nullptr;                       // R[n], n < roots_done, room for roots_cap: extended, never recomputed
+  uint64_t roots_cap = 0, roots_done = 0;
+  uint32_t* d_root_index = nullptr;            // a second leaf index, over d_roots (same salt): entries [0, roots_indexed)
+  uint32_t root_index_slots = 0;
+  uint64_t roots_indexed = 0;
 };
+// Resolves and checks `size` of an as-of call (SPP_TREE_SIZE_NOW, or <= the tree's size: else SPP_ERR_BAD_INPUT naming both) and
+// enqueues k_merkle_frontier for it on the context's stream, into t->d_frontier.  ctx->mu held, device set, constants ready
+// (spp_witness_api.cpp).
+int spp_tree_frontier_enqueue(spp_merkle_tree* t, uint64_t* size);
 // the pool's two resident sets (SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS) and their salt, for a launch that only reads them
 // (spp_pool_api.cpp).  Returns the pool's context; sets (two entries) and salt are written when sets is not NULL, which needs that
 // context locked
 struct spp_pool;
 spp_ctx* spp_pool_view(spp_pool* p, PoolSet* sets, uint64_t* salt);
+// current_root, then roots[0..31] of the pool's ring as spp_pool_state lays them out: 33 x 32 B.  Needs the pool's context locked
+void spp_pool_ring_words(spp_pool* p, uint8_t words[33 * 32]);
 template <class T>
 inline int ctx_upload(spp_ctx* ctx, T** dst, const std::vector<T>& src) {
   HIP_TRY(dev_upload(dst, src));

@@ -229,6 +229,10 @@ spp_ctx* spp_pool_view(spp_pool* p, PoolSet* sets, uint64_t* salt) {
   }
   return p->ctx;
 }
+void spp_pool_ring_words(spp_pool* p, uint8_t words[33 * 32]) {
+  memcpy(words, p->state.current_root, 32);
+  for (uint32_t k = 0; k < POOL_ROOTS; k++) memcpy(words + 32 * (1 + k), p->state.roots[k], 32);
+}
 
 extern "C" int spp_pool_set_verifier(spp_pool* p, int mode, uint32_t group) {
   if (!p) return fail(SPP_ERR_BAD_INPUT, "NULL argument");

@@ -400,16 +400,22 @@ static int withdraw_notes_args(spp_circuit* c, spp_merkle_tree* t) {
                 10 + t->depth);
   return SPP_OK;
 }
-extern "C" int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* t, size_t count, const void* d_notes, const void* d_rs,
-                                               void* d_proofs, void* d_pws, void* d_status) {
+// size == SPP_TREE_SIZE_NOW: the tree as it stands, the launches spp_prove_withdraw_notes_device always made.  Any other size: the
+// first `size` leaves (merkle_prefix.hpp) -- k_merkle_frontier, then the as-of rows kernel for body and tail, all on the tree's
+// stream in order; the size is checked under the lock, before a workspace is taken.
+static int prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* t, uint64_t size, size_t count, const void* d_notes, const void* d_rs,
+                                       void* d_proofs, void* d_pws, void* d_status) {
   if (!c || !t || !d_notes || !d_rs || !d_proofs || !d_pws || !d_status) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   if (int e = withdraw_notes_args(c, t)) return e;
-  if (count == 0) return SPP_OK;
+  const bool asof = size != SPP_TREE_SIZE_NOW;
+  if (count == 0 && !asof) return SPP_OK;
   if (count > (1u << 20)) return fail(SPP_ERR_BAD_INPUT, "batch too large");
   spp_ctx* ctx = c->ctx;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(hipSetDevice(ctx->device));
   if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  if (asof && size > t->n_leaves) return spp_tree_frontier_enqueue(t, &size);   // the refusal, also for count == 0
+  if (count == 0) return SPP_OK;
   Workspace* wp;
   if (int e = take_sized_workspace(c, count, c->generic_solver, &wp)) return e;
   Workspace &w = *wp, &wt = c->ws[c->next_ws];
@@ -417,8 +423,16 @@ extern "C" int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* 
   const uint8_t* notes = (const uint8_t*)d_notes;
   HIP_TRY(hipStreamWaitEvent(ctx->stream, w.ev_in, 0));
   if (tail) HIP_TRY(hipStreamWaitEvent(ctx->stream, wt.ev_in, 0));
-  launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes, w.d_inputs, (uint32_t)body);
-  if (tail) launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes + body * SPP_NOTE_LEN, wt.d_inputs, (uint32_t)tail);
+  if (asof) {
+    if (int e = spp_tree_frontier_enqueue(t, &size)) return e;
+    launch_withdraw_rows_at(ctx->stream, ctx->gk_table, ctx->hc, t->dev, size, t->d_frontier, notes, w.d_inputs, (uint32_t)body);
+    if (tail)
+      launch_withdraw_rows_at(ctx->stream, ctx->gk_table, ctx->hc, t->dev, size, t->d_frontier, notes + body * SPP_NOTE_LEN, wt.d_inputs,
+                              (uint32_t)tail);
+  } else {
+    launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes, w.d_inputs, (uint32_t)body);
+    if (tail) launch_withdraw_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, notes + body * SPP_NOTE_LEN, wt.d_inputs, (uint32_t)tail);
+  }
   HIP_TRY(hipEventRecord(w.ev_rows, ctx->stream));
   HIP_TRY(hipStreamWaitEvent(w.st, w.ev_rows, 0));
   if (tail) HIP_TRY(hipStreamWaitEvent(wt.st, w.ev_rows, 0));
@@ -426,6 +440,14 @@ extern "C" int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* 
   if (int e = prove_on_device(c, w, body, w.d_inputs, io)) return e;
   if (!tail) return SPP_OK;
   return prove_on_device(c, wt, tail, wt.d_inputs, io.at(c, body));
+}
+extern "C" int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* t, size_t count, const void* d_notes, const void* d_rs,
+                                               void* d_proofs, void* d_pws, void* d_status) {
+  return prove_withdraw_notes_device(c, t, SPP_TREE_SIZE_NOW, count, d_notes, d_rs, d_proofs, d_pws, d_status);
+}
+extern "C" int spp_prove_withdraw_notes_at_device(spp_circuit* c, spp_merkle_tree* t, uint64_t size, size_t count, const void* d_notes,
+                                                  const void* d_rs, void* d_proofs, void* d_pws, void* d_status) {
+  return prove_withdraw_notes_device(c, t, size, count, d_notes, d_rs, d_proofs, d_pws, d_status);
 }
 // Host form: all rows are built (one gather, one root) before spp_prove_batch proves them in chunks.
 extern "C" int spp_prove_withdraw_notes(spp_circuit* c, spp_merkle_tree* t, size_t count, const uint8_t* notes, const uint8_t* rs, uint8_t* proofs,
@@ -436,6 +458,17 @@ extern "C" int spp_prove_withdraw_notes(spp_circuit* c, spp_merkle_tree* t, size
   if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many notes in one call");
   std::vector<uint8_t> rows(count * c->in_stride);
   if (int e = spp_withdraw_rows_from_tree(t, count, notes, rows.data())) return e;
+  return spp_prove_batch(c, count, rows.data(), rs, proofs, pws, status);
+}
+extern "C" int spp_prove_withdraw_notes_at(spp_circuit* c, spp_merkle_tree* t, uint64_t size, size_t count, const uint8_t* notes, const uint8_t* rs,
+                                           uint8_t* proofs, uint8_t* pws, int32_t* status) {
+  if (size == SPP_TREE_SIZE_NOW) return spp_prove_withdraw_notes(c, t, count, notes, rs, proofs, pws, status);
+  if (!c || !t || !notes || !proofs || !pws) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int e = withdraw_notes_args(c, t)) return e;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many notes in one call");
+  std::vector<uint8_t> rows(std::max<size_t>(count, 1) * c->in_stride);
+  if (int e = spp_withdraw_rows_from_tree_at(t, size, count, notes, rows.data())) return e;   // refuses a size past the tree, also for count == 0
+  if (count == 0) return SPP_OK;
   return spp_prove_batch(c, count, rows.data(), rs, proofs, pws, status);
 }
 extern "C" int spp_commitment_challenge(spp_circuit* c, size_t count, const uint8_t* inputs, uint8_t* challenges) {

@@ -291,6 +291,9 @@ extern "C" void spp_merkle_tree_free(spp_merkle_tree* t) {
   if (t->dev) hipFree(t->dev);
   if (t->d_dflt) hipFree(t->d_dflt);
   if (t->d_index) hipFree(t->d_index);
+  if (t->d_frontier) hipFree(t->d_frontier);
+  if (t->d_roots) hipFree(t->d_roots);
+  if (t->d_root_index) hipFree(t->d_root_index);
   delete t;
 }
 extern "C" uint64_t spp_merkle_tree_size(const spp_merkle_tree* t) { return t ? t->n_leaves : 0; }
@@ -448,31 +451,36 @@ static int mt_index_salt(uint64_t* salt) {
 // Brings the index up to the tree (ctx->mu held, device set): leaves [indexed, n_leaves) are inserted in ONE launch on the context's
 // stream; the caller's query is a later launch.  A table that would pass half full is allocated again at the larger size and every
 // leaf reinserted.
-static int mt_index_sync(spp_merkle_tree* t, LeafIndex* ix) {
-  if (t->n_leaves > LEAF_INDEX_MAX_LEAVES)
-    return fail(SPP_ERR_BAD_INPUT, "the tree has %llu leaves: the leaf index covers at most 2^30", (unsigned long long)t->n_leaves);
+// The same for any table of the tree over an Fr array (the leaf index over level 0, the root index over d_roots): entries
+// [*indexed, n) of `values` are inserted, `want` slots wanted.
+static int mt_table_sync(spp_merkle_tree* t, uint32_t** d_slots, uint32_t* slots, uint64_t* indexed, const Fr* values, uint64_t n, uint32_t want,
+                         LeafIndex* ix) {
   if (!t->index_salted) {
     if (int e = mt_index_salt(&t->index_salt)) return e;
     t->index_salted = true;
   }
   hipStream_t st = t->ctx->stream;
-  const uint32_t want = leaf_index_slots(t->n_leaves);
-  if (!t->d_index || want > t->index_slots) {
-    if (t->d_index) {
+  if (!*d_slots || want > *slots) {
+    if (*d_slots) {
       HIP_TRY(hipStreamSynchronize(st));
-      hipFree(t->d_index);
-      t->d_index = nullptr;
+      hipFree(*d_slots);
+      *d_slots = nullptr;
     }
-    t->index_slots = 0;
-    t->indexed = 0;
-    HIP_TRY(hipMalloc((void**)&t->d_index, (size_t)want * sizeof(uint32_t)));
-    t->index_slots = want;
-    HIP_TRY(hipMemsetAsync(t->d_index, 0xFF, (size_t)want * sizeof(uint32_t), st));
+    *slots = 0;
+    *indexed = 0;
+    HIP_TRY(hipMalloc((void**)d_slots, (size_t)want * sizeof(uint32_t)));
+    *slots = want;
+    HIP_TRY(hipMemsetAsync(*d_slots, 0xFF, (size_t)want * sizeof(uint32_t), st));
   }
-  *ix = LeafIndex{t->d_index, t->index_slots - 1, t->index_salt};
-  launch_leaf_index_insert(st, *ix, t->host.level[0], (uint32_t)t->indexed, (uint32_t)(t->n_leaves - t->indexed));
-  t->indexed = t->n_leaves;
+  *ix = LeafIndex{*d_slots, *slots - 1, t->index_salt};
+  launch_leaf_index_insert(st, *ix, values, (uint32_t)*indexed, (uint32_t)(n - *indexed));
+  *indexed = n;
   return SPP_OK;
+}
+static int mt_index_sync(spp_merkle_tree* t, LeafIndex* ix) {
+  if (t->n_leaves > LEAF_INDEX_MAX_LEAVES)
+    return fail(SPP_ERR_BAD_INPUT, "the tree has %llu leaves: the leaf index covers at most 2^30", (unsigned long long)t->n_leaves);
+  return mt_table_sync(t, &t->d_index, &t->index_slots, &t->indexed, t->host.level[0], t->n_leaves, leaf_index_slots(t->n_leaves), ix);
 }
 
 extern "C" int spp_merkle_tree_find(spp_merkle_tree* t, size_t count, const uint8_t* leaves, const uint64_t* from, uint64_t* indices,
@@ -548,6 +556,201 @@ extern "C" int spp_wallet_sync(spp_merkle_tree* t, spp_pool* pool, size_t count,
   if (notes) HIP_TRY(hipMemcpyAsync(notes, dn.p, count * SPP_NOTE_LEN, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// The tree as of an earlier size: roots, paths and withdraw rows of the first `size` leaves, the roots of all sizes and the way
+// back from a root word to its size (include/spp.h; the rule and why stored nodes can be reused is merkle_prefix.hpp).  Every as-of
+// call enqueues k_merkle_frontier for its size and then the launch that reads t->d_frontier, both on the context's stream: a later
+// call's frontier is stream-ordered behind the earlier call's reader.
+// -----------------------------------------------------------------------------------------------------
+int spp_tree_frontier_enqueue(spp_merkle_tree* t, uint64_t* size) {
+  if (*size == SPP_TREE_SIZE_NOW) *size = t->n_leaves;
+  if (*size > t->n_leaves)
+    return fail(SPP_ERR_BAD_INPUT, "size %llu is larger than the tree, which has %llu leaves", (unsigned long long)*size,
+                (unsigned long long)t->n_leaves);
+  if (!t->d_frontier) HIP_TRY(hipMalloc((void**)&t->d_frontier, 33 * sizeof(Fr)));
+  launch_merkle_frontier(t->ctx->stream, t->ctx->hc, t->dev, *size, t->d_frontier);
+  return SPP_OK;
+}
+extern "C" int spp_merkle_tree_root_at(spp_merkle_tree* t, uint64_t size, uint8_t root[32]) {
+  if (!t || !root) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (size == SPP_TREE_SIZE_NOW) return spp_merkle_tree_root(t, root);
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  if (int e = spp_tree_frontier_enqueue(t, &size)) return e;
+  Fr v;
+  HIP_TRY(hipMemcpyAsync(&v, t->d_frontier + t->depth, sizeof(Fr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  v.to_bytes_be(root);
+  return SPP_OK;
+}
+extern "C" int spp_merkle_tree_proofs_at(spp_merkle_tree* t, uint64_t size, size_t n, const uint64_t* indices, uint8_t* siblings_out) {
+  if (!t || (n && (!indices || !siblings_out))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (size == SPP_TREE_SIZE_NOW) return spp_merkle_tree_proofs(t, n, indices, siblings_out);
+  if (n > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many queries in one call");
+  for (size_t q = 0; q < n; q++)
+    if (indices[q] >= ((uint64_t)1 << t->depth)) return fail(SPP_ERR_BAD_INPUT, "query index out of range");
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (size > t->n_leaves) return spp_tree_frontier_enqueue(t, &size);   // the refusal, also for n == 0
+  if (n == 0) return SPP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  if (int e = spp_tree_frontier_enqueue(t, &size)) return e;
+  DevBuf di, dout;
+  UP(di, indices, n * sizeof(uint64_t));
+  HIP_TRY(dout.alloc(n * t->depth * 32));
+  launch_merkle_gather_at(st, t->dev, t->depth, size, t->d_frontier, di.as<uint64_t>(), (uint32_t)n, dout.as<uint8_t>());
+  HIP_TRY(hipMemcpyAsync(siblings_out, dout.p, n * t->depth * 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+extern "C" int spp_withdraw_rows_from_tree_at(spp_merkle_tree* t, uint64_t size, size_t count, const uint8_t* notes, uint8_t* rows) {
+  if (!t || !notes || !rows) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (size == SPP_TREE_SIZE_NOW) return spp_withdraw_rows_from_tree(t, count, notes, rows);
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many notes in one call");
+  if (int e = spp_check_notes(count, notes)) return e;
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (size > t->n_leaves) return spp_tree_frontier_enqueue(t, &size);   // the refusal, also for count == 0
+  if (count == 0) return SPP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  if (int e = spp_tree_frontier_enqueue(t, &size)) return e;
+  const size_t row_bytes = (size_t)(10 + t->depth) * 32;
+  DevBuf dn, dr;
+  UP(dn, notes, count * SPP_NOTE_LEN);
+  HIP_TRY(dr.alloc(count * row_bytes));
+  launch_withdraw_rows_at(st, ctx->gk_table, ctx->hc, t->dev, size, t->d_frontier, dn.as<uint8_t>(), dr.as<uint8_t>(), (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(rows, dr.p, count * row_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+// R[0 .. n_leaves] resident (ctx->mu held, device set): the array grows by doubling, what was computed is copied, and only the
+// sizes that came since are walked -- a prefix root never changes (merkle_prefix.hpp)
+static int mt_roots_sync(spp_merkle_tree* t) {
+  spp_ctx* ctx = t->ctx;
+  hipStream_t st = ctx->stream;
+  const uint64_t want = t->n_leaves + 1;
+  if (want > t->roots_cap) {
+    uint64_t cap = std::max<uint64_t>(t->roots_cap, 1024);
+    while (cap < want) cap *= 2;
+    cap += 1;   // sizes 0 .. cap-1: a full tree of 2^k leaves has 2^k + 1 of them
+    Fr* nw = nullptr;
+    HIP_TRY(hipMalloc((void**)&nw, cap * sizeof(Fr)));
+    if (t->d_roots) {
+      hipError_t e = t->roots_done ? hipMemcpyAsync(nw, t->d_roots, t->roots_done * sizeof(Fr), hipMemcpyDeviceToDevice, st) : hipSuccess;
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e != hipSuccess) {
+        hipFree(nw);
+        return fail(SPP_ERR_HIP, "prefix roots: %s", hipGetErrorString(e));
+      }
+      hipFree(t->d_roots);
+    }
+    t->d_roots = nw;
+    t->roots_cap = cap;
+  }
+  while (t->roots_done < want) {
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(want - t->roots_done, (uint64_t)1 << 30);
+    launch_prefix_roots(st, ctx->hc, t->dev, t->roots_done, chunk, t->d_roots + t->roots_done);
+    t->roots_done += chunk;
+  }
+  return SPP_OK;
+}
+extern "C" int spp_merkle_tree_prefix_roots(spp_merkle_tree* t, uint64_t first_size, size_t count, uint8_t* roots) {
+  if (!t || (count && !roots)) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many sizes in one call (%zu; at most 2^24)", count);
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (count == 0 ? first_size > t->n_leaves : (first_size > t->n_leaves || count - 1 > t->n_leaves - first_size))
+    return fail(SPP_ERR_BAD_INPUT, "sizes %llu .. %llu reach past the tree, which has %llu leaves", (unsigned long long)first_size,
+                (unsigned long long)(first_size + count - (count ? 1 : 0)), (unsigned long long)t->n_leaves);
+  if (count == 0) return SPP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  hipStream_t st = ctx->stream;
+  if (int e = mt_roots_sync(t)) return e;
+  DevBuf dout;
+  HIP_TRY(dout.alloc(count * 32));
+  launch_fr_to_be(st, t->d_roots + first_size, dout.as<uint8_t>(), (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(roots, dout.p, count * 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+// The root index over R (leaf_index.hpp: same table, same fence, the tree's salt), brought up to the tree, then one query launch.
+// A word >= r is the encoding of no field element: it is answered here, and a zero word is queried in its place.  ctx->mu held,
+// device set, constants ready.
+static int mt_find_roots(spp_merkle_tree* t, size_t count, const uint8_t* roots, uint64_t* sizes, uint32_t* matches) {
+  if (t->n_leaves > LEAF_INDEX_MAX_LEAVES)
+    return fail(SPP_ERR_BAD_INPUT, "the tree has %llu leaves: the root index covers at most 2^30", (unsigned long long)t->n_leaves);
+  hipStream_t st = t->ctx->stream;
+  if (int e = mt_roots_sync(t)) return e;
+  const uint64_t entries = t->n_leaves + 1;
+  // 2^30 + 1 entries in 2^31 slots: a little over half full, which the probing does not mind (it needs one empty slot)
+  const uint32_t want = entries > LEAF_INDEX_MAX_LEAVES ? 1u << 31 : leaf_index_slots(entries);
+  LeafIndex ix;
+  if (int e = mt_table_sync(t, &t->d_root_index, &t->root_index_slots, &t->roots_indexed, t->d_roots, entries, want, &ix)) return e;
+  std::vector<uint8_t> keys(roots, roots + 32 * count);
+  std::vector<size_t> foreign;
+  for (size_t i = 0; i < count; i++)
+    if (!be_is_canonical<FrParams>(roots + 32 * i)) {
+      foreign.push_back(i);
+      memset(keys.data() + 32 * i, 0, 32);
+    }
+  DevBuf dk, di, dm;
+  UP(dk, keys.data(), count * 32);
+  HIP_TRY(di.alloc(count * sizeof(uint64_t)));
+  if (matches) HIP_TRY(dm.alloc(count * sizeof(uint32_t)));
+  launch_leaf_find(st, ix, t->d_roots, dk.as<uint8_t>(), nullptr, di.as<uint64_t>(), matches ? dm.as<uint32_t>() : nullptr, (uint32_t)count);
+  HIP_TRY(hipMemcpyAsync(sizes, di.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (matches) HIP_TRY(hipMemcpyAsync(matches, dm.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  for (size_t i : foreign) {
+    sizes[i] = SPP_TREE_NO_SIZE;
+    if (matches) matches[i] = 0;
+  }
+  return SPP_OK;
+}
+extern "C" int spp_merkle_tree_find_roots(spp_merkle_tree* t, size_t count, const uint8_t* roots, uint64_t* sizes, uint32_t* matches) {
+  if (!t || (count && (!roots || !sizes))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (count == 0) return SPP_OK;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many roots in one call (%zu; at most 2^24)", count);
+  spp_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  return mt_find_roots(t, count, roots, sizes, matches);
+}
+extern "C" int spp_pool_root_sizes(spp_pool* pool, spp_merkle_tree* t, uint64_t sizes[33], uint64_t* best) {
+  if (!pool || !t || !sizes) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  spp_ctx* ctx = t->ctx;
+  if (spp_pool_view(pool, nullptr, nullptr) != ctx) return fail(SPP_ERR_BAD_INPUT, "the pool belongs to another spp_ctx than the tree");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  uint8_t words[33 * 32];
+  spp_pool_ring_words(pool, words);
+  uint64_t found[33];
+  if (int e = mt_find_roots(t, 33, words, found, nullptr)) return e;
+  uint64_t top = SPP_TREE_NO_SIZE;
+  for (int k = 0; k < 33; k++) {
+    sizes[k] = found[k];
+    if (found[k] != SPP_TREE_NO_SIZE && (top == SPP_TREE_NO_SIZE || found[k] > top)) top = found[k];
+  }
+  if (best) *best = top;
   return SPP_OK;
 }
 

@@ -27,7 +27,12 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               #   {"deposit": {"root"}}  {"submit_audit": {"proof", "pw"}}  {"withdraw": {"proof", "pw", "recipient"}}
                               # prints one result name per line (OK, AUDIT_EXISTS, NO_AUDIT_RECORD, BAD_ROOT, NULLIFIER_USED,
                               # BAD_RECIPIENT, BAD_PROOF; a deposit only pushes its root and prints OK).  --verifier rlc checks
-                              # the proofs by random linear combination (spp_pool_set_verifier): the same lines
+                              # the proofs by random linear combination (spp_pool_set_verifier): the same lines.
+                              # A deposit may carry "commitment" beside "root" (all deposits of a log or none; --depth of the tree,
+                              # default 16): the leaves then go into a resident tree and a deposit's line reads `OK root-of-leaves`
+                              # or `OK NOT-root-of-leaves` (the program takes new_root as sent, instructions/deposit.rs:31-36,73),
+                              # an accepted withdraw's `OK size <n>` -- the size of the leaf list whose root it used -- or
+                              # `OK foreign`, and a closing `roots:` line counts both
     python -m spp.cli wallet-sync secrets.json leaves.txt [--spent nullifiers.txt] [--audited wa.txt] [--vk withdraw.vk audit.vk] [--recipient HEX]
                               # a wallet's DepositRecords (demo-frontend/app/lib/storage.ts:9-26) from its secrets -- a JSON list of
                               # {"secretKey", "amount", "randomness"} -- and the chain's leaves, one hex leaf per line in chain order
@@ -231,11 +236,81 @@ def parse_pool_log(lines):
     return out
 
 
+def parse_pool_commitments(lines, depth=16):
+    """The "commitment" a deposit line of a pool-replay log may carry beside "root" (the leaf the deposit appends,
+    instructions/deposit.rs:31-36), as ints in log order; None unless EVERY deposit of the log carries one (a log without any is
+    replayed as before).  Raises ValueError naming the line: some deposits with and some without, a commitment that is not 32
+    bytes or not a canonical field element, more deposits than a tree of `depth` holds."""
+    out, without = [], None
+    for no, line in enumerate(lines, 1):
+        if not line.strip():
+            continue
+        d = json.loads(line)
+        (kind, body), = d.items()
+        if kind != "deposit":
+            continue
+        if "commitment" not in body:
+            without = without or no
+            continue
+        try:
+            text = body["commitment"]
+            v = bytes.fromhex(text[2:] if text.lower().startswith("0x") else text)
+        except (ValueError, TypeError, AttributeError) as e:
+            raise ValueError("line %d: deposit.commitment is not a hexadecimal string (%s)" % (no, e))
+        if len(v) != 32:
+            raise ValueError("line %d: deposit.commitment must be 32 bytes, got %d" % (no, len(v)))
+        if int.from_bytes(v, "big") >= R:
+            raise ValueError("line %d: deposit.commitment is not a canonical field element" % no)
+        out.append(int.from_bytes(v, "big"))
+    if not out:
+        return None
+    if without:
+        raise ValueError("line %d: this deposit carries no commitment, others do (all of them or none)" % without)
+    if not 1 <= depth <= 32 or len(out) > 1 << depth:
+        raise ValueError("%d deposits do not fit a tree of depth %d (1..32)" % (len(out), depth))
+    return out
+
+
+def _print_root_audit(ctx, witness, depth, log, codes, commitments):
+    """pool-replay of a log whose deposits carry their commitments: the leaves go into a resident tree, and every line says what
+    the program cannot know (it takes new_root as sent, instructions/deposit.rs:31-36,73) -- a deposit whether the root it pushed is
+    the root of the leaves so far, an accepted withdraw which size of the leaf list its root belongs to, or `foreign`."""
+    with witness.ShieldedPoolMerkleTree(ctx, depth) as tree:
+        tree.insert_many(commitments)
+        honest = []                                          # honest[k]: the root after deposits 0..k (spp_merkle_tree_prefix_roots)
+        for i in range(0, len(commitments), _POOL_LOG_CHUNK):
+            honest += tree.prefix_roots(1 + i, min(_POOL_LOG_CHUNK, len(commitments) - i))
+        used = [vals[1][12:44] for (kind, vals), c in zip(log, codes) if kind == "withdraw" and c == lib.SPP_POOL_OK]
+        sizes = []                                           # of the root words of the accepted withdraws (spp_merkle_tree_find_roots)
+        for i in range(0, len(used), _POOL_LOG_CHUNK):
+            sizes += tree.find_roots(used[i:i + _POOL_LOG_CHUNK])[0]
+    sizes = iter(sizes)
+    deposits = differing = accepted = foreign = 0
+    for (kind, vals), c in zip(log, codes):
+        name = lib.POOL_RESULT_NAMES[c]
+        if kind == "deposit":
+            same = vals[0] == honest[deposits].to_bytes(32, "big")
+            deposits += 1
+            differing += not same
+            print("%s %s" % (name, "root-of-leaves" if same else "NOT-root-of-leaves"))
+        elif kind == "withdraw" and c == lib.SPP_POOL_OK:
+            size = next(sizes)
+            accepted += 1
+            foreign += size is None
+            print("%s %s" % (name, "foreign" if size is None else "size %d" % size))
+        else:
+            print(name)
+    print("roots: %d deposits, %d pushed a root that is not the root of the leaves; %d withdraws accepted, %d against a root of no size of the leaves"
+          % (deposits, differing, accepted, foreign))
+
+
 def _pool_replay(a):
     from . import witness
     try:   # everything that can be wrong with the files is found before a device is opened
         wvk, avk = open(a.withdraw_vk, "rb").read(), open(a.audit_vk, "rb").read()
-        log = parse_pool_log(open(a.log))
+        lines = open(a.log).readlines()
+        log = parse_pool_log(lines)
+        commitments = parse_pool_commitments(lines, a.depth)
     except (OSError, ValueError) as e:
         print("spp pool-replay: %s" % e, file=sys.stderr)
         return 2
@@ -244,10 +319,15 @@ def _pool_replay(a):
     try:
         with witness.Pool(ctx, wvk, avk, capacity, verifier=a.verifier, group=a.group) as pool:
             # the whole log in one call, whatever the interleaving of the kinds (consecutive chunks past 2^24 instructions)
+            all_codes = []
             for i in range(0, len(log), _POOL_LOG_CHUNK):
                 codes, _ = pool.settle_log([(kind,) + vals for kind, vals in log[i:i + _POOL_LOG_CHUNK]])
-                for c in codes:
-                    print(lib.POOL_RESULT_NAMES[c])
+                all_codes += codes
+                if commitments is None:
+                    for c in codes:
+                        print(lib.POOL_RESULT_NAMES[c])
+            if commitments is not None:
+                _print_root_audit(ctx, witness, a.depth, log, all_codes, commitments)
     except lib.SppError as e:
         print("spp pool-replay: %s" % e, file=sys.stderr)
         return 2
@@ -395,6 +475,7 @@ def main(argv=None):
     r.add_argument("--capacity", type=int, default=0, help="keys per set (default: enough for the log)")
     r.add_argument("--verifier", choices=("each", "rlc"), default="each", help="each: one lane per proof (default); rlc: random linear combination")
     r.add_argument("--group", type=int, default=0, help="with --verifier rlc: proofs per combined equation (a multiple of 64 in [64, 4096]; default 256)")
+    r.add_argument("--depth", type=int, default=16, help="of the tree the deposits' commitments go into, when the log carries them")
     r.add_argument("--device", type=int, default=0)
     w = sub.add_parser("wallet-sync"); w.add_argument("secrets", help="JSON list of {secretKey, amount, randomness}")
     w.add_argument("leaves", help="one hex leaf per line, in chain order")

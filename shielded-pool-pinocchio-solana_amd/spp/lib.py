@@ -46,6 +46,8 @@ SPP_WALLET_IN_TREE = 1              # the commitment is a leaf
 SPP_WALLET_SPENT = 2                # its nullifier is in the pool's nullifier set (status "withdrawn")
 SPP_WALLET_AUDITED = 4              # the pool holds the audit record of wa_commitment
 SPP_WALLET_REPEATED = 8             # the commitment sits at more than one leaf
+SPP_TREE_SIZE_NOW = (1 << 64) - 1   # the _at calls: the tree's size at the call (UINT64_MAX)
+SPP_TREE_NO_SIZE = (1 << 64) - 1    # spp_merkle_tree_find_roots / spp_pool_root_sizes: no prefix of this tree has that root
 SPP_ARITH_FR = 0x000                # spp_debug_arith: field bits of the selector (operation codes: csrc/arith_probe.hpp)
 SPP_ARITH_FQ = 0x100
 POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
@@ -157,6 +159,15 @@ def load_library():
     L.spp_withdraw_rows_from_tree.argtypes = [vp, sz, cp, vp]
     L.spp_prove_withdraw_notes_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     L.spp_prove_withdraw_notes.argtypes = [vp, vp, sz, cp, cp, vp, vp, vp]
+    u64 = ctypes.c_uint64               # the tree as of an earlier size (include/spp.h)
+    L.spp_merkle_tree_root_at.argtypes = [vp, u64, vp]
+    L.spp_merkle_tree_proofs_at.argtypes = [vp, u64, sz, vp, vp]
+    L.spp_merkle_tree_prefix_roots.argtypes = [vp, u64, sz, vp]
+    L.spp_merkle_tree_find_roots.argtypes = [vp, sz, cp, vp, vp]
+    L.spp_withdraw_rows_from_tree_at.argtypes = [vp, u64, sz, cp, vp]
+    L.spp_prove_withdraw_notes_at_device.argtypes = [vp, vp, u64, sz, vp, vp, vp, vp, vp]
+    L.spp_prove_withdraw_notes_at.argtypes = [vp, vp, u64, sz, cp, cp, vp, vp, vp]
+    L.spp_pool_root_sizes.argtypes = [vp, vp, vp, ctypes.POINTER(u64)]
     L.spp_shamir_reconstruct.argtypes = [vp, u32, vp, cp, sz, vp, vp]
     L.spp_rlwe_decrypt_batch.argtypes = [vp, vp, sz, vp, vp, vp]
     L.spp_rlwe_sample_key.argtypes = [sz, u32, vp, vp, vp]

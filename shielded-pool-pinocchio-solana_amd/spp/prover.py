@@ -342,9 +342,11 @@ class CircuitHandle:
         return ([proofs.raw[PROOF_LEN * i:PROOF_LEN * (i + 1)] for i in range(count)],
                 [pws.raw[self.pw_len * i:self.pw_len * (i + 1)] for i in range(count)], list(status)[:count], c0, c1)
 
-    def prove_withdraw_notes(self, tree, notes, rs=None):
+    def prove_withdraw_notes(self, tree, notes, rs=None, size=None):
         """Withdraw proofs from notes (spp.witness.pack_withdraw_notes tuples) against the resident tree `tree`
-        (ShieldedPoolMerkleTree of this handle's Context): spp_prove_withdraw_notes.  Same return shape as prove_batch."""
+        (ShieldedPoolMerkleTree of this handle's Context): spp_prove_withdraw_notes.  Same return shape as prove_batch.
+        size: against the tree of the first `size` leaves (spp_prove_withdraw_notes_at) -- Pool.root_sizes(tree) tells which size
+        a pool accepts."""
         from .witness import pack_withdraw_notes
         count = len(notes)
         buf = pack_withdraw_notes(notes)
@@ -354,17 +356,24 @@ class CircuitHandle:
         proofs = ctypes.create_string_buffer(PROOF_LEN * max(count, 1))
         pws = ctypes.create_string_buffer(self.pw_len * max(count, 1))
         status = (ctypes.c_int32 * max(count, 1))()
-        rc = self.L.spp_prove_withdraw_notes(self.h, tree.h, count, buf, rsb, ctypes.cast(proofs, ctypes.c_void_p),
-                                             ctypes.cast(pws, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p))
+        outs = (ctypes.cast(proofs, ctypes.c_void_p), ctypes.cast(pws, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p))
+        if size is None:
+            rc = self.L.spp_prove_withdraw_notes(self.h, tree.h, count, buf, rsb, *outs)
+        else:
+            rc = self.L.spp_prove_withdraw_notes_at(self.h, tree.h, int(size), count, buf, rsb, *outs)
         if rc != 0 and rc != SPP_ERR_UNSAT:
             check(rc)
         return ([proofs.raw[PROOF_LEN * i:PROOF_LEN * (i + 1)] for i in range(count)],
                 [pws.raw[self.pw_len * i:self.pw_len * (i + 1)] for i in range(count)], list(status)[:count])
 
-    def prove_withdraw_notes_device(self, tree, count, d_notes, d_rs, d_proofs, d_pws, d_status):
+    def prove_withdraw_notes_device(self, tree, count, d_notes, d_rs, d_proofs, d_pws, d_status, size=None):
         """Withdraw proofs from notes resident on the device against the resident tree (spp_prove_withdraw_notes_device):
-        asynchronous until sync(), every proof against the root at call time.  Raw device pointers (ints)."""
-        check(self.L.spp_prove_withdraw_notes_device(self.h, tree.h, count, d_notes, d_rs, d_proofs, d_pws, d_status))
+        asynchronous until sync(), every proof against the root at call time.  Raw device pointers (ints).
+        size: against the tree of the first `size` leaves (spp_prove_withdraw_notes_at_device)."""
+        if size is None:
+            check(self.L.spp_prove_withdraw_notes_device(self.h, tree.h, count, d_notes, d_rs, d_proofs, d_pws, d_status))
+        else:
+            check(self.L.spp_prove_withdraw_notes_at_device(self.h, tree.h, int(size), count, d_notes, d_rs, d_proofs, d_pws, d_status))
 
     def sync(self):
         check(self.L.spp_sync(self.h))

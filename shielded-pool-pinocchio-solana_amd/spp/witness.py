@@ -12,6 +12,10 @@
     ShieldedPoolMerkleTree.find / .sync
                              demo-frontend/app/lib/storage.ts:9-26,45-50,233-260: the leafIndex, nullifier, waCommitment and
                              status a wallet keeps per deposit, recomputed from its secrets, the tree and the pool's accounts
+    ShieldedPoolMerkleTree.root_at / .proofs_at / .prefix_roots / .find_roots / .withdraw_rows(size=), Pool.root_sizes
+                             the tree of the first `size` leaves: the root a deposit pushed (client/payroll-demo.ts:285-292,
+                             instructions/deposit.rs:31-36,73), and which size a pool still accepts (demo-frontend/app/lib/
+                             on-chain.ts:93-125,202-235)
     deposit_instruction_data shielded_pool_program/src/instructions/deposit.rs:21-37
     ct_commitment(...)       ct_helper/src/main.nr:15-34
     ciphertext_json(...)     scripts/generate_audit.py:590-606 (keys/ciphertext.json, what the prover leaves for the auditor)
@@ -27,7 +31,7 @@ import ctypes
 import numpy as np
 from .lib import (check, NOTE_LEN, DEPOSIT_LEN, PROOF_LEN, AUDIT_PW_LEN, WITHDRAW_PW_LEN, SPP_POOL_STATE_LEN,
                   SPP_POOL_NULLIFIERS, SPP_POOL_AUDIT_RECORDS, SPP_INSTR_DEPOSIT, SPP_INSTR_SUBMIT_AUDIT, SPP_INSTR_WITHDRAW,
-                  SPP_POOL_VERIFY_EACH, SPP_POOL_VERIFY_RLC, SPP_WALLET_RECORD_LEN)
+                  SPP_POOL_VERIFY_EACH, SPP_POOL_VERIFY_RLC, SPP_WALLET_RECORD_LEN, SPP_TREE_SIZE_NOW, SPP_TREE_NO_SIZE)
 
 TREE_DEPTH = 16
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -212,15 +216,57 @@ class ShieldedPoolMerkleTree:
                                                  ctypes.cast(roots, ctypes.c_void_p)))
         return int(first.value), _unbe(com.raw, n), _unbe(roots.raw, n)
 
-    def withdraw_rows(self, notes):
+    def withdraw_rows(self, notes, size=None):
         """Withdraw input rows for notes (pack_withdraw_notes) against the tree as it stands (spp_withdraw_rows_from_tree):
         per note [root, nullifier, recipient, amount, wa_commitment, secret_key, owner_x, owner_y, randomness, index,
-        *siblings] -- what client/payroll-demo.ts:323-340 assembles for generateProof, computed on the device."""
+        *siblings] -- what client/payroll-demo.ts:323-340 assembles for generateProof, computed on the device.
+        size: against the tree of the first `size` leaves instead (spp_withdraw_rows_from_tree_at)."""
         buf = pack_withdraw_notes(notes)
         n_in = 10 + self.depth
         rows = ctypes.create_string_buffer(32 * n_in * max(len(notes), 1))
-        check(self.ctx.L.spp_withdraw_rows_from_tree(self.h, len(notes), buf, ctypes.cast(rows, ctypes.c_void_p)))
+        if size is None:
+            check(self.ctx.L.spp_withdraw_rows_from_tree(self.h, len(notes), buf, ctypes.cast(rows, ctypes.c_void_p)))
+        else:
+            check(self.ctx.L.spp_withdraw_rows_from_tree_at(self.h, int(size), len(notes), buf, ctypes.cast(rows, ctypes.c_void_p)))
         return [_unbe(rows.raw[32 * n_in * i:], n_in) for i in range(len(notes))]
+
+    # ---- the tree as of an earlier size (include/spp.h): the root a deposit pushed is the root of the leaves its client knew,
+    # client/payroll-demo.ts:285-292, and the program takes it as sent, shielded_pool_program/src/instructions/deposit.rs:31-36,73.
+    # size: 0 .. len(self), or SPP_TREE_SIZE_NOW ----
+    def root_at(self, size):
+        """getRoot of the first `size` leaves (spp_merkle_tree_root_at)"""
+        root = ctypes.create_string_buffer(32)
+        check(self.ctx.L.spp_merkle_tree_root_at(self.h, int(size), ctypes.cast(root, ctypes.c_void_p)))
+        return int.from_bytes(root.raw, "big")
+
+    def proofs_at(self, size, indices, raw=False):
+        """getProofs in the tree of the first `size` leaves (spp_merkle_tree_proofs_at)"""
+        nq = len(indices)
+        q = (ctypes.c_uint64 * max(nq, 1))(*[int(i) for i in indices])
+        sib = ctypes.create_string_buffer(32 * self.depth * max(nq, 1))
+        check(self.ctx.L.spp_merkle_tree_proofs_at(self.h, int(size), nq, ctypes.cast(q, ctypes.c_void_p), ctypes.cast(sib, ctypes.c_void_p)))
+        if raw:
+            return sib.raw[:32 * self.depth * nq]
+        return [_unbe(sib.raw[32 * self.depth * i:], self.depth) for i in range(nq)]
+
+    def prefix_roots(self, first_size=0, count=None):
+        """the roots of sizes first_size .. first_size + count - 1 (count None: up to the tree's size): spp_merkle_tree_prefix_roots"""
+        if count is None:
+            count = len(self) + 1 - int(first_size)
+        out = ctypes.create_string_buffer(32 * max(count, 1))
+        check(self.ctx.L.spp_merkle_tree_prefix_roots(self.h, int(first_size), count, ctypes.cast(out, ctypes.c_void_p)))
+        return _unbe(out.raw, count)
+
+    def find_roots(self, roots):
+        """From root words back to sizes (spp_merkle_tree_find_roots).  roots: ints below 2^256 or 32-byte strings, any bytes -- a
+        word that is no field element matches nothing.  Returns (sizes, matches): the lowest size with that root or None, and how
+        many sizes have it (more than one only after zero-valued leaves)."""
+        buf = _key_bytes(roots)
+        n = len(buf) // 32
+        sizes = (ctypes.c_uint64 * max(n, 1))()
+        matches = (ctypes.c_uint32 * max(n, 1))()
+        check(self.ctx.L.spp_merkle_tree_find_roots(self.h, n, buf, ctypes.cast(sizes, ctypes.c_void_p), ctypes.cast(matches, ctypes.c_void_p)))
+        return [None if v == SPP_TREE_NO_SIZE else int(v) for v in sizes[:n]], [int(m) for m in matches[:n]]
 
     def find(self, leaves, start=None):
         """From leaf values back to positions (spp_merkle_tree_find; MerkleTreeState.leaves.indexOf, demo-frontend/app/lib/
@@ -355,6 +401,17 @@ class Pool:
         out = ctypes.create_string_buffer(SPP_POOL_STATE_LEN)
         check(self.ctx.L.spp_pool_state(self.h, ctypes.cast(out, ctypes.c_void_p)))
         return out.raw
+
+    def root_sizes(self, tree):
+        """Which size of `tree` (a ShieldedPoolMerkleTree of the same Context) can a proof be made against so that this pool accepts
+        it (spp_pool_root_sizes; isRootValid / getRootAge, demo-frontend/app/lib/on-chain.ts:93-125,202-235).  Returns (sizes, best):
+        sizes[0] for current_root and sizes[1 + k] for roots[k] of the state, None where the word is no prefix root of the tree;
+        best = the largest, or None."""
+        sizes = (ctypes.c_uint64 * 33)()
+        best = ctypes.c_uint64(0)
+        check(self.ctx.L.spp_pool_root_sizes(self.h, tree.h, ctypes.cast(sizes, ctypes.c_void_p), ctypes.byref(best)))
+        none = lambda v: None if v == SPP_TREE_NO_SIZE else int(v)
+        return [none(v) for v in sizes], none(best.value)
 
     def counts(self):
         """(spent nullifiers, audit records)"""
