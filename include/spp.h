@@ -158,6 +158,14 @@ int spp_circuit_msm_table_rows(const spp_circuit* c, uint32_t rows[7]);
 /* out[0] = rows of A / B / C that the matrix evaluation sums in integer arithmetic (every term a small coefficient times a wire the
  * lookup argument bounds to a byte range: the audit circuit's 1 088 quotient equations), out[1] = such wires (+1: the constant) */
 int spp_circuit_small_rows(const spp_circuit* c, uint32_t out[2]);
+/* What the load-time planners made of the circuit (read-only; for tests that must show which path a shape takes):
+ * out[0] = runs of constraints that share a B row, out[1] = terms of the longest row of A / B / C, out[2] = rows summed in integer
+ * arithmetic, out[3] = byte-ranged wires they read (+1: the constant), out[4] = long rows (16 lanes per proof);
+ * out[5..8] = items of the cooperative solver of kind SEQ, PAR, LEVELS, LEVEL_STREAM, out[9] = chunks of the level stream,
+ * out[10] = tracks in use (the most of any sequential stretch); out[11] = divisions of the largest wide OP_BATCH_DIV,
+ * out[12] = wide steps (OP_BATCH_DIV of 64 or more divisions and OP_COUNT8), out[13] = the wide OP_BATCH_DIV among them;
+ * out[14..15] = 0 */
+int spp_circuit_plan_stats(const spp_circuit* c, uint32_t out[16]);
 /* exact bytes of HBM held by the window tables, as allocated (rows sized by range included) */
 uint64_t spp_circuit_table_bytes(const spp_circuit* c);
 

@@ -863,8 +863,10 @@ __global__ void __launch_bounds__(256) k_small_extract(DevCircuit dc, const Fr* 
   }
   small[g] = (int16_t)v;
 }
-// small row r, proof p: sum of coefficient * small value as a 64-bit integer (|sum| < 2^31 * 2^15 * terms), stored as a field
-// element where k_spmv_check expects the row's value
+// small row r, proof p: sum of coefficient * small value as a 64-bit integer, stored as a field element where k_spmv_check expects
+// the row's value.  The sum and every partial sum stay inside the accumulator: small_rows_plan (spp_plan.cpp) admits a row only
+// while the sum of |coefficient| x (largest magnitude the slot's range allows) is below 2^63, and k_small_extract stores 0 for a
+// value outside its range
 __global__ void __launch_bounds__(256) k_spmv_small_rows(DevCircuit dc, const int16_t* __restrict__ small, const Fr* __restrict__ W,
                                                          Fr* __restrict__ abc, uint32_t n, uint32_t P) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

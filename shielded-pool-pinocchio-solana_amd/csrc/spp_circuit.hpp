@@ -113,6 +113,7 @@ struct spp_circuit {
   uint32_t c_bits = 10, n = 0, logn = 0;
   uint32_t max_batch_div = SOLVE_SCRATCH_MIN_ROWS;
   DevCoop coop{};
+  uint32_t coop_item_count[7] = {}, coop_stream_chunks = 0;   // what coop_plan made: items per COOP_* kind, chunks of the level stream (spp_circuit_plan_stats)
   Switches sw;
   bool generic_solver = false;    // the program is the solver of a decoded gnark system (OP_SOLVE_ROW ...): ~12 K dependent row solves per
                                   // proof on one lane -- a batch's solver phase outlasts the rest of it, so three batches take turns

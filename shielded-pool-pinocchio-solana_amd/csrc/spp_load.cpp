@@ -797,6 +797,20 @@ extern "C" int spp_circuit_small_rows(const spp_circuit* c, uint32_t out[2]) {
   out[1] = c->dc.sm_nslots;
   return SPP_OK;
 }
+extern "C" int spp_circuit_plan_stats(const spp_circuit* c, uint32_t out[16]) {
+  if (!c || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  for (int i = 0; i < 16; i++) out[i] = 0;
+  out[0] = c->dc.n_runs; out[1] = c->dc.max_row_terms; out[2] = c->dc.sm_nrows; out[3] = c->dc.sm_nslots; out[4] = c->dc.lg_n;
+  out[5] = c->coop_item_count[COOP_SEQ]; out[6] = c->coop_item_count[COOP_PAR]; out[7] = c->coop_item_count[COOP_LEVELS];
+  out[8] = c->coop_item_count[COOP_LEVEL_STREAM];
+  out[9] = c->coop_stream_chunks;
+  for (const SolveStep& s : c->schedule) {
+    if (s.kind == SolveStep::SEQ) out[10] = std::max(out[10], s.ntracks);
+    if (s.kind == SolveStep::BATCH_DIV) { out[11] = std::max(out[11], s.b); out[13]++; }
+    if (s.kind == SolveStep::BATCH_DIV || s.kind == SolveStep::COUNT8) out[12]++;
+  }
+  return SPP_OK;
+}
 extern "C" int spp_circuit_msm_windows(const spp_circuit* c, uint32_t bits[7]) {
   if (!c || !bits) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   bits[0] = c->A.c; bits[1] = c->B1.c; bits[2] = c->K.c; bits[3] = c->Z.c; bits[4] = c->CB.c; bits[5] = c->CS.c; bits[6] = c->B2.c;

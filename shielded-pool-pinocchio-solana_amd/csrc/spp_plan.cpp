@@ -347,6 +347,8 @@ int coop_plan(spp_circuit* c) {
       if (st.tr_end[t] > st.tr_begin[t]) st.ntracks = t + 1;
     }
   }
+  for (size_t i = 0; i < items.size(); i += 3) c->coop_item_count[items[i]]++;
+  c->coop_stream_chunks = (uint32_t)(stream.size() / COOP_CHUNK);
   if (items.empty()) items.assign(3, 0);
   if (par.empty()) par.assign(2, 0);
   if (lvl_rows.empty()) lvl_rows.push_back(0);
@@ -403,12 +405,20 @@ static int small_rows_plan(spp_circuit* c, std::vector<uint8_t>& flags_out) {
       if (e - b < SMALL_ROW_MIN || e - b > (1u << 20)) continue;
       // terms that qualify (small coefficient x byte-ranged wire) go to the integer sum, at most SMALL_ROW_REST others stay
       // field arithmetic (a quotient equation has nine: k * q and the eight message bits times Delta * 2^i)
+      // ... and only while the integer sum cannot leave a signed 64-bit accumulator whatever the values: the sum of |coefficient| x
+      // (largest magnitude the slot's range allows) stays below 2^63 (2^30 x 32 255 x 2^18 terms still does, twice that does not)
       uint32_t n_small = 0;
+      uint64_t bound = 0;
       for (uint32_t t = b; t < e; t++) {
         int64_t v;
-        if (slot_of[m.terms[t].wire] >= 0 && small_of(m.terms[t].coeff, &v)) n_small++;
+        if (slot_of[m.terms[t].wire] >= 0 && small_of(m.terms[t].coeff, &v)) {
+          n_small++;
+          const int64_t l = lo[slot_of[m.terms[t].wire]];
+          const uint64_t mag = m.terms[t].wire == 0 ? 1 : (uint64_t)std::max(l < 0 ? -l : l, l + 255 < 0 ? -(l + 255) : l + 255);
+          if (bound < (1ull << 63)) bound += (uint64_t)(v < 0 ? -v : v) * mag;   // each step adds less than 2^45
+        }
       }
-      if (n_small < SMALL_ROW_MIN || (e - b) - n_small > SMALL_ROW_REST) continue;
+      if (n_small < SMALL_ROW_MIN || (e - b) - n_small > SMALL_ROW_REST || bound >= (1ull << 63)) continue;
       for (uint32_t t = b; t < e; t++) {
         int64_t v = 0;
         if (slot_of[m.terms[t].wire] >= 0 && small_of(m.terms[t].coeff, &v)) {

@@ -255,6 +255,15 @@ class CircuitHandle:
         check(self.L.spp_circuit_small_rows(self.h, s))
         return list(s)
 
+    PLAN_STATS = ("n_runs", "max_row_terms", "sm_nrows", "sm_nslots", "lg_n", "items_seq", "items_par", "items_levels",
+                  "items_level_stream", "stream_chunks", "tracks", "max_wide_div", "wide_steps", "wide_divs")
+
+    def plan_stats(self):
+        """what the load-time planners made of the circuit, by name (spp_circuit_plan_stats in include/spp.h)"""
+        s = (ctypes.c_uint32 * 16)()
+        check(self.L.spp_circuit_plan_stats(self.h, s))
+        return dict(zip(self.PLAN_STATS, list(s)))
+
     def msm_table_rows(self):
         """table rows per base and set: 1 = single-row tables walked once per window (window_bits = 0)"""
         s = (ctypes.c_uint32 * 7)()
