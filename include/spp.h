@@ -51,6 +51,10 @@
  *   spp_merkle_tree_find_roots / spp_pool_root_sizes
  *                             from a root word back to the size it belongs to, and which size this pool accepts a proof against:
  *                             isRootValid / getRootAge / isRootNearExpiry (demo-frontend/app/lib/on-chain.ts:93-125,202-235)
+ *   spp_withdrawal_audit_plan / spp_prove_withdrawals
+ *                             the two transactions of a withdrawal, submit_audit then withdraw (demo-frontend/app/api/relay/withdraw/
+ *                             route.ts:129-287), for a batch of notes: every withdraw proof, and one audit record per identity that has
+ *                             none yet -- process_submit_audit answers Ok before the proof when it exists (submit_audit.rs:65-73)
  *   spp_msm_g1(_pippenger) / spp_ntt_fr   micro-benchmark entry points (BASELINE.json configs[4]); no reference equivalent
  *
  * Conventions: field elements cross the boundary as 32-byte big-endian canonical integers (the encoding
@@ -668,6 +672,65 @@ int spp_prove_withdraw_notes_at(spp_circuit* c, spp_merkle_tree* t, uint64_t siz
  * changes neither object's visible state.  Refused: NULL pool / t / sizes, a pool and a tree of different spp_ctx, a tree of more
  * than 2^30 leaves. */
 int spp_pool_root_sizes(spp_pool* pool, spp_merkle_tree* t, uint64_t sizes[33], uint64_t* best /* optional */);
+
+/* ---- withdrawals from notes: both proofs, one audit record per new identity ---- */
+/* A withdrawal costs the relayer two transactions, submit_audit and then withdraw (demo-frontend/app/api/relay/withdraw/route.ts:129-287:
+ * built at :129-218, sent at :238-287).  The audit record is keyed by wa_commitment = H(owner_x, owner_y) -- by the identity, not by
+ * the note -- and process_submit_audit answers Ok before it looks at the proof when the record exists (shielded_pool_program/src/
+ * instructions/submit_audit.rs:65-73; the relayer's own comment is "might be already initialized", route.ts:264-268).  A recipient
+ * who holds several notes under one key needs one audit proof, an identity the pool already knows none, and an audit proof costs
+ * about four withdraw proofs.  These two calls turn a batch of notes into exactly what has to be posted.
+ *
+ * The plan, for `count` 32-byte keys compared bytewise as the pool compares them (v and v + r are two keys) and an optional pool:
+ *   - key i is RESIDENT iff a pool is given and its audit-record set holds the key (what spp_pool_contains answers);
+ *   - otherwise rep(i) is the lowest j with key[j] == key[i];
+ *   - audit_note[0 .. *n_audits) is the ascending list of all i with rep(i) == i: the notes that get an audit record;
+ *   - audit_of[i] is the position of rep(i) in audit_note, or SPP_AUDIT_RESIDENT.
+ * Computed on the device, on the context's stream -- so ordered with the pool's commits and the tree's inserts -- with a fixed number
+ * of launches whatever the keys are, no workgroup waiting for another one; the result depends neither on scheduling nor on the salt
+ * of the per-call table (the pool's salt with a pool, else 64 bits from the operating system per call).  csrc/withdrawal_plan.hpp
+ * has the argument.  The pool is read and never written. */
+#define SPP_AUDIT_RESIDENT 0xFFFFFFFFu
+#define SPP_WITHDRAWALS_MAX 1048576       /* keys / notes per call: 2^20 */
+/* wa = count * 32 B: the wa_commitment words, e.g. word 2 of the records spp_wallet_sync writes.  audit_of and audit_note have room
+ * for count entries; only the first *n_audits of audit_note are written.  Host buffers, synchronous, serialised on the context.
+ * Refused with SPP_ERR_BAD_INPUT before any device work: NULL ctx, wa, audit_of, audit_note or n_audits (checked before the context is
+ * touched), count > 2^20, a pool of another spp_ctx.  count == 0 is SPP_OK with *n_audits = 0. */
+int spp_withdrawal_audit_plan(spp_ctx* ctx, spp_pool* pool /* optional */, size_t count, const uint8_t* wa /* count * 32 B */,
+                              uint32_t* audit_of /* count */, uint32_t* audit_note /* count */, uint32_t* n_audits);
+
+/* Both halves of `count` withdrawals in one call: the withdraw proof of every note, and the audit record of every identity that
+ * still needs one.
+ *   rows     the withdraw rows of all notes are built once, by the kernels of spp_withdraw_rows_from_tree(_at) on the tree's stream,
+ *            against the tree as of `size` (SPP_TREE_SIZE_NOW or an earlier size);
+ *   plan     the plan above over the wa_commitment word of each row (field 4), on the same stream; the plan arrays are then read back.
+ *            *n_audits > audit_cap is SPP_ERR_BAD_INPUT at this point, before any proving: *n_audits, audit_of and the first audit_cap
+ *            entries of audit_note are written, both numbers are in spp_last_error();
+ *   proving  the withdraw batch goes to the withdraw circuit's proving streams, the audit batch -- spp_prove_audit_records' pipeline
+ *            as it is, over secret_key, r, e1, e2 and rs_audit of note audit_note[s] for record s -- to the audit circuit's; each is
+ *            enqueued by a host thread of its own, so both are in flight together before either is waited for.
+ * Everything that belongs to note i sits at index i of its array, noise and blinding included (only the representatives' are read).
+ * r, e1, e2 all NULL: every coefficient is drawn uniformly from [-3, 3] by rejection from OS randomness (the range of
+ * scripts/generate_audit.py:469-506); one or two of them NULL is SPP_ERR_BAD_INPUT.  Host scratch that held noise or secret keys is wiped.
+ *   - proofs, pws, status are byte for byte what spp_prove_withdraw_notes_at(withdraw, t, size, count, notes, rs_withdraw, ...) returns:
+ *     a note that is no leaf (of that size) is refused in place, status SPP_ERR_UNSAT, proof bytes zero.
+ *   - record s (audit_proofs, audit_pws, audit_status, c0, c1; audit_cap entries each, audit_note too) is byte for byte what
+ *     spp_prove_audit_records returns for the representatives' secrets in slot order.
+ *   - A representative is chosen by identity alone: a note whose withdraw row the circuit refuses may still be the representative of
+ *     its identity, and its record is valid for the other notes of that identity.  This keeps the two batches independent.
+ * Returns SPP_ERR_UNSAT if any row of either side was refused.  Refused with SPP_ERR_BAD_INPUT before any proving: what the two calls
+ * refuse (wrong circuit kinds or input counts, a tree of another context, a note field >= r, a public-key coefficient >= q, a size
+ * past the tree), secret_key == 0, circuits, tree and pool that are not all of one spp_ctx, count > 2^20, and NULL arguments (checked
+ * before the context is touched; status, audit_status, the noise and the blinding may be NULL, the audit outputs when audit_cap is 0).
+ * count == 0 is SPP_OK with *n_audits = 0. */
+int spp_prove_withdrawals(spp_circuit* withdraw, spp_circuit* audit, spp_merkle_tree* t, spp_pool* pool /* optional */, uint64_t size,
+                          const uint32_t* pk_a, const uint32_t* pk_b, size_t count, const uint8_t* notes /* count * SPP_NOTE_LEN */,
+                          const int8_t* r, const int8_t* e1, const int8_t* e2 /* per NOTE: count*1024, count*64, count*1024; all three NULL = OS randomness */,
+                          const uint8_t* rs_withdraw, const uint8_t* rs_audit /* per NOTE, count*64 each; NULL = OS randomness */,
+                          uint8_t* proofs, uint8_t* pws, int32_t* status /* optional */,           /* the withdraw side, per note */
+                          uint32_t* audit_of, uint32_t* audit_note, uint32_t* n_audits,           /* the plan */
+                          size_t audit_cap, uint8_t* audit_proofs, uint8_t* audit_pws, int32_t* audit_status /* optional */,
+                          uint32_t* c0, uint32_t* c1);                                             /* per audit record, audit_cap entries */
 
 /* ---- micro-benchmark / unit entry points ---- */
 /* data: n = 2^logn elements, 32 B big-endian each, natural order in and out */

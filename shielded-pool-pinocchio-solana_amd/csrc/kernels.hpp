@@ -244,6 +244,13 @@ void launch_pool_resolve(hipStream_t st, uint32_t* slots, uint32_t mask, uint64_
                          const int32_t* prov, const int32_t* proof_ok, int32_t dup, int32_t* result);
 void launch_pool_commit(hipStream_t st, const PoolSet& set, uint64_t salt, const uint8_t* keys, uint32_t stride, uint32_t count, const int32_t* result,
                         uint32_t* set_count);
+// ---- withdrawal plan (kernels_withdrawals.hip); what a lane, a wave and a tile do lives in withdrawal_plan.hpp ----
+// Five launches whatever the keys are: claim, winners + tile counts, scan, scatter, assign.  count in [1, 2^20]; key i = keys + i * stride;
+// audits: the pool's audit-record set (read only) or nullptr; slots: mask + 1 words, all POOL_NONE; resident: count bytes; rep, pos,
+// audit_of, audit_note: count words; tile_counts, tile_base: 1024 words; *n_audits: one word
+void launch_withdrawal_plan(hipStream_t st, const PoolSet* audits, uint64_t salt, uint32_t* slots, uint32_t mask, const uint8_t* keys, size_t stride,
+                            uint32_t count, uint8_t* resident, uint32_t* rep, uint32_t* pos, uint32_t* tile_counts, uint32_t* tile_base,
+                            uint32_t* audit_of, uint32_t* audit_note, uint32_t* n_audits);
 // small: [sm_nslots][P] int16 scratch of the small rows (may be nullptr when the circuit has none)
 void launch_spmv_check(hipStream_t st, DevCircuit dc, const Fr* W, Fr* abc, uint32_t n, uint32_t P, uint32_t* status, int16_t* small = nullptr);
 

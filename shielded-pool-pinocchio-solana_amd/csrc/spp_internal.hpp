@@ -10,6 +10,7 @@
 //   spp_verify_api.cpp   verification and pairing checks
 //   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
+//   spp_withdrawals_api.cpp  the withdrawal plan: which notes of a batch still need an audit record (spp_prove_withdrawals itself is in spp_prove.cpp)
 //   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points, the raw-word arithmetic probe (spp_debug_arith)
 #pragma once
 #include "../../include/spp.h"
@@ -191,6 +192,12 @@ struct spp_pool;
 spp_ctx* spp_pool_view(spp_pool* p, PoolSet* sets, uint64_t* salt);
 // current_root, then roots[0..31] of the pool's ring as spp_pool_state lays them out: 33 x 32 B.  Needs the pool's context locked
 void spp_pool_ring_words(spp_pool* p, uint8_t words[33 * 32]);
+// The withdrawal plan as stream-ordered work on ctx->stream (spp_withdrawals_api.cpp; withdrawal_plan.hpp): key i = d_keys + i * stride,
+// count in [1, 2^20], pool optional (of this context); d_scratch: spp_withdrawal_plan_scratch_bytes(count); d_audit_of, d_audit_note:
+// count words, *d_n_audits one word.  ctx->mu held, device set
+size_t spp_withdrawal_plan_scratch_bytes(size_t count);
+int spp_withdrawal_plan_enqueue(spp_ctx* ctx, spp_pool* pool, const uint8_t* d_keys, size_t stride, size_t count, void* d_scratch,
+                                uint32_t* d_audit_of, uint32_t* d_audit_note, uint32_t* d_n_audits);
 template <class T>
 inline int ctx_upload(spp_ctx* ctx, T** dst, const std::vector<T>& src) {
   HIP_TRY(dev_upload(dst, src));

@@ -3,6 +3,8 @@
 // the experiment switches are fields of the circuit (Switches, spp_circuit.hpp).
 #include "spp_circuit.hpp"
 
+#include <thread>
+
 template <class T>
 static int ws_alloc(Workspace& w, T** p, size_t count) {
   HIP_TRY(hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1)));
@@ -631,6 +633,230 @@ extern "C" int spp_prove_batch(spp_circuit* c, size_t count, const uint8_t* inpu
     if (status) status[i] = v;
     if (v && rc == SPP_OK) rc = fail(SPP_ERR_UNSAT, "proof %zu: inputs do not satisfy the circuit", i);
     if (v) memset(proofs + (size_t)SPP_PROOF_LEN * i, 0, SPP_PROOF_LEN);
+  }
+  return rc;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// Withdrawals from notes: both proofs, one audit record per new identity (include/spp.h; the plan is withdrawal_plan.hpp)
+// -----------------------------------------------------------------------------------------------------
+namespace {
+void wipe_bytes(void* p, size_t bytes) {
+  volatile uint8_t* v = (volatile uint8_t*)p;
+  for (size_t i = 0; i < bytes; i++) v[i] = 0;
+}
+struct WipedI8 {   // host scratch that held noise or secret keys
+  std::vector<int8_t> v;
+  ~WipedI8() { wipe_bytes(v.data(), v.size()); }
+};
+// n coefficients uniform in [-3, 3] from OS randomness: three bits of a byte, the value 7 rejected (scripts/generate_audit.py:469-506
+// draws randint(-3, 3))
+int os_noise(int8_t* out, size_t n) {
+  FILE* f = fopen("/dev/urandom", "rb");
+  if (!f) return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+  uint8_t buf[4096];
+  size_t done = 0;
+  int rc = SPP_OK;
+  while (done < n && rc == SPP_OK) {
+    if (fread(buf, 1, sizeof buf, f) != sizeof buf) rc = fail(SPP_ERR_IO, "cannot read /dev/urandom");
+    for (size_t k = 0; k < sizeof buf && done < n && rc == SPP_OK; k++) {
+      const int v = buf[k] & 7;
+      if (v != 7) out[done++] = (int8_t)(v - 3);
+    }
+  }
+  wipe_bytes(buf, sizeof buf);
+  fclose(f);
+  return rc;
+}
+}  // namespace
+
+// The withdraw side of spp_prove_withdrawals: rows resident in the call's own device buffer (complete: the tree's stream has been
+// waited for), proved in the chunks spp_prove_batch cuts, on the circuit's proving streams.  Unlike spp_prove_batch the context is
+// locked per chunk, for the enqueue only, so that the audit batch of the same call gets its turns; therefore the outputs of a chunk
+// go to buffers of the call, not to the workspace's, which another caller may take over in between.
+static int prove_resident_rows(spp_circuit* c, size_t count, const uint8_t* d_rows, const uint8_t* rs, uint8_t* proofs, uint8_t* pws,
+                               std::vector<uint32_t>& stat) {
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  const size_t pref = c->circ.n_wires <= 16384 ? 4096 : 2048;
+  const size_t chunk = count <= pref + pref / 2 ? count : pref;
+  const size_t inl = c->in_stride, pwl = c->pw_stride;
+  struct CopyStream {
+    hipStream_t s = nullptr;
+    ~CopyStream() { if (s) hipStreamDestroy(s); }
+  } copy;
+  HIP_TRY(hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
+  hipStream_t st = copy.s;
+  struct Set {
+    DevBuf rs, proofs, pws, status;
+    hipStream_t proving = nullptr;
+    size_t off = 0, n = 0;
+  } sets[2];
+  std::vector<std::pair<size_t, size_t>> chunks;   // as spp_prove_batch: a last chunk that is no multiple of the wave width is body + tail
+  for (size_t off = 0; off < count; off += chunk) {
+    const size_t n = std::min(chunk, count - off), t = batch_tail(c, n);
+    if (t) {
+      chunks.push_back({off, n - t});
+      chunks.push_back({off + n - t, t});
+    } else chunks.push_back({off, n});
+  }
+  for (size_t k = 0; k < std::min<size_t>(2, chunks.size()); k++) {
+    Set& s = sets[k];
+    HIP_TRY(s.rs.alloc(chunk * 64)); HIP_TRY(s.proofs.alloc(chunk * SPP_PROOF_LEN)); HIP_TRY(s.pws.alloc(chunk * pwl)); HIP_TRY(s.status.alloc(chunk * 4));
+  }
+  auto fetch = [&](Set& s) -> int {
+    HIP_TRY(hipStreamSynchronize(s.proving));
+    HIP_TRY(hipMemcpyAsync(proofs + (size_t)SPP_PROOF_LEN * s.off, s.proofs.p, (size_t)SPP_PROOF_LEN * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pws + pwl * s.off, s.pws.p, pwl * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stat.data() + s.off, s.status.p, 4 * s.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s.n = 0;
+    return 0;
+  };
+  int k = 0;
+  for (const auto& ch : chunks) {
+    Set& s = sets[k];
+    k ^= 1;
+    if (s.n)
+      if (int e = fetch(s)) return e;
+    const size_t off = ch.first, n = ch.second;
+    HIP_TRY(hipMemcpyAsync(s.rs.p, rs + 64 * off, 64 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s.off = off;
+    s.n = n;
+    std::lock_guard<std::mutex> lk(c->ctx->mu);
+    Workspace& w = take_workspace(c, 2);
+    if (int e = ensure_workspace(c, w, n)) return e;
+    s.proving = w.st;
+    if (int e = prove_on_device(c, w, n, d_rows + inl * off, BatchIO{s.rs.as<uint8_t>(), s.proofs.as<uint8_t>(), s.pws.as<uint8_t>(), s.status.as<uint32_t>()}))
+      return e;
+  }
+  for (int j = 0; j < 2; j++) {      // the older chunk first
+    Set& s = sets[k ^ j];
+    if (s.n)
+      if (int e = fetch(s)) return e;
+  }
+  return SPP_OK;
+}
+
+extern "C" int spp_prove_withdrawals(spp_circuit* withdraw, spp_circuit* audit, spp_merkle_tree* t, spp_pool* pool, uint64_t size,
+                                     const uint32_t* pk_a, const uint32_t* pk_b, size_t count, const uint8_t* notes, const int8_t* r,
+                                     const int8_t* e1, const int8_t* e2, const uint8_t* rs_withdraw, const uint8_t* rs_audit, uint8_t* proofs,
+                                     uint8_t* pws, int32_t* status, uint32_t* audit_of, uint32_t* audit_note, uint32_t* n_audits,
+                                     size_t audit_cap, uint8_t* audit_proofs, uint8_t* audit_pws, int32_t* audit_status, uint32_t* c0,
+                                     uint32_t* c1) {
+  if (!withdraw || !audit || !t || !pk_a || !pk_b || !n_audits || (count && (!notes || !proofs || !pws || !audit_of)) ||
+      (count && audit_cap && (!audit_note || !audit_proofs || !audit_pws || !c0 || !c1)))
+    return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if ((r != nullptr) != (e1 != nullptr) || (r != nullptr) != (e2 != nullptr))
+    return fail(SPP_ERR_BAD_INPUT, "r, e1 and e2: all three, or all three NULL for noise from the operating system");
+  if (int e = withdraw_notes_args(withdraw, t)) return e;
+  if (audit->circ.id != SPP_CIRCUIT_AUDIT || audit->circ.n_inputs() != 3360) return fail(SPP_ERR_BAD_INPUT, "not the audit circuit");
+  spp_ctx* ctx = withdraw->ctx;
+  if (audit->ctx != ctx) return fail(SPP_ERR_BAD_INPUT, "the audit circuit belongs to another spp_ctx than the withdraw circuit");
+  if (pool && spp_pool_view(pool, nullptr, nullptr) != ctx) return fail(SPP_ERR_BAD_INPUT, "the pool belongs to another spp_ctx than the circuits");
+  if (count > SPP_WITHDRAWALS_MAX) return fail(SPP_ERR_BAD_INPUT, "too many notes in one call (%zu; at most 2^20)", count);
+  for (int i = 0; i < 1024; i++)
+    if (pk_a[i] >= 167772161u || pk_b[i] >= 167772161u) return fail(SPP_ERR_BAD_INPUT, "public key coefficient not in [0, q)");
+  if (int e = spp_check_notes(count, notes)) return e;
+  for (size_t i = 0; i < count; i++) {
+    bool sk_zero = true;
+    for (int b = 0; b < 32; b++) sk_zero &= notes[SPP_NOTE_LEN * i + 64 + b] == 0;
+    if (sk_zero) return fail(SPP_ERR_BAD_INPUT, "note %zu: secret_key is 0", i);
+  }
+  *n_audits = 0;
+  const bool asof = size != SPP_TREE_SIZE_NOW;
+  const size_t inl = withdraw->in_stride;
+  DevBuf drows;
+  uint32_t n = 0;
+  std::vector<uint32_t> note(count);
+  {
+    // rows and plan on the tree's stream, in order with inserts and the pool's commits; the plan is read back
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int e = spp_ensure_ctx_consts(ctx)) return e;
+    if (asof && size > t->n_leaves) return spp_tree_frontier_enqueue(t, &size);   // the refusal, also for count == 0
+    if (count == 0) return SPP_OK;
+    hipStream_t st = ctx->stream;
+    DevBuf dnotes, dscratch, dplan;
+    UP(dnotes, notes, count * SPP_NOTE_LEN);
+    HIP_TRY(drows.alloc(count * inl));
+    HIP_TRY(dscratch.alloc(spp_withdrawal_plan_scratch_bytes(count)));
+    HIP_TRY(dplan.alloc((2 * count + 1) * sizeof(uint32_t)));
+    if (asof) {
+      if (int e = spp_tree_frontier_enqueue(t, &size)) return e;
+      launch_withdraw_rows_at(st, ctx->gk_table, ctx->hc, t->dev, size, t->d_frontier, dnotes.as<uint8_t>(), drows.as<uint8_t>(), (uint32_t)count);
+    } else {
+      launch_withdraw_rows(st, ctx->gk_table, ctx->hc, t->dev, dnotes.as<uint8_t>(), drows.as<uint8_t>(), (uint32_t)count);
+    }
+    uint32_t *d_of = dplan.as<uint32_t>(), *d_note = d_of + count, *d_n = d_note + count;
+    if (int e = spp_withdrawal_plan_enqueue(ctx, pool, drows.as<uint8_t>() + 4 * 32, inl, count, dscratch.p, d_of, d_note, d_n)) return e;
+    HIP_TRY(hipMemcpyAsync(audit_of, d_of, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(note.data(), d_note, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+  }
+  *n_audits = n;
+  if (std::min<size_t>(n, audit_cap)) memcpy(audit_note, note.data(), std::min<size_t>(n, audit_cap) * sizeof(uint32_t));
+  if (n > audit_cap)
+    return fail(SPP_ERR_BAD_INPUT, "the batch needs %u audit records, audit_cap is %zu", n, audit_cap);
+
+  // the representatives' secrets in slot order
+  WipedI8 sk, gr, ge1, ge2;
+  std::vector<uint8_t> grs;
+  sk.v.resize((size_t)n * 32);
+  gr.v.resize((size_t)n * 1024); ge1.v.resize((size_t)n * 64); ge2.v.resize((size_t)n * 1024);
+  for (size_t s = 0; s < n; s++) memcpy(sk.v.data() + 32 * s, notes + SPP_NOTE_LEN * note[s] + 64, 32);
+  if (r) {
+    for (size_t s = 0; s < n; s++) {
+      memcpy(gr.v.data() + 1024 * s, r + (size_t)1024 * note[s], 1024);
+      memcpy(ge1.v.data() + 64 * s, e1 + (size_t)64 * note[s], 64);
+      memcpy(ge2.v.data() + 1024 * s, e2 + (size_t)1024 * note[s], 1024);
+    }
+  } else {
+    if (int e = os_noise(gr.v.data(), gr.v.size())) return e;
+    if (int e = os_noise(ge1.v.data(), ge1.v.size())) return e;
+    if (int e = os_noise(ge2.v.data(), ge2.v.size())) return e;
+  }
+  if (rs_audit) {
+    grs.resize((size_t)n * 64);
+    for (size_t s = 0; s < n; s++) memcpy(grs.data() + 64 * s, rs_audit + (size_t)64 * note[s], 64);
+  }
+  std::vector<uint8_t> rnd;
+  if (!rs_withdraw) {
+    if (int e = os_blinding(rnd, count)) return e;
+    rs_withdraw = rnd.data();
+  }
+
+  // both batches in flight together: the audit records on a host thread of their own (spp_prove_audit_records as it is, which locks
+  // the context for each enqueue only), the withdraw chunks on this one
+  int rc_audit = SPP_OK;
+  char audit_err[sizeof g_spp_err] = {0};
+  std::thread audit_thread;
+  if (n)
+    audit_thread = std::thread([&] {
+      rc_audit = spp_prove_audit_records(audit, pk_a, pk_b, n, (const uint8_t*)sk.v.data(), gr.v.data(), ge1.v.data(), ge2.v.data(),
+                                         rs_audit ? grs.data() : nullptr, audit_proofs, audit_pws, audit_status, c0, c1);
+      if (rc_audit) memcpy(audit_err, g_spp_err, sizeof audit_err);   // the message is thread-local
+    });
+  std::vector<uint32_t> stat(count);
+  const int rc_rows = prove_resident_rows(withdraw, count, drows.as<uint8_t>(), rs_withdraw, proofs, pws, stat);
+  if (audit_thread.joinable()) audit_thread.join();
+  if (rc_rows) return rc_rows;
+  if (rc_audit && rc_audit != SPP_ERR_UNSAT) {
+    memcpy(g_spp_err, audit_err, sizeof audit_err);
+    return rc_audit;
+  }
+  int rc = SPP_OK;
+  for (size_t i = 0; i < count; i++) {
+    const int32_t v = stat[i] ? SPP_ERR_UNSAT : SPP_OK;
+    if (status) status[i] = v;
+    if (v && rc == SPP_OK) rc = fail(SPP_ERR_UNSAT, "note %zu: inputs do not satisfy the circuit", i);
+    if (v) memset(proofs + (size_t)SPP_PROOF_LEN * i, 0, SPP_PROOF_LEN);
+  }
+  if (rc == SPP_OK && rc_audit) {
+    memcpy(g_spp_err, audit_err, sizeof audit_err);
+    rc = rc_audit;
   }
   return rc;
 }

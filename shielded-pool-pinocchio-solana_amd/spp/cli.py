@@ -41,6 +41,15 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # JSON object per secret: commitment, leafIndex, root, nullifier, waCommitment, siblings, publicKeyX/Y,
                               # status ("pending" | "withdrawn"; "absent" with leafIndex null when the commitment is no leaf), audited
                               # (null without --vk) and occurrences -- the form importDeposits (:233-260) reads
+    python -m spp.cli withdraw-bundle notes.jsonl withdraw.sppc withdraw.pk audit.sppc audit.pk rlwe_pk.json leaves.txt --out DIR
+                              [--audited wa.txt --vk withdraw.vk audit.vk] [--size N] [--with-deposits]
+                              # everything the relayer posts for the notes `wallet-sync --recipient` printed (demo-frontend/app/api/
+                              # relay/withdraw/route.ts:129-287): the withdraw proof of every note and ONE audit record per identity
+                              # that has none yet -- none for the wa_commitments of --audited (spp_prove_withdrawals).  Writes
+                              # DIR/log.jsonl in the relayer's order (a note's submit_audit, if it is the one that carries its
+                              # identity's record, then its withdraw), which pool-replay takes, and per record DIR/record_<s>.proof,
+                              # record_<s>.pw and ciphertext_<s>.json, which audit-open takes.  --with-deposits: the log begins with
+                              # the deposits of all leaves.  exit 1 if the circuit refused a row
     python -m spp.cli execute target/<name>.json Prover.toml [-o target/<name>.gz]               # `nargo execute`: ACIR witness stack
     python -m spp.cli prove   target/<name>.json target/<name>.gz target/<name>.sppc target/<name>.pk
                               # sunspot's own argument order (acir, witness, constraint system, proving key;
@@ -425,6 +434,105 @@ def _wallet_sync(a):
     return 0
 
 
+def parse_bundle_notes(lines):
+    """[(note, address)] from the JSON lines `wallet-sync --recipient` prints: note = (recipient, amount, secret_key, randomness,
+    index) as prove_withdrawals takes it, address = the 32 bytes the withdraw instruction names -- the record's "address" (hex) when
+    it has one, else the recipient word's 30 bytes and two zero bytes (shielded_pool_program/src/instructions/withdraw.rs:150-154
+    compares the first 30).  ValueError names the line: no leaf, no recipient, already withdrawn, a value out of range."""
+    out = []
+    for no, line in enumerate(lines, 1):
+        if not line.strip():
+            continue
+        try:
+            d = json.loads(line)
+            sk, amount, rnd = (_num(str(d[k])) for k in ("secretKey", "amount", "randomness"))
+            index, recipient = d["leafIndex"], d.get("recipient")
+        except (ValueError, KeyError, TypeError) as e:
+            raise ValueError("line %d: not a wallet-sync record (%s)" % (no, e))
+        if index is None:
+            raise ValueError("line %d: the commitment is no leaf (status absent)" % no)
+        if recipient is None:
+            raise ValueError("line %d: no recipient (run wallet-sync with --recipient)" % no)
+        if d.get("status") == "withdrawn":
+            raise ValueError("line %d: the note is withdrawn" % no)
+        recipient, index = _num(str(recipient)), int(index)
+        if not (0 < sk < R and 0 <= rnd < R and 0 <= recipient < 1 << 240 and 0 <= amount < 1 << 64 and 0 <= index < 1 << 32):
+            raise ValueError("line %d: secretKey in [1, r), randomness in [0, r), a recipient word of 30 bytes, a 64-bit amount" % no)
+        address = bytes.fromhex(d["address"][2:] if d["address"].lower().startswith("0x") else d["address"]) if "address" in d \
+            else recipient.to_bytes(30, "big") + bytes(2)
+        if len(address) != 32 or int.from_bytes(address[:30], "big") != recipient:
+            raise ValueError("line %d: address is not 32 bytes that begin with the recipient word" % no)
+        out.append(((recipient, amount, sk, rnd, index), address))
+    return out
+
+
+def _withdraw_bundle(a):
+    from . import witness
+    from .prover import prove_withdrawals
+    try:   # everything that can be wrong with the arguments and the files is found before a device is opened
+        pairs = parse_bundle_notes(open(a.notes).readlines())
+        if not pairs:
+            raise ValueError("%s holds no note" % a.notes)
+        pk_a, pk_b = witness.load_rlwe_pk_json(a.rlwe_pk)
+        leaves = _hex_lines(a.leaves, "leaf")
+        if any(v >= R for v in leaves):
+            raise ValueError("%s: leaf %d is not a canonical field element" % (a.leaves, next(i for i, v in enumerate(leaves) if v >= R)))
+        if not 1 <= a.depth <= 32 or len(leaves) > 1 << a.depth:
+            raise ValueError("%d leaves do not fit a tree of depth %d (1..32)" % (len(leaves), a.depth))
+        if a.size is not None and not 0 <= a.size <= len(leaves):
+            raise ValueError("--size %d: the leaves file holds %d leaves" % (a.size, len(leaves)))
+        if a.audited and not a.vk:
+            raise ValueError("--audited describes a pool: it needs --vk withdraw.vk audit.vk")
+        audited = _hex_lines(a.audited, "wa_commitment") if a.audited else []
+        wvk, avk = (open(p, "rb").read() for p in a.vk) if a.vk else (None, None)
+        for p in (a.withdraw_sppc, a.withdraw_pk, a.audit_sppc, a.audit_pk):
+            open(p, "rb").close()
+        os.makedirs(a.out, exist_ok=True)
+    except (OSError, ValueError) as e:
+        print("spp withdraw-bundle: %s" % e, file=sys.stderr)
+        return 2
+    notes, addresses = [n for n, _ in pairs], [ad for _, ad in pairs]
+    ctx = Context(a.device)
+    hw = ha = pool = None
+    try:
+        hw = ctx.load_circuit(a.withdraw_sppc, a.withdraw_pk, a.window)
+        ha = ctx.load_circuit(a.audit_sppc, a.audit_pk, a.window)
+        with witness.ShieldedPoolMerkleTree(ctx, a.depth) as tree:
+            tree.insert_many(leaves)
+            if audited:
+                pool = witness.Pool(ctx, wvk, avk, len(audited))
+                pool.import_keys(lib.SPP_POOL_AUDIT_RECORDS, audited)
+            bundle = prove_withdrawals(hw, ha, tree, notes, pk_a, pk_b, pool=pool, size=a.size)
+            roots = tree.prefix_roots(1, len(leaves)) if a.with_deposits and leaves else []
+    except (lib.SppError, ValueError) as e:
+        print("spp withdraw-bundle: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        for h in (pool, hw, ha):
+            if h is not None:
+                h.close()
+        ctx.close()
+    with open(os.path.join(a.out, "log.jsonl"), "w") as f:
+        for leaf, root in zip(leaves, roots):
+            f.write(json.dumps({"deposit": {"root": "%064x" % root, "commitment": "%064x" % leaf}}) + "\n")
+        for ins in bundle.log(addresses):
+            names = [name for name, _ in _POOL_FIELDS[ins[0]]]
+            f.write(json.dumps({ins[0]: {name: v.hex() for name, v in zip(names, ins[1:])}}) + "\n")
+    for s in range(bundle.n_audits):
+        open(os.path.join(a.out, "record_%d.proof" % s), "wb").write(bundle.audit_proofs[s])
+        open(os.path.join(a.out, "record_%d.pw" % s), "wb").write(bundle.audit_pws[s])
+        with open(os.path.join(a.out, "ciphertext_%d.json" % s), "w") as f:
+            json.dump(witness.ciphertext_json(bundle.c0[s], bundle.c1[s]), f)
+    refused = sum(1 for v in bundle.status if v) + sum(1 for v in bundle.audit_status if v)
+    print("withdraw-bundle: %d notes, %d audit records (%d identities already audited), %d rows refused; %s" %
+          (len(notes), bundle.n_audits, len({n[2] for n, s in zip(notes, bundle.audit_of) if s == lib.SPP_AUDIT_RESIDENT}), refused,
+           os.path.join(a.out, "log.jsonl")))
+    for i, v in enumerate(bundle.status):
+        if v:
+            print("note %d: the withdraw circuit refuses it (not the leaf at its index%s)" % (i, "" if a.size is None else " of that size"))
+    return 1 if refused else 0
+
+
 def _verify_batch(a):
     try:   # everything that can be wrong with the files is found before a device is opened
         if not a.files or len(a.files) % 2:
@@ -484,6 +592,15 @@ def main(argv=None):
     w.add_argument("--vk", nargs=2, default=None, metavar=("WITHDRAW.vk", "AUDIT.vk"))
     w.add_argument("--recipient", default=None, metavar="HEX", help="recipient word copied into every record")
     w.add_argument("--depth", type=int, default=16); w.add_argument("--device", type=int, default=0)
+    wb = sub.add_parser("withdraw-bundle"); wb.add_argument("notes", help="the JSON lines of `wallet-sync --recipient`")
+    wb.add_argument("withdraw_sppc"); wb.add_argument("withdraw_pk"); wb.add_argument("audit_sppc"); wb.add_argument("audit_pk")
+    wb.add_argument("rlwe_pk", help="rlwe_pk.json"); wb.add_argument("leaves", help="one hex leaf per line, in chain order")
+    wb.add_argument("--out", required=True, metavar="DIR", help="log.jsonl, record_<s>.proof / .pw and ciphertext_<s>.json go here")
+    wb.add_argument("--audited", default=None, metavar="WA.txt", help="wa_commitments with an audit record, one hex key per line (needs --vk)")
+    wb.add_argument("--vk", nargs=2, default=None, metavar=("WITHDRAW.vk", "AUDIT.vk"))
+    wb.add_argument("--size", type=int, default=None, help="prove against the tree of the first SIZE leaves (a root the pool still holds)")
+    wb.add_argument("--with-deposits", action="store_true", help="begin the log with one deposit line per leaf, so that it replays on a fresh pool")
+    wb.add_argument("--window", type=int, default=0); wb.add_argument("--depth", type=int, default=16); wb.add_argument("--device", type=int, default=0)
     k = sub.add_parser("rlwe-keygen"); k.add_argument("--out", required=True, metavar="DIR")
     k.add_argument("--threshold", type=int, default=2); k.add_argument("--shares", type=int, default=3)
     k.add_argument("--reference-seed", type=int, default=None, metavar="N",
@@ -507,6 +624,8 @@ def main(argv=None):
         return _pool_replay(a)
     if a.cmd == "wallet-sync":
         return _wallet_sync(a)
+    if a.cmd == "withdraw-bundle":
+        return _withdraw_bundle(a)
     if a.cmd == "compile" and a.circuit.endswith(".ccs"):
         from . import ccs
         c = ccs.load_ccs(a.circuit)

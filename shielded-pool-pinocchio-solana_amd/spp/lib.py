@@ -48,7 +48,9 @@ SPP_WALLET_AUDITED = 4              # the pool holds the audit record of wa_comm
 SPP_WALLET_REPEATED = 8             # the commitment sits at more than one leaf
 SPP_TREE_SIZE_NOW = (1 << 64) - 1   # the _at calls: the tree's size at the call (UINT64_MAX)
 SPP_TREE_NO_SIZE = (1 << 64) - 1    # spp_merkle_tree_find_roots / spp_pool_root_sizes: no prefix of this tree has that root
-SPP_ARITH_FR = 0x000                # spp_debug_arith: field bits of the selector (operation codes: csrc/arith_probe.hpp)
+SPP_AUDIT_RESIDENT = 0xFFFFFFFF     # spp_withdrawal_audit_plan / spp_prove_withdrawals: the pool holds this identity's audit record
+SPP_WITHDRAWALS_MAX = 1 << 20       # ... keys / notes per call
+SPP_ARITH_FR = 0x000               # spp_debug_arith: field bits of the selector (operation codes: csrc/arith_probe.hpp)
 SPP_ARITH_FQ = 0x100
 POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
 
@@ -169,6 +171,10 @@ def load_library():
     L.spp_prove_withdraw_notes_at_device.argtypes = [vp, vp, u64, sz, vp, vp, vp, vp, vp]
     L.spp_prove_withdraw_notes_at.argtypes = [vp, vp, u64, sz, cp, cp, vp, vp, vp]
     L.spp_pool_root_sizes.argtypes = [vp, vp, vp, ctypes.POINTER(u64)]
+    # withdrawals from notes: the audit plan, and both proofs in one call (include/spp.h)
+    L.spp_withdrawal_audit_plan.argtypes = [vp, vp, sz, cp, vp, vp, ctypes.POINTER(u32)]
+    L.spp_prove_withdrawals.argtypes = [vp, vp, vp, vp, u64, vp, vp, sz, cp, vp, vp, vp, cp, cp, vp, vp, vp, vp, vp, ctypes.POINTER(u32),
+                                        sz, vp, vp, vp, vp, vp]
     L.spp_shamir_reconstruct.argtypes = [vp, u32, vp, cp, sz, vp, vp]
     L.spp_rlwe_decrypt_batch.argtypes = [vp, vp, sz, vp, vp, vp]
     L.spp_rlwe_sample_key.argtypes = [sz, u32, vp, vp, vp]

@@ -1,7 +1,7 @@
 """Thin object layer over the C ABI: Context (one GPU), CircuitHandle (R1CS + pk + tables in HBM)."""
 import ctypes
 import numpy as np
-from .lib import load_library, check, SppError, PROOF_LEN, SPP_ERR_UNSAT, AUDIT_PW_LEN
+from .lib import load_library, check, SppError, PROOF_LEN, SPP_ERR_UNSAT, AUDIT_PW_LEN, SPP_AUDIT_RESIDENT, SPP_TREE_SIZE_NOW
 
 
 def build_circuit(circuit_id, out_path, aux=None):
@@ -196,6 +196,23 @@ class Context:
         res = ([(int.from_bytes(owners[i, :32].tobytes(), "big"), int.from_bytes(owners[i, 32:].tobytes(), "big")) for i in range(count)],
                [int(f) for f in flags[:count]])
         return res + (tuple(int(v) for v in stats),) if want_stats else res
+
+    def withdrawal_audit_plan(self, keys, pool=None):
+        """Which notes of a batch still need an audit record (spp_withdrawal_audit_plan).  keys: one wa_commitment per note, ints
+        or 32-byte strings compared bytewise (word 2 of ShieldedPoolMerkleTree.sync's records); pool: a Pool of this Context whose
+        audit-record set is consulted and not changed.  Returns (audit_of, audit_note): audit_note the ascending list of the notes
+        that are the first of an identity the pool does not hold, audit_of[i] the position of note i's identity in it, or
+        SPP_AUDIT_RESIDENT."""
+        buf = b"".join(int(k).to_bytes(32, "big") if isinstance(k, int) else bytes(k) for k in keys)
+        if len(buf) % 32:
+            raise ValueError("a key is 32 bytes")
+        count = len(buf) // 32
+        audit_of = (ctypes.c_uint32 * max(count, 1))()
+        audit_note = (ctypes.c_uint32 * max(count, 1))()
+        n = ctypes.c_uint32(0)
+        check(self.L.spp_withdrawal_audit_plan(self.h, None if pool is None else pool.h, count, buf, ctypes.cast(audit_of, ctypes.c_void_p),
+                                               ctypes.cast(audit_note, ctypes.c_void_p), ctypes.byref(n)))
+        return list(audit_of)[:count], list(audit_note)[:n.value]
 
     def msm_g1_pippenger_bench(self, n, seed=5, scale=None, iters=1, small_permille=0):
         """Returns (result bytes, ms per MSM, ms of the bucket kernel). small_permille: share of byte-sized scalars."""
@@ -406,3 +423,88 @@ class CircuitHandle:
         buf = ctypes.create_string_buffer(32 * self.n_wires)
         check(self.L.spp_debug_witness(self.h, ctypes.cast(buf, ctypes.c_void_p), self.n_wires))
         return [int.from_bytes(buf.raw[32 * i:32 * i + 32], "big") for i in range(self.n_wires)]
+
+
+class WithdrawalBundle:
+    """What prove_withdrawals returns: everything the relayer has to post for a batch of notes.
+    proofs, pws, status           the withdraw side, per note (as CircuitHandle.prove_withdraw_notes)
+    audit_of, audit_note          the plan: audit_note[s] is the note whose secrets made record s, audit_of[i] the record of note
+                                  i's identity or SPP_AUDIT_RESIDENT when the pool already holds it
+    audit_proofs, audit_pws, audit_status, c0, c1
+                                  the audit records, per entry of audit_note (as CircuitHandle.prove_audit_records)"""
+
+    def __init__(self, proofs, pws, status, audit_of, audit_note, audit_proofs, audit_pws, audit_status, c0, c1):
+        self.proofs, self.pws, self.status = proofs, pws, status
+        self.audit_of, self.audit_note = audit_of, audit_note
+        self.audit_proofs, self.audit_pws, self.audit_status, self.c0, self.c1 = audit_proofs, audit_pws, audit_status, c0, c1
+
+    @property
+    def n_audits(self):
+        return len(self.audit_note)
+
+    def log(self, addresses):
+        """The instruction list Pool.settle_log takes, in the relayer's order (demo-frontend/app/api/relay/withdraw/route.ts:238-287):
+        for note i its submit_audit first, if note i is the one whose record was proved, then its withdraw to addresses[i]."""
+        if len(addresses) != len(self.proofs):
+            raise ValueError("log: one 32-byte account address per note")
+        out = []
+        for i, address in enumerate(addresses):
+            s = self.audit_of[i]
+            if s != SPP_AUDIT_RESIDENT and self.audit_note[s] == i:
+                out.append(("submit_audit", self.audit_proofs[s], self.audit_pws[s]))
+            out.append(("withdraw", self.proofs[i], self.pws[i], bytes(address)))
+        return out
+
+
+def prove_withdrawals(withdraw_handle, audit_handle, tree, notes, pk_a, pk_b, r=None, e1=None, e2=None, pool=None, size=None,
+                      rs_withdraw=None, rs_audit=None, audit_cap=None):
+    """Both proofs of a batch of withdrawals, one audit record per identity the pool does not hold yet (spp_prove_withdrawals).
+    withdraw_handle / audit_handle: the two CircuitHandles, tree (ShieldedPoolMerkleTree) and pool (Pool, optional) of one Context;
+    notes: (recipient, amount, secret_key, randomness, index) tuples, e.g. from ShieldedPoolMerkleTree.sync; pk_a, pk_b: the RLWE
+    public key; r / e2 [count, 1024] and e1 [count, 64] int8 per NOTE, or all None for noise from the operating system; size: prove
+    against the tree of the first `size` leaves (Pool.root_sizes); rs_withdraw / rs_audit: lists of (r, s) ints per NOTE or None;
+    audit_cap: room for audit records (default: one per note).  Returns a WithdrawalBundle; a refused row has a non-zero status on
+    its side and zero proof bytes.  Raises SppError when the batch needs more than audit_cap records."""
+    from .witness import pack_withdraw_notes
+    L = withdraw_handle.L
+    count = len(notes)
+    buf = pack_withdraw_notes(notes)
+    cap = count if audit_cap is None else int(audit_cap)
+    if (r is None) != (e1 is None) or (r is None) != (e2 is None):
+        raise ValueError("r, e1 and e2: all three or none")
+    p = lambda x: None if x is None else x.ctypes.data_as(ctypes.c_void_p)
+    if r is not None:
+        r = np.ascontiguousarray(r, dtype=np.int8).reshape(count, 1024)
+        e1 = np.ascontiguousarray(e1, dtype=np.int8).reshape(count, 64)
+        e2 = np.ascontiguousarray(e2, dtype=np.int8).reshape(count, 1024)
+    a = np.ascontiguousarray(pk_a, dtype=np.uint32)
+    b = np.ascontiguousarray(pk_b, dtype=np.uint32)
+    if a.shape != (1024,) or b.shape != (1024,):
+        raise ValueError("the public key is two polynomials of 1024 coefficients")
+    rsb = lambda rs: None if rs is None else b"".join(int(x).to_bytes(32, "big") + int(y).to_bytes(32, "big") for x, y in rs)
+    if any(rs is not None and len(rs) != count for rs in (rs_withdraw, rs_audit)):
+        raise ValueError("rs_withdraw / rs_audit: one (r, s) pair per note")
+    wpl, apl = withdraw_handle.pw_len, audit_handle.pw_len
+    proofs = ctypes.create_string_buffer(PROOF_LEN * max(count, 1))
+    pws = ctypes.create_string_buffer(wpl * max(count, 1))
+    status = (ctypes.c_int32 * max(count, 1))()
+    audit_of = (ctypes.c_uint32 * max(count, 1))()
+    audit_note = (ctypes.c_uint32 * max(cap, 1))()
+    n = ctypes.c_uint32(0)
+    aproofs = ctypes.create_string_buffer(PROOF_LEN * max(cap, 1))
+    apws = ctypes.create_string_buffer(apl * max(cap, 1))
+    astatus = (ctypes.c_int32 * max(cap, 1))()
+    c0 = np.zeros((max(cap, 1), 64), dtype=np.uint32)
+    c1 = np.zeros((max(cap, 1), 1024), dtype=np.uint32)
+    vp = lambda x: ctypes.cast(x, ctypes.c_void_p)
+    rc = L.spp_prove_withdrawals(withdraw_handle.h, audit_handle.h, tree.h, None if pool is None else pool.h,
+                                 SPP_TREE_SIZE_NOW if size is None else int(size), p(a), p(b), count, buf, p(r), p(e1), p(e2),
+                                 rsb(rs_withdraw), rsb(rs_audit), vp(proofs), vp(pws), vp(status), vp(audit_of), vp(audit_note),
+                                 ctypes.byref(n), cap, vp(aproofs), vp(apws), vp(astatus), p(c0), p(c1))
+    if rc != 0 and rc != SPP_ERR_UNSAT:
+        check(rc)
+    na = n.value
+    return WithdrawalBundle([proofs.raw[PROOF_LEN * i:PROOF_LEN * (i + 1)] for i in range(count)],
+                            [pws.raw[wpl * i:wpl * (i + 1)] for i in range(count)], list(status)[:count], list(audit_of)[:count],
+                            list(audit_note)[:na], [aproofs.raw[PROOF_LEN * s:PROOF_LEN * (s + 1)] for s in range(na)],
+                            [apws.raw[apl * s:apl * (s + 1)] for s in range(na)], list(astatus)[:na], c0[:na], c1[:na])
