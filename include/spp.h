@@ -745,6 +745,17 @@ int spp_msm_g2(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_
  * redo kernel (0 when all bases are distinct, up to coincidence). */
 int spp_msm_flat_unit(spp_ctx* ctx, int group, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t P, int window_bits, uint8_t* out,
                       uint32_t* redo_lanes);
+/* TEST ONLY: the signed-digit planes of the table walks on their own -- the recoding kernel launched as the MSM stage launches it,
+ * nothing summed.  scalars: M x P values, 32 B big-endian, scalar row m of proof p at scalars + 32 * (m * P + p) (the [wire][proof]
+ * order the kernel reads); rows: N indices < M (base i takes scalar row rows[i]; repeats allowed).  With W = ceil(254 / window_bits)
+ * and Pp = *padded_batch (P, rounded up to a multiple of 64 from 64 proofs on), planes receives W * N * Pp int16 digits, digit j of
+ * (base i, proof p) at planes[(j * N + i) * Pp + p]: for the signed representative v of the scalar (v = s for s <= (r-1)/2, else
+ * s - r) the unique digits in [-2^(c-1), 2^(c-1) - 1] with sum_j d_j 2^(c j) = v.  Entries with p >= P are unspecified.
+ * planes_elems: the capacity of planes in digits (W * N * (P rounded up to 64) always suffices).
+ * SPP_ERR_BAD_INPUT: NULL pointers, window_bits outside [4,16], M, N or P zero, M or N > 2^20, P > 2^16, a row index >= M, a
+ * buffer smaller than the planes. */
+int spp_debug_msm_digits(spp_ctx* ctx, const uint8_t* scalars, size_t M, size_t P, const uint32_t* rows, size_t N, int window_bits,
+                         int16_t* planes, size_t planes_elems, uint32_t* padded_batch);
 
 /* General-base Pippenger (16-bit signed windows, bucket sort + accumulate + reduce) for large n; same conventions. */
 int spp_msm_g1_pippenger(spp_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t out[64]);

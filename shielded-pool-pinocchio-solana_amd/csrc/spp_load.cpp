@@ -982,3 +982,34 @@ extern "C" int spp_msm_flat_unit(spp_ctx* ctx, int group, const uint8_t* bases, 
   if (group == 2) return msm_flat_unit<Fq2, 128>(ctx, bases, n, scalars, P, window_bits, out, redo_lanes);
   return fail(SPP_ERR_BAD_INPUT, "group is 1 or 2");
 }
+// The digit planes on their own (test only): launch_msm_digits as run_msm and the two unit entries above launch it, and the planes
+// as the walks read them -- dig[j][i][p], Pp per row.  The device buffer is zeroed first: entries with p >= P, which the kernel
+// does not write, come back as 0 rather than as whatever the allocation held.
+extern "C" int spp_debug_msm_digits(spp_ctx* ctx, const uint8_t* scalars, size_t M, size_t P, const uint32_t* rows, size_t N, int window_bits,
+                                    int16_t* planes, size_t planes_elems, uint32_t* padded_batch) {
+  if (!ctx || !scalars || !rows || !planes || !padded_batch) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (window_bits < 4 || window_bits > 16) return fail(SPP_ERR_BAD_INPUT, "window_bits outside [4,16]");
+  if (M == 0 || N == 0 || P == 0 || M > (1u << 20) || N > (1u << 20) || P > (1u << 16)) return fail(SPP_ERR_BAD_INPUT, "M, N in [1, 2^20], P in [1, 2^16]");
+  for (size_t i = 0; i < N; i++)
+    if (rows[i] >= M) return fail(SPP_ERR_BAD_INPUT, "rows[%zu] = %u is no scalar row (M = %zu)", i, rows[i], M);
+  const uint32_t cb = (uint32_t)window_bits;
+  const size_t elems = msm_digit_elems((uint32_t)N, (uint32_t)P, cb);
+  if (planes_elems < elems) return fail(SPP_ERR_BAD_INPUT, "the planes of this call hold %zu digits, the buffer %zu", elems, planes_elems);
+  if (elems > ((size_t)1 << 28)) return fail(SPP_ERR_BAD_INPUT, "more than 2^28 digits");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  std::vector<Fr> sc(M * P);
+  for (size_t k = 0; k < M * P; k++) sc[k] = Fr::from_bytes_be(scalars + 32 * k);
+  DevBuf d_sc, d_rows, dig;
+  UP(d_sc, sc.data(), sizeof(Fr) * sc.size());
+  UP(d_rows, rows, sizeof(uint32_t) * N);
+  HIP_TRY(dig.alloc(sizeof(int16_t) * elems));
+  HIP_TRY(hipMemsetAsync(dig.p, 0, sizeof(int16_t) * elems, st));
+  launch_msm_digits(st, d_rows.as<uint32_t>(), d_sc.as<Fr>(), dig.as<int16_t>(), (uint32_t)N, (uint32_t)P, cb);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(planes, dig.p, sizeof(int16_t) * elems, hipMemcpyDeviceToHost));
+  *padded_batch = msm_padded_batch((uint32_t)P);
+  return SPP_OK;
+}

@@ -185,6 +185,7 @@ def load_library():
     L.spp_msm_g1.argtypes = [vp, cp, cp, sz, i32, vp]
     L.spp_msm_g2.argtypes = [vp, cp, cp, sz, i32, vp]
     L.spp_msm_flat_unit.argtypes = [vp, i32, cp, sz, cp, sz, i32, vp, ctypes.POINTER(ctypes.c_uint32)]
+    L.spp_debug_msm_digits.argtypes = [vp, cp, sz, sz, vp, sz, i32, vp, sz, ctypes.POINTER(u32)]
     L.spp_msm_g1_pippenger.argtypes = [vp, cp, cp, sz, vp]
     L.spp_msm_g2_pippenger.argtypes = [vp, cp, cp, sz, vp]
     L.spp_msm_g1_pippenger_bench.argtypes = [vp, sz, ctypes.c_uint64, cp, i32, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]

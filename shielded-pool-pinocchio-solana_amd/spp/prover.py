@@ -111,6 +111,21 @@ class Context:
                                        ctypes.cast(out, ctypes.c_void_p), ctypes.byref(redo)))
         return [out.raw[size * p:size * (p + 1)] for p in range(len(scalar_rows))], redo.value
 
+    def debug_msm_digits(self, scalar_rows, rows, window_bits):
+        """Test only (spp_debug_msm_digits): the signed-digit planes of the table walks, nothing summed.  scalar_rows = M lists of P
+        ints (scalar row m, proof p); rows = N indices < M.  Returns (int16 array W x N x Pp, Pp): digit j of (base i, proof p) at
+        [j][i][p]; entries with p >= P are unspecified."""
+        M, P, N = len(scalar_rows), len(scalar_rows[0]), len(rows)
+        assert all(len(r) == P for r in scalar_rows)
+        W = (254 + int(window_bits) - 1) // int(window_bits)
+        sc = b"".join(int(s).to_bytes(32, "big") for r in scalar_rows for s in r)
+        idx = np.ascontiguousarray(rows, dtype=np.uint32)
+        buf = np.zeros(W * N * ((P + 63) // 64 * 64), dtype=np.int16)
+        pp = ctypes.c_uint32(0)
+        check(self.L.spp_debug_msm_digits(self.h, sc, M, P, idx.ctypes.data_as(ctypes.c_void_p), N, int(window_bits),
+                                          buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(pp)))
+        return buf[:W * N * pp.value].reshape(W, N, pp.value), pp.value
+
     def msm_g1_pippenger(self, bases_bytes, scalars):
         out = ctypes.create_string_buffer(64)
         sc = b"".join(int(s).to_bytes(32, "big") for s in scalars)

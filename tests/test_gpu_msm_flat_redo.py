@@ -3,7 +3,6 @@ unit entry spp_msm_flat_unit: one table row per base, 8-bit windows (32 passes, 
 64-row block, more than one group of four prefetched digits per slice) and 1, 3 or 70 scalar rows (70 is padded to 128 lanes per
 slice: two waves, the second partly filled).  Every row is compared with the CPU oracle's MSM over the same bases and scalars,
 bit for bit; redo_lanes tells which kernel produced the sums."""
-import ctypes
 import random
 
 import pytest
@@ -11,6 +10,8 @@ try:
     import torch  # noqa: F401  (before libspp: both must share ONE HIP runtime; torch's has to be loaded first)
 except Exception:  # pragma: no cover
     torch = None
+
+from msm_group import Group
 
 pytestmark = pytest.mark.gpu
 
@@ -28,53 +29,9 @@ def ctx():
     c.close()
 
 
-class Group:
-    """Points, bytes and the oracle of one group; the oracle's sum of a (bases, scalar row) pair is computed once."""
-
-    def __init__(self, group):
-        from oracle import bn254 as B, native
-        self.B, self.group, self.size = B, group, 64 if group == 1 else 128
-        rng = random.Random(100 + group)
-        if group == 1:
-            gen, add, mul, self.to_bytes = B.G1_GEN, B.g1_add, B.g1_mul, B.g1_to_bytes
-            self.neg = lambda q: (q[0], (B.P - q[1]) % B.P)
-            self.orc = native.lib().orc_msm_g1
-        else:
-            gen, add, mul, self.to_bytes = B.G2_GEN, B.g2_add, B.g2_mul, B.g2_to_bytes
-            self.neg = B.g2_neg
-            self.orc = native.lib().orc_msm_g2
-        pts, p = [], gen
-        for _ in range(N):
-            p = add(p, mul(gen, rng.randrange(1, 1 << 64)))
-            pts.append(p)
-        self.random_pts = pts
-        self.g = mul(gen, 0x1234567)
-        self.other = mul(gen, 99)
-        self.cache = {}
-
-    def raw(self, pts):
-        return b"".join(self.to_bytes(q) for q in pts)
-
-    def oracle(self, bases, row):
-        key = (bases, tuple(row))
-        if key not in self.cache:
-            out = ctypes.create_string_buffer(self.size)
-            self.orc(bases, b"".join(int(s).to_bytes(32, "big") for s in row), len(row), ctypes.cast(out, ctypes.c_void_p))
-            self.cache[key] = out.raw
-        return self.cache[key]
-
-    def check(self, ctx, bases, rows, what, oracle_bases=None, keep=None):
-        got, redo = ctx.msm_flat(self.group, bases, rows, WINDOW)
-        print("%s G%d P=%d: redo_lanes %d" % (what, self.group, len(rows), redo))
-        for p, row in enumerate(rows):
-            exp = self.oracle(bases, row) if keep is None else self.oracle(oracle_bases, [row[i] for i in keep])
-            assert got[p] == exp, (what, self.group, len(rows), p)
-        return redo
-
-
 @pytest.fixture(scope="module")
 def groups():
-    return {g: Group(g) for g in GROUPS}
+    return {g: Group(g, N, WINDOW) for g in GROUPS}
 
 
 def _edge_rows(B, rng, P):
