@@ -168,7 +168,8 @@ int spp_circuit_small_rows(const spp_circuit* c, uint32_t out[2]);
  * out[5..8] = items of the cooperative solver of kind SEQ, PAR, LEVELS, LEVEL_STREAM, out[9] = chunks of the level stream,
  * out[10] = tracks in use (the most of any sequential stretch); out[11] = divisions of the largest wide OP_BATCH_DIV,
  * out[12] = wide steps (OP_BATCH_DIV of 64 or more divisions and OP_COUNT8), out[13] = the wide OP_BATCH_DIV among them;
- * out[14..15] = 0 */
+ * out[14] = OP_SOLVE_ROW rows (the solver of a decoded gnark system) that the cooperative solver takes in level items, out[15] = those
+ * among them whose other factor is inverted at run time; both 0 for a circuit without such rows and under SPP_NO_COOP=1 */
 int spp_circuit_plan_stats(const spp_circuit* c, uint32_t out[16]);
 /* exact bytes of HBM held by the window tables, as allocated (rows sized by range included) */
 uint64_t spp_circuit_table_bytes(const spp_circuit* c);

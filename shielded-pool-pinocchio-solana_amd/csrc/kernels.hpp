@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bn254.hpp"
+#include "coop_items.hpp"
 #include "f29.hpp"
 #include "msm_plan.hpp"
 #include "msm_ragged.hpp"
@@ -25,9 +26,7 @@ struct DevSparse {
   const uint32_t* lit;     // 0, or the coefficient itself when |c| < 2^28: magnitude, bit31 = negative (matrix evaluation
                            // accumulates those terms as wide integers instead of doing a field multiplication each)
 };
-static constexpr uint32_t COEFF_ONE = 0x80000000u;
-static constexpr uint32_t COEFF_MINUS_ONE = 0x40000000u;
-static constexpr uint32_t COEFF_MASK = 0x3fffffffu;
+// COEFF_ONE, COEFF_MINUS_ONE, COEFF_MASK: coop_items.hpp
 
 // Poseidon / Poseidon2 constants in HBM (Montgomery form): one upload per context (spp_ensure_ctx_consts), read by the solver
 // through DevCircuit::hc and by the stand-alone hash kernels
@@ -170,23 +169,21 @@ void launch_load_inputs(hipStream_t st, const uint8_t* d_inputs_be, const uint8_
 // runs the solver program from word `pc` until OP_COMMIT / OP_END; scratch: [SOLVE_SCRATCH_ROWS or more][P] Fr
 static constexpr uint32_t SOLVE_SCRATCH_MIN_ROWS = 324;
 void launch_solve(hipStream_t st, DevCircuit dc, Fr* W, Fr* scratch, uint32_t pc_begin, uint32_t pc_end, uint32_t P);
-// cooperative solver for small batches (one wave per proof; kernels_solve.hip): items = (kind, a, b) triples
-enum : uint32_t { COOP_SEQ = 0, COOP_PAR = 1, COOP_LEVELS = 2, COOP_POSEIDON = 3, COOP_POSEIDON2 = 4, COOP_GRUMPKIN = 5, COOP_LEVEL_STREAM = 6 };
+// cooperative solver for small batches (one wave per proof; kernels_solve.hip): items = (kind, a, b) triples, kinds in coop_items.hpp
 struct DevCoop {
   const uint32_t* items;      // 3 words per item
   const uint32_t* par;        // COOP_PAR: (pc_begin, pc_end) pairs of independent instructions
   const uint32_t* lvl_ptr;    // COOP_LEVELS: rows lvl_rows[lvl_ptr[l] .. lvl_ptr[l+1]) form dependency level l
   const uint32_t* lvl_rows;
+  const uint32_t* lvl_gen;    // three words per entry of lvl_rows: side (COOP_NONE: a plain OP_SOLVE_C row), inv, odiv of an OP_SOLVE_ROW row
   // COOP_LEVEL_STREAM (a = first chunk, b = chunks): the same levels flattened into self-contained records, in chunks of
   // COOP_CHUNK words that the wave stages through LDS one ahead.  Level: [rows n | lanes per row << 24 | some A form << 29 | some C rest << 30][words in the level][offset of row 0..n-1]
   // then per row [output wire][terms of A | bit 31: A = B][terms of B][terms of C without the output][(wire, coefficient word) ...];
-  // 0xffffffff instead of n: the rest of the chunk is padding.  No level crosses a chunk boundary.
+  // 0xffffffff instead of n: the rest of the chunk is padding.  No level crosses a chunk boundary.  A generic row (OP_SOLVE_ROW) has
+  // COOP_ROW_GENERIC | side << 29 in its B word, counts its own side without the output, and carries [inv][odiv] before its terms.
   const uint32_t* lvl_stream;
+  uint32_t generic;           // the program holds the generic solver instructions: the kernel instance that knows them runs
 };
-static constexpr uint32_t COOP_CHUNK = 1024;
-// independent item ranges of one stretch: track t (blockIdx.y) runs items [begin[t], end[t]); only track 0 may use `scratch`
-static constexpr uint32_t COOP_TRACKS = 4;
-struct CoopTracks { uint32_t n; uint32_t begin[COOP_TRACKS], end[COOP_TRACKS]; };
 void launch_solve_coop(hipStream_t st, DevCircuit dc, DevCoop co, Fr* W, Fr* scratch, CoopTracks tracks, uint32_t P);
 // wide forms of the two data-parallel solver instructions (one lane per (element chunk, proof) instead of one per proof)
 void launch_batch_div(hipStream_t st, DevCircuit dc, Fr* W, Fr* scratch, uint32_t k0, uint32_t n, uint32_t P);

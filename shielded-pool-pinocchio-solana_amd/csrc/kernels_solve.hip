@@ -182,9 +182,10 @@ __device__ __noinline__ void dev_grumpkin(const DevCircuit& dc, Fr* __restrict__
   }
 }
 
-// instructions [pc, pc_end) of the solver program for proof p, one lane
+// instructions [pc, pc_end) of the solver program for proof p, one lane.  limb_words: eight words of the lane's own for OP_LIMBS
+// (the cooperative solver, where the lanes of a wave share a proof and so its scratch rows); nullptr: scratch row 0 of the proof
 __device__ __forceinline__ void solve_range(const DevCircuit& dc, Fr* __restrict__ W, Fr* __restrict__ scratch, uint32_t pc, uint32_t pc_end,
-                                            uint32_t P, uint32_t p) {
+                                            uint32_t P, uint32_t p, uint32_t* limb_words = nullptr) {
   const uint32_t* __restrict__ pr = dc.program;
   uint32_t last_k = 0xffffffffu;      // constraint whose B value is cached in last_b (dc.row_flags)
   Fr last_b = Fr::zero();
@@ -309,7 +310,7 @@ __device__ __forceinline__ void solve_range(const DevCircuit& dc, Fr* __restrict
         dev_row_dot(dc.H, dc.coeffs, h, 0, W, P, p).to_canonical(c);
         c[8] = 0;
         // the canonical words go through the lane's scratch row (dynamic word indexing; a handful of calls per proof)
-        uint32_t* cw = reinterpret_cast<uint32_t*>(&scratch[(size_t)0 * P + p]);
+        uint32_t* cw = limb_words ? limb_words : reinterpret_cast<uint32_t*>(&scratch[(size_t)0 * P + p]);
         SPP_UNROLL for (int i = 0; i < 8; i++) cw[i] = c[i];
         for (uint32_t i = 0; i < nl; i++) {
           uint32_t o[8];
@@ -461,14 +462,18 @@ void launch_solve(hipStream_t st, DevCircuit dc, Fr* W, Fr* scratch, uint32_t pc
 // With one lane per proof a single proof is one lane's serial work: 14 ms for the withdraw circuit, 29 ms for the audit
 // circuit, three quarters of the drop-in generateProof latency, almost all of it inside the hash permutations (a lone wave
 // issues one dependent multiplication after the other on one of the chip's 1024 SIMDs).  Here the 64 lanes of a wave belong
-// to ONE proof and the host-built item list (spp_plan.cpp, coop_plan) says how each stretch of the program uses them:
+// to ONE proof and the host-built item list (coop_plan.hpp, coop_build_plan) says how each stretch of the program uses them:
 //   COOP_SEQ       [pc_a, pc_b) on lane 0 (whatever has no parallel form)
-//   COOP_PAR       independent BITS / LIMBS8 / INV_H instructions, one per lane
-//   COOP_LEVELS    a run of SOLVE_C rows in dependency levels: the rows of a level are solved by different lanes
+//   COOP_PAR       independent BITS / LIMBS8 / LIMBS / INV_H instructions, one per lane
+//   COOP_LEVELS    a run of SOLVE_C / SOLVE_ROW rows in dependency levels: the rows of a level are solved by different lanes
+//   COOP_LEVEL_STREAM  the same, the levels as records staged through LDS
+//   COOP_COUNTN    a lookup histogram: the queries dealt over the lanes, the counts in LDS
 //   COOP_POSEIDON  one permutation: state words, the two halves of every S-box (x^3 | x^4) and the MDS products on
 //   COOP_POSEIDON2 different lanes -- three dependent multiplications per partial round instead of 13 (t = 3) / 8
 //   COOP_GRUMPKIN  the fixed-base ladder as a 64-lane prefix sum, one window per lane
 // The values written are the same field elements as the one-lane solver's (the words may be another representative < 2p).
+// The kernel has two instances: programs of a decoded gnark system (DevCoop::generic) run the one that knows OP_SOLVE_ROW rows,
+// their shared inversions and OP_COUNTN; every other circuit runs the one without them.
 
 // Poseidon2 (t = 4) in lane-parallel form: poseidon2.hpp, coop_p2_permute; the S-box powers go to the witness as they appear
 __device__ __noinline__ void coop_poseidon2(const DevCircuit& dc, Fr* __restrict__ W, uint32_t h0, uint32_t out, uint32_t P, uint32_t p,
@@ -574,9 +579,60 @@ __device__ __forceinline__ void solve_c_row(const DevCircuit& dc, Fr* __restrict
   W[(size_t)out * P + p] = a * b - rest;
 }
 
+// Inverses for the lanes of a wave that `need` one (0 for a zero value), every lane of the wave calling: no lane needs one -> nothing;
+// one lane -> that lane inverts; several -> ONE inversion for the wave by prefix / suffix products over the 64 lanes (the scheme of
+// k_batch_div_wave), with one in the lanes that need none or hold zero.
+__device__ __noinline__ Fr wave_shared_inv(const Fr& v, bool need, uint32_t lane) {
+  const bool use = need && !v.is_zero();
+  const uint32_t cnt = (uint32_t)__popcll(__ballot(use));
+  if (cnt == 0) return Fr::zero();
+  if (cnt == 1) {
+    Fr r = Fr::zero();
+    if (use) r = v.inv();
+    return r;
+  }
+  const Fr den = use ? v : Fr::one();
+  Fr pre = den, suf = den;                       // inclusive prefix / suffix products over the wave
+  SPP_UNROLL for (uint32_t off = 1; off < 64; off <<= 1) {
+    const Fr a = lane_get(pre, lane >= off ? lane - off : lane);
+    const Fr b = lane_get(suf, lane + off < 64 ? lane + off : lane);
+    if (lane >= off) pre = pre * a;
+    if (lane + off < 64) suf = suf * b;
+  }
+  Fr inv_all = Fr::zero();
+  if (lane == 63) inv_all = pre.inv();           // pre of lane 63 = product of all 64
+  inv_all = lane_bcast<63>(inv_all);
+  const Fr before = lane_get(pre, lane ? lane - 1 : 0), after = lane_get(suf, lane < 63 ? lane + 1 : 63);
+  Fr inv = inv_all;
+  if (lane > 0) inv = inv * before;
+  if (lane < 63) inv = inv * after;
+  return use ? inv : Fr::zero();
+}
+// The leader lane's step of a generic row (OP_SOLVE_ROW, circuit.hpp): av, bv, cv = <A>, <B>, <C> without the output's term, oi = the
+// inverse of the other factor (sides 0 and 1).
+__device__ __forceinline__ Fr generic_row_value(uint32_t side, const Fr& av, const Fr& bv, const Fr& cv, const Fr& oi, uint32_t inv_ci,
+                                                const Fr* __restrict__ coeffs) {
+  Fr v = side == 2 ? av * bv - cv : cv * oi - (side == 0 ? av : bv);
+  if (inv_ci != COOP_NONE) v = v * coeffs[inv_ci];
+  return v;
+}
+// the other factor's inverse for the rows of one pass of a level: a constant, or shared over the wave; every lane calls
+__device__ __forceinline__ Fr generic_other_inv(bool leader, uint32_t side, uint32_t odiv_ci, const Fr& av, const Fr& bv,
+                                                const Fr* __restrict__ coeffs, uint32_t lane) {
+  const bool divides = leader && side < 2;
+  const bool need = divides && odiv_ci == COOP_NONE;
+  Fr oi = Fr::zero();
+  if (__ballot(need)) oi = wave_shared_inv(side == 0 ? bv : av, need, lane);
+  if (divides && !need) oi = coeffs[odiv_ci];
+  return oi;
+}
+
+template <bool GENERIC>
 __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr* __restrict__ W, Fr* __restrict__ scratch, CoopTracks tracks,
                                                    uint32_t P) {
   __shared__ uint32_t lvl_buf[2][COOP_CHUNK];
+  __shared__ uint32_t gen_words[GENERIC ? 64 * 8 : 1];   // OP_LIMBS: eight words per lane; COOP_COUNTN: up to 256 counts
+  uint32_t* const limb_words = GENERIC ? &gen_words[8 * threadIdx.x] : nullptr;
   const uint32_t p = blockIdx.x, lane = threadIdx.x;
   uint32_t item = tracks.begin[blockIdx.y];
   const uint32_t item_end = tracks.end[blockIdx.y];
@@ -590,7 +646,7 @@ __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr
         const uint32_t n = kind == COOP_SEQ ? 1 : b - a;
         for (uint32_t i = lane; i < n; i += 64) {
           const uint32_t pa = kind == COOP_SEQ ? a : co.par[2 * (a + i)], pb = kind == COOP_SEQ ? b : co.par[2 * (a + i) + 1];
-          solve_range(dc, W, scratch, pa, pb, P, p);
+          solve_range(dc, W, scratch, pa, pb, P, p, limb_words);
         }
         break;
       }
@@ -607,18 +663,30 @@ __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr
             const bool live = mine < r1;
             const uint32_t k = live ? co.lvl_rows[mine] : 0;
             Fr bv = Fr::zero(), av = Fr::zero(), rest = Fr::zero();
-            const bool square = live && (dc.row_flags[k] & 2);
+            // a generic row: the output is the last term of its side, which the side's sum leaves out
+            uint32_t side = COOP_NONE, inv_ci = COOP_NONE, odiv_ci = COOP_NONE;
+            if (GENERIC && live) { side = co.lvl_gen[3 * mine]; inv_ci = co.lvl_gen[3 * mine + 1]; odiv_ci = co.lvl_gen[3 * mine + 2]; }
+            const bool gen = GENERIC && side != COOP_NONE;
+            const bool square = live && !gen && (dc.row_flags[k] & 2);
             if (live) {
-              bv = dev_row_dot(dc.B, dc.coeffs, k, 0, W, P, p, sub, G);
-              if (!square) av = dev_row_dot(dc.A, dc.coeffs, k, 0, W, P, p, sub, G);
-              rest = dev_row_dot(dc.C, dc.coeffs, k, 1, W, P, p, sub, G);
+              bv = dev_row_dot(dc.B, dc.coeffs, k, gen && side == 1 ? 1 : 0, W, P, p, sub, G);
+              if (!square) av = dev_row_dot(dc.A, dc.coeffs, k, gen && side == 0 ? 1 : 0, W, P, p, sub, G);
+              rest = dev_row_dot(dc.C, dc.coeffs, k, gen && side != 2 ? 0 : 1, W, P, p, sub, G);
             }
             for (uint32_t off = G >> 1; off >= 1; off >>= 1) {
               bv = bv + lane_get(bv, lane ^ off);
               av = av + lane_get(av, lane ^ off);
               rest = rest + lane_get(rest, lane ^ off);
             }
-            if (live && sub == 0) {
+            const bool leader = live && sub == 0;
+            if constexpr (GENERIC) {
+              const Fr oi = generic_other_inv(leader && gen, side, odiv_ci, av, bv, dc.coeffs, lane);
+              if (leader && gen) {
+                const DevSparse& m = side == 0 ? dc.A : side == 1 ? dc.B : dc.C;
+                W[(size_t)m.wire[m.rowptr[k + 1] - 1] * P + p] = generic_row_value(side, av, bv, rest, oi, inv_ci, dc.coeffs);
+              }
+            }
+            if (leader && !gen) {
               if (square) av = bv;
               W[(size_t)dc.C.wire[dc.C.rowptr[k + 1] - 1] * P + p] = av * bv - rest;
             }
@@ -651,7 +719,10 @@ __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr
               const bool live = mine < nr;
               const uint32_t base = pos + (live ? sb[pos + 2 + mine] : 2 + nr);
               const uint32_t out = live ? sb[base] : 0, na_w = live ? sb[base + 1] : 0;
-              const uint32_t nA = na_w & 0x7fffffffu, nB = live ? sb[base + 2] : 0, nC = live ? sb[base + 3] : 0;
+              const uint32_t nb_w = live ? sb[base + 2] : 0;
+              const bool gen = GENERIC && (nb_w & COOP_ROW_GENERIC);
+              const uint32_t side = (nb_w >> COOP_ROW_SIDE_SHIFT) & 3u, terms0 = base + (gen ? 6 : 4);
+              const uint32_t nA = na_w & 0x7fffffffu, nB = GENERIC ? nb_w & COOP_ROW_COUNT_MASK : nb_w, nC = live ? sb[base + 3] : 0;
               auto dot = [&](uint32_t start, uint32_t n) {
                 Fr acc = Fr::zero();
                 for (uint32_t t = sub; t < n; t += G) {
@@ -663,13 +734,19 @@ __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr
                 }
                 return acc;
               };
-              Fr av = dot(base + 4, nA), bv = dot(base + 4 + 2 * nA, nB), rest = dot(base + 4 + 2 * (nA + nB), nC);
+              Fr av = dot(terms0, nA), bv = dot(terms0 + 2 * nA, nB), rest = dot(terms0 + 2 * (nA + nB), nC);
               for (uint32_t off = G >> 1; off >= 1; off >>= 1) {
                 bv = bv + lane_get(bv, lane ^ off);
                 av = av + lane_get(av, lane ^ off);
                 rest = rest + lane_get(rest, lane ^ off);
               }
-              if (live && sub == 0) {
+              const bool leader = live && sub == 0;
+              if constexpr (GENERIC) {
+                const uint32_t inv_ci = gen ? sb[base + 4] : COOP_NONE, odiv_ci = gen ? sb[base + 5] : COOP_NONE;
+                const Fr oi = generic_other_inv(leader && gen, side, odiv_ci, av, bv, dc.coeffs, lane);
+                if (leader && gen) W[(size_t)out * P + p] = generic_row_value(side, av, bv, rest, oi, inv_ci, dc.coeffs);
+              }
+              if (leader && !gen) {
                 if (na_w >> 31) av = bv;
                 W[(size_t)out * P + p] = av * bv - rest;
               }
@@ -696,6 +773,22 @@ __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr
       case COOP_GRUMPKIN:
         coop_grumpkin(dc, W, pr + a, P, p, lane);
         break;
+      case COOP_COUNTN:
+        // OP_COUNTN (h0 n out0 size, size <= 256): the queries dealt over the lanes, integer counts in LDS (a sum of ones: the order
+        // of the additions cannot show), then one count per lane to the witness
+        if constexpr (GENERIC) {
+          const uint32_t h0 = pr[a + 1], n = pr[a + 2], out0 = pr[a + 3], size = pr[a + 4] < 256 ? pr[a + 4] : 256;
+          for (uint32_t j = lane; j < 256; j += 64) gen_words[j] = 0;
+          __syncthreads();
+          for (uint32_t i = lane; i < n; i += 64) {
+            uint32_t c[8];
+            dev_row_dot(dc.H, dc.coeffs, h0 + i, 0, W, P, p).to_canonical(c);
+            if (c[0] < size && (c[1] | c[2] | c[3] | c[4] | c[5] | c[6] | c[7]) == 0) atomicAdd(&gen_words[c[0]], 1u);
+          }
+          __syncthreads();
+          for (uint32_t j = lane; j < size; j += 64) W[(size_t)(out0 + j) * P + p] = Fr::from_u64(gen_words[j]);
+        }
+        break;
       default:
         return;
     }
@@ -704,7 +797,8 @@ __global__ void __launch_bounds__(64) k_solve_coop(DevCircuit dc, DevCoop co, Fr
 }
 void launch_solve_coop(hipStream_t st, DevCircuit dc, DevCoop co, Fr* W, Fr* scratch, CoopTracks tracks, uint32_t P) {
   if (tracks.n == 0 || P == 0) return;
-  hipLaunchKernelGGL(k_solve_coop, dim3(P, tracks.n), dim3(64), 0, st, dc, co, W, scratch, tracks, P);
+  if (co.generic) hipLaunchKernelGGL(k_solve_coop<true>, dim3(P, tracks.n), dim3(64), 0, st, dc, co, W, scratch, tracks, P);
+  else hipLaunchKernelGGL(k_solve_coop<false>, dim3(P, tracks.n), dim3(64), 0, st, dc, co, W, scratch, tracks, P);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 #pragma once
 #include "spp_internal.hpp"
 #include "msm_classes.hpp"
+#include "coop_plan.hpp"   // SolveStep, the schedule and the cooperative solver's items
 
 template <class F>
 struct MsmSet {
@@ -65,12 +66,6 @@ struct PendingTable {
   MsmRagged layout;              // flat sets; empty: the uniform layout
   const MsmBlock* blocks;        // its copy on the device
 };
-struct SolveStep {
-  enum Kind { SEQ, BATCH_DIV, COUNT8, COMMIT } kind;
-  uint32_t a = 0, b = 0, c = 0;   // SEQ: [pc_begin, pc_end) ; BATCH_DIV: k0, n ; COUNT8: h0, n, out0
-  // SEQ: the same stretch as items of the cooperative solver (small batches), dealt over independent tracks (coop_plan)
-  uint32_t ntracks = 0, tr_begin[COOP_TRACKS] = {}, tr_end[COOP_TRACKS] = {};
-};
 // Experiment and diagnostic switches that steer the proving path.  Read from the environment by read_switches (spp_load.cpp)
 // every time a circuit is loaded; nothing below the load reads the environment.
 struct Switches {
@@ -89,6 +84,9 @@ struct Switches {
   // batches up to this size are solved by one wave per proof (k_solve_coop); above it the wave-per-64-proofs solver has the
   // better throughput (a cooperative wave runs ~1/3 of the dependent instructions, but 64 times as many waves)
   uint32_t coop_max_batch = 1024;   // SPP_COOP_MAX (experiment) overrides
+  // the same threshold for a program of generic solver instructions (a decoded gnark system: ~7 800 dependency levels of one to
+  // four rows, profiles/generic_coop_probe.json); load_program copies it into coop_max_batch unless SPP_COOP_MAX is set
+  uint32_t coop_max_batch_generic = 1024;
   bool no_side = false;           // SPP_NO_SIDE=1 (experiment): the G2 sum of a small batch on the batch's own stream
   int forced_depth = 0;           // SPP_DEPTH (experiment): batches in flight, 1 .. SPP_NWS; 0: by batch size (ws_depth)
   bool no_split = false;          // SPP_NO_SPLIT=1 (experiment): no cut of a batch into a 64-aligned body and a tail
@@ -113,10 +111,12 @@ struct spp_circuit {
   uint32_t c_bits = 10, n = 0, logn = 0;
   uint32_t max_batch_div = SOLVE_SCRATCH_MIN_ROWS;
   DevCoop coop{};
-  uint32_t coop_item_count[7] = {}, coop_stream_chunks = 0;   // what coop_plan made: items per COOP_* kind, chunks of the level stream (spp_circuit_plan_stats)
+  uint32_t coop_item_count[COOP_KINDS] = {}, coop_stream_chunks = 0;   // what coop_plan made: items per COOP_* kind, chunks of the level stream (spp_circuit_plan_stats)
+  uint32_t coop_generic_rows = 0, coop_generic_divs = 0;   // OP_SOLVE_ROW rows in level items, those with a run-time division
   Switches sw;
-  bool generic_solver = false;    // the program is the solver of a decoded gnark system (OP_SOLVE_ROW ...): ~12 K dependent row solves per
-                                  // proof on one lane -- a batch's solver phase outlasts the rest of it, so three batches take turns
+  bool generic_solver = false;    // the program is the solver of a decoded gnark system (OP_SOLVE_ROW ...): above the cooperative
+                                  // solver's threshold ~12 K dependent row solves per proof on one lane -- a batch's solver phase
+                                  // outlasts the rest of it, so three batches take turns
   uint32_t row_r = 0, row_s = 0, row_rs = 0, n_rows = 0;
   size_t in_stride = 0, pw_stride = 0;   // bytes of one proof's input row and of its public witness (blinding: 64, proof: SPP_PROOF_LEN)
   uint64_t table_bytes = 0;

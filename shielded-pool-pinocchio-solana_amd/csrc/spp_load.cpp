@@ -388,67 +388,20 @@ static int load_r1cs(spp_circuit* c) {
 
 static int load_program(spp_circuit* c) {
   const Circuit& circ = c->circ;
-  // program scan: split into sequential segments (one lane per proof) and wide steps (data-parallel instructions
-  // that get their own kernels: batch divisions and lookup histograms), with the commitment boundary in between
+  // the schedule (coop_plan.hpp, solver_schedule): sequential segments and wide steps, the commitment boundary in between.
+  // SPP_SOLVE_TRACE=1 (diagnostic): one launch per instruction class run, so a kernel trace of a proof shows where the
+  // sequential solver spends its time
   bool generic_ops = false;
-  {
-    const auto& pr = circ.program;
-    size_t pc = 0, seg = 0;
-    auto flush = [&](size_t end) {
-      if (end > seg) c->schedule.push_back({SolveStep::SEQ, (uint32_t)seg, (uint32_t)end, 0});
-    };
-    // SPP_SOLVE_TRACE=1 (diagnostic): one launch per instruction class run, so a kernel trace of a proof shows where the
-    // sequential solver spends its time
-    const bool trace_ops = getenv("SPP_SOLVE_TRACE") != nullptr;
-    if (trace_ops) c->sw.no_coop = true;
-    uint32_t prev_op = OP_END;
-    while (pc < pr.size() && pr[pc] != OP_END) {
-      if (trace_ops && pr[pc] != prev_op) {
-        flush(pc);
-        seg = std::max(seg, pc);
-      }
-      prev_op = pr[pc];
-      switch (pr[pc]) {
-        case OP_SOLVE_C: case OP_SOLVE_A: case OP_MASK: pc += 2; break;
-        case OP_BATCH_DIV:
-          c->max_batch_div = std::max(c->max_batch_div, pr[pc + 2]);
-          if (pr[pc + 2] >= 64) {
-            flush(pc);
-            c->schedule.push_back({SolveStep::BATCH_DIV, pr[pc + 1], pr[pc + 2], 0});
-            seg = pc + 3;
-          }
-          pc += 3;
-          break;
-        case OP_COUNT8:
-          flush(pc);
-          c->schedule.push_back({SolveStep::COUNT8, pr[pc + 1], pr[pc + 2], pr[pc + 3]});
-          seg = pc + 4;
-          pc += 4;
-          break;
-        case OP_BITS: case OP_LIMBS8: case OP_POSEIDON: pc += 4; break;
-        case OP_POSEIDON2: case OP_INV_H: pc += 3; break;
-        case OP_COMMIT:
-          flush(pc);
-          c->schedule.push_back({SolveStep::COMMIT, 0, 0, 0});
-          pc += 1;
-          seg = pc;
-          break;
-        case OP_GRUMPKIN: pc += 5 + pr[pc + 4]; break;
-        // the solver of a decoded gnark system (spp/ccs.py to_sppc_solved): one lane per proof, whatever the batch size -- the
-        // cooperative planner knows nothing of these instructions
-        case OP_SOLVE_ROW: case OP_LIMBS: case OP_COUNTN: pc += 5; generic_ops = true; break;
-        case OP_GK_MUL: pc += 7; generic_ops = true; break;
-        case OP_GLV: pc += 3 + 28; generic_ops = true; break;
-        case OP_EMUL: pc += 3 + 16; generic_ops = true; break;
-        default: return fail(SPP_ERR_FORMAT, "bad opcode %u in solver program", pr[pc]);
-      }
-    }
-    flush(pc);
-  }
+  const bool trace_ops = getenv("SPP_SOLVE_TRACE") != nullptr;
+  if (trace_ops) c->sw.no_coop = true;
+  if (const uint32_t bad = solver_schedule(circ.program, trace_ops, &c->schedule, &c->max_batch_div, &generic_ops))
+    return fail(SPP_ERR_FORMAT, "bad opcode %u in solver program", bad);
 
+  // the solver of a decoded gnark system (spp/ccs.py to_sppc_solved) is planned like any other program: coop_build_plan puts its
+  // rows into levels and its hints into items; only the batch size up to which one wave per proof pays is the program's own
   c->generic_solver = generic_ops;
-  if (generic_ops) c->sw.no_coop = true;
-  else if (int e = coop_plan(c)) return e;
+  if (generic_ops && !getenv("SPP_COOP_MAX")) c->sw.coop_max_batch = c->sw.coop_max_batch_generic;
+  if (int e = coop_plan(c)) return e;
   if (int e = row_paths_plan(c)) return e;
   return 0;
 }
@@ -804,6 +757,7 @@ extern "C" int spp_circuit_plan_stats(const spp_circuit* c, uint32_t out[16]) {
   out[5] = c->coop_item_count[COOP_SEQ]; out[6] = c->coop_item_count[COOP_PAR]; out[7] = c->coop_item_count[COOP_LEVELS];
   out[8] = c->coop_item_count[COOP_LEVEL_STREAM];
   out[9] = c->coop_stream_chunks;
+  if (!c->sw.no_coop) { out[14] = c->coop_generic_rows; out[15] = c->coop_generic_divs; }
   for (const SolveStep& s : c->schedule) {
     if (s.kind == SolveStep::SEQ) out[10] = std::max(out[10], s.ntracks);
     if (s.kind == SolveStep::BATCH_DIV) { out[11] = std::max(out[11], s.b); out[13]++; }

@@ -3,362 +3,26 @@
 // Circuit and uploads them in its last lines; called once per circuit by load_circuit_impl (spp_load.cpp).
 #include "spp_circuit.hpp"
 
-// Item list of the cooperative solver (kernels_solve.hip, k_solve_coop) for every sequential stretch of the schedule.
-// Nothing here changes what is computed: permutations become their lane-parallel form, runs of SOLVE_C rows are ordered
-// by dependency level (level of a row = 1 + the highest level among the rows of the run that write one of its inputs),
-// runs of independent BITS / LIMBS8 / INV_H instructions go one per lane, the rest stays on lane 0.  Items that share no
-// wire (directly or through other items of the stretch) form independent components; the components are dealt over up to
-// COOP_TRACKS waves per proof, longest first (the Merkle chain beside the key derivation; the ciphertext sponge beside the
-// rest of the audit circuit).  Components that use the per-proof scratch rows stay together on track 0.
+// Item list of the cooperative solver (kernels_solve.hip, k_solve_coop) for every sequential stretch of the schedule: built by
+// coop_build_plan (coop_plan.hpp), uploaded here.
 int coop_plan(spp_circuit* c) {
-  const Circuit& circ = c->circ;
-  const auto& pr = circ.program;
-  struct Item { uint32_t kind, a, b; };
-  std::vector<uint32_t> items, par, lvl_ptr{0}, lvl_rows, stream;
-  const Fr f_one = Fr::one(), f_mone = Fr::one().neg();
-  auto coeff_word = [&](uint32_t ci) -> uint32_t {
-    return ci | (circ.coeffs[ci] == f_one ? COEFF_ONE : circ.coeffs[ci] == f_mone ? COEFF_MINUS_ONE : 0u);
-  };
-  // one row of the level stream (see DevCoop::lvl_stream)
-  auto row_record = [&](uint32_t k, std::vector<uint32_t>& out) {
-    const bool square = [&] {
-      const uint32_t a0 = circ.A.rowptr[k], a1 = circ.A.rowptr[k + 1], b0 = circ.B.rowptr[k], b1 = circ.B.rowptr[k + 1];
-      if (a1 - a0 != b1 - b0) return false;
-      for (uint32_t i = 0; i < a1 - a0; i++)
-        if (circ.A.terms[a0 + i].wire != circ.B.terms[b0 + i].wire || circ.A.terms[a0 + i].coeff != circ.B.terms[b0 + i].coeff) return false;
-      return true;
-    }();
-    const uint32_t nA = square ? 0 : circ.A.rowptr[k + 1] - circ.A.rowptr[k], nB = circ.B.rowptr[k + 1] - circ.B.rowptr[k],
-                   nC = circ.C.rowptr[k + 1] - circ.C.rowptr[k] - 1;
-    out.push_back(circ.C.terms[circ.C.rowptr[k + 1] - 1].wire);
-    out.push_back(nA | (square ? 0x80000000u : 0u));
-    out.push_back(nB);
-    out.push_back(nC);
-    auto put = [&](const Sparse& m, uint32_t n) {
-      for (uint32_t t = m.rowptr[k]; t < m.rowptr[k] + n; t++) { out.push_back(m.terms[t].wire); out.push_back(coeff_word(m.terms[t].coeff)); }
-    };
-    put(circ.A, nA); put(circ.B, nB); put(circ.C, nC);
-  };
-  std::vector<uint32_t> level_of(circ.n_wires + 3, 0), stamp(circ.n_wires + 3, 0), writer(circ.n_wires + 3, 0);
-  uint32_t epoch = 0;
-  auto op_len = [&](size_t pc) -> uint32_t {
-    switch (pr[pc]) {
-      case OP_SOLVE_C: case OP_SOLVE_A: case OP_MASK: return 2;
-      case OP_BATCH_DIV: case OP_POSEIDON2: case OP_INV_H: return 3;
-      case OP_COUNT8: case OP_BITS: case OP_LIMBS8: case OP_POSEIDON: return 4;
-      case OP_COMMIT: return 1;
-      case OP_GRUMPKIN: return 5 + pr[pc + 4];
-      default: return 0;
-    }
-  };
-  auto is_par_op = [&](uint32_t op) { return op == OP_BITS || op == OP_LIMBS8 || op == OP_INV_H; };
-  // wires an instruction reads / writes, a rough cost in microseconds of a lone wave, whether it uses the scratch rows
-  struct RW { std::vector<uint32_t> rd, wr; double cost = 0; bool scratch = false; };
-  auto row_rd = [&](RW& x, const Sparse& m, uint32_t k, uint32_t skip_last) {
-    for (uint32_t t = m.rowptr[k]; t + skip_last < m.rowptr[k + 1]; t++) x.rd.push_back(m.terms[t].wire);
-  };
-  auto solve_c_rw = [&](RW& x, uint32_t k) {
-    row_rd(x, circ.A, k, 0); row_rd(x, circ.B, k, 0); row_rd(x, circ.C, k, 1);
-    x.wr.push_back(circ.C.terms[circ.C.rowptr[k + 1] - 1].wire);
-  };
-  auto div_rw = [&](RW& x, uint32_t k) {
-    row_rd(x, circ.B, k, 0); row_rd(x, circ.C, k, 0);
-    x.wr.push_back(circ.A.terms[circ.A.rowptr[k]].wire);
-  };
-  auto op_rw = [&](RW& x, size_t pc, bool coop_form) {
-    switch (pr[pc]) {
-      case OP_SOLVE_C: solve_c_rw(x, pr[pc + 1]); x.cost += 5; break;
-      case OP_SOLVE_A: div_rw(x, pr[pc + 1]); x.cost += 60; x.scratch = true; break;
-      case OP_BATCH_DIV:
-        for (uint32_t k = 0; k < pr[pc + 2]; k++) div_rw(x, pr[pc + 1] + k);
-        x.cost += 60 + 10.0 * pr[pc + 2]; x.scratch = true;
-        break;
-      case OP_BITS: case OP_LIMBS8:
-        row_rd(x, circ.H, pr[pc + 1], 0);
-        for (uint32_t i = 0; i < pr[pc + 2]; i++) x.wr.push_back(pr[pc + 3] + i);
-        x.cost += 5 + 0.2 * pr[pc + 2];
-        break;
-      case OP_INV_H: row_rd(x, circ.H, pr[pc + 1], 0); x.wr.push_back(pr[pc + 2]); x.cost += 40; break;
-      case OP_MASK: x.wr.push_back(pr[pc + 1]); x.cost += 5; break;
-      case OP_POSEIDON: {
-        const uint32_t t = pr[pc + 1], nsbox = 8 * t + (t == 3 ? 57 : 60);
-        for (uint32_t i = 0; i < t; i++) row_rd(x, circ.H, pr[pc + 2] + i, 0);
-        for (uint32_t i = 0; i < 4 * nsbox; i++) x.wr.push_back(pr[pc + 3] + i);
-        x.cost += coop_form ? 175 : 450;
-        break;
-      }
-      case OP_POSEIDON2:
-        for (uint32_t i = 0; i < 4; i++) row_rd(x, circ.H, pr[pc + 1] + i, 0);
-        for (uint32_t i = 0; i < 4 * 88; i++) x.wr.push_back(pr[pc + 2] + i);
-        x.cost += coop_form ? 185 : 480;
-        break;
-      case OP_GRUMPKIN:
-        for (uint32_t i = 0; i < pr[pc + 2]; i++) x.rd.push_back(pr[pc + 1] + i);
-        for (uint32_t i = 0; i < pr[pc + 4]; i++) x.wr.push_back(pr[pc + 5 + i]);
-        x.cost += coop_form ? 300 : 1800;
-        x.scratch = x.scratch || !coop_form;
-        break;
-      default: break;
-    }
-  };
-  for (SolveStep& st : c->schedule) {
-    if (st.kind != SolveStep::SEQ) continue;
-    std::vector<Item> its;
-    size_t pc = st.a, seq0 = st.a;
-    auto push = [&](uint32_t kind, uint32_t a, uint32_t b) { its.push_back({kind, a, b}); };
-    auto flush = [&](size_t end) {
-      if (end > seq0) push(COOP_SEQ, (uint32_t)seq0, (uint32_t)end);
-    };
-    while (pc < st.b) {
-      const uint32_t op = pr[pc];
-      if (op == OP_POSEIDON || op == OP_POSEIDON2 || (op == OP_GRUMPKIN && pr[pc + 4] >= 64 && pr[pc + 4] <= 65)) {
-        flush(pc);
-        push(op == OP_POSEIDON ? COOP_POSEIDON : op == OP_POSEIDON2 ? COOP_POSEIDON2 : COOP_GRUMPKIN, (uint32_t)pc, 0);
-        pc += op_len(pc);
-        seq0 = pc;
-      } else if (op == OP_SOLVE_C) {
-        size_t e = pc;
-        while (e < st.b && pr[e] == OP_SOLVE_C) e += 2;
-        const size_t nrows = (e - pc) / 2;
-        if (nrows < 8) { pc = e; continue; }
-        flush(pc);
-        epoch++;
-        std::vector<std::pair<uint32_t, uint32_t>> rows;   // (level, constraint)
-        uint32_t max_level = 0;
-        for (size_t q = pc; q < e; q += 2) {
-          const uint32_t k = pr[q + 1];
-          uint32_t lv = 0;
-          auto scan = [&](const Sparse& m, uint32_t skip_last) {
-            for (uint32_t t = m.rowptr[k]; t + skip_last < m.rowptr[k + 1]; t++) {
-              const uint32_t w = m.terms[t].wire;
-              if (stamp[w] == epoch) lv = std::max(lv, level_of[w]);
-            }
-          };
-          scan(circ.A, 0); scan(circ.B, 0); scan(circ.C, 1);
-          const uint32_t out = circ.C.terms[circ.C.rowptr[k + 1] - 1].wire;
-          stamp[out] = epoch;
-          level_of[out] = lv + 1;
-          rows.push_back({lv, k});
-          max_level = std::max(max_level, lv);
-        }
-        // rows of the run that share no wire written inside it are independent of each other: one LEVELS item per connected
-        // component (small ones lumped together), so that the tracks below can take them apart (a compiled program keeps the
-        // key derivation and the hash chain in the same run of rows)
-        std::vector<uint32_t> rp(rows.size());
-        for (size_t i = 0; i < rows.size(); i++) rp[i] = (uint32_t)i;
-        auto rfind = [&](uint32_t x) { while (rp[x] != x) x = rp[x] = rp[rp[x]]; return x; };
-        epoch++;
-        for (size_t i = 0; i < rows.size(); i++) {
-          const uint32_t k = rows[i].second;
-          auto link = [&](const Sparse& m, uint32_t skip_last) {
-            for (uint32_t t = m.rowptr[k]; t + skip_last < m.rowptr[k + 1]; t++) {
-              const uint32_t w = m.terms[t].wire;
-              if (stamp[w] == epoch) { const uint32_t ra = rfind((uint32_t)i), rb = rfind(writer[w]); if (ra != rb) rp[ra] = rb; }
-            }
-          };
-          link(circ.A, 0); link(circ.B, 0); link(circ.C, 1);
-          const uint32_t out = circ.C.terms[circ.C.rowptr[k + 1] - 1].wire;
-          stamp[out] = epoch;
-          writer[out] = (uint32_t)i;
-        }
-        std::vector<uint32_t> comp_size(rows.size(), 0), comp_id(rows.size(), 0);
-        for (size_t i = 0; i < rows.size(); i++) comp_size[rfind((uint32_t)i)]++;
-        const uint32_t MISC = 0xffffffffu;
-        std::vector<uint32_t> comp_order;     // big components in order of first appearance, then the lump of small ones
-        bool any_misc = false;
-        for (size_t i = 0; i < rows.size(); i++) {
-          const uint32_t r = rfind((uint32_t)i);
-          if (comp_size[r] < 32) { comp_id[i] = MISC; any_misc = true; continue; }
-          comp_id[i] = r;
-          if (std::find(comp_order.begin(), comp_order.end(), r) == comp_order.end()) comp_order.push_back(r);
-        }
-        if (any_misc) comp_order.push_back(MISC);
-        std::vector<size_t> order(rows.size());
-        for (size_t i = 0; i < rows.size(); i++) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return rows[x].first < rows[y].first; });
-        for (uint32_t cid : comp_order) {
-          const uint32_t l0 = (uint32_t)lvl_ptr.size() - 1;
-          uint32_t cur = 0xffffffffu;
-          std::vector<std::vector<uint32_t>> by_level;      // constraints of this component, level by level
-          for (size_t oi : order) {
-            if (comp_id[oi] != cid) continue;
-            if (rows[oi].first != cur) {
-              if (cur != 0xffffffffu) lvl_ptr.push_back((uint32_t)lvl_rows.size());
-              cur = rows[oi].first;
-              by_level.emplace_back();
-            }
-            lvl_rows.push_back(rows[oi].second);
-            by_level.back().push_back(rows[oi].second);
-          }
-          lvl_ptr.push_back((uint32_t)lvl_rows.size());
-          // the streamed form: levels as self-contained records in chunks of COOP_CHUNK words; a level too big for a chunk is cut
-          // into consecutive sub-levels (its rows are independent), a single row too big for one sends the component down the
-          // table-driven path
-          std::vector<uint32_t> local;          // this component's chunks
-          uint32_t used = 0;                    // words used in the current chunk
-          bool fits = !c->sw.no_level_stream;
-          auto close_chunk = [&] {
-            if (used < COOP_CHUNK) local.push_back(0xffffffffu), used++;
-            local.resize(local.size() + (COOP_CHUNK - used), 0xffffffffu);
-            used = 0;
-          };
-          for (const auto& lv : by_level) {
-            if (!fits) break;
-            size_t i = 0;
-            while (i < lv.size() && fits) {
-              // greedily take rows while the sub-level record fits one chunk
-              std::vector<std::vector<uint32_t>> recs;
-              uint32_t words = 2;
-              while (i < lv.size()) {
-                std::vector<uint32_t> rec;
-                row_record(lv[i], rec);
-                if (words + 1 + rec.size() > COOP_CHUNK - 1) break;
-                words += 1 + (uint32_t)rec.size();
-                recs.push_back(std::move(rec));
-                i++;
-              }
-              if (recs.empty()) { fits = false; break; }
-              if (used + words > COOP_CHUNK - 1 && used) close_chunk();
-              // lanes per row: enough for the longest linear form of the sub-level (every extra doubling costs three shuffle-add
-              // rounds), at most 16, and rows x lanes within the wave when possible
-              uint32_t longest = 1;
-              for (const auto& rec : recs) longest = std::max({longest, rec[1] & 0x7fffffffu, rec[2], rec[3]});
-              uint32_t G = 1;
-              while (G < 16 && G < longest && recs.size() * (G * 2) <= 64) G *= 2;
-              uint32_t need = 0;
-              for (const auto& rec : recs) need |= ((rec[1] & 0x7fffffffu) ? 1u << 29 : 0u) | (rec[3] ? 1u << 30 : 0u);
-              local.push_back((uint32_t)recs.size() | (G << 24) | need);
-              local.push_back(words);
-              uint32_t off = 2 + (uint32_t)recs.size();
-              for (const auto& rec : recs) { local.push_back(off); off += (uint32_t)rec.size(); }
-              for (const auto& rec : recs) local.insert(local.end(), rec.begin(), rec.end());
-              used += words;
-            }
-          }
-          if (fits && !local.empty()) {
-            if (used) close_chunk();
-            const uint32_t chunk0 = (uint32_t)(stream.size() / COOP_CHUNK);
-            stream.insert(stream.end(), local.begin(), local.end());
-            push(COOP_LEVEL_STREAM, chunk0, (uint32_t)(local.size() / COOP_CHUNK));
-          } else {
-            push(COOP_LEVELS, l0, (uint32_t)lvl_ptr.size() - 1);
-          }
-        }
-        pc = e;
-        seq0 = pc;
-      } else if (is_par_op(op)) {
-        // maximal run of lane-independent instructions: none may read a wire an earlier one of the run writes
-        size_t e = pc;
-        epoch++;
-        std::vector<uint32_t> group;
-        while (e < st.b && is_par_op(pr[e])) {
-          const uint32_t h = pr[e + 1];
-          bool dep = false;
-          for (uint32_t t = circ.H.rowptr[h]; t < circ.H.rowptr[h + 1]; t++) dep = dep || stamp[circ.H.terms[t].wire] == epoch;
-          if (dep) break;
-          if (pr[e] == OP_INV_H) stamp[pr[e + 2]] = epoch;
-          else for (uint32_t i = 0; i < pr[e + 2]; i++) stamp[pr[e + 3] + i] = epoch;
-          group.push_back((uint32_t)e);
-          e += op_len(e);
-        }
-        if (group.size() < 4) { pc = group.empty() ? pc + op_len(pc) : e; continue; }
-        flush(pc);
-        const uint32_t g0 = (uint32_t)(par.size() / 2);
-        for (uint32_t q : group) { par.push_back(q); par.push_back(q + op_len(q)); }
-        push(COOP_PAR, g0, g0 + (uint32_t)group.size());
-        pc = e;
-        seq0 = pc;
-      } else {
-        const uint32_t n = op_len(pc);
-        if (n == 0) return fail(SPP_ERR_FORMAT, "bad opcode %u in solver program", op);
-        pc += n;
-      }
-    }
-    flush(st.b);
-
-    // ---- independent components of this stretch -> tracks ----
-    const size_t n = its.size();
-    std::vector<RW> rw(n);
-    for (size_t i = 0; i < n; i++) {
-      const Item& it = its[i];
-      switch (it.kind) {
-        case COOP_SEQ:
-          for (size_t q = it.a; q < it.b; q += op_len(q)) op_rw(rw[i], q, false);
-          break;
-        case COOP_PAR:
-          for (uint32_t g = it.a; g < it.b; g++) op_rw(rw[i], par[2 * g], false);
-          rw[i].cost = 10 + rw[i].cost / 32;
-          break;
-        case COOP_LEVELS:
-          for (uint32_t r = lvl_ptr[it.a]; r < lvl_ptr[it.b]; r++) solve_c_rw(rw[i], lvl_rows[r]);
-          rw[i].cost = 4.5 * (it.b - it.a);
-          break;
-        case COOP_LEVEL_STREAM: {
-          uint32_t nlev = 0;
-          for (uint32_t ch = it.a; ch < it.a + it.b; ch++) {
-            const uint32_t* sb = stream.data() + (size_t)ch * COOP_CHUNK;
-            for (uint32_t pos = 0; pos < COOP_CHUNK && sb[pos] != 0xffffffffu; pos += sb[pos + 1]) {
-              nlev++;
-              for (uint32_t r = 0; r < (sb[pos] & 0xffffffu); r++) {
-                const uint32_t base = pos + sb[pos + 2 + r];
-                const uint32_t nt = (sb[base + 1] & 0x7fffffffu) + sb[base + 2] + sb[base + 3];
-                rw[i].wr.push_back(sb[base]);
-                for (uint32_t t = 0; t < nt; t++) rw[i].rd.push_back(sb[base + 4 + 2 * t]);
-              }
-            }
-          }
-          rw[i].cost = 3.0 * nlev;
-          break;
-        }
-        default: op_rw(rw[i], it.a, true); break;
-      }
-    }
-    std::vector<uint32_t> parent(n);
-    for (size_t i = 0; i < n; i++) parent[i] = (uint32_t)i;
-    auto find = [&](uint32_t x) { while (parent[x] != x) x = parent[x] = parent[parent[x]]; return x; };
-    epoch++;
-    for (size_t i = 0; i < n; i++) {
-      for (uint32_t w : rw[i].rd)
-        if (stamp[w] == epoch) { const uint32_t ra = find((uint32_t)i), rb = find(writer[w]); if (ra != rb) parent[ra] = rb; }
-      for (uint32_t w : rw[i].wr) { stamp[w] = epoch; writer[w] = (uint32_t)i; }
-    }
-    std::vector<double> comp_cost(n, 0.0);
-    std::vector<char> comp_scratch(n, 0);
-    for (size_t i = 0; i < n; i++) { const uint32_t r = find((uint32_t)i); comp_cost[r] += rw[i].cost; comp_scratch[r] |= rw[i].scratch; }
-    std::vector<uint32_t> roots;
-    for (size_t i = 0; i < n; i++) if (find((uint32_t)i) == i) roots.push_back((uint32_t)i);
-    std::sort(roots.begin(), roots.end(), [&](uint32_t x, uint32_t y) { return comp_cost[x] > comp_cost[y]; });
-    double load[COOP_TRACKS] = {};
-    std::vector<uint32_t> track_of(n, 0);
-    for (uint32_t r : roots) if (comp_scratch[r]) { track_of[r] = 0; load[0] += comp_cost[r]; }
-    for (uint32_t r : roots) {
-      if (comp_scratch[r]) continue;
-      uint32_t best = 0;
-      for (uint32_t t = 1; t < COOP_TRACKS; t++) if (load[t] < load[best]) best = t;
-      track_of[r] = best;
-      load[best] += comp_cost[r];
-    }
-    st.ntracks = 0;
-    for (uint32_t t = 0; t < COOP_TRACKS; t++) {
-      st.tr_begin[t] = (uint32_t)(items.size() / 3);
-      for (size_t i = 0; i < n; i++)
-        if (track_of[find((uint32_t)i)] == t) { items.push_back(its[i].kind); items.push_back(its[i].a); items.push_back(its[i].b); }
-      st.tr_end[t] = (uint32_t)(items.size() / 3);
-      if (st.tr_end[t] > st.tr_begin[t]) st.ntracks = t + 1;
-    }
-  }
-  for (size_t i = 0; i < items.size(); i += 3) c->coop_item_count[items[i]]++;
-  c->coop_stream_chunks = (uint32_t)(stream.size() / COOP_CHUNK);
-  if (items.empty()) items.assign(3, 0);
-  if (par.empty()) par.assign(2, 0);
-  if (lvl_rows.empty()) lvl_rows.push_back(0);
-  if (stream.empty()) stream.assign(COOP_CHUNK, 0xffffffffu);
-  uint32_t *d_items, *d_par, *d_lp, *d_lr, *d_ls;
+  CoopPlan pl;
+  if (!coop_build_plan(c->circ, c->schedule, c->sw.no_level_stream, &pl)) return fail(SPP_ERR_FORMAT, "bad opcode %u in solver program", pl.bad_opcode);
+  for (uint32_t k = 0; k < COOP_KINDS; k++) c->coop_item_count[k] = pl.item_count[k];
+  c->coop_stream_chunks = pl.stream_chunks;
+  c->coop_generic_rows = pl.generic_rows;
+  c->coop_generic_divs = pl.generic_divs;
+  if (pl.items.empty()) pl.items.assign(3, 0);
+  if (pl.par.empty()) pl.par.assign(2, 0);
+  if (pl.lvl_rows.empty()) { pl.lvl_rows.push_back(0); pl.lvl_gen.assign(3, COOP_NONE); }
+  if (pl.stream.empty()) pl.stream.assign(COOP_CHUNK, 0xffffffffu);
+  uint32_t *d_items, *d_par, *d_lp, *d_lr, *d_lg, *d_ls;
   int e;
-  if ((e = own_upload(c, &d_items, items)) || (e = own_upload(c, &d_par, par)) || (e = own_upload(c, &d_lp, lvl_ptr)) ||
-      (e = own_upload(c, &d_lr, lvl_rows)) || (e = own_upload(c, &d_ls, stream)))
+  if ((e = own_upload(c, &d_items, pl.items)) || (e = own_upload(c, &d_par, pl.par)) || (e = own_upload(c, &d_lp, pl.lvl_ptr)) ||
+      (e = own_upload(c, &d_lr, pl.lvl_rows)) || (e = own_upload(c, &d_lg, pl.lvl_gen)) || (e = own_upload(c, &d_ls, pl.stream)))
     return e;
-  c->coop.items = d_items; c->coop.par = d_par; c->coop.lvl_ptr = d_lp; c->coop.lvl_rows = d_lr; c->coop.lvl_stream = d_ls;
+  c->coop.items = d_items; c->coop.par = d_par; c->coop.lvl_ptr = d_lp; c->coop.lvl_rows = d_lr; c->coop.lvl_gen = d_lg; c->coop.lvl_stream = d_ls;
+  c->coop.generic = c->generic_solver ? 1u : 0u;
   return 0;
 }
 

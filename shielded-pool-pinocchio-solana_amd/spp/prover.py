@@ -288,7 +288,7 @@ class CircuitHandle:
         return list(s)
 
     PLAN_STATS = ("n_runs", "max_row_terms", "sm_nrows", "sm_nslots", "lg_n", "items_seq", "items_par", "items_levels",
-                  "items_level_stream", "stream_chunks", "tracks", "max_wide_div", "wide_steps", "wide_divs")
+                  "items_level_stream", "stream_chunks", "tracks", "max_wide_div", "wide_steps", "wide_divs", "generic_rows", "generic_divs")
 
     def plan_stats(self):
         """what the load-time planners made of the circuit, by name (spp_circuit_plan_stats in include/spp.h)"""
