@@ -159,6 +159,11 @@ int spp_circuit_msm_windows(const spp_circuit* c, uint32_t bits[7]);
 /* table rows per base of each of those sets (same order): 1 = one row of up to 2^(bits-1) multiples, walked once per window
  * (the throughput layout chosen with window_bits = 0); ceil(254 / bits) = one row per window (explicit window_bits) */
 int spp_circuit_msm_table_rows(const spp_circuit* c, uint32_t rows[7]);
+/* out[0] = lookup-inverse wires 1 / (X - looked-up byte) on the flat A and K sets whose share of those sums is added up by byte
+ * bucket instead of one table walk each (0: fewer than 4 096 of them, the sets are not flat, or env SPP_LOOKUP_BUCKETS=0 at load),
+ * out[1] = the smallest batch (or 64-aligned batch body) that does so: 1024.  Env SPP_LOOKUP_BUCKETS=N at load (experiment): any
+ * circuit with such a wire, batches from N >= 64 proofs.  Same proof bytes either way. */
+int spp_circuit_lookup_buckets(const spp_circuit* c, uint32_t out[2]);
 /* out[0] = rows of A / B / C that the matrix evaluation sums in integer arithmetic (every term a small coefficient times a wire the
  * lookup argument bounds to a byte range: the audit circuit's 1 088 quotient equations), out[1] = such wires (+1: the constant) */
 int spp_circuit_small_rows(const spp_circuit* c, uint32_t out[2]);

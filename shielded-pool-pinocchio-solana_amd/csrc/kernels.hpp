@@ -293,7 +293,8 @@ struct MsmWalk<Fq2> {
 template <class F>
 void launch_build_table(hipStream_t st, const Affine<F>* bases, uint32_t N, uint32_t c, uint32_t Wt, uint32_t row0, uint32_t nrows,
                         Affine<F>* table, XYZZ<F>* tmp, F* tmp_pre, const MsmBlock* blocks = nullptr, uint32_t E = 0);
-// signed c-bit digits of scalars[rows[i]][p] as int16 planes dig[j][i][p] (Pp = msm_padded_batch(P) per row; msm_digit_elems)
+// signed c-bit digits of scalars[rows[i]][p] as int16 planes dig[j][i][p] (Pp = msm_padded_batch(P) per row; msm_digit_elems);
+// rows[i] = 0xffffffff (MSM_ROW_ZERO, msm_lookup.hpp): zero digits, whatever the scalars
 void launch_msm_digits(hipStream_t st, const uint32_t* rows, const Fr* scalars, int16_t* dig, uint32_t N, uint32_t P, uint32_t c);
 // lane g -> (pass, slice, proof); partial[R * Sg][P].  blocks: the block table of a flat set (pl.Wt == 1), required there
 template <class F>
@@ -314,6 +315,23 @@ struct MsmFoldSets {
 };
 template <class F>
 void launch_msm_reduce_multi(hipStream_t st, MsmFoldSets<F> fs, uint32_t nsets, uint32_t P);
+
+// ---- the lookup-inverse wires' share of the A and K sums by byte bucket (kernels_msm_lookup.hip; the method: msm_lookup.hpp) ----
+struct LkbSets {               // index 0: A, 1: K
+  const Affine<Fq>* table[2];
+  const MsmBlock* blocks[2];
+  const uint32_t* pos[2];      // per lookup: its base's index in the set (0xffffffff: the set has no base for it)
+  XYZZ<Fq>* out[2];            // the set's sum (launch_lkb_join)
+};
+size_t lkb_bucket_elems(size_t P);   // elements of `bkt` for a batch of P proofs
+// bytes[j][p] = the value hint row hints[j] takes in proof p if it is a byte, else 0 (kernels_solve.hip)
+void launch_lookup_bytes(hipStream_t st, DevCircuit dc, const Fr* W, const uint32_t* hints, uint32_t L, uint32_t P, uint8_t* bytes);
+// inv[t][p] = 1 / (X_p - t), t < 256, and its digit planes dig[window][t][p]; a proof with X_p = t is refused through status
+void launch_lkb_inverses(hipStream_t st, const Fr* W, uint32_t challenge_wire, uint32_t P, Fr* inv, int8_t* dig, uint32_t* status);
+// both levels for both sets: win[set][window][p] = sum_t dig[window][t][p] * Bkt[set][t][p], the pass sums of a Horner with
+// Sg = 1, R = LKB_WINDOWS, c = LKB_C (launch_msm_reduce_multi)
+void launch_lkb_sums(hipStream_t st, const LkbSets& s, const uint8_t* bytes, const int8_t* dig, XYZZ<Fq>* bkt, XYZZ<Fq>* win, uint32_t L, uint32_t P);
+void launch_lkb_join(hipStream_t st, const LkbSets& s, const XYZZ<Fq>* sum, uint32_t P);   // out[set][p] += sum[set][p]
 
 // the H bases of a proving key in the evaluation basis on the coset (kernels_msm.hip): out[bitrev(i)] = Z'_i
 void launch_g1_eval_basis(hipStream_t st, const G1Affine* pts, uint32_t n_pts, uint32_t logn, const Fr* scale, const Fr* tw_inv, G1XYZZ* work,

@@ -27,7 +27,13 @@ __global__ void __launch_bounds__(256) k_msm_digits(const uint32_t* __restrict__
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t p = (uint32_t)(g % Pp), i = (uint32_t)(g / Pp);
   if (i >= N || p >= P) return;
-  const Fr s = scalars[(size_t)rows[i] * P + p];
+  const uint32_t row = rows[i];
+  if (row == 0xffffffffu) {   // MSM_ROW_ZERO: a base whose share is summed elsewhere (msm_lookup.hpp) -- the walk skips zero digits
+#pragma unroll 1
+    for (uint32_t j = 0; j < W; j++) dig[(size_t)j * N * Pp + (size_t)i * Pp + p] = 0;
+    return;
+  }
+  const Fr s = scalars[(size_t)row * P + p];
   uint32_t l[8];
   s.to_canonical(l);
   const bool neg = canonical_gt_half<FrParams>(l);

@@ -879,6 +879,21 @@ __global__ void __launch_bounds__(256) k_count8_store(const uint32_t* __restrict
   if (g >= 256 * P) return;
   W[(size_t)out0 * P + g] = Fr::from_u64(counters[g]);
 }
+// the looked-up values of the lookup-inverse wires as bytes (msm_lookup.hpp): lane -> (lookup j, proof).  A value that is no byte
+// belongs to a row the satisfaction check refuses; it is stored as 0 so that the bucket index stays inside the bucket array.
+__global__ void __launch_bounds__(256) k_lookup_bytes(DevCircuit dc, const Fr* __restrict__ W, const uint32_t* __restrict__ hints, uint32_t L,
+                                                      uint32_t P, uint8_t* __restrict__ bytes) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (uint64_t)L * P) return;
+  const uint32_t p = (uint32_t)(g % P), j = (uint32_t)(g / P);
+  uint32_t c[8];
+  dev_row_dot(dc.H, dc.coeffs, hints[j], 0, W, P, p).to_canonical(c);
+  bytes[g] = (c[0] < 256 && (c[1] | c[2] | c[3] | c[4] | c[5] | c[6] | c[7]) == 0) ? (uint8_t)c[0] : (uint8_t)0;
+}
+void launch_lookup_bytes(hipStream_t st, DevCircuit dc, const Fr* W, const uint32_t* hints, uint32_t L, uint32_t P, uint8_t* bytes) {
+  const uint64_t lanes = (uint64_t)L * P;
+  if (lanes) hipLaunchKernelGGL(k_lookup_bytes, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, dc, W, hints, L, P, bytes);
+}
 void launch_count8(hipStream_t st, DevCircuit dc, Fr* W, uint32_t* counters, uint32_t h0, uint32_t n, uint32_t out0, uint32_t P) {
   (void)hipMemsetAsync(counters, 0, sizeof(uint32_t) * 256 * (size_t)P, st);
   uint64_t lanes = (uint64_t)n * P;

@@ -3,6 +3,7 @@
 #pragma once
 #include "spp_internal.hpp"
 #include "msm_classes.hpp"
+#include "msm_lookup.hpp"
 #include "coop_plan.hpp"   // SolveStep, the schedule and the cooperative solver's items
 
 template <class F>
@@ -50,6 +51,11 @@ struct Workspace {
   int16_t *dig1 = nullptr, *dig2 = nullptr;
   size_t dig1_cap = 0, dig2_cap = 0;
   int16_t* small = nullptr;           // [sm_nslots][P]: byte-ranged wires as integers (small rows of the matrix evaluation)
+  // byte-bucket sums of the lookup-inverse wires (msm_lookup.hpp, kernels_msm_lookup.hip); lk_bkt = nullptr: not allocated
+  XYZZ<Fq>*lk_bkt = nullptr, *lk_win = nullptr, *lk_sum = nullptr;
+  Fr* lk_inv = nullptr;
+  int8_t* lk_dig = nullptr;
+  uint8_t* lk_bytes = nullptr;
   void* audit_scratch = nullptr;      // temporaries of the audit input pipeline (spp_prove_audit_from_secrets_device), P = cap
   size_t audit_scratch_cap = 0;
   std::vector<void*> owned;
@@ -91,6 +97,11 @@ struct Switches {
   int forced_depth = 0;           // SPP_DEPTH (experiment): batches in flight, 1 .. SPP_NWS; 0: by batch size (ws_depth)
   bool no_split = false;          // SPP_NO_SPLIT=1 (experiment): no cut of a batch into a 64-aligned body and a tail
   bool ragged = true;             // SPP_RAGGED=0 (comparison, fallback): every base wide -- full table rows for all, the windows that affords
+  // Lookup-inverse wires summed by byte bucket (msm_lookup.hpp).  Unset: circuits with at least LKB_MIN_LOOKUPS such wires, batches
+  // from LKB_MIN_BATCH proofs.  SPP_LOOKUP_BUCKETS=N (experiment, tests): every circuit that has such a wire, batches from N
+  // proofs (at least 64); 0: never -- the library then runs the table walks alone, as before the path existed
+  uint32_t lookup_min_batch = LKB_MIN_BATCH;
+  bool lookup_forced = false;
   MsmTuning msm;                  // SPP_MSM_WAVES, SPP_MSM_WAVES_SMALL (experiment): rounds of resident waves per table walk (msm_plan.hpp)
 };
 // Up to a batch size that depends on the circuit s*Ar and r*Bs1 are two more fixed-base sums (sets A and B1 over the witness scaled by s and r) instead of
@@ -122,6 +133,11 @@ struct spp_circuit {
   uint64_t table_bytes = 0;
   MsmSet<Fq> A, B1, K, Z, CB, CS;
   MsmSet<Fq2> B2;
+  // lookup-inverse wires on the flat A (index 0) and K (1) sets (msm_lookup.hpp): lk_n of them (0: the path is off for this
+  // circuit), the hint row of each, its base's index in the set, and the set's rows with MSM_ROW_ZERO for these bases
+  uint32_t lk_n = 0;
+  uint32_t* lk_hints = nullptr;
+  uint32_t *lk_pos[2] = {nullptr, nullptr}, *lk_rows[2] = {nullptr, nullptr};
   Fr *tw_fwd = nullptr, *tw_inv = nullptr, *coset_br = nullptr, *coset_inv_br = nullptr;
   Fr zinv;
   // device copies owned here

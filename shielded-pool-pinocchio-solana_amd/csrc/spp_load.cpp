@@ -114,7 +114,7 @@ static int build_table_chunked(spp_circuit* c, const std::vector<Affine<F>>& pts
 // table layout (msm_ragged.hpp); with every base wide both leave the set as it is, the uniform layout bit for bit.
 template <class F>
 static int make_set(spp_circuit* c, MsmSet<F>* set, std::vector<uint32_t> rows, std::vector<Affine<F>> pts, bool from_h, uint32_t cbits,
-                    bool flat, std::vector<uint32_t> bound = {}) {
+                    bool flat, std::vector<uint32_t> bound = {}, std::vector<uint32_t>* rows_kept = nullptr) {
   set->N = (uint32_t)pts.size();
   set->from_h = from_h;
   set->c = cbits;
@@ -138,6 +138,7 @@ static int make_set(spp_circuit* c, MsmSet<F>* set, std::vector<uint32_t> rows, 
   MsmRagged layout = msm_ragged_layout(bound_o.data(), bound_o.size(), cbits);
   set->narrow = layout.narrow(cbits);
   if (int e = own_upload(c, &set->rows, rows_o)) return e;
+  if (rows_kept) *rows_kept = rows_o;   // the set's rows in table order (load_lookup_buckets)
   if (layout.blocks.empty()) layout.blocks.push_back({0, 1u << (cbits - 1), 0});   // an empty set: nothing is read, the upload is not empty
   if (int e = own_upload(c, &set->blocks, layout.blocks)) return e;
   if (int e = alloc_table_elems<F>(c, layout.elems(), &set->table)) return e;
@@ -248,6 +249,7 @@ struct LoadState {
   WireClasses wc;   // range class of every wire (msm_classes.hpp; all wide under SPP_RAGGED=0)
   bool flat[7] = {false, false, false, false, false, false, false};   // one table row per base (else one per window)
   // the H bases as rows / points of the Z set and, in the product form, the per-wire column sums that join the K set
+  std::vector<uint32_t> rows_a, rows_k;   // rows of the flat A and K sets in table order (empty: not flat)
   std::vector<uint32_t> z_w, xk_w;
   std::vector<G1Affine> z_p, xk_p;
 };
@@ -270,6 +272,11 @@ static Switches read_switches() {
   sw.no_split = getenv("SPP_NO_SPLIT") != nullptr;
   const char* rg = getenv("SPP_RAGGED");
   sw.ragged = !(rg && rg[0] == '0');
+  if (const char* lb = getenv("SPP_LOOKUP_BUCKETS")) {
+    const int v = atoi(lb);
+    sw.lookup_min_batch = v <= 0 ? 0u : (uint32_t)std::max(v, 64);
+    sw.lookup_forced = v > 0;
+  }
   sw.msm = msm_tuning_from_env(getenv("SPP_MSM_WAVES"), getenv("SPP_MSM_WAVES_SMALL"));
   return sw;
 }
@@ -443,7 +450,7 @@ static int load_ntt_tables(spp_circuit* c) {
 }
 
 // the sets whose bases come straight from the key: A, B1, B2
-static int load_key_sets(spp_circuit* c, const LoadState& s) {
+static int load_key_sets(spp_circuit* c, LoadState& s) {
   const PkFile& pk = s.pk;
   const uint32_t* cw = s.cw;
   const bool* flat = s.flat;
@@ -453,7 +460,7 @@ static int load_key_sets(spp_circuit* c, const LoadState& s) {
     std::vector<G1Affine> p = pk.A;
     merge_point(w, p, 0u, pk.alpha1);
     w.push_back(c->row_r); p.push_back(pk.delta1);
-    if ((e = make_set(c, &c->A, w, p, false, cw[0], flat[0], msm_base_bounds(s.wc, w)))) return e;
+    if ((e = make_set(c, &c->A, w, p, false, cw[0], flat[0], msm_base_bounds(s.wc, w), &s.rows_a))) return e;
   }
   {
     std::vector<uint32_t> w = pk.B1_w;
@@ -573,7 +580,7 @@ static int load_h_bases(spp_circuit* c, LoadState& s) {
 }
 
 // the sets that depend on the H bases (K, Z) and the two commitment sets; then every table is built
-static int load_h_sets(spp_circuit* c, const LoadState& s) {
+static int load_h_sets(spp_circuit* c, LoadState& s) {
   const PkFile& pk = s.pk;
   const uint32_t* cw = s.cw;
   const bool* flat = s.flat;
@@ -601,12 +608,45 @@ static int load_h_sets(spp_circuit* c, const LoadState& s) {
     // the key's own K bases inherit the class of their wire (a column sum added to the point does not change the scalar); the
     // wires that join the set through their column sum alone stay wide, like the blinding row
     std::vector<uint32_t> kb = msm_base_bounds(s.wc, pk.K_w);
-    if ((e = make_set(c, &c->K, w, p, false, cw[2], flat[2], kb))) return e;
+    if ((e = make_set(c, &c->K, w, p, false, cw[2], flat[2], kb, &s.rows_k))) return e;
   }
   if ((e = make_set(c, &c->Z, z_w, z_p, true, cw[3], flat[3]))) return e;
   if ((e = make_set(c, &c->CB, pk.CB_w, pk.CB, false, cw[4], false))) return e;
   if ((e = make_set(c, &c->CS, pk.CS_w, pk.CS, false, cw[5], false))) return e;
   return build_pending(c);
+}
+
+// The lookup-inverse wires of the circuit on the flat A and K sets (msm_lookup.hpp): where their bases sit, and a copy of each
+// set's rows in which they read MSM_ROW_ZERO.  Nothing is made -- and the proving path is the table walks alone -- when the switch
+// is off, when either set has a table row per window, or when the scan finds too few such wires to pay for the second level
+// (LKB_MIN_LOOKUPS; none at all under SPP_LOOKUP_BUCKETS=N).
+static int load_lookup_buckets(spp_circuit* c, const LoadState& s) {
+  if (c->sw.lookup_min_batch == 0 || c->A.Wt != 1 || c->K.Wt != 1 || c->A.N == 0 || c->K.N == 0) return 0;
+  const std::vector<LookupInverse> lk = msm_lookup_inverses(c->circ);
+  if (lk.empty() || (!c->sw.lookup_forced && lk.size() < LKB_MIN_LOOKUPS)) return 0;
+  std::vector<int32_t> at(c->circ.n_wires, -1);
+  std::vector<uint32_t> hints(lk.size());
+  for (size_t j = 0; j < lk.size(); j++) {
+    at[lk[j].wire] = (int32_t)j;
+    hints[j] = lk[j].hint;
+  }
+  const std::vector<uint32_t>* rows[2] = {&s.rows_a, &s.rows_k};
+  size_t found = 0;
+  for (int k = 0; k < 2; k++) {
+    std::vector<uint32_t> pos(lk.size(), MSM_ROW_ZERO), zeroed = *rows[k];
+    for (size_t i = 0; i < zeroed.size(); i++)
+      if (zeroed[i] < at.size() && at[zeroed[i]] >= 0) {
+        pos[at[zeroed[i]]] = (uint32_t)i;
+        zeroed[i] = MSM_ROW_ZERO;
+        found++;
+      }
+    if (int e = own_upload(c, &c->lk_pos[k], pos)) return e;
+    if (int e = own_upload(c, &c->lk_rows[k], zeroed)) return e;
+  }
+  if (found == 0) return 0;
+  if (int e = own_upload(c, &c->lk_hints, hints)) return e;
+  c->lk_n = (uint32_t)lk.size();
+  return 0;
 }
 
 // streams and events of the batch workspaces
@@ -687,7 +727,7 @@ static int load_circuit_impl(spp_ctx* ctx, const char* circuit_path, const char*
   c->pw_stride = 12 + 32 * (size_t)(circ.n_public - 1);
   int e;
   if ((e = load_r1cs(c)) || (e = load_program(c)) || (e = load_ntt_tables(c)) || (e = load_key_sets(c, s)) || (e = load_h_bases(c, s)) ||
-      (e = load_h_sets(c, s)) || (e = load_streams(c)))
+      (e = load_h_sets(c, s)) || (e = load_lookup_buckets(c, s)) || (e = load_streams(c)))
     return e;
   guard.c = nullptr;
   *out = c;
@@ -773,6 +813,12 @@ extern "C" int spp_circuit_msm_windows(const spp_circuit* c, uint32_t bits[7]) {
 extern "C" int spp_circuit_msm_table_rows(const spp_circuit* c, uint32_t rows[7]) {
   if (!c || !rows) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   rows[0] = c->A.Wt; rows[1] = c->B1.Wt; rows[2] = c->K.Wt; rows[3] = c->Z.Wt; rows[4] = c->CB.Wt; rows[5] = c->CS.Wt; rows[6] = c->B2.Wt;
+  return SPP_OK;
+}
+extern "C" int spp_circuit_lookup_buckets(const spp_circuit* c, uint32_t out[2]) {
+  if (!c || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  out[0] = c->lk_n;
+  out[1] = c->lk_n ? c->sw.lookup_min_batch : 0;
   return SPP_OK;
 }
 extern "C" int spp_circuit_msm_sizes(const spp_circuit* c, uint32_t sizes[7]) {

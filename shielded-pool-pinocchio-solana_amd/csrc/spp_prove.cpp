@@ -18,6 +18,9 @@ static int ws_set(const spp_circuit* c, Workspace& w, const MsmSet<F>* s, MsmBuf
   if ((e = ws_alloc(w, &b->partial, b->partial_cap))) return e;
   return ws_alloc(w, &b->out, P);
 }
+// whether a batch (or batch body) of P proofs sums its lookup-inverse wires by byte bucket: the circuit has such wires on flat A
+// and K sets (spp_load.cpp) and the batch reaches the threshold (Switches::lookup_min_batch)
+static bool lookup_buckets_on(const spp_circuit* c, size_t P) { return c->lk_n != 0 && c->sw.lookup_min_batch != 0 && P >= c->sw.lookup_min_batch; }
 static int ensure_workspace(spp_circuit* c, Workspace& w, size_t P) {
   if (P <= w.cap) return 0;
   HIP_TRY(hipStreamSynchronize(w.st));
@@ -48,6 +51,15 @@ static int ensure_workspace(spp_circuit* c, Workspace& w, size_t P) {
     if ((e = ws_alloc(w, &w.dig1, w.dig1_cap)) || (e = ws_alloc(w, &w.dig2, w.dig2_cap))) return e;
     if (c->dc.sm_nrows && (e = ws_alloc(w, &w.small, (size_t)c->dc.sm_nslots * P))) return e;
   }
+  w.lk_bkt = nullptr;
+  if (lookup_buckets_on(c, P)) {
+    // the byte-bucket sums of the lookup-inverse wires (msm_lookup.hpp): 2 sets x LKB_SLICES x 256 buckets of 128 B = 512 KiB per
+    // proof, plus 34 KiB of inverses, digits and window sums and one byte per lookup -- 1.1 GB for a workspace of 2 048 audit proofs
+    if ((e = ws_alloc(w, &w.lk_bkt, lkb_bucket_elems(P))) || (e = ws_alloc(w, &w.lk_win, (size_t)2 * LKB_WINDOWS * P)) ||
+        (e = ws_alloc(w, &w.lk_sum, (size_t)2 * P)) || (e = ws_alloc(w, &w.lk_inv, (size_t)LKB_VALUES * P)) ||
+        (e = ws_alloc(w, &w.lk_dig, (size_t)LKB_WINDOWS * LKB_VALUES * P)) || (e = ws_alloc(w, &w.lk_bytes, (size_t)c->lk_n * P)))
+      return e;
+  }
   w.cap = P;
   return 0;
 }
@@ -57,7 +69,8 @@ static int16_t* ws_dig(Workspace& w, Fq2*) { return w.dig2; }
 // digits + accumulate of one set; the caller folds (several sets share the fold launches): b.plan holds the lane layout
 template <class F>
 static void run_msm(spp_circuit* c, Workspace& w, const MsmSet<F>& s, MsmBuf<F>& b, uint32_t P, bool timed, hipStream_t st_override = nullptr,
-                    std::pair<hipEvent_t, hipEvent_t>* ev_override = nullptr, bool fold = true, const Fr* scal_override = nullptr) {
+                    std::pair<hipEvent_t, hipEvent_t>* ev_override = nullptr, bool fold = true, const Fr* scal_override = nullptr,
+                    const uint32_t* rows_override = nullptr) {
   hipStream_t st = st_override ? st_override : w.st;
   const Fr* scal = scal_override ? scal_override : s.from_h ? w.abc : w.W;
   MsmPlan pl = msm_plan(s.N, P, s.c, s.Wt, MsmWalk<F>::occ(s.Wt), c->sw.msm);
@@ -67,7 +80,7 @@ static void run_msm(spp_circuit* c, Workspace& w, const MsmSet<F>& s, MsmBuf<F>&
   if (timed && w.msm_ev_used < w.msm_ev.size()) ev = &w.msm_ev[w.msm_ev_used++];
   if (ev_override) ev = ev_override;
   int16_t* dig = ws_dig(w, (F*)nullptr);
-  launch_msm_digits(st, s.rows, scal, dig, s.N, P, s.c);
+  launch_msm_digits(st, rows_override ? rows_override : s.rows, scal, dig, s.N, P, s.c);
   // the event pair receives the dispatch's own start/stop timestamps (what rocprofv3 reports as the kernel's duration)
   launch_msm_accumulate<F>(st, s.table, s.blocks, dig, b.partial, s.N, P, s.c, pl, ev ? ev->first : nullptr, ev ? ev->second : nullptr);
   if (fold) launch_msm_reduce<F>(st, b.partial, b.out, P, pl, s.c, s.N == 0);
@@ -149,8 +162,28 @@ static int prove_on_device(spp_circuit* c, Workspace& w, uint32_t P, const uint8
     const Fr* scal[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, w.Ws, w.Wr};
     const int nsets = scaled_blind ? 7 : 5;
     if (scaled_blind) launch_scale_witness(st, w.W, w.Ws, w.Wr, c->n_rows, c->row_r, c->row_s, P);
+    // The lookup-inverse wires of A and K (msm_lookup.hpp): their digit planes are zero in the two walks below, their share is
+    // summed by byte bucket here and joins A.out / K.out behind the folds.  Inside this stage, so the stage times stay comparable
+    // (spp_timings: msm_g1); the per-launch times of spp_msm_kernel_ms are those of the walks alone, as before.
+    const bool lkb = lookup_buckets_on(c, P) && w.lk_bkt;
+    const LkbSets lks{{c->A.table, c->K.table}, {c->A.blocks, c->K.blocks}, {c->lk_pos[0], c->lk_pos[1]}, {w.A.out, w.K.out}};
+    const uint32_t* rows[7] = {lkb ? c->lk_rows[0] : nullptr, nullptr, lkb ? c->lk_rows[1] : nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (lkb) {
+      launch_lookup_bytes(st, c->dc, w.W, c->lk_hints, c->lk_n, P, w.lk_bytes);
+      launch_lkb_inverses(st, w.W, circ.challenge_wire, P, w.lk_inv, w.lk_dig, d_status);
+      launch_lkb_sums(st, lks, w.lk_bytes, w.lk_dig, w.lk_bkt, w.lk_win, c->lk_n, P);
+      MsmFoldSets<Fq> lf{};
+      for (uint32_t k = 0; k < 2; k++) {
+        lf.partial[k] = w.lk_win + (size_t)k * LKB_WINDOWS * P;
+        lf.out[k] = w.lk_sum + (size_t)k * P;
+        lf.Sg[k] = 1;
+        lf.R[k] = LKB_WINDOWS;
+        lf.c[k] = LKB_C;
+      }
+      launch_msm_reduce_multi<Fq>(st, lf, 2, P);   // no slices to fold: the Horner over the window sums
+    }
     for (int i = 0; i < nsets; i++) {
-      run_msm(c, w, *sets[i], *bufs[i], P, i < 5, nullptr, nullptr, false, scal[i]);
+      run_msm(c, w, *sets[i], *bufs[i], P, i < 5, nullptr, nullptr, false, scal[i], rows[i]);
       fs.partial[i] = bufs[i]->partial;
       fs.out[i] = bufs[i]->out;
       fs.Sg[i] = sets[i]->N ? bufs[i]->plan.Sg : 0;
@@ -158,6 +191,7 @@ static int prove_on_device(spp_circuit* c, Workspace& w, uint32_t P, const uint8
       fs.c[i] = sets[i]->c;
     }
     launch_msm_reduce_multi<Fq>(st, fs, nsets, P);   // the slice sums are folded level by level in shared launches, then Horner
+    if (lkb) launch_lkb_join(st, lks, w.lk_sum, P);
   }
   hipEventRecord(w.ev[4], st);
   hipStreamWaitEvent(st, w.ev_b2, 0);   // join the G2 MSM
@@ -538,7 +572,9 @@ extern "C" int spp_timings(spp_circuit* c, int which, float ms[9]) {
   return SPP_OK;
 }
 
-// per-launch durations of the MSM kernels of one batch, in launch order: commitment (CB), A, B1, K, Z, PoK (CS), then the G2 set
+// per-launch durations of the MSM kernels of one batch, in launch order: commitment (CB), A, B1, K, Z, PoK (CS), then the G2 set.
+// The table walks alone: the byte-bucket kernels of the lookup-inverse wires (msm_lookup.hpp) are not in A or K here; their time
+// is in stage 3 of spp_timings (msm_g1, ev[3] .. ev[4]) with the walks, the folds and the Horner launches.
 extern "C" int spp_msm_kernel_ms(spp_circuit* c, int which, float ms[7]) {
   if (!c || !ms) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   HIP_TRY(hipSetDevice(c->ctx->device));

@@ -287,6 +287,12 @@ class CircuitHandle:
         check(self.L.spp_circuit_small_rows(self.h, s))
         return list(s)
 
+    def lookup_buckets(self):
+        """(lookup-inverse wires summed by byte bucket, smallest batch that does so) -- spp_circuit_lookup_buckets"""
+        s = (ctypes.c_uint32 * 2)()
+        check(self.L.spp_circuit_lookup_buckets(self.h, s))
+        return list(s)
+
     PLAN_STATS = ("n_runs", "max_row_terms", "sm_nrows", "sm_nslots", "lg_n", "items_seq", "items_par", "items_levels",
                   "items_level_stream", "stream_chunks", "tracks", "max_wide_div", "wide_steps", "wide_divs", "generic_rows", "generic_divs")
 
