@@ -424,7 +424,10 @@ int spp_pairing_check_host(uint32_t n_pairs, const uint8_t* g1s, const uint8_t* 
 int spp_shamir_reconstruct(spp_ctx* ctx, uint32_t t, const uint32_t* xs, const uint8_t* ys, size_t n, uint8_t* secret_be,
                            uint32_t* sk_mod_q);
 /* rlweDecrypt (shamir.ts:134-169 / rlwe_decrypt.py:106-132) for `count` ciphertexts: c0 count*64, c1 count*1024 in
- * [0,q); msg = count * 64 recovered byte slots (owner_x = slots 0..31 little-endian, owner_y = slots 32..63). */
+ * [0,q); msg = count * 64 recovered byte slots (owner_x = slots 0..31 little-endian, owner_y = slots 32..63).
+ * A sk_mod_q, c0 or c1 value >= q is refused with SPP_ERR_BAD_INPUT before any device work, the ciphertext and the coefficient
+ * named in spp_last_error(), msg untouched: the kernel's sums are sized for coefficients below q.  Records that may be
+ * malformed are opened in place by spp_audit_open_batch, which decrypts the residues and raises SPP_AUDIT_BAD_CIPHERTEXT. */
 int spp_rlwe_decrypt_batch(spp_ctx* ctx, const uint32_t* sk_mod_q, size_t count, const uint32_t* c0, const uint32_t* c1, uint8_t* msg);
 
 /* ---- auditor key generation (scripts/rlwe_keygen.py:98-182, shamir_share_field :51-65) ----

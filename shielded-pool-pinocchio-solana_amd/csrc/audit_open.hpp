@@ -79,6 +79,21 @@ SPP_HD uint8_t ao_decrypt_slot(const uint32_t* sk2, const uint32_t* c1, uint32_t
   return (uint8_t)(((k % 256) + 256) % 256);
 }
 
+// one reconstructed key coefficient as k_shamir_combine hands it to the decryption (reconstructSk, shamir.ts:97-120 /
+// rlwe_decrypt.py:73-91): c, the canonical limbs of a value v of Fr, stands for v when v <= (r - 1) / 2 and for v - r above
+// that; the result is that integer mod q in [0, q).  An honest coefficient has |v| <= 3; any other value is reduced all the
+// same: |v| mod q by Horner over the eight limbs (the remainder stays below q < 2^28, so remainder * 2^32 + limb < 2^60), then
+// q minus that on the negative side.
+SPP_HD uint32_t ao_centred_mod_q(const uint32_t c[8]) {
+  const bool neg = canonical_gt_half<FrParams>(c);
+  uint32_t m[8];
+  if (neg) canonical_negate<FrParams>(c, m);
+  else { SPP_UNROLL for (int i = 0; i < 8; i++) m[i] = c[i]; }
+  unsigned long long r = 0;
+  for (int i = 7; i >= 0; i--) r = ((r << 32) | m[i]) % (unsigned long long)AO_Q;
+  return neg ? (r ? (uint32_t)(AO_Q - (uint32_t)r) : 0u) : (uint32_t)r;
+}
+
 // where slot t of the message lands in the 64-byte owner record owner_x | owner_y, each 32 B big-endian: the slots are the
 // little-endian bytes of owner_x (0..31) then of owner_y (32..63) (generate_audit.py:489-496, rlwe_decrypt.py:127-132)
 SPP_HD uint32_t ao_owner_byte(uint32_t t) { return t < 32 ? 31 - t : 95 - t; }

@@ -765,14 +765,7 @@ __global__ void __launch_bounds__(256) k_shamir_combine(const Fr* __restrict__ l
   if (sk_mod_q) {
     uint32_t c[8];
     acc.to_canonical(c);
-    // centred value must be small (|v| < 2^31) for a key coefficient; larger values are reduced limb-wise
-    const bool neg = canonical_gt_half<FrParams>(c);
-    uint32_t m[8];
-    if (neg) canonical_negate<FrParams>(c, m);
-    else { SPP_UNROLL for (int i = 0; i < 8; i++) m[i] = c[i]; }
-    unsigned long long r = 0;   // |v| mod q by Horner over the limbs
-    for (int i = 7; i >= 0; i--) r = ((r << 32) | m[i]) % (unsigned long long)RL_Q;
-    sk_mod_q[k] = neg ? (r ? (uint32_t)(RL_Q - (long long)r) : 0u) : (uint32_t)r;
+    sk_mod_q[k] = ao_centred_mod_q(c);   // audit_open.hpp: small for a key coefficient, reduced limb-wise whatever it is
   }
 }
 void launch_shamir_combine(hipStream_t st, const Fr* lambda, const uint8_t* ys_be, uint32_t t, uint32_t n, uint8_t* secret_be,

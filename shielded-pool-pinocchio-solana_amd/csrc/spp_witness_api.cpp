@@ -935,6 +935,14 @@ extern "C" int spp_rlwe_decrypt_batch(spp_ctx* ctx, const uint32_t* sk_mod_q, si
   if (count == 0) return SPP_OK;
   for (int i = 0; i < 1024; i++)
     if (sk_mod_q[i] >= 167772161u) return fail(SPP_ERR_BAD_INPUT, "secret key coefficient not in [0, q)");
+  // k_rlwe_decrypt takes the coefficients as they are: its 64-bit sums are sized for values below q (audit_open.hpp).  A record
+  // that may be malformed is opened by spp_audit_open_batch, which reduces the coefficient and flags the record.
+  for (size_t k = 0; k < count; k++) {
+    for (int i = 0; i < 64; i++)
+      if (c0[k * 64 + i] >= 167772161u) return fail(SPP_ERR_BAD_INPUT, "ciphertext %zu: c0[%d] not in [0, q)", k, i);
+    for (int i = 0; i < 1024; i++)
+      if (c1[k * 1024 + i] >= 167772161u) return fail(SPP_ERR_BAD_INPUT, "ciphertext %zu: c1[%d] not in [0, q)", k, i);
+  }
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;

@@ -543,7 +543,8 @@ def reconstruct_sk(ctx, shares):
 
 
 def rlwe_decrypt(ctx, sk_mod_q, c0, c1):
-    """Batch: c0 [count,64], c1 [count,1024] -> list of (owner_x, owner_y) and the raw byte slots."""
+    """Batch: c0 [count,64], c1 [count,1024] -> list of (owner_x, owner_y) and the raw byte slots.  Coefficients in [0, q): a
+    larger one is refused (SppError); Context.audit_open opens and flags records that may be malformed."""
     c0 = np.ascontiguousarray(c0, dtype=np.uint32).reshape(-1, MSG_SLOTS)
     count = c0.shape[0]
     c1 = np.ascontiguousarray(c1, dtype=np.uint32).reshape(count, RLWE_N)
