@@ -784,6 +784,59 @@ int spp_msm_g1_pippenger_bench_dist(spp_ctx* ctx, size_t n, uint64_t seed, uint3
  * (spp/multi.py msm_g1_sharded).  out = this share's partial sum. */
 int spp_msm_g1_pippenger_bench_shard(spp_ctx* ctx, size_t n_total, size_t first, size_t count, uint64_t seed, uint32_t small_permille,
                                      const uint8_t scale_be[32], int iters, uint8_t out[64], float* ms_total, float* ms_bucket_kernel);
+/* out[i] = scalar * points[i] for ONE scalar and n G1 points (64 B each, 64 zero bytes = infinity, which maps to infinity): the
+ * kernel of the setup ceremony below, one lane per point.  n = 0 is SPP_OK.  SPP_ERR_BAD_INPUT: scalar 0, a scalar >= r, a point
+ * that is not on the curve or has a coordinate >= q. */
+int spp_g1_scale_points(spp_ctx* ctx, const uint8_t* points /* n*64 */, size_t n, const uint8_t scalar_be[32], uint8_t* out /* n*64 */);
+/* The same with timings (profiles/setup_ceremony_probe.py): *kernel_ms = the scaling kernel alone, between two events; *host_ms = one
+ * host thread running scalar_mul (csrc/bn254.hpp) and to_affine over the first min(host_points, n) points, whose bytes must equal
+ * the kernel's (else SPP_ERR_HIP).  kernel_ms and host_ms may be NULL. */
+int spp_g1_scale_points_timed(spp_ctx* ctx, const uint8_t* points, size_t n, const uint8_t scalar_be[32], uint8_t* out, float* kernel_ms,
+                              size_t host_points, float* host_ms);
+
+/* ---- setup ceremony: contributions to the delta of a proving key (Groth16 phase 2) ----
+ * spp_setup derives all toxic waste from one seed, so whoever ran it can forge proofs for its key.  A contribution multiplies delta
+ * by a secret d nobody else learns: delta1' = d delta1, delta2' = d delta2, K' = K / d (the private wires' section), Z' = Z / d;
+ * every other byte of the proving key (SPPK layout) and of the verifying key (gnark raw layout) is copied.  After a chain of
+ * contributions the key is sound if ONE contributor was honest and forgot d.  The contributed key loads, proves and verifies
+ * through the existing calls; the on-chain verifier is redeployed from the final vk, as after spp_setup.
+ *
+ * (d, k) = fr.Hash(entropy, "spp-groth16-contribute-v1", 2 elements) -- the derivation of spp_setup's toxic waste; entropy NULL:
+ * 32 bytes from the operating system.  The same entropy and inputs give the same three outputs byte for byte.  d = 0 is refused.
+ * receipt = delta1' (64) | T = k delta1 (64) | z = k + c d mod r (32, big-endian), a proof of knowledge of d with
+ * c = fr.Hash(SHA256(pk_in bytes) | delta1 | delta1' | T, "spp-groth16-contribute-c1"), points as 64 B raw.
+ * d, 1/d, k and the digits of 1/d are overwritten in host and device memory before the call returns, on every path.
+ * SPP_ERR_IO: a file cannot be read or written; SPP_ERR_FORMAT: pk_in / vk_in do not parse or hold an invalid point;
+ * SPP_ERR_BAD_INPUT: NULL, vk_in does not carry pk_in's delta, d = 0. */
+#define SPP_CONTRIB_RECEIPT_LEN 160
+int spp_setup_contribute(spp_ctx* ctx, const char* pk_in, const char* vk_in, const uint8_t entropy[32] /* NULL = OS randomness */,
+                         const char* pk_out, const char* vk_out, uint8_t receipt[SPP_CONTRIB_RECEIPT_LEN]);
+/* One link of a chain: is (pk_after, vk_after) a contribution to (pk_before, vk_before) with this receipt?  *ok = 1 and *reason = 0,
+ * or *ok = 0 and *reason = the FIRST check that fails, in this order:
+ *   SPP_CONTRIB_FORMAT              a file does not parse
+ *   SPP_CONTRIB_NOT_A_DELTA_CHANGE  the proving keys differ outside delta1, delta2, the K points and the Z points (header, counts,
+ *                                   wire lists and every other section are compared byte for byte)
+ *   SPP_CONTRIB_POINT_INVALID       a delta1, a K or a Z point of either key is not on the curve or has a coordinate >= q (checked on
+ *                                   the device before any sum touches them); delta1' is infinity; a delta2 is not a point of the
+ *                                   order-r subgroup of the twist; `after` has a point at infinity where `before` has none
+ *   SPP_CONTRIB_RECEIPT             the receipt's delta1' is not pk_after's, T is no point, z >= r, or z delta1 != T + c delta1'
+ *   SPP_CONTRIB_DELTA_PAIR          e(delta1', G2) e(-G1, delta2') != 1 (the generators of spp_setup)
+ *   SPP_CONTRIB_SCALING             with rho_i = the first 128 bits of SHA256(SHA256(pk_before) | SHA256(pk_after) | i as 8 bytes
+ *                                   big-endian), P = sum rho_i (K | Z)_i of pk_before and P' the same of pk_after (device Pippenger):
+ *                                   e(P', delta2') e(-P, delta2) != 1.  The rho_i are fixed only once both files are: a key in which
+ *                                   some point is not (1/d) times its original passes with probability about 2^-128
+ *   SPP_CONTRIB_VK                  vk_after differs from vk_before outside delta1 | delta2, or does not carry pk_after's
+ * A refusal is SPP_OK with *ok = 0.  The return value is an error only for I/O (SPP_ERR_IO), NULL arguments or the device. */
+#define SPP_CONTRIB_OK 0
+#define SPP_CONTRIB_FORMAT 1
+#define SPP_CONTRIB_NOT_A_DELTA_CHANGE 2
+#define SPP_CONTRIB_POINT_INVALID 3
+#define SPP_CONTRIB_RECEIPT 4
+#define SPP_CONTRIB_DELTA_PAIR 5
+#define SPP_CONTRIB_SCALING 6
+#define SPP_CONTRIB_VK 7
+int spp_setup_verify_contribution(spp_ctx* ctx, const char* pk_before, const char* vk_before, const char* pk_after, const char* vk_after,
+                                  const uint8_t receipt[SPP_CONTRIB_RECEIPT_LEN], int* ok, uint32_t* reason);
 
 #ifdef __cplusplus
 }

@@ -377,5 +377,10 @@ void launch_scale_witness(hipStream_t st, const Fr* W, Fr* Ws, Fr* Wr, uint32_t 
 // out[i] = scalars[i] * G for a generator table built with launch_build_table (N=1)
 template <class F>
 void launch_fixed_base_mul(hipStream_t st, const Affine<F>* gen_table, uint32_t c, const Fr* scalars, uint32_t n, Affine<F>* out);
+// ---- setup ceremony (kernels_setup.hip; the method: setup_contrib.hpp) ----
+// out[i] = k * pts[i] for ONE scalar k, given as the len digits of its non-adjacent form (sc_naf_recode), least significant first
+void launch_g1_scale(hipStream_t st, const G1Affine* pts, uint32_t n, const int8_t* dig, uint32_t len, G1Affine* out);
+// raw: n points of 64 B (X | Y big-endian) -> pts[i] in Montgomery form and flags[i] = SC_POINT_OK / SC_POINT_INF / SC_POINT_BAD
+void launch_g1_decode_check(hipStream_t st, const uint8_t* raw, uint32_t n, G1Affine* pts, uint32_t* flags);
 
 }  // namespace spp

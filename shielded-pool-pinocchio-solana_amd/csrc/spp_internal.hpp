@@ -11,6 +11,7 @@
 //   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
 //   spp_withdrawals_api.cpp  the withdrawal plan: which notes of a batch still need an audit record (spp_prove_withdrawals itself is in spp_prove.cpp)
+//   spp_ceremony_api.cpp the setup ceremony: contributions to a key's delta, their receipts and verifier, the scaling unit call
 //   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points, the raw-word arithmetic probe (spp_debug_arith)
 #pragma once
 #include "../../include/spp.h"
@@ -250,5 +251,7 @@ int spp_check_notes(size_t count, const uint8_t* notes);
 // points into it (load_r1cs), so the buffers are in ctx->owned and live until the context goes, whatever circuits close first.
 int spp_ensure_ctx_consts(spp_ctx* ctx);
 int spp_ensure_rlwe(spp_ctx* ctx);         // NTT tables of the RLWE witness kernel
+// Horner over the window sums launch_pippenger_g1 left on the device, after the stream was synchronised (spp_micro_api.cpp)
+G1Affine pippenger_finish(const G1XYZZ* d_windows);
 // a new stream that really runs beside `ref` (spp_api.cpp)
 __attribute__((visibility("hidden"))) int pick_concurrent_stream(hipStream_t ref, hipStream_t* out);

@@ -64,7 +64,7 @@ extern "C" int spp_debug_arith(spp_ctx* ctx, uint32_t selector, uint32_t arg, si
 // -----------------------------------------------------------------------------------------------------
 // general-base Pippenger MSM (BASELINE.json configs[4])
 // -----------------------------------------------------------------------------------------------------
-static G1Affine pippenger_finish(const G1XYZZ* d_windows) {
+G1Affine pippenger_finish(const G1XYZZ* d_windows) {
   // Horner over the 16 window sums: r = sum_j 2^(16 j) W_j
   std::vector<G1XYZZ> w(pippenger_windows());
   hipMemcpy(w.data(), d_windows, sizeof(G1XYZZ) * w.size(), hipMemcpyDeviceToHost);

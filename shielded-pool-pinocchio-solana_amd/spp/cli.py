@@ -50,6 +50,14 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # identity's record, then its withdraw), which pool-replay takes, and per record DIR/record_<s>.proof,
                               # record_<s>.pw and ciphertext_<s>.json, which audit-open takes.  --with-deposits: the log begins with
                               # the deposits of all leaves.  exit 1 if the circuit refused a row
+    python -m spp.cli setup-contribute <name>.pk <name>.vk --out DIR [--entropy HEX32]
+                              # one contribution to a setup ceremony: multiplies the key's delta by a secret drawn from the operating
+                              # system (--entropy: for reproducible tests only) and writes DIR/<name>.pk, DIR/<name>.vk and
+                              # DIR/<name>.receipt; prints the SHA-256 of the receipt, which the contributor publishes
+    python -m spp.cli setup-verify <pk0> <vk0> <pk1> <vk1> <receipt1> [<pk2> <vk2> <receipt2> ...]
+                              # a chain of contributions, link by link: exit 0 if every link is a contribution to the key before it,
+                              # else exit 1 naming the first failing link and its reason (FORMAT, NOT_A_DELTA_CHANGE, POINT_INVALID,
+                              # RECEIPT, DELTA_PAIR, SCALING, VK)
     python -m spp.cli execute target/<name>.json Prover.toml [-o target/<name>.gz]               # `nargo execute`: ACIR witness stack
     python -m spp.cli prove   target/<name>.json target/<name>.gz target/<name>.sppc target/<name>.pk
                               # sunspot's own argument order (acir, witness, constraint system, proving key;
@@ -558,6 +566,76 @@ def _verify_batch(a):
     return 0 if all(got) else 1
 
 
+def _setup_contribute(a):
+    import hashlib
+    try:   # everything that can be wrong with the arguments and the files is found before a device is opened
+        entropy = None
+        if a.entropy is not None:
+            entropy = bytes.fromhex(a.entropy[2:] if a.entropy.lower().startswith("0x") else a.entropy)
+            if len(entropy) != 32:
+                raise ValueError("--entropy is 32 bytes of hexadecimal")
+        for p in (a.pk, a.vk):
+            open(p, "rb").close()
+        os.makedirs(a.out, exist_ok=True)
+    except (OSError, ValueError) as e:
+        print("spp setup-contribute: %s" % e, file=sys.stderr)
+        return 2
+    name = os.path.splitext(os.path.basename(a.pk))[0]
+    pk_out, vk_out, receipt_out = (os.path.join(a.out, name + ext) for ext in (".pk", ".vk", ".receipt"))
+    if os.path.exists(pk_out) and os.path.samefile(pk_out, a.pk):
+        print("spp setup-contribute: --out is the directory of the key itself; the key before is needed to verify the contribution", file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        receipt = ctx.setup_contribute(a.pk, a.vk, pk_out, vk_out, entropy)
+    except lib.SppError as e:
+        print("spp setup-contribute: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    open(receipt_out, "wb").write(receipt)
+    print("setup-contribute: %s, %s" % (pk_out, vk_out))
+    print("receipt %s sha256 %s" % (receipt_out, hashlib.sha256(receipt).hexdigest()))
+    return 0
+
+
+def parse_ceremony_chain(files):
+    """[(pk_before, vk_before, pk_after, vk_after, receipt path)] per link from the arguments of setup-verify, or ValueError"""
+    if len(files) < 5 or (len(files) - 2) % 3:
+        raise ValueError("setup-verify takes <pk0> <vk0> and then triples <pk> <vk> <receipt>")
+    keys = [(files[0], files[1])] + [(files[i], files[i + 1]) for i in range(2, len(files), 3)]
+    return [keys[k] + keys[k + 1] + (files[4 + 3 * k],) for k in range(len(keys) - 1)]
+
+
+def _setup_verify(a):
+    try:   # everything that can be wrong with the arguments and the files is found before a device is opened
+        links = parse_ceremony_chain(a.files)
+        for p in a.files:
+            open(p, "rb").close()
+        receipts = [open(link[4], "rb").read() for link in links]
+    except (OSError, ValueError) as e:
+        print("spp setup-verify: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        for k, (link, receipt) in enumerate(zip(links, receipts), 1):
+            if len(receipt) != lib.SPP_CONTRIB_RECEIPT_LEN:
+                ok, reason = False, lib.SPP_CONTRIB_FORMAT
+            else:
+                ok, reason = ctx.setup_verify_contribution(*link[:4], receipt)
+            if not ok:
+                print("link %d (%s): REFUSED, %s" % (k, link[2], lib.CONTRIB_REASON_NAMES[reason]))
+                return 1
+            print("link %d (%s): a contribution to %s" % (k, link[2], link[0]))
+    except lib.SppError as e:
+        print("spp setup-verify: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    print("setup-verify: %d links verified" % len(links))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="spp")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -611,7 +689,17 @@ def main(argv=None):
     kc.add_argument("--shares", nargs="+", required=True, metavar="SHARE.json", help="threshold many share files")
     kc.add_argument("--params", default=None, help="rlwe_params.json (default: next to the public key; without one the bound is 3)")
     kc.add_argument("--device", type=int, default=0)
+    sc = sub.add_parser("setup-contribute"); sc.add_argument("pk"); sc.add_argument("vk")
+    sc.add_argument("--out", required=True, metavar="DIR", help="<name>.pk, <name>.vk and <name>.receipt go here (not the key's own directory)")
+    sc.add_argument("--entropy", default=None, metavar="HEX32", help="for reproducible tests only: the default draws from the operating system")
+    sc.add_argument("--device", type=int, default=0)
+    sv = sub.add_parser("setup-verify"); sv.add_argument("files", nargs="+", metavar="FILE", help="<pk0> <vk0> then <pk> <vk> <receipt> per link")
+    sv.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.cmd == "setup-contribute":
+        return _setup_contribute(a)
+    if a.cmd == "setup-verify":
+        return _setup_verify(a)
     if a.cmd == "rlwe-keygen":
         return _rlwe_keygen(a)
     if a.cmd == "rlwe-key-check":

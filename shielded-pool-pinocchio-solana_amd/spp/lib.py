@@ -52,6 +52,17 @@ SPP_AUDIT_RESIDENT = 0xFFFFFFFF     # spp_withdrawal_audit_plan / spp_prove_with
 SPP_WITHDRAWALS_MAX = 1 << 20       # ... keys / notes per call
 SPP_ARITH_FR = 0x000               # spp_debug_arith: field bits of the selector (operation codes: csrc/arith_probe.hpp)
 SPP_ARITH_FQ = 0x100
+# the setup ceremony, spp_setup_contribute / spp_setup_verify_contribution (include/spp.h)
+SPP_CONTRIB_RECEIPT_LEN = 160       # delta1_after | T | z
+SPP_CONTRIB_OK = 0
+SPP_CONTRIB_FORMAT = 1
+SPP_CONTRIB_NOT_A_DELTA_CHANGE = 2
+SPP_CONTRIB_POINT_INVALID = 3
+SPP_CONTRIB_RECEIPT = 4
+SPP_CONTRIB_DELTA_PAIR = 5
+SPP_CONTRIB_SCALING = 6
+SPP_CONTRIB_VK = 7
+CONTRIB_REASON_NAMES = ("OK", "FORMAT", "NOT_A_DELTA_CHANGE", "POINT_INVALID", "RECEIPT", "DELTA_PAIR", "SCALING", "VK")
 POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
 
 
@@ -188,6 +199,10 @@ def load_library():
     L.spp_debug_msm_digits.argtypes = [vp, cp, sz, sz, vp, sz, i32, vp, sz, ctypes.POINTER(u32)]
     L.spp_msm_g1_pippenger.argtypes = [vp, cp, cp, sz, vp]
     L.spp_msm_g2_pippenger.argtypes = [vp, cp, cp, sz, vp]
+    L.spp_g1_scale_points.argtypes = [vp, cp, sz, cp, vp]
+    L.spp_g1_scale_points_timed.argtypes = [vp, cp, sz, cp, vp, ctypes.POINTER(ctypes.c_float), sz, ctypes.POINTER(ctypes.c_float)]
+    L.spp_setup_contribute.argtypes = [vp, cp, cp, cp, cp, cp, vp]
+    L.spp_setup_verify_contribution.argtypes = [vp, cp, cp, cp, cp, cp, ctypes.POINTER(i32), ctypes.POINTER(u32)]
     L.spp_msm_g1_pippenger_bench.argtypes = [vp, sz, ctypes.c_uint64, cp, i32, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.spp_msm_g1_pippenger_bench_dist.argtypes = [vp, sz, ctypes.c_uint64, ctypes.c_uint32, cp, i32, vp, ctypes.POINTER(ctypes.c_float),
                                                   ctypes.POINTER(ctypes.c_float)]

@@ -1,6 +1,7 @@
 """Thin object layer over the C ABI: Context (one GPU), CircuitHandle (R1CS + pk + tables in HBM)."""
 import ctypes
 import numpy as np
+from . import lib
 from .lib import load_library, check, SppError, PROOF_LEN, SPP_ERR_UNSAT, AUDIT_PW_LEN, SPP_AUDIT_RESIDENT, SPP_TREE_SIZE_NOW
 
 
@@ -46,6 +47,41 @@ class Context:
     def setup(self, circuit_path, seed32, pk_path, vk_path):
         assert len(seed32) == 32
         check(self.L.spp_setup(self.h, circuit_path.encode(), bytes(seed32), pk_path.encode(), vk_path.encode()))
+
+    def setup_contribute(self, pk_in, vk_in, pk_out, vk_out, entropy=None):
+        """One contribution to the delta of a proving key (spp_setup_contribute): writes pk_out / vk_out, returns the 160-byte
+        receipt.  entropy: 32 bytes, or None for the operating system's randomness (what every real contribution uses)."""
+        assert entropy is None or len(entropy) == 32
+        receipt = ctypes.create_string_buffer(lib.SPP_CONTRIB_RECEIPT_LEN)
+        check(self.L.spp_setup_contribute(self.h, pk_in.encode(), vk_in.encode(), None if entropy is None else bytes(entropy),
+                                          pk_out.encode(), vk_out.encode(), ctypes.cast(receipt, ctypes.c_void_p)))
+        return receipt.raw
+
+    def setup_verify_contribution(self, pk_before, vk_before, pk_after, vk_after, receipt):
+        """One link of a ceremony chain (spp_setup_verify_contribution): (accepted, reason) with reason one of lib.SPP_CONTRIB_*
+        (0 when accepted; lib.CONTRIB_REASON_NAMES has the names).  A refusal is a result, not an SppError."""
+        assert len(receipt) == lib.SPP_CONTRIB_RECEIPT_LEN
+        ok, reason = ctypes.c_int(0), ctypes.c_uint32(0)
+        check(self.L.spp_setup_verify_contribution(self.h, pk_before.encode(), vk_before.encode(), pk_after.encode(), vk_after.encode(),
+                                                   bytes(receipt), ctypes.byref(ok), ctypes.byref(reason)))
+        return bool(ok.value), reason.value
+
+    def g1_scale_points(self, points_bytes, scalar):
+        """scalar * P for every 64-byte point of points_bytes (spp_g1_scale_points): the ceremony's kernel on its own."""
+        n = len(points_bytes) // 64
+        assert len(points_bytes) == 64 * n
+        out = ctypes.create_string_buffer(max(64 * n, 1))
+        check(self.L.spp_g1_scale_points(self.h, points_bytes, n, int(scalar).to_bytes(32, "big"), ctypes.cast(out, ctypes.c_void_p)))
+        return out.raw[:64 * n]
+
+    def g1_scale_points_timed(self, points_bytes, scalar, host_points=0):
+        """(scaled points, ms of the kernel alone, ms of one host thread over the first host_points points)"""
+        n = len(points_bytes) // 64
+        out = ctypes.create_string_buffer(max(64 * n, 1))
+        kernel_ms, host_ms = ctypes.c_float(0), ctypes.c_float(0)
+        check(self.L.spp_g1_scale_points_timed(self.h, points_bytes, n, int(scalar).to_bytes(32, "big"), ctypes.cast(out, ctypes.c_void_p),
+                                               ctypes.byref(kernel_ms), int(host_points), ctypes.byref(host_ms)))
+        return out.raw[:64 * n], kernel_ms.value, host_ms.value
 
     def load_circuit(self, circuit_path, pk_path, window_bits=0, bits=None):
         """bits: 7 planned window sizes (plan_windows) instead of window_bits / a budget of this circuit's own."""
