@@ -29,6 +29,9 @@
  *   spp_audit_open_batch      scripts/rlwe_decrypt.py:61-149 for a batch of such records, after `sunspot verify`
  *                             (audit_circuit/prove_audit.sh:98-99) and with the two binding checks the script leaves out
  *   spp_audit_open_batch_rlc  the same, the proofs verified by random linear combination
+ *   spp_rlwe_partial_decrypt_batch / spp_rlwe_combine_partials / spp_audit_open_batch_partials / spp_rlwe_sample_smudge
+ *                             the same opening by t of m auditors who never rebuild the key (no counterpart in the reference, whose
+ *                             rlwe_decrypt.py:61-91 and shamir.ts:97-169 reconstruct it)
  *   spp_pool_*                the pool program's state and decisions, shielded_pool_program/src: ShieldedPoolState and its root ring
  *                             (state.rs:6-46, instructions/initialize.rs:65-69), process_submit_audit
  *                             (instructions/submit_audit.rs:41-87) and process_withdraw (instructions/withdraw.rs:94-175) for a
@@ -478,6 +481,51 @@ int spp_audit_open_batch(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, const u
 int spp_audit_open_batch_rlc(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint32_t* sk_mod_q, size_t count, const uint8_t* proofs,
                              const uint8_t* pws, const uint32_t* c0, const uint32_t* c1, uint32_t group, uint8_t* owners, uint32_t* flags,
                              uint32_t stats[4] /* optional */);
+
+/* ---- threshold opening: t of m auditors open records and nobody ever holds the key ----
+ * spp_shamir_reconstruct puts the whole RLWE key on one machine, which can then open every record, past and future.  Here each
+ * auditor i of a participating set S (|S| = t) computes a PARTIAL decryption from its own share s_i (the share files of
+ * spp_shamir_split, unchanged) and a combiner who holds no share turns t partials into the message:
+ *   p_i[k] = lambda_i * (s_i * c1 mod X^1024+1)[k] + blind_i[k]  over BN254 Fr, for the 64 message slots k, lambda_i the Lagrange
+ *            coefficient at 0 of x_i in S;  sum_i lambda_i s_i = sk coefficient by coefficient and the product is linear, so
+ *   sum_i p_i[k] = (sk * c1)[k] + sum_i blind_i[k], a small integer whose centred lift is exact: reduced mod q, added to c0[k] and
+ *            rounded it is the byte spp_rlwe_decrypt_batch gives, bit for bit (with e = 0; see below).
+ *   blind_i[k] = e + q * rho + sum_{j in S, j != i} sgn(x_i, x_j) * M(seed_ij, ct_commitment, k):  e (int32) and rho (uint64) are the
+ *            caller's smudging noise (spp_rlwe_sample_smudge): q * rho vanishes mod q, e joins the ciphertext's noise -- the sum over S
+ *            must stay well below Delta/2 = 327 680 together with the ciphertext's own (<= 18 435 when honest).  M is fr.Hash
+ *            (expand_message_xmd, SHA-256, 48 bytes mod r) under the tag "spp-partial-mask" of the 64 bytes seed_ij | bytes 4..31 of the
+ *            big-endian ct_commitment | k as 4 bytes big-endian; sgn = +1 when x_i < x_j, else -1: the masks of a pair cancel in
+ *            the sum, and a single partial is uniformly masked.  The commitment is the Poseidon2 sponge RECOMPUTED from the c0 and c1
+ *            handed in, so a mask is never used for two different c1.
+ * What this does and does not protect is spelt out in INTEGRATION.md, "Threat model of the threshold opening".
+ * All three device calls refuse with SPP_ERR_BAD_INPUT before any device work, naming the offending index in spp_last_error() and
+ * leaving the outputs untouched: NULL required pointers, t == 0, t > 64, self >= t, an x equal to 0 or repeated, a share value or a
+ * partial >= r, a c0 or c1 value >= q (the partial and the combine call; the open call flags bit 2 as spp_audit_open_batch does),
+ * count > 2^24.  count == 0 is SPP_OK.  Synchronous and serialised on the context.  Device buffers that held the share, the scaled
+ * share or the pair seeds are zeroed before they are freed. */
+#define SPP_PARTIAL_LEN 32
+#define SPP_AUDIT_BAD_PARTIALS 8   /* some slot of the combined partials is not a small integer (|.| >= 2^104; honest ones stay
+                                      below 2^99): a wrong share, set or record */
+/* host-only, OS randomness, uniform by rejection: e[n] in [-bound, bound] (bound <= 2^20), rho[n] uniform 64-bit */
+int spp_rlwe_sample_smudge(size_t n, uint32_t bound, int32_t* e, uint64_t* rho);
+/* Auditor `self` (a position in xs) of the set xs[t]: partials = count*64*32 B, record-major, 32 B big-endian canonical each.
+ * share_be: 1024*32 B canonical, the auditor's own share.  c0 count*64, c1 count*1024 in [0,q).  e, rho: count*64 each, or NULL
+ * (= 0).  pair_seeds: t*32 B in xs order, entry j the seed shared with auditor xs[j] (entry `self` is not read), or NULL: no masks --
+ * for tests and for t == 1 only, an unmasked partial is a linear equation in the share.  ct_commitments (optional out): count*32 B,
+ * the commitments the masks were keyed by; the caller compares them with the records' public witnesses.
+ * With t == 1 the partial is s * c1 + blind. */
+int spp_rlwe_partial_decrypt_batch(spp_ctx* ctx, uint32_t t, const uint32_t* xs, uint32_t self, const uint8_t* share_be, size_t count,
+                                   const uint32_t* c0, const uint32_t* c1, const int32_t* e, const uint64_t* rho,
+                                   const uint8_t* pair_seeds, uint8_t* partials, uint8_t* ct_commitments);
+/* The combiner: partials = t*count*64*32 B, auditor-major (auditor i's output of the call above at i*count*64*32).  msg: count*64
+ * byte slots as spp_rlwe_decrypt_batch writes them, always written; flags (optional): count, 0 or SPP_AUDIT_BAD_PARTIALS. */
+int spp_rlwe_combine_partials(spp_ctx* ctx, uint32_t t, size_t count, const uint8_t* partials, const uint32_t* c0, uint8_t* msg,
+                              uint32_t* flags);
+/* spp_audit_open_batch with t partials per record in the place of sk_mod_q: same vk == NULL behaviour, same owners, bits 1, 2 and 4
+ * decided as there on the combined decryption, bit 8 (SPP_AUDIT_BAD_PARTIALS) added. */
+int spp_audit_open_batch_partials(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, uint32_t t, const uint8_t* partials, size_t count,
+                                  const uint8_t* proofs, const uint8_t* pws, const uint32_t* c0, const uint32_t* c1, uint8_t* owners,
+                                  uint32_t* flags);
 
 /* ---- the pool ledger: which of these proofs would the pool accept? ---- */
 /* A device-resident restatement of the state the pool program decides on (shielded_pool_program/src): ShieldedPoolState's root ring

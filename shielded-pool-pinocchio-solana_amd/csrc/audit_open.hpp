@@ -54,6 +54,21 @@ SPP_HD void ao_sk2_entry(uint32_t s, uint32_t& lo, uint32_t& hi) {
   lo = s;
   hi = s ? AO_Q - s : 0u;
 }
+// the rounding tail of one slot, shared by ao_decrypt_slot and the threshold path (rlwe_partial.hpp):
+//   round(centred(c0[t] + prod) / Delta) mod 256 -- floor division, then Python's round(): half to even.
+// c0_t and prod = (sk * c1)[t] mod q: both below q.
+SPP_HD uint8_t ao_round_slot(uint32_t c0_t, uint32_t prod) {
+  const long long q = (long long)AO_Q, delta = (long long)AO_DELTA;
+  long long noisy = ((long long)c0_t + (long long)prod) % q;
+  if (noisy > q / 2) noisy -= q;                              // centered_mod (rlwe_decrypt.py:54-58)
+  long long k = noisy / delta, rem = noisy % delta;
+  if (rem < 0) {
+    rem += delta;
+    k -= 1;
+  }
+  if (2 * rem > delta || (2 * rem == delta && (k & 1))) k += 1;
+  return (uint8_t)(((k % 256) + 256) % 256);
+}
 // message slot t of rlweDecrypt (rlwe_decrypt.py:101-118, shamir.ts:134-169), as k_rlwe_decrypt computes it:
 //   (sk * c1)[t] = sum_j sk2[(t - j) mod 2048] * c1[j]   -- 28 x 28-bit products, the 64-bit sum folded mod q every 128 terms;
 //   round(centred(c0[t] + (sk * c1)[t]) / Delta) mod 256 -- floor division, then Python's round(): half to even.
@@ -67,16 +82,7 @@ SPP_HD uint8_t ao_decrypt_slot(const uint32_t* sk2, const uint32_t* c1, uint32_t
       acc = 0;
     }
   }
-  const long long q = (long long)AO_Q, delta = (long long)AO_DELTA;
-  long long noisy = ((long long)c0_t + (long long)(total % (unsigned long long)AO_Q)) % q;
-  if (noisy > q / 2) noisy -= q;                              // centered_mod (rlwe_decrypt.py:54-58)
-  long long k = noisy / delta, rem = noisy % delta;
-  if (rem < 0) {
-    rem += delta;
-    k -= 1;
-  }
-  if (2 * rem > delta || (2 * rem == delta && (k & 1))) k += 1;
-  return (uint8_t)(((k % 256) + 256) % 256);
+  return ao_round_slot(c0_t, (uint32_t)(total % (unsigned long long)AO_Q));
 }
 
 // one reconstructed key coefficient as k_shamir_combine hands it to the decryption (reconstructSk, shamir.ts:97-120 /

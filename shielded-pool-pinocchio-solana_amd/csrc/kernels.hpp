@@ -158,6 +158,20 @@ void launch_shamir_split(hipStream_t st, const Fr* xs, const uint8_t* secrets_be
 // of launch_verify for the same records, enqueued before on `st`
 void launch_audit_open(hipStream_t st, HashConsts hc, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, const uint8_t* pws,
                        const int32_t* proof_ok, uint8_t* owners, uint32_t* flags, uint32_t count);
+// the threshold form (rlwe_partial.hpp): residues count * 64 = (sk * c1)[t] mod q from launch_rlwe_combine in the place of the key,
+// bad_partials[i] != 0 adds SPP_AUDIT_BAD_PARTIALS
+void launch_audit_open_partials(hipStream_t st, HashConsts hc, const uint32_t* residues, const uint32_t* bad_partials, const uint32_t* c0,
+                                const uint32_t* c1, const uint8_t* pws, const int32_t* proof_ok, uint8_t* owners, uint32_t* flags, uint32_t count);
+// U: 8 * 1024 words, the limb-major table of lambda * share (share_be 1024 * 32 B canonical)
+void launch_partial_scale(hipStream_t st, const Fr& lambda, const uint8_t* share_be, uint32_t* U);
+// one block per record: partials count * 64 * 32 B; xs[t], seeds t * 32 B or nullptr, e / rho count * 64 or nullptr; ct_be count * 32 B,
+// always written: the commitments the masks are keyed by (a kernel of their own above RP_COOP_SPONGE_MAX records)
+void launch_rlwe_partial(hipStream_t st, HashConsts hc, const uint32_t* U, uint32_t t, const uint32_t* xs, uint32_t self, const uint8_t* seeds,
+                         const uint32_t* c0, const uint32_t* c1, const int32_t* e, const uint64_t* rho, uint8_t* partials, uint8_t* ct_be,
+                         uint32_t count);
+// partials t * count * 64 * 32 B auditor-major -> residues count * 64, msg count * 64 (needs c0), flags count: each optional
+void launch_rlwe_combine(hipStream_t st, uint32_t t, const uint8_t* partials, const uint32_t* c0, uint32_t* residues, uint8_t* msg, uint32_t* flags,
+                         uint32_t count);
 void launch_audit_msg(hipStream_t st, const uint8_t* xy_be, uint8_t* msg, uint32_t count);
 void launch_audit_assemble(hipStream_t st, const uint8_t* wa_be, const uint8_t* ct_be, const uint8_t* packed_be, const uint8_t* sk_be,
                            const int8_t* r, const int8_t* e1, const int8_t* e2, const int32_t* k0, const int32_t* k1, uint8_t* rows,

@@ -18,6 +18,9 @@
 //                         a deposit pushed (instructions/deposit.rs:31-36,73), which demo-frontend/app/lib/on-chain.ts:93-125 looks for
 //   k_poseidon2_sponge    ct_helper/src/main.nr:15-34 (= scripts/generate_audit.py:355-374)
 //   k_audit_open          scripts/rlwe_decrypt.py:61-149 for a batch of (pw, ciphertext) records, with the binding checks it omits
+//   k_partial_scale / k_partial_commit / k_rlwe_partial / k_rlwe_combine
+//                         no counterpart (the reference rebuilds the key, rlwe_decrypt.py:61-91): one auditor's partial decryptions
+//                         from its own share and their combination (rlwe_partial.hpp); k_audit_open<true> opens records from them
 //   k_rlwe_keygen         scripts/rlwe_keygen.py:98-116 (the audit key pair), k_rlwe_key_noise: the check a key holder can make
 //   k_shamir_split        scripts/rlwe_keygen.py:51-65 (shamir_share_field), the inverse of k_shamir_combine
 #include "kernels.hpp"
@@ -25,6 +28,7 @@
 #include "poseidon2.hpp"
 #include "rlwe_ntt.hpp"
 #include "audit_open.hpp"
+#include "rlwe_partial.hpp"
 #include "rlwe_keygen.hpp"
 #include "leaf_index.hpp"
 #include "merkle_prefix.hpp"
@@ -896,19 +900,37 @@ void launch_shamir_split(hipStream_t st, const Fr* xs, const uint8_t* secrets_be
 // LDS per block: 8 KB key + 4.25 KB ciphertext + 4.25 KB tile = 16.6 KB; a block is one wave and 2^15 records are 512 blocks on
 // 256 CUs, so neither LDS nor registers limit what is resident.
 // ----------------------------------------------------------------------------------------------------
+// ct_commitment of one record by one lane: the rate-3 sponge over the 157 packed fields (ct_helper/src/main.nr:15-34),
+// 157 = 52 * 3 + 1, the fields formed word by word from the record's coefficients
+__device__ __forceinline__ Fr ao_ct_commitment_lane(const HashConsts& hc, const uint32_t* my0, const uint32_t* my1) {
+  Fr s[4] = {Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
+#pragma unroll 1
+  for (uint32_t i = 0; i < AO_FIELDS / 3; i++) {
+    SPP_UNROLL for (uint32_t j = 0; j < 3; j++) s[j] = s[j] + ao_packed_field(my0, my1, 3 * i + j);
+    poseidon2_permute(s, hc.p2_rc, hc.p2_mu);
+  }
+  static_assert(AO_FIELDS % 3 == 1, "one field left for the last absorption");
+  s[0] = s[0] + ao_packed_field(my0, my1, AO_FIELDS - 1);
+  poseidon2_permute(s, hc.p2_rc, hc.p2_mu);
+  return s[0];
+}
 static constexpr uint32_t AO_TILE_STRIDE = 68;   // bytes per record in the message tile: 17 words, so the lanes of phase 2 spread over the banks
+// PARTIALS: the threshold form (rlwe_partial.hpp).  No key: sk_mod_q is then the table k_rlwe_combine left, count * 64 residues
+// (sk * c1)[t] mod q, read where the other form sums SK2 against c1, and bad_partials[i] != 0 adds bit 8.  All the rest is shared.
+template <bool PARTIALS>
 __global__ void __launch_bounds__(64) k_audit_open(HashConsts hc, const uint32_t* __restrict__ sk_mod_q, const uint32_t* __restrict__ c0,
                                                    const uint32_t* __restrict__ c1, const uint8_t* __restrict__ pws,
-                                                   const int32_t* __restrict__ proof_ok, uint8_t* __restrict__ owners,
-                                                   uint32_t* __restrict__ flags, uint32_t count) {
-  __shared__ uint32_t SK2[2 * AO_N];
+                                                   const int32_t* __restrict__ proof_ok, const uint32_t* __restrict__ bad_partials,
+                                                   uint8_t* __restrict__ owners, uint32_t* __restrict__ flags, uint32_t count) {
+  __shared__ uint32_t SK2[PARTIALS ? 1 : 2 * AO_N];
   __shared__ __attribute__((aligned(16))) uint32_t ct[AO_CT_WORDS];
   __shared__ __attribute__((aligned(4))) uint8_t tile[64 * AO_TILE_STRIDE];
   __shared__ uint8_t coeff_bad[64];
   const uint32_t lane = threadIdx.x, first = blockIdx.x * 64;
   if (first >= count) return;
   const uint32_t nrec = count - first < 64 ? count - first : 64;
-  for (uint32_t i = lane; i < AO_N; i += 64) ao_sk2_entry(sk_mod_q[i], SK2[i], SK2[AO_N + i]);
+  if (!PARTIALS)
+    for (uint32_t i = lane; i < AO_N; i += 64) ao_sk2_entry(sk_mod_q[i], SK2[i], SK2[AO_N + i]);
   // ---- phase 1 ----
 #pragma unroll 1
   for (uint32_t k = 0; k < nrec; k++) {
@@ -926,26 +948,16 @@ __global__ void __launch_bounds__(64) k_audit_open(HashConsts hc, const uint32_t
     const bool any_bad = __any(bad ? 1 : 0) != 0;
     if (lane == 0) coeff_bad[k] = any_bad ? 1 : 0;
     __syncthreads();
-    const uint8_t m = ao_decrypt_slot(SK2, ct + AO_SLOTS, ct[lane], lane);
+    const uint8_t m = PARTIALS ? ao_round_slot(ct[lane], sk_mod_q[inst * AO_SLOTS + lane]) : ao_decrypt_slot(SK2, ct + AO_SLOTS, ct[lane], lane);
     tile[k * AO_TILE_STRIDE + lane] = m;
     owners[inst * 64 + ao_owner_byte(lane)] = m;               // always written, whatever the decisions below
     __syncthreads();                                            // ct is overwritten by the next record
   }
   if (lane >= nrec) return;
-  // ---- phase 2: ct_commitment, the rate-3 sponge over the packed fields (ct_helper/src/main.nr:15-34), 157 = 52 * 3 + 1 ----
+  // ---- phase 2: ct_commitment (ao_ct_commitment_lane), then the identity ----
   const size_t inst = (size_t)first + lane;
-  const uint32_t *my0 = c0 + inst * AO_SLOTS, *my1 = c1 + inst * AO_N;
-  Fr s[4] = {Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
-#pragma unroll 1
-  for (uint32_t i = 0; i < AO_FIELDS / 3; i++) {
-    SPP_UNROLL for (uint32_t j = 0; j < 3; j++) s[j] = s[j] + ao_packed_field(my0, my1, 3 * i + j);
-    poseidon2_permute(s, hc.p2_rc, hc.p2_mu);
-  }
-  static_assert(AO_FIELDS % 3 == 1, "one field left for the last absorption");
-  s[0] = s[0] + ao_packed_field(my0, my1, AO_FIELDS - 1);
-  poseidon2_permute(s, hc.p2_rc, hc.p2_mu);
   uint8_t ct_be[32], wa_be[32];
-  s[0].to_bytes_be(ct_be);
+  ao_ct_commitment_lane(hc, c0 + inst * AO_SLOTS, c1 + inst * AO_N).to_bytes_be(ct_be);
   uint32_t x[8], y[8];
   ao_owner_limbs(tile + lane * AO_TILE_STRIDE, x, y);
   Fr fx, fy;
@@ -953,11 +965,142 @@ __global__ void __launch_bounds__(64) k_audit_open(HashConsts hc, const uint32_t
   if (point_ok) poseidon_hash2(hc, fx, fy).to_bytes_be(wa_be);
   uint32_t f = ao_decide(coeff_bad[lane] != 0, ct_be, point_ok, wa_be, pws + inst * 76);
   if (proof_ok && !proof_ok[inst]) f |= AO_BAD_PROOF;
+  if (PARTIALS && bad_partials[inst]) f |= RP_BAD_PARTIALS;
   flags[inst] = f;
 }
 void launch_audit_open(hipStream_t st, HashConsts hc, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, const uint8_t* pws,
                        const int32_t* proof_ok, uint8_t* owners, uint32_t* flags, uint32_t count) {
-  if (count) hipLaunchKernelGGL(k_audit_open, dim3((count + 63) / 64), dim3(64), 0, st, hc, sk_mod_q, c0, c1, pws, proof_ok, owners, flags, count);
+  if (count)
+    hipLaunchKernelGGL(k_audit_open<false>, dim3((count + 63) / 64), dim3(64), 0, st, hc, sk_mod_q, c0, c1, pws, proof_ok, (const uint32_t*)nullptr,
+                       owners, flags, count);
+}
+void launch_audit_open_partials(hipStream_t st, HashConsts hc, const uint32_t* residues, const uint32_t* bad_partials, const uint32_t* c0,
+                                const uint32_t* c1, const uint8_t* pws, const int32_t* proof_ok, uint8_t* owners, uint32_t* flags, uint32_t count) {
+  if (count)
+    hipLaunchKernelGGL(k_audit_open<true>, dim3((count + 63) / 64), dim3(64), 0, st, hc, residues, c0, c1, pws, proof_ok, bad_partials, owners,
+                       flags, count);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Threshold opening (rlwe_partial.hpp): an auditor's partial decryptions from its own share, and their combination
+// ----------------------------------------------------------------------------------------------------
+// the scaled share, once per call: U[1024 i + j] = limb i of lambda * s[j], the limb-major table rp_dot_slot reads
+__global__ void __launch_bounds__(256) k_partial_scale(Fr lambda, const uint8_t* __restrict__ share_be, uint32_t* __restrict__ U) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= AO_N) return;
+  uint8_t s[32];
+  for (int i = 0; i < 32; i++) s[i] = share_be[(size_t)j * 32 + i];
+  uint32_t u[RP_LIMBS];
+  rp_scaled_share(lambda, s, u);
+  SPP_UNROLL for (uint32_t i = 0; i < RP_LIMBS; i++) U[AO_N * i + j] = u[i];
+}
+// One 64-lane block per record, lane k owns slot k.  The table (32 KB) and the ciphertext (4.25 KB) go into LDS with 16-byte
+// loads; the wave computes the record's ct_commitment with the lane-parallel sponge (poseidon2.hpp: 53 chained permutations over
+// the 157 packed fields, formed from the ciphertext in LDS) -- the value the masks are keyed by is the one of the c0 and c1 in
+// hand; then each lane runs its wide dot product against the table (consecutive lanes read consecutive words of a limb row: no
+// bank is read twice; c1[j] is one address for the wave), adds its blinding and writes 32 bytes.
+// LDS per block 36.4 KB: four blocks per CU, one wave per SIMD -- the dot product's sixteen-term unrolled body is what keeps a
+// lone wave's LDS reads in flight.
+// ct_in: the commitments are there already (k_partial_commit, large batches: launch_rlwe_partial draws the line) and the wave
+// does not hash; otherwise it does and leaves them in ct_out.
+__global__ void __launch_bounds__(64) k_rlwe_partial(HashConsts hc, const uint32_t* __restrict__ U_dev, uint32_t t, const uint32_t* __restrict__ xs,
+                                                     uint32_t self, const uint8_t* __restrict__ seeds, const uint32_t* __restrict__ c0,
+                                                     const uint32_t* __restrict__ c1, const int32_t* __restrict__ e,
+                                                     const unsigned long long* __restrict__ rho, uint8_t* __restrict__ partials,
+                                                     const uint8_t* __restrict__ ct_in, uint8_t* __restrict__ ct_out, uint32_t count) {
+  __shared__ __attribute__((aligned(16))) uint32_t U[RP_TABLE_WORDS];
+  __shared__ __attribute__((aligned(16))) uint32_t ct[AO_CT_WORDS];
+  __shared__ uint8_t ct_be[32];
+  const uint32_t lane = threadIdx.x;
+  const size_t inst = blockIdx.x;
+  if (inst >= count) return;
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(U_dev);
+#pragma unroll 4
+    for (uint32_t i = lane; i < RP_TABLE_WORDS / 4; i += 64) reinterpret_cast<uint4*>(U)[i] = src[i];
+    ct[lane] = c0[inst * AO_SLOTS + lane];
+    const uint4* s1 = reinterpret_cast<const uint4*>(c1 + inst * AO_N);      // rows of 4 KB: 16-byte aligned
+#pragma unroll
+    for (uint32_t j = 0; j < AO_N / 4 / 64; j++) reinterpret_cast<uint4*>(ct + AO_SLOTS)[lane + 64 * j] = s1[lane + 64 * j];
+  }
+  __syncthreads();
+  if (ct_in) {
+    if (lane < 32) ct_be[lane] = ct_in[inst * 32 + lane];
+  } else {
+    // ---- ct_commitment: the rate-3 sponge over the packed fields (ct_helper/src/main.nr:15-34), lanes 0..2 absorb ----
+    Fr s = Fr::zero();
+#pragma unroll 1
+    for (uint32_t i = 0; i < AO_FIELDS / 3; i++) {
+      if (lane < 3) s = s + ao_packed_field(ct, ct + AO_SLOTS, 3 * i + lane);
+      s = coop_p2_permute(hc.p2_rc, hc.p2_mu, s, lane, Poseidon2NoEmit{});
+    }
+    static_assert(AO_FIELDS % 3 == 1, "one field left for the last absorption");
+    if (lane == 0) s = s + ao_packed_field(ct, ct + AO_SLOTS, AO_FIELDS - 1);
+    s = coop_p2_permute(hc.p2_rc, hc.p2_mu, s, lane, Poseidon2NoEmit{});
+    if (lane == 0) {
+      uint8_t buf[32];
+      s.to_bytes_be(buf);
+      for (int i = 0; i < 32; i++) ct_be[i] = buf[i];
+      for (int i = 0; i < 32; i++) ct_out[inst * 32 + i] = buf[i];
+    }
+  }
+  __syncthreads();
+  // ---- the slot ----
+  const Fr d = rp_dot_slot(U, ct + AO_SLOTS, lane);
+  uint8_t key[32];
+  for (int i = 0; i < 32; i++) key[i] = ct_be[i];
+  const size_t slot = inst * AO_SLOTS + lane;
+  const Fr b = rp_blind_slot(e ? e[slot] : 0, rho ? rho[slot] : 0ull, t, xs, self, seeds, key, lane);
+  store_be(partials + slot * RP_PARTIAL_LEN, d + b);
+}
+// The commitments of a large batch, one LANE per record (the sponge of k_audit_open's phase 2): 53 chained permutations cost a wave
+// the same whether its lanes hold one record or 64, so from RP_COOP_SPONGE_MAX records on the wave form above would be the bulk
+// of the call.  Measured at 2^15 records: 246 ms per launch with the sponge inside k_rlwe_partial; in this form 20.0 ms here and
+// 2.4 ms for k_rlwe_partial (profiles/partial_decrypt_kernel_stats.csv).
+__global__ void __launch_bounds__(64) k_partial_commit(HashConsts hc, const uint32_t* __restrict__ c0, const uint32_t* __restrict__ c1,
+                                                       uint8_t* __restrict__ ct_be, uint32_t count) {
+  const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (g >= count) return;
+  store_be(ct_be + g * 32, ao_ct_commitment_lane(hc, c0 + g * AO_SLOTS, c1 + g * AO_N));
+}
+// One 64-lane block per record: lane k sums slot k of the t partials (auditor-major: partial i of record r at (i count + r) 64 + k),
+// centres the sum and reduces it mod q (rp_combine_residue).  residues / msg / flags: each optional; msg needs c0 (below q).
+__global__ void __launch_bounds__(64) k_rlwe_combine(uint32_t t, const uint8_t* __restrict__ partials, const uint32_t* __restrict__ c0,
+                                                     uint32_t* __restrict__ residues, uint8_t* __restrict__ msg, uint32_t* __restrict__ flags,
+                                                     uint32_t count) {
+  const uint32_t lane = threadIdx.x;
+  const size_t inst = blockIdx.x;
+  if (inst >= count) return;
+  const size_t slot = inst * AO_SLOTS + lane;
+  Fr acc = Fr::zero();
+  for (uint32_t i = 0; i < t; i++) acc = acc + load_be(partials + ((size_t)i * count * AO_SLOTS + slot) * RP_PARTIAL_LEN);
+  uint32_t w[8];
+  acc.to_canonical(w);
+  bool bad = false;
+  const uint32_t res = rp_combine_residue(w, bad);
+  const bool any_bad = __any(bad ? 1 : 0) != 0;
+  if (residues) residues[slot] = res;
+  if (msg) msg[slot] = ao_round_slot(c0[slot], res);
+  if (flags && lane == 0) flags[inst] = any_bad ? RP_BAD_PARTIALS : 0u;
+}
+void launch_partial_scale(hipStream_t st, const Fr& lambda, const uint8_t* share_be, uint32_t* U) {
+  hipLaunchKernelGGL(k_partial_scale, dim3(AO_N / 256), dim3(256), 0, st, lambda, share_be, U);
+}
+void launch_rlwe_partial(hipStream_t st, HashConsts hc, const uint32_t* U, uint32_t t, const uint32_t* xs, uint32_t self, const uint8_t* seeds,
+                         const uint32_t* c0, const uint32_t* c1, const int32_t* e, const uint64_t* rho, uint8_t* partials, uint8_t* ct_be,
+                         uint32_t count) {
+  if (count == 0) return;
+  // one record's sponge is 53 chained permutations either way: a wave per record (inside k_rlwe_partial) while the chip has
+  // room for all of them at once and a few rounds more, a lane per record beyond that (launch_poseidon2_sponge draws its line
+  // the same way; four blocks per CU here: 1 024 in flight)
+  const bool lanes = count > RP_COOP_SPONGE_MAX;
+  if (lanes) hipLaunchKernelGGL(k_partial_commit, dim3((count + 63) / 64), dim3(64), 0, st, hc, c0, c1, ct_be, count);
+  hipLaunchKernelGGL(k_rlwe_partial, dim3(count), dim3(64), 0, st, hc, U, t, xs, self, seeds, c0, c1, e, (const unsigned long long*)rho, partials,
+                     lanes ? ct_be : (const uint8_t*)nullptr, lanes ? (uint8_t*)nullptr : ct_be, count);
+}
+void launch_rlwe_combine(hipStream_t st, uint32_t t, const uint8_t* partials, const uint32_t* c0, uint32_t* residues, uint8_t* msg, uint32_t* flags,
+                         uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_rlwe_combine, dim3(count), dim3(64), 0, st, t, partials, c0, residues, msg, flags, count);
 }
 
 // ----------------------------------------------------------------------------------------------------

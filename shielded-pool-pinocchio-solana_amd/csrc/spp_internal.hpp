@@ -246,6 +246,10 @@ int spp_audit_inputs_enqueue(spp_ctx* ctx, hipStream_t st, void* scratch, const 
                              uint32_t* d_c1_out);
 // withdraw notes (spp_witness_api.cpp): SPP_ERR_BAD_INPUT unless every field of every note is canonical
 int spp_check_notes(size_t count, const uint8_t* notes);
+// threshold opening (spp_partial_api.cpp): SPP_ERR_BAD_INPUT unless t is in [1, 64] and xs (optional) holds t distinct nonzero
+// indices; unless every one of the t * count * 64 partials is a canonical field element
+int spp_check_share_set(uint32_t t, const uint32_t* xs);
+int spp_check_partials(uint32_t t, size_t count, const uint8_t* partials);
 // lazily built per-context constants (spp_witness_api.cpp), called with ctx->mu held
 // Poseidon / Poseidon2 constants and the Grumpkin window table.  The ONE copy of the hash constants: a circuit's DevCircuit::hc
 // points into it (load_r1cs), so the buffers are in ctx->owned and live until the context goes, whatever circuits close first.

@@ -3,6 +3,7 @@
 // (Shamir reconstruction, BFV decryption), batched on the GPU.
 #include "spp_internal.hpp"
 #include "leaf_index.hpp"
+#include "secret_buffers.hpp"
 
 int spp_ensure_ctx_consts(spp_ctx* ctx) {
   if (ctx->consts_ready) return 0;
@@ -963,51 +964,6 @@ extern "C" int spp_rlwe_decrypt_batch(spp_ctx* ctx, const uint32_t* sk_mod_q, si
 namespace {
 const uint32_t RLWE_Q = 167772161u;
 const size_t KEYGEN_MAX_KEYS = (size_t)1 << 16, SHAMIR_MAX_VALUES = (size_t)1 << 20;
-void wipe(void* p, size_t bytes) {
-  volatile uint8_t* v = (volatile uint8_t*)p;
-  for (size_t i = 0; i < bytes; i++) v[i] = 0;
-}
-// OS randomness in blocks; wiped when it goes
-struct OsRandom {
-  FILE* f = nullptr;
-  uint8_t buf[4096];
-  size_t pos = sizeof buf;
-  ~OsRandom() {
-    if (f) fclose(f);
-    wipe(buf, sizeof buf);
-  }
-  bool next(uint8_t* out, size_t n) {
-    for (size_t i = 0; i < n; i++) {
-      if (pos == sizeof buf) {
-        if (!f) {
-          f = fopen("/dev/urandom", "rb");
-          if (f) setvbuf(f, nullptr, _IONBF, 0);   // no second copy of the bytes in a stdio buffer
-        }
-        if (!f || fread(buf, 1, sizeof buf, f) != sizeof buf) return false;
-        pos = 0;
-      }
-      out[i] = buf[pos++];
-    }
-    return true;
-  }
-};
-// device buffer of secrets: zeroed on its stream before DevBuf's destructor frees it, on every return path
-struct WipedDevBuf : DevBuf {
-  size_t bytes = 0;
-  hipStream_t st = nullptr;
-  ~WipedDevBuf() {
-    if (p && bytes) {
-      (void)hipMemsetAsync(p, 0, bytes, st);
-      (void)hipStreamSynchronize(st);
-    }
-  }
-};
-#define UP_SECRET(buf, src, nbytes) \
-  do {                              \
-    buf.bytes = (nbytes);           \
-    buf.st = st;                    \
-    UP(buf, src, nbytes);           \
-  } while (0)
 int check_below_q(const char* what, const uint32_t* v, size_t n) {
   for (size_t i = 0; i < n; i++)
     if (v[i] >= RLWE_Q) return fail(SPP_ERR_BAD_INPUT, "%s[%zu] = %u is not in [0, q)", what, i, v[i]);

@@ -15,6 +15,17 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # the auditor's `python scripts/rlwe_decrypt.py`: reconstructs the key from the shares, verifies the
                               # proof (`-`: already verified elsewhere), checks that the ciphertext is the one the proof commits
                               # to and that it decrypts to the identity the proof commits to; exit 0 only if all three hold
+    python -m spp.cli audit-open target/<name>.vk|- <name>.proof <name>.pw ciphertext.json --partials partial_1.json partial_2.json
+                              # the same from the auditors' partial decryptions: nobody rebuilds the key (exactly one of --shares
+                              # and --partials); a fourth line reports whether the partials belong together
+    python -m spp.cli audit-pair-seeds --shares M --out DIR
+                              # DIR/pair_seeds_<i>.json for the auditors 1..M: one 32-byte seed from the operating system per pair,
+                              # the same value at both ends; file i goes to auditor i alone, over the channel its share took
+    python -m spp.cli audit-partial share_i.json --with X1 X2 ... ciphertext.json <name>.pw [--pair-seeds pair_seeds_i.json]
+                              [--smudge B] --out partial_i.json
+                              # auditor i's partial decryption of one record within the set {i, X1, X2, ...}, from its own share:
+                              # masked with the pair seeds, smudged with noise in [-B, B] (default 1024; threshold * B <= 2^17).
+                              # Refuses a ciphertext that is not the one the public witness commits to
     python -m spp.cli rlwe-keygen --out DIR [--threshold 2 --shares 3] [--reference-seed N]
                               # `python scripts/rlwe_keygen.py`: DIR/rlwe_pk.json, DIR/rlwe_params.json and
                               # DIR/rlwe_sk_shares/share_<i>.json, from the operating system's randomness; then checks its own
@@ -113,24 +124,49 @@ def input_vector(vals):
     return lib.SPP_CIRCUIT_AUDIT, [v % R for v in row]
 
 
+def _load_partials(paths, pw):
+    """the partial files of one record, one per member of one set, as [t, 1, 64, 32] bytes; ValueError otherwise"""
+    import numpy as np
+    from . import witness
+    parts = [witness.load_partial_json(p) for p in paths]
+    group = parts[0]["with"]
+    if any(q["with"] != group for q in parts) or sorted(q["x"] for q in parts) != group:
+        raise ValueError("the partials must be one from every auditor of one set (sets %s, from %s)"
+                         % (sorted({tuple(q["with"]) for q in parts}), [q["x"] for q in parts]))
+    ct = int.from_bytes(pw[44:76], "big")
+    for path, q in zip(paths, parts):
+        if q["ct_commitment"] != ct:
+            raise ValueError("%s was made for another ciphertext than the one this public witness commits to" % path)
+    if len(parts) > 1 and not all(q["masked"] for q in parts):
+        print("spp audit-open: warning: unmasked partials -- each of them is a linear equation in its auditor's share", file=sys.stderr)
+    return np.stack([q["partial"] for q in parts])[:, None]
+
+
 def _audit_open(a):
     from . import witness
     try:   # everything that can be wrong with the files is found before a device is opened
-        shares = [witness.load_share_json(p) for p in a.shares]
-        if len({s["x"] for s in shares}) != len(shares) or len(shares) < max(s["threshold"] for s in shares):
-            raise ValueError("need %d shares with distinct indices, got %d" % (max(s["threshold"] for s in shares), len(shares)))
-        c0, c1, claimed = witness.load_ciphertext_json(a.ciphertext)
-        vk = None if a.vk == "-" else open(a.vk, "rb").read()
         proof, pw = open(a.proof, "rb").read(), open(a.pw, "rb").read()
         if len(proof) != lib.PROOF_LEN or len(pw) != lib.AUDIT_PW_LEN:
             raise ValueError("an audit record is a proof of %d bytes and a public witness of %d" % (lib.PROOF_LEN, lib.AUDIT_PW_LEN))
+        shares = partials = None
+        if a.partials is not None:
+            partials = _load_partials(a.partials, pw)
+        else:
+            shares = [witness.load_share_json(p) for p in a.shares]
+            if len({s["x"] for s in shares}) != len(shares) or len(shares) < max(s["threshold"] for s in shares):
+                raise ValueError("need %d shares with distinct indices, got %d" % (max(s["threshold"] for s in shares), len(shares)))
+        c0, c1, claimed = witness.load_ciphertext_json(a.ciphertext)
+        vk = None if a.vk == "-" else open(a.vk, "rb").read()
     except (OSError, ValueError) as e:
         print("spp audit-open: %s" % e, file=sys.stderr)
         return 2
     ctx = Context(a.device)
     try:
-        sk = witness.reconstruct_sk(ctx, shares)
-        owners, flags = ctx.audit_open(vk, sk, [proof], [pw], [c0], [c1])
+        if partials is not None:
+            owners, flags = ctx.audit_open(vk, None, [proof], [pw], [c0], [c1], partials=partials)
+        else:
+            sk = witness.reconstruct_sk(ctx, shares)
+            owners, flags = ctx.audit_open(vk, sk, [proof], [pw], [c0], [c1])
     finally:
         ctx.close()
     f = flags[0]
@@ -138,9 +174,83 @@ def _audit_open(a):
     print("proof: %s" % ("not checked" if vk is None else "FAILED" if f & lib.SPP_AUDIT_BAD_PROOF else "verified"))
     print("ciphertext: %s" % ("NOT the one the proof commits to" if f & lib.SPP_AUDIT_BAD_CIPHERTEXT else "bound to the proof (ct_commitment)"))
     print("identity: %s" % ("NOT the one the proof commits to" if f & lib.SPP_AUDIT_BAD_IDENTITY else "bound to the proof (wa_commitment)"))
+    if partials is not None:
+        print("partials: %s" % ("do NOT combine to a decryption (a wrong share, set or record)" if f & lib.SPP_AUDIT_BAD_PARTIALS
+                                else "combine to a decryption (%d auditors, no key rebuilt)" % len(partials)))
     if claimed is not None and claimed != owners[0]:
         print("note: the prover's expected_owner differs from the decrypted owner")
     return 0 if f == 0 else 1
+
+
+def _audit_pair_seeds(a):
+    from . import witness
+    if not 2 <= a.shares <= 255:
+        print("spp audit-pair-seeds: need 2 <= shares <= 255", file=sys.stderr)
+        return 2
+    try:
+        os.makedirs(a.out, exist_ok=True)
+        seeds = witness.new_pair_seeds(a.shares)
+        for i in range(1, a.shares + 1):
+            witness.write_pair_seeds_json(os.path.join(a.out, "pair_seeds_%d.json" % i), i, a.shares, seeds[i])
+    except OSError as e:
+        print("spp audit-pair-seeds: %s" % e, file=sys.stderr)
+        return 2
+    print("audit-pair-seeds: pair_seeds_1.json .. pair_seeds_%d.json in %s; file i is for auditor i alone" % (a.shares, a.out))
+    return 0
+
+
+def _audit_partial(a):
+    from . import witness
+    try:   # everything that can be wrong with the files is found before a device is opened
+        # `--with 2 3 ciphertext.json a.pw`: the option takes what follows it, the two files included
+        others = [int(v) for v in a.others if re.fullmatch(r"\d+", v)]
+        rest = [v for v in a.others if not re.fullmatch(r"\d+", v)]
+        files = [f for f in (a.ciphertext, a.pw) if f is not None] + rest
+        if len(files) != 2:
+            raise ValueError("need ciphertext.json and <name>.pw")
+        share = witness.load_share_json(a.share)
+        xs = [share["x"]] + [x for x in dict.fromkeys(others) if x != share["x"]]
+        t = len(xs)
+        if min(xs) <= 0 or max(xs) >= 1 << 32 or t > 64:
+            raise ValueError("the set is at most 64 distinct share indices in [1, 2^32)")
+        if t < share["threshold"]:
+            raise ValueError("the key needs %d auditors, the set %s has %d" % (share["threshold"], sorted(xs), t))
+        if a.smudge < 0 or t * a.smudge > witness.SMUDGE_BUDGET:
+            raise ValueError("--smudge %d with %d auditors: threshold * bound may not exceed 2^17, the ciphertext's own noise needs the rest of "
+                             "Delta/2" % (a.smudge, t))
+        c0, c1, _ = witness.load_ciphertext_json(files[0])
+        pw = open(files[1], "rb").read()
+        if len(pw) != lib.AUDIT_PW_LEN:
+            raise ValueError("a public witness is %d bytes" % lib.AUDIT_PW_LEN)
+        seeds = None
+        if a.pair_seeds:
+            x, held = witness.load_pair_seeds_json(a.pair_seeds)
+            if x != share["x"] or any(j not in held for j in xs[1:]):
+                raise ValueError("%s: not the pair seeds of auditor %d with %s" % (a.pair_seeds, share["x"], xs[1:]))
+            seeds = [None] + [held[j] for j in xs[1:]]
+        elif t > 1:
+            print("spp audit-partial: warning: no --pair-seeds: this partial is a linear equation in the share; about 16 of them give it away",
+                  file=sys.stderr)
+        e, rho = witness.rlwe_sample_smudge(lib.load_library(), 64, a.smudge)
+    except (OSError, ValueError, lib.SppError) as e:
+        print("spp audit-partial: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        part, cts = witness.rlwe_partial_decrypt(ctx, xs, 0, share["y"], [c0], [c1], e, rho, seeds, want_commitments=True)
+    except lib.SppError as e:
+        print("spp audit-partial: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    if cts[0] != int.from_bytes(pw[44:76], "big"):
+        print("spp audit-partial: REFUSED: %s is not the ciphertext %s commits to (ct_commitment 0x%064x); nothing written"
+              % (files[0], files[1], cts[0]), file=sys.stderr)
+        return 1
+    with open(a.out, "w") as f:
+        json.dump(witness.partial_json(share["x"], xs, cts[0], seeds is not None, a.smudge, part[0]), f, indent=1)
+    print("audit-partial: %s: auditor %d within %s, %s, smudged within %d" % (a.out, share["x"], sorted(xs), "masked" if seeds is not None else "UNMASKED", a.smudge))
+    return 0
 
 
 def _load_shares(paths):
@@ -655,8 +765,17 @@ def main(argv=None):
     vb.add_argument("--device", type=int, default=0)
     o = sub.add_parser("audit-open"); o.add_argument("vk", help="verifying key, or - for a record already verified elsewhere")
     o.add_argument("proof"); o.add_argument("pw"); o.add_argument("ciphertext", help="ciphertext.json (scripts/generate_audit.py:590-606)")
-    o.add_argument("--shares", nargs="+", required=True, metavar="SHARE.json", help="threshold many share files (scripts/rlwe_keygen.py)")
+    og = o.add_mutually_exclusive_group(required=True)
+    og.add_argument("--shares", nargs="+", default=None, metavar="SHARE.json", help="threshold many share files (scripts/rlwe_keygen.py)")
+    og.add_argument("--partials", nargs="+", default=None, metavar="PARTIAL.json", help="instead of --shares: one audit-partial file per auditor of one set")
     o.add_argument("--device", type=int, default=0)
+    ps = sub.add_parser("audit-pair-seeds"); ps.add_argument("--shares", type=int, required=True, metavar="M"); ps.add_argument("--out", required=True, metavar="DIR")
+    pa = sub.add_parser("audit-partial"); pa.add_argument("share", help="this auditor's share_<i>.json")
+    pa.add_argument("ciphertext", nargs="?", default=None); pa.add_argument("pw", nargs="?", default=None)
+    pa.add_argument("--with", dest="others", nargs="+", default=[], metavar="X", help="the share indices of the other auditors of the set")
+    pa.add_argument("--pair-seeds", default=None, metavar="pair_seeds_<i>.json")
+    pa.add_argument("--smudge", type=int, default=1024, metavar="B", help="noise bound per slot (default 1024; threshold * B <= 2^17)")
+    pa.add_argument("--out", required=True, metavar="partial_<i>.json"); pa.add_argument("--device", type=int, default=0)
     r = sub.add_parser("pool-replay"); r.add_argument("withdraw_vk"); r.add_argument("audit_vk"); r.add_argument("log", help="one instruction per line (JSON)")
     r.add_argument("--capacity", type=int, default=0, help="keys per set (default: enough for the log)")
     r.add_argument("--verifier", choices=("each", "rlc"), default="each", help="each: one lane per proof (default); rlc: random linear combination")
@@ -706,6 +825,10 @@ def main(argv=None):
         return _rlwe_key_check(a)
     if a.cmd == "audit-open":
         return _audit_open(a)
+    if a.cmd == "audit-pair-seeds":
+        return _audit_pair_seeds(a)
+    if a.cmd == "audit-partial":
+        return _audit_partial(a)
     if a.cmd == "verify-batch":
         return _verify_batch(a)
     if a.cmd == "pool-replay":

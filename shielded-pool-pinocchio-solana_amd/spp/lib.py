@@ -23,6 +23,8 @@ SPP_RLC_NO_FALLBACK = 2
 SPP_AUDIT_BAD_PROOF = 1
 SPP_AUDIT_BAD_CIPHERTEXT = 2
 SPP_AUDIT_BAD_IDENTITY = 4
+SPP_AUDIT_BAD_PARTIALS = 8          # spp_audit_open_batch_partials, spp_rlwe_combine_partials
+PARTIAL_LEN = 32
 # the pool ledger, spp_pool_* (include/spp.h)
 WITHDRAW_PW_LEN = 172               # withdraw public witness: header | root | nullifier | recipient | amount | wa_commitment
 SPP_POOL_STATE_LEN = 1072           # size_of::<ShieldedPoolState>()
@@ -192,6 +194,11 @@ def load_library():
     L.spp_rlwe_keygen_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.spp_rlwe_key_check.argtypes = [vp, sz, vp, vp, vp, vp]
     L.spp_shamir_split.argtypes = [vp, u32, u32, vp, sz, cp, cp, vp]
+    # threshold opening (include/spp.h)
+    L.spp_rlwe_sample_smudge.argtypes = [sz, u32, vp, vp]
+    L.spp_rlwe_partial_decrypt_batch.argtypes = [vp, u32, vp, u32, cp, sz, vp, vp, vp, vp, cp, vp, vp]
+    L.spp_rlwe_combine_partials.argtypes = [vp, u32, sz, cp, vp, vp, vp]
+    L.spp_audit_open_batch_partials.argtypes = [vp, cp, sz, u32, cp, sz, cp, cp, vp, vp, vp, vp]
     L.spp_ntt_fr.argtypes = [vp, vp, u32, i32]
     L.spp_msm_g1.argtypes = [vp, cp, cp, sz, i32, vp]
     L.spp_msm_g2.argtypes = [vp, cp, cp, sz, i32, vp]

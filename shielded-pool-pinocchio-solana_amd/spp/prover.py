@@ -215,19 +215,30 @@ class Context:
             return res
         return (res,) + ((tuple(stats),) if want_stats else ()) + ((ms.value,) if want_ms else ())
 
-    def audit_open(self, vk, sk_mod_q, proofs, pws, c0, c1, rlc=False, group=0, want_stats=False):
+    def audit_open(self, vk, sk_mod_q, proofs, pws, c0, c1, rlc=False, group=0, want_stats=False, partials=None):
         """Opens audit records in one pass on the GPU (spp_audit_open_batch): verification, ciphertext binding, decryption,
         identity binding.  rlc: verify by random linear combination (spp_audit_open_batch_rlc; groups of `group`, 0 = 256, a fresh
         seed from the OS) -- the same flags except with probability ~2^-127 per call; want_stats (with rlc): a third result,
         (groups, groups refused, proofs re-verified, proofs dropped).  vk: bytes, or None for records already verified elsewhere (proofs may then be None); sk_mod_q: 1024
         ints (witness.reconstruct_sk); proofs / pws: lists of bytes (or one bytes object each); c0 [count, 64], c1 [count, 1024].
+        partials: the threshold form (spp_audit_open_batch_partials) -- sk_mod_q is then None and partials holds the results of
+        witness.rlwe_partial_decrypt of the t auditors of one set on these ciphertexts, [t, count, 64, 32]; nobody holds the key,
+        and SPP_AUDIT_BAD_PARTIALS (8) joins the flags.  Not with rlc.
         Returns (owners, flags): owners[i] = (owner_x, owner_y) as decrypted, flags[i] = SPP_AUDIT_* bits, 0 = all three hold."""
         c0 = np.ascontiguousarray(c0, dtype=np.uint32).reshape(-1, 64)
         count = c0.shape[0]
         c1 = np.ascontiguousarray(c1, dtype=np.uint32).reshape(count, 1024)
-        sk = np.ascontiguousarray(sk_mod_q, dtype=np.uint32)
-        if sk.shape != (1024,):
-            raise ValueError("sk_mod_q must hold 1024 coefficients")
+        if (partials is None) == (sk_mod_q is None):
+            raise ValueError("audit_open: exactly one of sk_mod_q and partials")
+        if partials is not None:
+            if rlc:
+                raise ValueError("audit_open: partials do not go with rlc=True")
+            from .witness import _partials_array
+            parts = _partials_array(partials, count) if count else np.zeros((max(len(partials), 1), 0, 64, 32), dtype=np.uint8)
+        else:
+            sk = np.ascontiguousarray(sk_mod_q, dtype=np.uint32)
+            if sk.shape != (1024,):
+                raise ValueError("sk_mod_q must hold 1024 coefficients")
         join = lambda v: None if v is None else (bytes(v) if isinstance(v, (bytes, bytearray)) else b"".join(v))
         pb, wb = join(proofs), join(pws)
         if wb is None or len(wb) != AUDIT_PW_LEN * count or (pb is not None and len(pb) != PROOF_LEN * count):
@@ -243,7 +254,11 @@ class Context:
         else:
             if group or want_stats:
                 raise ValueError("audit_open: group and want_stats go with rlc=True")
-            check(self.L.spp_audit_open_batch(self.h, vk, len(vk) if vk is not None else 0, p(sk), count, pb, wb, p(c0), p(c1), p(owners), p(flags)))
+            if partials is not None:
+                check(self.L.spp_audit_open_batch_partials(self.h, vk, len(vk) if vk is not None else 0, parts.shape[0], parts.tobytes(), count,
+                                                           pb, wb, p(c0), p(c1), p(owners), p(flags)))
+            else:
+                check(self.L.spp_audit_open_batch(self.h, vk, len(vk) if vk is not None else 0, p(sk), count, pb, wb, p(c0), p(c1), p(owners), p(flags)))
         res = ([(int.from_bytes(owners[i, :32].tobytes(), "big"), int.from_bytes(owners[i, 32:].tobytes(), "big")) for i in range(count)],
                [int(f) for f in flags[:count]])
         return res + (tuple(int(v) for v in stats),) if want_stats else res

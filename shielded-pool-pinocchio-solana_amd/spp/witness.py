@@ -25,6 +25,9 @@
     write_rlwe_pk_json / write_rlwe_params_json / write_share_json
                              scripts/rlwe_keygen.py:124-127, 133-142, 161-169: the files `cli compile --rlwe-pk` and
                              load_share_json read
+    rlwe_sample_smudge / rlwe_partial_decrypt / rlwe_combine_partials, new_pair_seeds, partial_json / load_partial_json
+                             no counterpart in the reference, which rebuilds the key (scripts/rlwe_decrypt.py:61-91): t of m
+                             auditors open a ciphertext from partial decryptions of their own shares (include/spp.h)
 All of them take and return Python ints / lists; field elements cross the C ABI as 32-byte big-endian.
 """
 import ctypes
@@ -554,6 +557,138 @@ def rlwe_decrypt(ctx, sk_mod_q, c0, c1):
     check(ctx.L.spp_rlwe_decrypt_batch(ctx.h, p(sk), count, p(c0), p(c1), p(msg)))
     owners = [(int.from_bytes(msg[i, :32].tobytes(), "little"), int.from_bytes(msg[i, 32:].tobytes(), "little")) for i in range(count)]
     return owners, msg
+
+
+# ---- threshold opening: partial decryptions from single shares, nobody rebuilds the key (include/spp.h) ----
+SMUDGE_BOUND = 1024
+SMUDGE_BUDGET = 1 << 17     # threshold * bound may not exceed it: 196 608 of Delta/2 = 327 680 stay for the ciphertext's own noise
+
+
+def rlwe_sample_smudge(L, n, bound=SMUDGE_BOUND):
+    """n smudging values from the operating system's randomness (host only; L: the loaded library): e int32 in [-bound, bound]
+    and rho uint64, the forms rlwe_partial_decrypt takes."""
+    e = np.zeros(n, dtype=np.int32)
+    rho = np.zeros(n, dtype=np.uint64)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    check(L.spp_rlwe_sample_smudge(n, int(bound), p(e), p(rho)))
+    return e, rho
+
+
+def rlwe_partial_decrypt(ctx, xs, me, share, c0, c1, e=None, rho=None, pair_seeds=None, want_commitments=False):
+    """One auditor's partial decryptions (spp_rlwe_partial_decrypt_batch).  xs: the share indices of the participating set, `me`
+    this auditor's position in it, share: its 1024 field elements (ints).  c0 [count, 64], c1 [count, 1024] in [0, q).  e, rho:
+    [count, 64] smudging values (rlwe_sample_smudge) or None for 0.  pair_seeds: one 32-byte seed per member of xs, in xs order
+    (the entry at `me` is ignored; bytes or None there), or None for unmasked partials.  Returns uint8 [count, 64, 32], big-endian
+    field elements; with want_commitments also the ct_commitments (ints) the masks were keyed by."""
+    c0 = np.ascontiguousarray(c0, dtype=np.uint32).reshape(-1, MSG_SLOTS)
+    count, t = c0.shape[0], len(xs)
+    c1 = np.ascontiguousarray(c1, dtype=np.uint32).reshape(count, RLWE_N)
+    share = [int(v) for v in share]
+    if len(share) != RLWE_N:
+        raise ValueError("a share is 1024 field elements")
+    cx = (ctypes.c_uint32 * max(t, 1))(*[int(x) for x in xs])
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    ce = None if e is None else np.ascontiguousarray(e, dtype=np.int32).reshape(count, MSG_SLOTS)
+    cr = None if rho is None else np.ascontiguousarray(rho, dtype=np.uint64).reshape(count, MSG_SLOTS)
+    seeds = None
+    if pair_seeds is not None:
+        if len(pair_seeds) != t or any(len(s) != 32 for j, s in enumerate(pair_seeds) if j != me):
+            raise ValueError("pair_seeds: one 32-byte seed per member of the set")
+        seeds = b"".join(bytes(32) if j == me else bytes(s) for j, s in enumerate(pair_seeds))
+    out = np.zeros((max(count, 1), MSG_SLOTS, 32), dtype=np.uint8)
+    cts = ctypes.create_string_buffer(32 * max(count, 1)) if want_commitments else None
+    check(ctx.L.spp_rlwe_partial_decrypt_batch(ctx.h, t, ctypes.cast(cx, ctypes.c_void_p), int(me), _be(share), count, p(c0), p(c1),
+                                               None if ce is None else p(ce), None if cr is None else p(cr), seeds, p(out),
+                                               None if cts is None else ctypes.cast(cts, ctypes.c_void_p)))
+    out = out[:count]
+    return (out, _unbe(cts.raw, count)) if want_commitments else out
+
+
+def _partials_array(partials, count):
+    a = np.ascontiguousarray(partials, dtype=np.uint8)
+    if a.ndim != 4 or a.shape[1:] != (count, MSG_SLOTS, 32) or a.shape[0] == 0:
+        raise ValueError("partials: [t, %d, 64, 32] bytes, one rlwe_partial_decrypt result per auditor" % count)
+    return a
+
+
+def rlwe_combine_partials(ctx, partials, c0):
+    """The combiner (spp_rlwe_combine_partials): partials = the results of rlwe_partial_decrypt of the t auditors of one set on
+    the same ciphertexts, [t, count, 64, 32].  Returns (owners, msg, flags) -- owners and msg as rlwe_decrypt gives them,
+    flags[i] = 0 or SPP_AUDIT_BAD_PARTIALS."""
+    c0 = np.ascontiguousarray(c0, dtype=np.uint32).reshape(-1, MSG_SLOTS)
+    count = c0.shape[0]
+    a = _partials_array(partials, count)
+    msg = np.zeros((max(count, 1), MSG_SLOTS), dtype=np.uint8)
+    flags = np.zeros(max(count, 1), dtype=np.uint32)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    check(ctx.L.spp_rlwe_combine_partials(ctx.h, a.shape[0], count, a.tobytes(), p(c0), p(msg), p(flags)))
+    msg = msg[:count]
+    owners = [(int.from_bytes(msg[i, :32].tobytes(), "little"), int.from_bytes(msg[i, 32:].tobytes(), "little")) for i in range(count)]
+    return owners, msg, [int(f) for f in flags[:count]]
+
+
+def new_pair_seeds(num_shares):
+    """One 32-byte seed from the operating system per pair of the auditors 1..num_shares: {i: {j: seed}} with
+    seeds[i][j] == seeds[j][i].  The dealer of a key sees every share already, so dealing the seeds adds no trust; auditors
+    may as well agree them pairwise over an authenticated channel."""
+    import os
+    m = int(num_shares)
+    seeds = {i: {} for i in range(1, m + 1)}
+    for i in range(1, m + 1):
+        for j in range(i + 1, m + 1):
+            seeds[i][j] = seeds[j][i] = os.urandom(32)
+    return seeds
+
+
+def write_pair_seeds_json(path, x, num_shares, seeds):
+    """pair_seeds_<x>.json: {"x", "num_shares", "seeds": {"<x of the other end>": hex}}"""
+    import json
+    with open(path, "w") as f:
+        json.dump({"x": int(x), "num_shares": int(num_shares), "seeds": {str(j): bytes(s).hex() for j, s in sorted(seeds.items())}}, f, indent=1)
+
+
+def load_pair_seeds_json(path):
+    """(x, {x of the other end: 32 bytes}) of a pair_seeds_<x>.json; ValueError if it is not one"""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    try:
+        x, seeds = int(d["x"]), {int(j): bytes.fromhex(s) for j, s in d["seeds"].items()}
+    except (KeyError, TypeError, ValueError, AttributeError) as e:
+        raise ValueError("%s: not a pair-seeds file (%s)" % (path, e))
+    if x <= 0 or x in seeds or any(len(s) != 32 or j <= 0 for j, s in seeds.items()):
+        raise ValueError("%s: pair seeds are 32 bytes each, keyed by the other auditor's index" % path)
+    return x, seeds
+
+
+PARTIAL_KEYS = ("x", "with", "ct_commitment", "masked", "smudge_bound", "partial")
+
+
+def partial_json(x, xs, ct_commitment, masked, smudge_bound, partial):
+    """the dict of one partial_<x>.json: auditor x's partial decryption of ONE ciphertext within the set xs"""
+    vals = _unbe(np.ascontiguousarray(partial, dtype=np.uint8).tobytes(), MSG_SLOTS)
+    return {"x": int(x), "with": sorted(int(v) for v in xs), "ct_commitment": "0x%064x" % int(ct_commitment), "masked": bool(masked),
+            "smudge_bound": int(smudge_bound), "partial": ["0x%064x" % v for v in vals]}
+
+
+def load_partial_json(path):
+    """Reads a partial_<x>.json into {"x", "with": sorted xs, "ct_commitment": int, "masked", "smudge_bound", "partial": uint8 [64, 32]};
+    ValueError if it is not one."""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    if not isinstance(d, dict) or set(PARTIAL_KEYS) - set(d):
+        raise ValueError("%s: not a partial decryption (keys %s)" % (path, ", ".join(PARTIAL_KEYS)))
+    try:
+        vals = [int(v, 16) for v in d["partial"]]
+        out = {"x": int(d["x"]), "with": sorted(int(v) for v in d["with"]), "ct_commitment": int(d["ct_commitment"], 16),
+               "masked": bool(d["masked"]), "smudge_bound": int(d["smudge_bound"])}
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: not a partial decryption (%s)" % (path, e))
+    if len(vals) != MSG_SLOTS or not all(0 <= v < FR_MODULUS for v in vals) or out["x"] not in out["with"] or len(set(out["with"])) != len(out["with"]):
+        raise ValueError("%s: a partial is 64 field elements of an auditor inside its set" % path)
+    out["partial"] = np.frombuffer(_be(vals), dtype=np.uint8).reshape(MSG_SLOTS, 32).copy()
+    return out
 
 
 # ---- the files the prover and the key holders leave for the auditor ----
