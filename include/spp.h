@@ -846,8 +846,12 @@ int spp_g1_scale_points_timed(spp_ctx* ctx, const uint8_t* points, size_t n, con
  * spp_setup derives all toxic waste from one seed, so whoever ran it can forge proofs for its key.  A contribution multiplies delta
  * by a secret d nobody else learns: delta1' = d delta1, delta2' = d delta2, K' = K / d (the private wires' section), Z' = Z / d;
  * every other byte of the proving key (SPPK layout) and of the verifying key (gnark raw layout) is copied.  After a chain of
- * contributions the key is sound if ONE contributor was honest and forgot d.  The contributed key loads, proves and verifies
- * through the existing calls; the on-chain verifier is redeployed from the final vk, as after spp_setup.
+ * contributions nobody can forge THROUGH DELTA if ONE contributor was honest and forgot d.  That makes the key sound only when
+ * nobody knows its other secrets either: a key that started in spp_setup does NOT get that, because whoever ran spp_setup still
+ * knows tau, alpha, beta and gamma as field elements and forges without delta (C = 0, A = a G1, B = b G2 with
+ * a b = alpha beta + gamma sum x_i k_i), and knows sigma, the trapdoor of the commitment's proof of knowledge.  The first phase, which
+ * re-randomises tau, alpha and beta, is the powers-of-tau transcript below (spp_ptau_*).  The contributed key loads, proves and
+ * verifies through the existing calls; the on-chain verifier is redeployed from the final vk, as after spp_setup.
  *
  * (d, k) = fr.Hash(entropy, "spp-groth16-contribute-v1", 2 elements) -- the derivation of spp_setup's toxic waste; entropy NULL:
  * 32 bytes from the operating system.  The same entropy and inputs give the same three outputs byte for byte.  d = 0 is refused.
@@ -885,6 +889,116 @@ int spp_setup_contribute(spp_ctx* ctx, const char* pk_in, const char* vk_in, con
 #define SPP_CONTRIB_VK 7
 int spp_setup_verify_contribution(spp_ctx* ctx, const char* pk_before, const char* vk_before, const char* pk_after, const char* vk_after,
                                   const uint8_t receipt[SPP_CONTRIB_RECEIPT_LEN], int* ok, uint32_t* reason);
+
+/* ---- setup ceremony: contributions to sigma, the trapdoor of the commitment's proof of knowledge ----
+ * CS = sigma CB (the committed wires' second section) and the vk's LAST G2 point H = -rho sigma G2 are all that depends on sigma.  A
+ * contribution with secret s sets CS' = s CS (the scaling kernel of the delta contributions) and H' = s H (host) and copies every
+ * other byte; after a chain nobody knows sigma if ONE contributor was honest.  Sigma links and delta links are separate files of a
+ * chain: each verifier compares every section it does not own byte for byte.
+ * (s, k) = fr.Hash(entropy, "spp-groth16-sigma-v1", 2 elements); receipt = CS'_0 (64) | T = k CS_0 (64) | z = k + c s (32) with
+ * c = fr.Hash(SHA256(pk_in bytes) | CS_0 | CS'_0 | T, "spp-groth16-sigma-c1").  Same entropy and inputs, same bytes; s = 0 refused;
+ * the secrets are cleared as in spp_setup_contribute.  A key without committed wires: SPP_ERR_BAD_INPUT (both calls). */
+int spp_setup_contribute_sigma(spp_ctx* ctx, const char* pk_in, const char* vk_in, const uint8_t entropy[32] /* NULL = OS randomness */,
+                               const char* pk_out, const char* vk_out, uint8_t receipt[SPP_CONTRIB_RECEIPT_LEN]);
+/* One sigma link.  *ok = 1 and *reason = 0, or *ok = 0 and *reason:
+ *   SPP_SIGMA_FORMAT              a file does not parse
+ *   SPP_SIGMA_NOT_A_SIGMA_CHANGE  the proving keys differ outside the CS points, or the verifying keys outside their last G2 point
+ *   SPP_SIGMA_POINT_INVALID       a CS point of either key is not on the curve or has a coordinate >= q (the device's check); CS_0 or
+ *                                 CS'_0 is infinity; `after` has infinity where `before` has none; H or H' is not in the order-r subgroup
+ *   SPP_SIGMA_RECEIPT             the receipt's CS'_0 is not pk_after's, T is no point, z >= r, or z CS_0 != T + c CS'_0
+ *   SPP_SIGMA_SCALING             with rho_i as in spp_setup_verify_contribution: e(sum rho_i CS'_i, H) != e(sum rho_i CS_i, H')
+ *   SPP_SIGMA_VK                  vk_after does not carry s H for the receipt's s: e(CS'_0, H) != e(CS_0, H')
+ * The scaling is tested against the point the vk carries, so SPP_SIGMA_VK is decided first: a vk that kept the old point is
+ * SPP_SIGMA_VK whatever the CS points are; otherwise the reason is the first failing check in the order above. */
+#define SPP_SIGMA_OK 0
+#define SPP_SIGMA_FORMAT 1
+#define SPP_SIGMA_NOT_A_SIGMA_CHANGE 2
+#define SPP_SIGMA_POINT_INVALID 3
+#define SPP_SIGMA_RECEIPT 4
+#define SPP_SIGMA_SCALING 5
+#define SPP_SIGMA_VK 6
+int spp_setup_verify_sigma_contribution(spp_ctx* ctx, const char* pk_before, const char* vk_before, const char* pk_after, const char* vk_after,
+                                        const uint8_t receipt[SPP_CONTRIB_RECEIPT_LEN], int* ok, uint32_t* reason);
+
+/* ---- setup ceremony, first phase: the powers-of-tau transcript ----
+ * A transcript holds powers of a secret tau in both groups, with alpha and beta applied, and nothing circuit-specific:
+ *   'SPPT' | version 1 | domain_log L (u32 little-endian each), n = 2^L |
+ *   T1: tau^i G1, i < 2n - 1 (64 B raw) | T2: tau^i G2, i < n (128 B raw) | A1: alpha tau^i G1, i < n | B1: beta tau^i G1, i < n |
+ *   beta2 = beta G2.  No counts are stored (they follow from L); raw points as spp_setup writes them.
+ * Anyone may contribute: with secrets t, a, b point i of T1 and T2 is multiplied by t^i, of A1 by a t^i, of B1 by b t^i, beta2 by b, so
+ * tau' = t tau, alpha' = a alpha, beta' = b beta.  After a chain of contributions nobody knows tau, alpha or beta if ONE
+ * contributor was honest and forgot t, a and b.  Anyone may verify a link from the two files and the receipt.
+ *
+ * spp_ptau_new writes the transcript of tau = alpha = beta = 1 (every point a generator), host only; domain_log in [1, 20].
+ *
+ * spp_ptau_contribute: (t, a, b, k_t, k_a, k_b) = fr.Hash(entropy, "spp-ptau-contribute-v1", 6 elements), entropy NULL: 32 bytes
+ * from the operating system; a zero among t, a, b is refused.  The same entropy and input give the same bytes.  Every input point is
+ * checked before anything multiplies it: coordinates below q and the curve equation on the device (G2 included), the order-r
+ * subgroup of the G2 points on the host; infinity, or powers that do not start at the generators, are refused (SPP_ERR_FORMAT).
+ * The per-point scalars are built on the host and uploaded once; the products run on the device, one lane per point with that
+ * lane's scalar.  receipt = three proofs of knowledge, 160 B each, for (t, T1_1), (a, A1_0), (b, B1_0):
+ *   base' (64, the point of the file after) | T = k base (64) | z = k + c s mod r (32, big-endian),
+ *   c = fr.Hash(SHA256(in file) | base | base' | T, "spp-ptau-contribute-c1").
+ * The secrets, the scalar array and their copies are overwritten in host and device memory before the call returns, on every path. */
+#define SPP_PTAU_RECEIPT_LEN 480
+int spp_ptau_new(uint32_t domain_log, const char* path);
+int spp_ptau_contribute(spp_ctx* ctx, const char* in_path, const uint8_t entropy[32] /* NULL = OS randomness */, const char* out_path,
+                        uint8_t receipt[SPP_PTAU_RECEIPT_LEN]);
+/* One link: is `after` a contribution to `before` with this receipt?  *ok = 1 and *reason = 0, or *ok = 0 and *reason = the FIRST
+ * check that fails, in this order:
+ *   SPP_PTAU_FORMAT         a file does not parse (magic, version, L in [1, 20], the length L gives)
+ *   SPP_PTAU_SIZE           the two transcripts differ in L
+ *   SPP_PTAU_POINT_INVALID  in `after`: a point off the curve or with a coordinate >= q (checked on the device before any sum
+ *                           touches it); infinity anywhere; T1'_0 != G1 or T2'_0 != G2; T2'_1, beta2' or one of the two
+ *                           combinations of T2' points that TAU_G2 pairs is outside the order-r subgroup of the twist
+ *   SPP_PTAU_RECEIPT        a proof's base' is not the file's, T is no point, z >= r, or z base != T + c base'
+ *   SPP_PTAU_TAU_G1         with rho_i = the first 128 bits of SHA256(SHA256(before) | SHA256(after) | tag | i as 8 bytes big-endian)
+ *                           (tag, one byte: 1 T1, 2 T2, 3 A1, 4 B1): e(sum rho_i T1'_{i+1}, G2) e(-sum rho_i T1'_i, T2'_1) != 1, i < 2n - 2
+ *   SPP_PTAU_TAU_G2         e(T1'_1, sum rho_i T2'_i) e(-G1, sum rho_i T2'_{i+1}) != 1, i < n - 1
+ *   SPP_PTAU_ALPHA          the T1 test over A1', i < n - 1 (A1'_0 is tied to the receipt)
+ *   SPP_PTAU_BETA           the same over B1', or e(B1'_0, G2) e(-G1, beta2') != 1
+ * The sums run on the device (the resident-buffer Pippenger, G1 and G2), the Miller loops on the host.  A refusal is SPP_OK with
+ * *ok = 0; the return value is an error only for I/O, NULL arguments or the device. */
+#define SPP_PTAU_OK 0
+#define SPP_PTAU_FORMAT 1
+#define SPP_PTAU_SIZE 2
+#define SPP_PTAU_POINT_INVALID 3
+#define SPP_PTAU_RECEIPT 4
+#define SPP_PTAU_TAU_G1 5
+#define SPP_PTAU_TAU_G2 6
+#define SPP_PTAU_ALPHA 7
+#define SPP_PTAU_BETA 8
+int spp_ptau_verify_contribution(spp_ctx* ctx, const char* before_path, const char* after_path, const uint8_t receipt[SPP_PTAU_RECEIPT_LEN],
+                                 int* ok, uint32_t* reason);
+/* The transcript's kernels on their own: out[i] = scalar_i * points[i], a scalar per point (scalars_be: n * 32 B big-endian), G1
+ * points 64 B and G2 points 128 B raw; infinity maps to infinity; n = 0 is SPP_OK.  SPP_ERR_BAD_INPUT: a scalar 0 or >= r, a point
+ * that is not on the curve or has a coordinate >= q.  G2 points are NOT tested for the subgroup. */
+int spp_g1_mul_each(spp_ctx* ctx, const uint8_t* points /* n*64 */, size_t n, const uint8_t* scalars_be /* n*32 */, uint8_t* out /* n*64 */);
+int spp_g2_mul_each(spp_ctx* ctx, const uint8_t* points /* n*128 */, size_t n, const uint8_t* scalars_be /* n*32 */, uint8_t* out /* n*128 */);
+
+/* ---- setup ceremony: a circuit's keys from a transcript ----
+ * Deterministic and without a secret: the SPPK container and the gnark raw vk exactly as spp_setup lays them out, for the tau,
+ * alpha and beta of the transcript and gamma = delta = sigma = rho = 1 (delta1 = G1, delta2 = gamma2 = G2, CS = CB, the vk's last two
+ * G2 points (G2, -G2)); the sections list the same wires by the same predicates.  Checking a published derivation is re-running it
+ * and comparing the files.  The delta contributions above (spp_setup_contribute) then re-randomise delta.
+ *   Lagrange points  L_k = (1 / n) sum_i w^(-k i) T_i, an inverse NTT of size n = 2^domain_log over POINTS with w the root spp_setup
+ *                    takes: three times in G1 (over T1[0 .. n), A1, B1) and once in G2 (over T2), on the device
+ *   column gather    A_j = sum_k A[k][j] L_k, B_j the same in G1 and in G2, K_j = sum_k A[k][j] beta L_k + B[k][j] alpha L_k + C[k][j] L_k:
+ *                    the host transposes the matrices and plans, the device multiplies and sums
+ *   Z_i = T1_{i+n} - T1_i (i < n - 1), alpha1 = A1_0, beta1 = B1_0, beta2 from the file
+ * A transcript of a larger domain_log serves (a prefix of the powers is a transcript) and gives the same bytes; a smaller one is
+ * SPP_ERR_BAD_INPUT.  Every transcript point that is used is checked first (the device's range and curve checks, the G2 subgroup on
+ * the host): SPP_ERR_FORMAT.  The derived key loads through spp_load_circuit. */
+int spp_setup_from_ptau(spp_ctx* ctx, const char* circuit_path, const char* ptau_path, const char* pk_path, const char* vk_path);
+/* The transform alone: out[k] = (1 / n) sum_i w^(-k i) points[i] for n = 2^logn raw points (logn in [1, 20]; infinity allowed).
+ * SPP_ERR_BAD_INPUT: a point that is not on the curve or has a coordinate >= q.  G2 points are NOT tested for the subgroup. */
+int spp_ec_intt_g1(spp_ctx* ctx, const uint8_t* points /* n*64 */, uint32_t logn, uint8_t* out /* n*64 */);
+int spp_ec_intt_g2(spp_ctx* ctx, const uint8_t* points /* n*128 */, uint32_t logn, uint8_t* out /* n*128 */);
+/* The same with timings (profiles/ptau_probe.py), group 1 = G1, 2 = G2: ms[0] = the logn stages, ms[1] = the scaling by 1 / n and the
+ * conversion to affine, between events; *host_ms = one host thread over the first min(host_butterflies, n / 2) butterflies of stage 0,
+ * the text the lanes run.  ms and host_ms may be NULL. */
+int spp_ec_intt_timed(spp_ctx* ctx, int group, const uint8_t* points, uint32_t logn, uint8_t* out, float ms[2], size_t host_butterflies,
+                      float* host_ms);
 
 #ifdef __cplusplus
 }

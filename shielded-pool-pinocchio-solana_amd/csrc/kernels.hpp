@@ -396,5 +396,24 @@ void launch_fixed_base_mul(hipStream_t st, const Affine<F>* gen_table, uint32_t 
 void launch_g1_scale(hipStream_t st, const G1Affine* pts, uint32_t n, const int8_t* dig, uint32_t len, G1Affine* out);
 // raw: n points of 64 B (X | Y big-endian) -> pts[i] in Montgomery form and flags[i] = SC_POINT_OK / SC_POINT_INF / SC_POINT_BAD
 void launch_g1_decode_check(hipStream_t st, const uint8_t* raw, uint32_t n, G1Affine* pts, uint32_t* flags);
+// ---- powers-of-tau transcript (kernels_ptau.hip; the method: ptau.hpp) ----
+// out[i] = sc[i] * pts[i]: a scalar of its own per point, 8 canonical words each (least significant first), 0 < sc[i] < r
+void launch_g1_mul_each(hipStream_t st, const G1Affine* pts, uint32_t n, const uint32_t* sc, G1Affine* out);
+void launch_g2_mul_each(hipStream_t st, const G2Affine* pts, uint32_t n, const uint32_t* sc, G2Affine* out);
+// raw: n points of 128 B -> pts[i] and flags[i] = SC_POINT_*: coordinates below q, on the twist y^2 = x^3 + twist_b; NOT the subgroup
+void launch_g2_decode_check(hipStream_t st, const uint8_t* raw, uint32_t n, const Fq2& twist_b, G2Affine* pts, uint32_t* flags);
+// nbatch inverse NTTs over points, each 2^logn (logn >= 1) elements laid end to end: out[b][k] = (1 / n) sum_i w^(-k i) in[b][i].
+// work: 2 * (nbatch << logn) elements (the stages go from one half to the other); tw: w^-j, j < n / 2, 8 canonical words each; dig, len: the NAF digits of 1 / n (sc_naf_recode).
+// ev_passes / ev_finish (optional): recorded after the last stage and after the scaling
+template <class F>
+void launch_ec_intt(hipStream_t st, const Affine<F>* in, XYZZ<F>* work, uint32_t logn, uint32_t nbatch, const uint32_t* tw, const int8_t* dig,
+                    uint32_t len, Affine<F>* out, hipEvent_t ev_passes = nullptr, hipEvent_t ev_finish = nullptr);
+// out[j] = sum of column j's terms (row, coefficient) * bases[row] for a ColPlan (ptau.hpp): terms, chunk_ptr (nchunks + 1), col_ptr
+// (ncols + 1); mags / meta: the signed coefficient table (pt_signed_coeff); partial: nchunks elements
+template <class F>
+void launch_col_gather(hipStream_t st, const Affine<F>* bases, const uint32_t* terms, const uint32_t* chunk_ptr, uint32_t nchunks,
+                       const uint32_t* col_ptr, uint32_t ncols, const uint32_t* mags, const uint32_t* meta, XYZZ<F>* partial, Affine<F>* out);
+// out[i] = pts[i + n] - pts[i], i < count
+void launch_g1_shifted_diff(hipStream_t st, const G1Affine* pts, uint32_t n, uint32_t count, G1Affine* out);
 
 }  // namespace spp

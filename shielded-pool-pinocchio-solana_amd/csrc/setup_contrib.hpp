@@ -57,9 +57,11 @@ SPP_HD uint32_t sc_naf_recode(const uint32_t k[8], int8_t dig[SC_MAX_DIGITS]) {
 }
 
 // k * p from the digits of sc_naf_recode, most significant first.  `dig` is read at indices that do not depend on the lane.
-SPP_HD XYZZ<Fq> sc_scale_point(const Affine<Fq>& p, const int8_t* dig, uint32_t len) {
-  XYZZ<Fq> acc = XYZZ<Fq>::infinity();
-  const Affine<Fq> np = p.neg();
+// (F = Fq: the ceremony's K | Z and CS points; F = Fq2: the 1 / n of the group transform over G2, ptau.hpp)
+template <class F>
+SPP_HD XYZZ<F> sc_scale_point(const Affine<F>& p, const int8_t* dig, uint32_t len) {
+  XYZZ<F> acc = XYZZ<F>::infinity();
+  const Affine<F> np = p.neg();
 #if defined(__HIPCC__)
 #pragma unroll 1
 #endif
@@ -93,7 +95,7 @@ SPP_HD uint32_t sc_decode_point(const uint8_t raw[64], Affine<Fq>* out) {
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
-// The SPPK container (written by spp_setup.cpp only) as byte ranges.
+// The SPPK container (written by sppk_write.hpp only) as byte ranges.
 //   header 7 words | alpha1 beta1 delta1 (64 B each) | beta2 delta2 (128 B each) | A: count, wires, points | B1: the same |
 //   B2: count, wires, 128 B points | K: count, wires, points | Z: count, points | CB: count, wires, points | CS: the same
 // ----------------------------------------------------------------------------------------------------------------------
@@ -101,6 +103,8 @@ struct SppkLayout {
   size_t delta1 = 0, delta2 = 0;       // offsets of delta1 (64 B) and delta2 (128 B)
   size_t k_points = 0, z_points = 0;   // offsets of the first K point and the first Z point
   uint32_t n_k = 0, n_z = 0;
+  size_t cs_points = 0;                // offset of the first CS point (the sigma contributions' section), n_cs of them
+  uint32_t n_cs = 0;
 };
 inline bool sppk_layout(const uint8_t* b, size_t len, SppkLayout* L) {
   size_t p = 0;
@@ -128,7 +132,7 @@ inline bool sppk_layout(const uint8_t* b, size_t len, SppkLayout* L) {
   L->n_k = u32(); skip((uint64_t)L->n_k * 4); L->k_points = p; skip((uint64_t)L->n_k * 64);
   L->n_z = u32(); L->z_points = p; skip((uint64_t)L->n_z * 64);
   { const uint32_t n = u32(); skip((uint64_t)n * 4); skip((uint64_t)n * 64); }
-  { const uint32_t n = u32(); skip((uint64_t)n * 4); skip((uint64_t)n * 64); }
+  L->n_cs = u32(); skip((uint64_t)L->n_cs * 4); L->cs_points = p; skip((uint64_t)L->n_cs * 64);
   return ok && p == len;
 }
 // The gnark raw verifying key: alpha1 beta1 | beta2 gamma2 | delta1 (at 384) delta2 (at 448) | count (big-endian) | K | 12 B | two G2

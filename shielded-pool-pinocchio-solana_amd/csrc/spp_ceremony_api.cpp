@@ -1,44 +1,12 @@
 // libspp C ABI, the setup ceremony: a contribution to the delta of a proving key, its receipt and the verifier of one link of a
-// chain of contributions (include/spp.h has the protocol; setup_contrib.hpp the kernel's method and the container's byte ranges).
+// chain of contributions; the same pair for sigma, the trapdoor of the commitment's proof of knowledge (include/spp.h has the
+// protocols; setup_contrib.hpp the kernel's method and the container's byte ranges).
 #include "spp_internal.hpp"
-#include "setup_contrib.hpp"
+#include "ceremony_host.hpp"
 
 #include <chrono>
 
 namespace {
-// overwrites on every return path; the volatile stores are not removed as dead
-struct Wipe {
-  void* p;
-  size_t n;
-  ~Wipe() {
-    volatile uint8_t* q = (volatile uint8_t*)p;
-    for (size_t i = 0; i < n; i++) q[i] = 0;
-  }
-};
-// the same for a device buffer, declared AFTER the DevBuf it clears (so it runs before the buffer is released)
-struct DevWipe {
-  DevBuf& b;
-  size_t n;
-  hipStream_t st;
-  ~DevWipe() {
-    if (!b.p) return;
-    hipMemsetAsync(b.p, 0, n, st);
-    hipStreamSynchronize(st);
-  }
-};
-
-// count values of fr.Hash(msg, dst): 48 bytes per element, as the toxic waste of spp_setup
-void hash_to_fr(const uint8_t* msg, size_t len, const char* dst, Fr* out, int count) {
-  std::vector<uint8_t> u((size_t)48 * count);
-  Wipe wu{u.data(), u.size()};
-  expand_message_xmd(msg, len, (const uint8_t*)dst, strlen(dst), u.data(), u.size());
-  for (int i = 0; i < count; i++) {
-    uint32_t w[12];
-    Wipe ww{w, sizeof w};
-    for (int k = 0; k < 12; k++) w[k] = sc_load_be32(u.data() + 48 * i + 4 * k);
-    out[i] = fr_from_wide48(w);
-  }
-}
 Fr schnorr_challenge(const uint8_t pk_hash[32], const uint8_t* delta1, const uint8_t* delta1_after, const uint8_t* T) {
   uint8_t m[32 + 3 * 64];
   memcpy(m, pk_hash, 32);
@@ -48,54 +16,6 @@ Fr schnorr_challenge(const uint8_t pk_hash[32], const uint8_t* delta1, const uin
   Fr c;
   hash_to_fr(m, sizeof m, "spp-groth16-contribute-c1", &c, 1);
   return c;
-}
-bool g1_raw_valid(const uint8_t* raw, G1Affine* out) { return sc_decode_point(raw, out) != SC_POINT_BAD; }
-// a G2 point of the order-r subgroup with canonical coordinates, not infinity
-bool g2_raw_valid(const uint8_t* raw, G2Affine* out) {
-  for (int o = 0; o < 128; o += 32)
-    if (!be_is_canonical<FqParams>(raw + o)) return false;
-  *out = g2_from_raw(raw);
-  return !out->is_inf() && g2_on_curve(*out) && g2_in_subgroup(*out);
-}
-G2Affine g2_generator() {
-  auto dec = [](const char* s) {
-    Fq acc = Fq::zero(), ten = Fq::from_u64(10);
-    for (; *s; s++) acc = acc * ten + Fq::from_u64((uint64_t)(*s - '0'));
-    return acc;
-  };
-  G2Affine g;
-  g.x.c0 = dec("10857046999023057135944570762232829481370756359578518086990519993285655852781");
-  g.x.c1 = dec("11559732032986387107991004021392285783925812861821192530917403151452391805634");
-  g.y.c0 = dec("8495653923123431417604973247489272438418190587263600148770280649306958101930");
-  g.y.c1 = dec("4082367875863433681332203403145435568316851327593401208105741076214120093531");
-  return g;
-}
-// prod e(P, Q) == 1 for pairs whose Q are valid; a pair with P = infinity contributes 1
-bool pairing_is_one(std::vector<std::pair<G1Affine, G2Affine>> pairs) {
-  std::vector<std::pair<G1Affine, G2Affine>> live;
-  for (auto& pq : pairs)
-    if (!pq.first.is_inf()) live.push_back(pq);
-  return live.empty() || pairing_product_is_one(live);
-}
-bool write_bytes(const char* path, const uint8_t* p, size_t n) {
-  FILE* f = fopen(path, "wb");
-  if (!f) return false;
-  const bool ok = fwrite(p, 1, n, f) == n;
-  return fclose(f) == 0 && ok;
-}
-
-// raw[n * 64] -> d_pts (Montgomery form) and flags (host) by k_g1_decode_check.  ctx->mu held, device set.
-int decode_points(hipStream_t st, const uint8_t* raw, size_t n, DevBuf& d_pts, std::vector<uint32_t>& flags) {
-  DevBuf d_raw, d_flags;
-  UP(d_raw, raw, n * 64);
-  HIP_TRY(d_pts.alloc(n * sizeof(G1Affine)));
-  HIP_TRY(d_flags.alloc(n * sizeof(uint32_t)));
-  launch_g1_decode_check(st, d_raw.as<uint8_t>(), (uint32_t)n, d_pts.as<G1Affine>(), d_flags.as<uint32_t>());
-  HIP_TRY(hipGetLastError());
-  flags.resize(n);
-  if (n) HIP_TRY(hipMemcpyAsync(flags.data(), d_flags.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return SPP_OK;
 }
 // out[i] = k * points[i] (raw in, raw out) for the canonical limbs k != 0; *bad = index of the first point that is not on the
 // curve (then nothing is written), else n.  The digits are cleared in host and device memory on every path.  kernel_ms
@@ -351,5 +271,154 @@ extern "C" int spp_setup_verify_contribution(spp_ctx* ctx, const char* pk_before
     return refuse(SPP_CONTRIB_VK);
   *ok = 1;
   *reason = SPP_CONTRIB_OK;
+  return SPP_OK;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// sigma contributions: the trapdoor of the commitment's proof of knowledge (CS = sigma CB, the vk's last G2 point -rho sigma G2)
+// -----------------------------------------------------------------------------------------------------
+namespace {
+Fr sigma_challenge(const uint8_t pk_hash[32], const uint8_t* cs0, const uint8_t* cs0_after, const uint8_t* T) {
+  uint8_t m[32 + 3 * 64];
+  memcpy(m, pk_hash, 32);
+  memcpy(m + 32, cs0, 64);
+  memcpy(m + 96, cs0_after, 64);
+  memcpy(m + 160, T, 64);
+  Fr c;
+  hash_to_fr(m, sizeof m, "spp-groth16-sigma-c1", &c, 1);
+  return c;
+}
+// the vk's last G2 point
+size_t vk_sigma_point(size_t vk_len) { return vk_len - 128; }
+}  // namespace
+
+extern "C" int spp_setup_contribute_sigma(spp_ctx* ctx, const char* pk_in, const char* vk_in, const uint8_t entropy[32], const char* pk_out,
+                                          const char* vk_out, uint8_t receipt[SPP_CONTRIB_RECEIPT_LEN]) {
+  if (!ctx || !pk_in || !vk_in || !pk_out || !vk_out || !receipt) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  std::vector<uint8_t> pk, vk;
+  if (!read_file(pk_in, pk)) return fail(SPP_ERR_IO, "cannot read %s", pk_in);
+  if (!read_file(vk_in, vk)) return fail(SPP_ERR_IO, "cannot read %s", vk_in);
+  SppkLayout L;
+  if (!sppk_layout(pk.data(), pk.size(), &L)) return fail(SPP_ERR_FORMAT, "%s is not a proving key", pk_in);
+  if (!vk_layout_ok(vk.data(), vk.size())) return fail(SPP_ERR_FORMAT, "%s is not a verifying key", vk_in);
+  if (L.n_cs == 0) return fail(SPP_ERR_BAD_INPUT, "%s has no committed wires: there is no sigma to contribute to", pk_in);
+  G1Affine cs0;
+  G2Affine H;
+  if (sc_decode_point(pk.data() + L.cs_points, &cs0) != SC_POINT_OK || !g2_raw_valid(vk.data() + vk_sigma_point(vk.size()), &H))
+    return fail(SPP_ERR_FORMAT, "%s / %s hold an invalid commitment key", pk_in, vk_in);
+
+  // the secrets: s (the contribution), k (the nonce of the receipt) and their limbs; all cleared on every path
+  uint8_t seed[32];
+  Fr sk[2];
+  uint32_t sl[8], kl[8];
+  Wipe w0{seed, sizeof seed}, w1{sk, sizeof sk}, w2{sl, sizeof sl}, w3{kl, sizeof kl};
+  if (!ceremony_seed(entropy, seed)) return fail(SPP_ERR_IO, "no randomness from the operating system");
+  hash_to_fr(seed, 32, "spp-groth16-sigma-v1", sk, 2);
+  if (sk[0].is_zero()) return fail(SPP_ERR_BAD_INPUT, "the entropy gives the contribution zero: use another");
+  sk[0].to_canonical(sl);
+  sk[1].to_canonical(kl);
+
+  // CS by s on the device
+  std::vector<uint8_t> after((size_t)L.n_cs * 64);
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    size_t bad = L.n_cs;
+    if (int e = scale_raw_points(ctx, pk.data() + L.cs_points, L.n_cs, sl, after.data(), &bad)) return e;
+    if (bad != L.n_cs) return fail(SPP_ERR_FORMAT, "%s: point %zu of CS is not on the curve", pk_in, bad);
+  }
+  // the vk's point and the receipt on the host
+  uint8_t T[64], pk_hash[32];
+  g1_to_raw(scalar_mul(cs0, kl).to_affine(), T);
+  sha256_bytes(pk.data(), pk.size(), pk_hash);
+  const Fr c = sigma_challenge(pk_hash, pk.data() + L.cs_points, after.data(), T);
+  const Fr z = sk[1] + c * sk[0];   // public
+  memcpy(receipt, after.data(), 64);
+  memcpy(receipt + 64, T, 64);
+  z.to_bytes_be(receipt + 128);
+  memcpy(pk.data() + L.cs_points, after.data(), after.size());
+  g2_to_raw(scalar_mul(H, sl).to_affine(), vk.data() + vk_sigma_point(vk.size()));
+  if (!write_bytes(pk_out, pk.data(), pk.size())) return fail(SPP_ERR_IO, "cannot write %s", pk_out);
+  if (!write_bytes(vk_out, vk.data(), vk.size())) return fail(SPP_ERR_IO, "cannot write %s", vk_out);
+  return SPP_OK;
+}
+
+extern "C" int spp_setup_verify_sigma_contribution(spp_ctx* ctx, const char* pk_before, const char* vk_before, const char* pk_after,
+                                                   const char* vk_after, const uint8_t receipt[SPP_CONTRIB_RECEIPT_LEN], int* ok, uint32_t* reason) {
+  if (!ctx || !pk_before || !vk_before || !pk_after || !vk_after || !receipt || !ok || !reason) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  *ok = 0;
+  *reason = SPP_SIGMA_FORMAT;
+  std::vector<uint8_t> pb, vb, pa, va;
+  for (auto f : {std::make_pair(pk_before, &pb), std::make_pair(vk_before, &vb), std::make_pair(pk_after, &pa), std::make_pair(vk_after, &va)})
+    if (!read_file(f.first, *f.second)) return fail(SPP_ERR_IO, "cannot read %s", f.first);
+  auto refuse = [&](uint32_t why) { *reason = why; return SPP_OK; };
+
+  // 1. the files parse; 2. they differ in the CS points and the vk's last G2 point only
+  SppkLayout L, La;
+  if (!sppk_layout(pb.data(), pb.size(), &L) || !sppk_layout(pa.data(), pa.size(), &La) || !vk_layout_ok(vb.data(), vb.size()) ||
+      !vk_layout_ok(va.data(), va.size()))
+    return refuse(SPP_SIGMA_FORMAT);
+  if (L.n_cs == 0) return fail(SPP_ERR_BAD_INPUT, "%s has no committed wires: there is no sigma to contribute to", pk_before);
+  const size_t n = L.n_cs, cs_end = L.cs_points + n * 64, hp = vk_sigma_point(vb.size());
+  if (pa.size() != pb.size() || va.size() != vb.size() || memcmp(pb.data(), pa.data(), L.cs_points) != 0 ||
+      memcmp(pb.data() + cs_end, pa.data() + cs_end, pb.size() - cs_end) != 0 || memcmp(vb.data(), va.data(), hp) != 0)
+    return refuse(SPP_SIGMA_NOT_A_SIGMA_CHANGE);
+
+  // 3. every CS point of both keys is a point (the device's check), the first ones are not infinity, the two G2 points are in the group
+  std::vector<uint8_t> raw(pb.begin() + L.cs_points, pb.begin() + cs_end);
+  raw.insert(raw.end(), pa.begin() + L.cs_points, pa.begin() + cs_end);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf d_pts;
+  std::vector<uint32_t> flags;
+  if (int e = decode_points(st, raw.data(), 2 * n, d_pts, flags)) return e;
+  for (size_t i = 0; i < 2 * n; i++)
+    if (flags[i] == SC_POINT_BAD) return refuse(SPP_SIGMA_POINT_INVALID);
+  for (size_t i = 0; i < n; i++)
+    if (flags[n + i] == SC_POINT_INF && flags[i] != SC_POINT_INF) return refuse(SPP_SIGMA_POINT_INVALID);
+  if (flags[0] != SC_POINT_OK || flags[n] != SC_POINT_OK) return refuse(SPP_SIGMA_POINT_INVALID);
+  G1Affine cs0, cs0a, T;
+  G2Affine H, Ha;
+  sc_decode_point(pb.data() + L.cs_points, &cs0);
+  sc_decode_point(pa.data() + L.cs_points, &cs0a);
+  if (!g2_raw_valid(vb.data() + hp, &H) || !g2_raw_valid(va.data() + hp, &Ha)) return refuse(SPP_SIGMA_POINT_INVALID);
+
+  // 4. the receipt: knowledge of s with CS'_0 = s CS_0, bound to the key it was applied to
+  uint8_t hb[32], ha[32];
+  sha256_bytes(pb.data(), pb.size(), hb);
+  sha256_bytes(pa.data(), pa.size(), ha);
+  if (memcmp(receipt, pa.data() + L.cs_points, 64) != 0) return refuse(SPP_SIGMA_RECEIPT);
+  if (sc_decode_point(receipt + 64, &T) == SC_POINT_BAD || !be_is_canonical<FrParams>(receipt + 128)) return refuse(SPP_SIGMA_RECEIPT);
+  if (!schnorr_holds(cs0, cs0a, T, sigma_challenge(hb, pb.data() + L.cs_points, receipt, receipt + 64), receipt + 128)) return refuse(SPP_SIGMA_RECEIPT);
+
+  // 5., 6. the scaling is tested against the G2 point the vk carries, so that point is tied to the receipt's s first: a vk whose
+  //    point is not s H (e(CS'_0, H) != e(CS_0, H')) is SPP_SIGMA_VK, whatever the CS points are; with it, all points at once:
+  //    e(sum rho_i CS'_i, H) = e(sum rho_i CS_i, H'), rho_i as in the delta verifier
+  if (!pairing_is_one({{cs0a, H}, {cs0.neg(), Ha}})) return refuse(SPP_SIGMA_VK);
+  std::vector<Fr> rho(n);
+  uint8_t m[72], dg[32];
+  memcpy(m, hb, 32);
+  memcpy(m + 32, ha, 32);
+  for (size_t i = 0; i < n; i++) {
+    for (int b = 0; b < 8; b++) m[64 + b] = (uint8_t)((uint64_t)i >> (8 * (7 - b)));
+    sha256_bytes(m, sizeof m, dg);
+    uint32_t w[8] = {sc_load_be32(dg + 12), sc_load_be32(dg + 8), sc_load_be32(dg + 4), sc_load_be32(dg), 0, 0, 0, 0};
+    rho[i] = Fr::from_canonical(w);
+  }
+  DevBuf d_rho, d_ws;
+  UP(d_rho, rho.data(), n * sizeof(Fr));
+  HIP_TRY(d_ws.alloc(pippenger_workspace_bytes((uint32_t)n)));
+  G1Affine sum[2];
+  for (int side = 0; side < 2; side++) {
+    G1XYZZ* win = nullptr;
+    launch_pippenger_g1(st, d_pts.as<G1Affine>() + side * n, d_rho.as<Fr>(), (uint32_t)n, d_ws.p, &win, nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    sum[side] = pippenger_finish(win);
+  }
+  if (!pairing_is_one({{sum[1], H}, {sum[0].neg(), Ha}})) return refuse(SPP_SIGMA_SCALING);
+  *ok = 1;
+  *reason = SPP_SIGMA_OK;
   return SPP_OK;
 }

@@ -11,7 +11,8 @@
 //   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
 //   spp_withdrawals_api.cpp  the withdrawal plan: which notes of a batch still need an audit record (spp_prove_withdrawals itself is in spp_prove.cpp)
-//   spp_ceremony_api.cpp the setup ceremony: contributions to a key's delta, their receipts and verifier, the scaling unit call
+//   spp_ceremony_api.cpp the setup ceremony: contributions to a key's delta and to its sigma, their receipts and verifiers, the scaling unit call
+//   spp_ptau_api.cpp     the ceremony's first phase: the powers-of-tau transcript, the derivation of a circuit's keys from it, unit calls
 //   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points, the raw-word arithmetic probe (spp_debug_arith)
 #pragma once
 #include "../../include/spp.h"

@@ -1,5 +1,6 @@
 // libspp C ABI, what comes before a circuit is loaded: circuit construction (host only) and the trusted setup on the GPU.
 #include "spp_internal.hpp"
+#include "sppk_write.hpp"
 
 // -----------------------------------------------------------------------------------------------------
 // circuit construction (host only)
@@ -39,18 +40,6 @@ extern "C" int spp_circuit_build_acir(const uint8_t* blob, size_t blob_len, int 
 // -----------------------------------------------------------------------------------------------------
 // setup on the GPU
 // -----------------------------------------------------------------------------------------------------
-static void wr32(std::vector<uint8_t>& o, uint32_t v) { for (int i = 0; i < 4; i++) o.push_back((uint8_t)(v >> (8 * i))); }
-static void wr32be(std::vector<uint8_t>& o, uint32_t v) { for (int i = 3; i >= 0; i--) o.push_back((uint8_t)(v >> (8 * i))); }
-static void wr_g1(std::vector<uint8_t>& o, const G1Affine& p) { uint8_t b[64]; g1_to_raw(p, b); o.insert(o.end(), b, b + 64); }
-static void wr_g2(std::vector<uint8_t>& o, const G2Affine& p) { uint8_t b[128]; g2_to_raw(p, b); o.insert(o.end(), b, b + 128); }
-static bool write_file(const char* path, const std::vector<uint8_t>& o) {
-  FILE* f = fopen(path, "wb");
-  if (!f) return false;
-  bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
-  fclose(f);
-  return ok;
-}
-
 extern "C" int spp_setup(spp_ctx* ctx, const char* circuit_path, const uint8_t seed[32], const char* pk_path, const char* vk_path) {
   if (!ctx || !circuit_path || !seed || !pk_path || !vk_path) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -107,10 +96,7 @@ extern "C" int spp_setup(spp_ctx* ctx, const char* circuit_path, const uint8_t s
           (*O[m])[t.wire] = (*O[m])[t.wire] + circ.coeffs[t.coeff] * L[k];
         }
   }
-  std::vector<uint8_t> cls(W, 0);
-  for (uint32_t j = 0; j < circ.n_public; j++) cls[j] = 1;
-  cls[circ.challenge_wire] = 1;
-  for (uint32_t w : circ.committed) cls[w] = 2;
+  const std::vector<uint8_t> cls = wire_classes(circ);
   const Fr gi = gamma.inv(), di = delta.inv();
   // scalar vectors, one fixed-base multiplication each:
   //   G1: [A(W) | B1(W) | K(W) | S(W) | Z(n-1) | alpha beta delta]    G2: [B2(W) | beta gamma delta rho -rho*sigma]
@@ -172,44 +158,10 @@ extern "C" int spp_setup(spp_ctx* ctx, const char* circuit_path, const uint8_t s
   const G2Affine* pB2 = p2.data();
   const G2Affine* pC2 = pB2 + W;
 
-  std::vector<uint8_t> o;
-  wr32(o, 0x4b505053u); wr32(o, 1);
-  wr32(o, circ.id); wr32(o, W); wr32(o, logn); wr32(o, circ.n_public); wr32(o, circ.challenge_wire);
-  wr_g1(o, pC[0]); wr_g1(o, pC[1]); wr_g1(o, pC[2]); wr_g2(o, pC2[0]); wr_g2(o, pC2[2]);
-  auto sec1 = [&](const G1Affine* pts, auto pred) {
-    uint32_t cnt = 0;
-    for (uint32_t j = 0; j < W; j++) cnt += pred(j) ? 1 : 0;
-    wr32(o, cnt);
-    for (uint32_t j = 0; j < W; j++) if (pred(j)) wr32(o, j);
-    for (uint32_t j = 0; j < W; j++) if (pred(j)) wr_g1(o, pts[j]);
-  };
-  sec1(pA, [&](uint32_t j) { return !pA[j].is_inf(); });
-  sec1(pB1, [&](uint32_t j) { return !pB1[j].is_inf(); });
-  {
-    uint32_t cnt = 0;
-    for (uint32_t j = 0; j < W; j++) cnt += !pB2[j].is_inf();
-    wr32(o, cnt);
-    for (uint32_t j = 0; j < W; j++) if (!pB2[j].is_inf()) wr32(o, j);
-    for (uint32_t j = 0; j < W; j++) if (!pB2[j].is_inf()) wr_g2(o, pB2[j]);
-  }
-  sec1(pK, [&](uint32_t j) { return cls[j] == 0 && !pK[j].is_inf(); });
-  wr32(o, n - 1);
-  for (uint32_t i = 0; i + 1 < n; i++) wr_g1(o, pZ[i]);
-  wr32(o, (uint32_t)circ.committed.size());
-  for (uint32_t w : circ.committed) wr32(o, w);
-  for (uint32_t w : circ.committed) wr_g1(o, pK[w]);
-  wr32(o, (uint32_t)circ.committed.size());
-  for (uint32_t w : circ.committed) wr32(o, w);
-  for (uint32_t w : circ.committed) wr_g1(o, pS[w]);
+  KeyPoints kp{pA, pB1, pK, pS, pB2, pZ, pC[0], pC[1], pC[2], pC2[0], pC2[1], pC2[2], pC2[3], pC2[4]};
+  std::vector<uint8_t> o, v;
+  key_files(circ, cls, kp, o, v);
   if (!write_file(pk_path, o)) return fail(SPP_ERR_IO, "cannot write %s", pk_path);
-
-  std::vector<uint8_t> v;
-  wr_g1(v, pC[0]); wr_g1(v, pC[1]); wr_g2(v, pC2[0]); wr_g2(v, pC2[1]); wr_g1(v, pC[2]); wr_g2(v, pC2[2]);
-  wr32be(v, circ.n_public + 1);
-  for (uint32_t j = 0; j < circ.n_public; j++) wr_g1(v, pK[j]);
-  wr_g1(v, pK[circ.challenge_wire]);
-  wr32be(v, 1); wr32be(v, 0); wr32be(v, 1);
-  wr_g2(v, pC2[3]); wr_g2(v, pC2[4]);
   if (!write_file(vk_path, v)) return fail(SPP_ERR_IO, "cannot write %s", vk_path);
   return SPP_OK;
 }

@@ -69,6 +69,25 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # a chain of contributions, link by link: exit 0 if every link is a contribution to the key before it,
                               # else exit 1 naming the first failing link and its reason (FORMAT, NOT_A_DELTA_CHANGE, POINT_INVALID,
                               # RECEIPT, DELTA_PAIR, SCALING, VK)
+    python -m spp.cli ptau-new <log> --out <name>.ptau
+                              # the first phase of a ceremony starts here: the powers-of-tau transcript of tau = alpha = beta = 1 for
+                              # domains up to 2^log (host only)
+    python -m spp.cli ptau-contribute <name>.ptau --out DIR [--entropy HEX32]
+                              # one contribution to the transcript: multiplies tau, alpha and beta by secrets drawn from the operating
+                              # system (--entropy: for reproducible tests only) and writes DIR/<name>.ptau and DIR/<name>.receipt;
+                              # prints the SHA-256 of the receipt, which the contributor publishes
+    python -m spp.cli ptau-verify <t0> <t1> <receipt1> [<t2> <receipt2> ...]
+                              # a chain of transcript contributions, link by link: exit 0 if every link is a contribution to the
+                              # transcript before it, else exit 1 naming the first failing link and its reason (FORMAT, SIZE,
+                              # POINT_INVALID, RECEIPT, TAU_G1, TAU_G2, ALPHA, BETA)
+    python -m spp.cli setup-derive <name>.sppc <name>.ptau --out DIR
+                              # the circuit's keys from a transcript of at least its domain size, no secret involved: DIR/<name>.pk
+                              # and DIR/<name>.vk with gamma = delta = sigma = 1; checking a published derivation is re-running it
+    python -m spp.cli setup-contribute-sigma <name>.pk <name>.vk --out DIR [--entropy HEX32]
+    python -m spp.cli setup-verify-sigma <pk0> <vk0> <pk1> <vk1> <receipt1> [...]
+                              # the setup-contribute / setup-verify pair for sigma, the trapdoor of the commitment's proof of
+                              # knowledge (reasons: FORMAT, NOT_A_SIGMA_CHANGE, POINT_INVALID, RECEIPT, SCALING, VK); sigma links and
+                              # delta links are separate links of a chain
     python -m spp.cli execute target/<name>.json Prover.toml [-o target/<name>.gz]               # `nargo execute`: ACIR witness stack
     python -m spp.cli prove   target/<name>.json target/<name>.gz target/<name>.sppc target/<name>.pk
                               # sunspot's own argument order (acir, witness, constraint system, proving key;
@@ -676,8 +695,9 @@ def _verify_batch(a):
     return 0 if all(got) else 1
 
 
-def _setup_contribute(a):
+def _setup_contribute(a, sigma=False):
     import hashlib
+    cmd = "setup-contribute-sigma" if sigma else "setup-contribute"
     try:   # everything that can be wrong with the arguments and the files is found before a device is opened
         entropy = None
         if a.entropy is not None:
@@ -688,23 +708,23 @@ def _setup_contribute(a):
             open(p, "rb").close()
         os.makedirs(a.out, exist_ok=True)
     except (OSError, ValueError) as e:
-        print("spp setup-contribute: %s" % e, file=sys.stderr)
+        print("spp %s: %s" % (cmd, e), file=sys.stderr)
         return 2
     name = os.path.splitext(os.path.basename(a.pk))[0]
     pk_out, vk_out, receipt_out = (os.path.join(a.out, name + ext) for ext in (".pk", ".vk", ".receipt"))
     if os.path.exists(pk_out) and os.path.samefile(pk_out, a.pk):
-        print("spp setup-contribute: --out is the directory of the key itself; the key before is needed to verify the contribution", file=sys.stderr)
+        print("spp %s: --out is the directory of the key itself; the key before is needed to verify the contribution" % cmd, file=sys.stderr)
         return 2
     ctx = Context(a.device)
     try:
-        receipt = ctx.setup_contribute(a.pk, a.vk, pk_out, vk_out, entropy)
+        receipt = (ctx.setup_contribute_sigma if sigma else ctx.setup_contribute)(a.pk, a.vk, pk_out, vk_out, entropy)
     except lib.SppError as e:
-        print("spp setup-contribute: %s" % e, file=sys.stderr)
+        print("spp %s: %s" % (cmd, e), file=sys.stderr)
         return 2
     finally:
         ctx.close()
     open(receipt_out, "wb").write(receipt)
-    print("setup-contribute: %s, %s" % (pk_out, vk_out))
+    print("%s: %s, %s" % (cmd, pk_out, vk_out))
     print("receipt %s sha256 %s" % (receipt_out, hashlib.sha256(receipt).hexdigest()))
     return 0
 
@@ -717,14 +737,16 @@ def parse_ceremony_chain(files):
     return [keys[k] + keys[k + 1] + (files[4 + 3 * k],) for k in range(len(keys) - 1)]
 
 
-def _setup_verify(a):
+def _setup_verify(a, sigma=False):
+    cmd = "setup-verify-sigma" if sigma else "setup-verify"
+    names = lib.SIGMA_REASON_NAMES if sigma else lib.CONTRIB_REASON_NAMES
     try:   # everything that can be wrong with the arguments and the files is found before a device is opened
         links = parse_ceremony_chain(a.files)
         for p in a.files:
             open(p, "rb").close()
         receipts = [open(link[4], "rb").read() for link in links]
     except (OSError, ValueError) as e:
-        print("spp setup-verify: %s" % e, file=sys.stderr)
+        print("spp %s: %s" % (cmd, e), file=sys.stderr)
         return 2
     ctx = Context(a.device)
     try:
@@ -732,17 +754,123 @@ def _setup_verify(a):
             if len(receipt) != lib.SPP_CONTRIB_RECEIPT_LEN:
                 ok, reason = False, lib.SPP_CONTRIB_FORMAT
             else:
-                ok, reason = ctx.setup_verify_contribution(*link[:4], receipt)
+                ok, reason = (ctx.setup_verify_sigma_contribution if sigma else ctx.setup_verify_contribution)(*link[:4], receipt)
             if not ok:
-                print("link %d (%s): REFUSED, %s" % (k, link[2], lib.CONTRIB_REASON_NAMES[reason]))
+                print("link %d (%s): REFUSED, %s" % (k, link[2], names[reason]))
                 return 1
             print("link %d (%s): a contribution to %s" % (k, link[2], link[0]))
     except lib.SppError as e:
-        print("spp setup-verify: %s" % e, file=sys.stderr)
+        print("spp %s: %s" % (cmd, e), file=sys.stderr)
         return 2
     finally:
         ctx.close()
-    print("setup-verify: %d links verified" % len(links))
+    print("%s: %d links verified" % (cmd, len(links)))
+    return 0
+
+
+def _hex32(text, what):
+    raw = bytes.fromhex(text[2:] if text.lower().startswith("0x") else text)
+    if len(raw) != 32:
+        raise ValueError("%s is 32 bytes of hexadecimal" % what)
+    return raw
+
+
+def _setup_derive(a):
+    try:
+        for p in (a.sppc, a.ptau):
+            open(p, "rb").close()
+        os.makedirs(a.out, exist_ok=True)
+    except OSError as e:
+        print("spp setup-derive: %s" % e, file=sys.stderr)
+        return 2
+    name = os.path.splitext(os.path.basename(a.sppc))[0]
+    pk, vk = (os.path.join(a.out, name + ext) for ext in (".pk", ".vk"))
+    ctx = Context(a.device)
+    try:
+        ctx.setup_from_ptau(a.sppc, a.ptau, pk, vk)
+    except lib.SppError as e:
+        print("spp setup-derive: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    print("setup-derive: %s, %s (gamma = delta = sigma = 1: contribute to delta and sigma next)" % (pk, vk))
+    return 0
+
+
+def _ptau_new(a):
+    try:
+        if not 1 <= a.log <= 20:
+            raise ValueError("the domain's logarithm is in [1, 20]")
+        lib.check(lib.load_library().spp_ptau_new(a.log, a.out.encode()))   # host only: no device is opened
+    except (ValueError, lib.SppError) as e:
+        print("spp ptau-new: %s" % e, file=sys.stderr)
+        return 2
+    print("ptau-new: %s (tau = alpha = beta = 1, domains up to 2^%d)" % (a.out, a.log))
+    return 0
+
+
+def _ptau_contribute(a):
+    import hashlib
+    try:   # everything that can be wrong with the arguments and the files is found before a device is opened
+        entropy = None if a.entropy is None else _hex32(a.entropy, "--entropy")
+        open(a.ptau, "rb").close()
+        os.makedirs(a.out, exist_ok=True)
+    except (OSError, ValueError) as e:
+        print("spp ptau-contribute: %s" % e, file=sys.stderr)
+        return 2
+    name = os.path.splitext(os.path.basename(a.ptau))[0]
+    out, receipt_out = (os.path.join(a.out, name + ext) for ext in (".ptau", ".receipt"))
+    if os.path.exists(out) and os.path.samefile(out, a.ptau):
+        print("spp ptau-contribute: --out is the directory of the transcript itself; the transcript before is needed to verify the contribution",
+              file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        receipt = ctx.ptau_contribute(a.ptau, out, entropy)
+    except lib.SppError as e:
+        print("spp ptau-contribute: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    open(receipt_out, "wb").write(receipt)
+    print("ptau-contribute: %s" % out)
+    print("receipt %s sha256 %s" % (receipt_out, hashlib.sha256(receipt).hexdigest()))
+    return 0
+
+
+def parse_ptau_chain(files):
+    """[(transcript before, transcript after, receipt path)] per link from the arguments of ptau-verify, or ValueError"""
+    if len(files) < 3 or (len(files) - 1) % 2:
+        raise ValueError("ptau-verify takes <t0> and then pairs <transcript> <receipt>")
+    return [(files[0] if k == 0 else files[2 * k - 1], files[2 * k + 1], files[2 * k + 2]) for k in range((len(files) - 1) // 2)]
+
+
+def _ptau_verify(a):
+    try:   # everything that can be wrong with the arguments and the files is found before a device is opened
+        links = parse_ptau_chain(a.files)
+        for p in a.files:
+            open(p, "rb").close()
+        receipts = [open(link[2], "rb").read() for link in links]
+    except (OSError, ValueError) as e:
+        print("spp ptau-verify: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        for k, (link, receipt) in enumerate(zip(links, receipts), 1):
+            if len(receipt) != lib.SPP_PTAU_RECEIPT_LEN:
+                ok, reason = False, lib.SPP_PTAU_FORMAT
+            else:
+                ok, reason = ctx.ptau_verify_contribution(link[0], link[1], receipt)
+            if not ok:
+                print("link %d (%s): REFUSED, %s" % (k, link[1], lib.PTAU_REASON_NAMES[reason]))
+                return 1
+            print("link %d (%s): a contribution to %s" % (k, link[1], link[0]))
+    except lib.SppError as e:
+        print("spp ptau-verify: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    print("ptau-verify: %d links verified" % len(links))
     return 0
 
 
@@ -814,7 +942,34 @@ def main(argv=None):
     sc.add_argument("--device", type=int, default=0)
     sv = sub.add_parser("setup-verify"); sv.add_argument("files", nargs="+", metavar="FILE", help="<pk0> <vk0> then <pk> <vk> <receipt> per link")
     sv.add_argument("--device", type=int, default=0)
+    pn = sub.add_parser("ptau-new"); pn.add_argument("log", type=int, help="domains up to 2^log"); pn.add_argument("--out", required=True, metavar="FILE")
+    pc = sub.add_parser("ptau-contribute"); pc.add_argument("ptau")
+    pc.add_argument("--out", required=True, metavar="DIR", help="<name>.ptau and <name>.receipt go here (not the transcript's own directory)")
+    pc.add_argument("--entropy", default=None, metavar="HEX32", help="for reproducible tests only: the default draws from the operating system")
+    pc.add_argument("--device", type=int, default=0)
+    pv = sub.add_parser("ptau-verify"); pv.add_argument("files", nargs="+", metavar="FILE", help="<t0> then <transcript> <receipt> per link")
+    pv.add_argument("--device", type=int, default=0)
+    sd = sub.add_parser("setup-derive"); sd.add_argument("sppc"); sd.add_argument("ptau")
+    sd.add_argument("--out", required=True, metavar="DIR", help="<name>.pk and <name>.vk go here"); sd.add_argument("--device", type=int, default=0)
+    ss = sub.add_parser("setup-contribute-sigma"); ss.add_argument("pk"); ss.add_argument("vk")
+    ss.add_argument("--out", required=True, metavar="DIR", help="<name>.pk, <name>.vk and <name>.receipt go here (not the key's own directory)")
+    ss.add_argument("--entropy", default=None, metavar="HEX32", help="for reproducible tests only: the default draws from the operating system")
+    ss.add_argument("--device", type=int, default=0)
+    sw = sub.add_parser("setup-verify-sigma"); sw.add_argument("files", nargs="+", metavar="FILE", help="<pk0> <vk0> then <pk> <vk> <receipt> per link")
+    sw.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.cmd == "setup-derive":
+        return _setup_derive(a)
+    if a.cmd == "setup-contribute-sigma":
+        return _setup_contribute(a, sigma=True)
+    if a.cmd == "setup-verify-sigma":
+        return _setup_verify(a, sigma=True)
+    if a.cmd == "ptau-new":
+        return _ptau_new(a)
+    if a.cmd == "ptau-contribute":
+        return _ptau_contribute(a)
+    if a.cmd == "ptau-verify":
+        return _ptau_verify(a)
     if a.cmd == "setup-contribute":
         return _setup_contribute(a)
     if a.cmd == "setup-verify":

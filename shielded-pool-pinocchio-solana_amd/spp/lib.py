@@ -9,6 +9,7 @@ _LIB = None
 SPP_OK = 0
 SPP_ERR_BAD_INPUT = -1
 SPP_ERR_UNSAT = -4
+SPP_ERR_FORMAT = -7
 SPP_CIRCUIT_WITHDRAW = 1
 SPP_CIRCUIT_AUDIT = 2
 SPP_CIRCUIT_WITHDRAW_DEPTH20 = 4     # build only: withdraw over a depth-20 tree (synthetic variant)
@@ -65,6 +66,27 @@ SPP_CONTRIB_DELTA_PAIR = 5
 SPP_CONTRIB_SCALING = 6
 SPP_CONTRIB_VK = 7
 CONTRIB_REASON_NAMES = ("OK", "FORMAT", "NOT_A_DELTA_CHANGE", "POINT_INVALID", "RECEIPT", "DELTA_PAIR", "SCALING", "VK")
+# sigma contributions, spp_setup_contribute_sigma / spp_setup_verify_sigma_contribution (include/spp.h); the receipt has the delta one's length
+SPP_SIGMA_OK = 0
+SPP_SIGMA_FORMAT = 1
+SPP_SIGMA_NOT_A_SIGMA_CHANGE = 2
+SPP_SIGMA_POINT_INVALID = 3
+SPP_SIGMA_RECEIPT = 4
+SPP_SIGMA_SCALING = 5
+SPP_SIGMA_VK = 6
+SIGMA_REASON_NAMES = ("OK", "FORMAT", "NOT_A_SIGMA_CHANGE", "POINT_INVALID", "RECEIPT", "SCALING", "VK")
+# the powers-of-tau transcript, spp_ptau_contribute / spp_ptau_verify_contribution (include/spp.h)
+SPP_PTAU_RECEIPT_LEN = 480          # three proofs of knowledge (t, a, b): base_after | T | z each
+SPP_PTAU_OK = 0
+SPP_PTAU_FORMAT = 1
+SPP_PTAU_SIZE = 2
+SPP_PTAU_POINT_INVALID = 3
+SPP_PTAU_RECEIPT = 4
+SPP_PTAU_TAU_G1 = 5
+SPP_PTAU_TAU_G2 = 6
+SPP_PTAU_ALPHA = 7
+SPP_PTAU_BETA = 8
+PTAU_REASON_NAMES = ("OK", "FORMAT", "SIZE", "POINT_INVALID", "RECEIPT", "TAU_G1", "TAU_G2", "ALPHA", "BETA")
 POOL_RESULT_NAMES = ("OK", "AUDIT_EXISTS", "NO_AUDIT_RECORD", "BAD_ROOT", "NULLIFIER_USED", "BAD_RECIPIENT", "BAD_PROOF")
 
 
@@ -210,6 +232,17 @@ def load_library():
     L.spp_g1_scale_points_timed.argtypes = [vp, cp, sz, cp, vp, ctypes.POINTER(ctypes.c_float), sz, ctypes.POINTER(ctypes.c_float)]
     L.spp_setup_contribute.argtypes = [vp, cp, cp, cp, cp, cp, vp]
     L.spp_setup_verify_contribution.argtypes = [vp, cp, cp, cp, cp, cp, ctypes.POINTER(i32), ctypes.POINTER(u32)]
+    L.spp_setup_contribute_sigma.argtypes = [vp, cp, cp, cp, cp, cp, vp]
+    L.spp_setup_verify_sigma_contribution.argtypes = [vp, cp, cp, cp, cp, cp, ctypes.POINTER(i32), ctypes.POINTER(u32)]
+    L.spp_ptau_new.argtypes = [u32, cp]
+    L.spp_ptau_contribute.argtypes = [vp, cp, cp, cp, vp]
+    L.spp_ptau_verify_contribution.argtypes = [vp, cp, cp, cp, ctypes.POINTER(i32), ctypes.POINTER(u32)]
+    L.spp_g1_mul_each.argtypes = [vp, cp, sz, cp, vp]
+    L.spp_g2_mul_each.argtypes = [vp, cp, sz, cp, vp]
+    L.spp_setup_from_ptau.argtypes = [vp, cp, cp, cp, cp]
+    L.spp_ec_intt_g1.argtypes = [vp, cp, u32, vp]
+    L.spp_ec_intt_g2.argtypes = [vp, cp, u32, vp]
+    L.spp_ec_intt_timed.argtypes = [vp, i32, cp, u32, vp, ctypes.POINTER(ctypes.c_float), sz, ctypes.POINTER(ctypes.c_float)]
     L.spp_msm_g1_pippenger_bench.argtypes = [vp, sz, ctypes.c_uint64, cp, i32, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.spp_msm_g1_pippenger_bench_dist.argtypes = [vp, sz, ctypes.c_uint64, ctypes.c_uint32, cp, i32, vp, ctypes.POINTER(ctypes.c_float),
                                                   ctypes.POINTER(ctypes.c_float)]

@@ -66,6 +66,92 @@ class Context:
                                                    bytes(receipt), ctypes.byref(ok), ctypes.byref(reason)))
         return bool(ok.value), reason.value
 
+    def setup_contribute_sigma(self, pk_in, vk_in, pk_out, vk_out, entropy=None):
+        """One contribution to the sigma of a key's commitment (spp_setup_contribute_sigma): writes pk_out / vk_out, returns the
+        160-byte receipt.  entropy as in setup_contribute."""
+        assert entropy is None or len(entropy) == 32
+        receipt = ctypes.create_string_buffer(lib.SPP_CONTRIB_RECEIPT_LEN)
+        check(self.L.spp_setup_contribute_sigma(self.h, pk_in.encode(), vk_in.encode(), None if entropy is None else bytes(entropy),
+                                                pk_out.encode(), vk_out.encode(), ctypes.cast(receipt, ctypes.c_void_p)))
+        return receipt.raw
+
+    def setup_verify_sigma_contribution(self, pk_before, vk_before, pk_after, vk_after, receipt):
+        """One sigma link (spp_setup_verify_sigma_contribution): (accepted, reason) with reason one of lib.SPP_SIGMA_*
+        (lib.SIGMA_REASON_NAMES has the names).  A refusal is a result, not an SppError."""
+        assert len(receipt) == lib.SPP_CONTRIB_RECEIPT_LEN
+        ok, reason = ctypes.c_int(0), ctypes.c_uint32(0)
+        check(self.L.spp_setup_verify_sigma_contribution(self.h, pk_before.encode(), vk_before.encode(), pk_after.encode(),
+                                                         vk_after.encode(), bytes(receipt), ctypes.byref(ok), ctypes.byref(reason)))
+        return bool(ok.value), reason.value
+
+    def ptau_new(self, domain_log, path):
+        """The transcript of tau = alpha = beta = 1 for domains up to 2^domain_log (spp_ptau_new; host only)."""
+        check(self.L.spp_ptau_new(int(domain_log), path.encode()))
+
+    def ptau_contribute(self, in_path, out_path, entropy=None):
+        """One contribution to a powers-of-tau transcript (spp_ptau_contribute): writes out_path, returns the 480-byte receipt.
+        entropy: 32 bytes, or None for the operating system's randomness (what every real contribution uses)."""
+        assert entropy is None or len(entropy) == 32
+        receipt = ctypes.create_string_buffer(lib.SPP_PTAU_RECEIPT_LEN)
+        check(self.L.spp_ptau_contribute(self.h, in_path.encode(), None if entropy is None else bytes(entropy), out_path.encode(),
+                                         ctypes.cast(receipt, ctypes.c_void_p)))
+        return receipt.raw
+
+    def ptau_verify_contribution(self, before_path, after_path, receipt):
+        """One link of a transcript chain (spp_ptau_verify_contribution): (accepted, reason) with reason one of lib.SPP_PTAU_*
+        (0 when accepted; lib.PTAU_REASON_NAMES has the names).  A refusal is a result, not an SppError."""
+        assert len(receipt) == lib.SPP_PTAU_RECEIPT_LEN
+        ok, reason = ctypes.c_int(0), ctypes.c_uint32(0)
+        check(self.L.spp_ptau_verify_contribution(self.h, before_path.encode(), after_path.encode(), bytes(receipt), ctypes.byref(ok),
+                                                  ctypes.byref(reason)))
+        return bool(ok.value), reason.value
+
+    def _mul_each(self, call, size, points_bytes, scalars):
+        n = len(scalars)
+        assert len(points_bytes) == size * n
+        out = ctypes.create_string_buffer(max(size * n, 1))
+        sc = b"".join(int(s).to_bytes(32, "big") for s in scalars)
+        check(call(self.h, points_bytes, n, sc, ctypes.cast(out, ctypes.c_void_p)))
+        return out.raw[:size * n]
+
+    def g1_mul_each(self, points_bytes, scalars):
+        """scalars[i] * P_i for every 64-byte point of points_bytes (spp_g1_mul_each): the transcript's kernel on its own."""
+        return self._mul_each(self.L.spp_g1_mul_each, 64, points_bytes, scalars)
+
+    def g2_mul_each(self, points_bytes, scalars):
+        """The same over 128-byte G2 points (spp_g2_mul_each)."""
+        return self._mul_each(self.L.spp_g2_mul_each, 128, points_bytes, scalars)
+
+    def setup_from_ptau(self, circuit_path, ptau_path, pk_path, vk_path):
+        """A circuit's proving and verifying key from a powers-of-tau transcript (spp_setup_from_ptau): no secret, gamma = delta =
+        sigma = rho = 1; the delta contributions (setup_contribute) come after it."""
+        check(self.L.spp_setup_from_ptau(self.h, circuit_path.encode(), ptau_path.encode(), pk_path.encode(), vk_path.encode()))
+
+    def _ec_intt(self, call, size, points_bytes, logn):
+        n = 1 << logn
+        assert len(points_bytes) == size * n
+        out = ctypes.create_string_buffer(size * n)
+        check(call(self.h, points_bytes, int(logn), ctypes.cast(out, ctypes.c_void_p)))
+        return out.raw
+
+    def ec_intt_g1(self, points_bytes, logn):
+        """out[k] = (1 / n) sum_i w^(-k i) P_i over 2^logn 64-byte points (spp_ec_intt_g1): monomial powers to Lagrange points."""
+        return self._ec_intt(self.L.spp_ec_intt_g1, 64, points_bytes, logn)
+
+    def ec_intt_g2(self, points_bytes, logn):
+        """The same over 128-byte G2 points (spp_ec_intt_g2)."""
+        return self._ec_intt(self.L.spp_ec_intt_g2, 128, points_bytes, logn)
+
+    def ec_intt_timed(self, group, points_bytes, logn, host_butterflies=0):
+        """(outputs, ms of the stages, ms of the scaling, ms of one host thread over host_butterflies butterflies); group 1 or 2"""
+        size = 64 if group == 1 else 128
+        assert len(points_bytes) == size << logn
+        out = ctypes.create_string_buffer(size << logn)
+        ms, host_ms = (ctypes.c_float * 2)(), ctypes.c_float(0)
+        check(self.L.spp_ec_intt_timed(self.h, int(group), points_bytes, int(logn), ctypes.cast(out, ctypes.c_void_p), ms,
+                                       int(host_butterflies), ctypes.byref(host_ms)))
+        return out.raw, ms[0], ms[1], host_ms.value
+
     def g1_scale_points(self, points_bytes, scalar):
         """scalar * P for every 64-byte point of points_bytes (spp_g1_scale_points): the ceremony's kernel on its own."""
         n = len(points_bytes) // 64
