@@ -14,6 +14,7 @@
 //   ./ec_ntt_check gather in.txt      line 1 "nbases ncoef ncols nentries", then the G1 bases, the coefficients, "col row coeff" entries
 //                                     -> "PLAN 0" when col_plan refuses, else "PLAN 1 | terms | chunk_ptr | col_ptr" and per column
 //                                     "COL hex" by pt_gather_chunk and pt_gather_combine
+//   ./ec_ntt_check gather2 in.txt     the same over Fq2, the instance the G2 gather compiles: the bases are 128 B G2 points
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -59,6 +60,56 @@ static bool slurp(const char* path, std::vector<uint8_t>& out) {
   while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + n);
   fclose(f);
   return true;
+}
+
+// one raw base of a gather file: 64 B in G1, 128 B in G2 (on the curve; the subgroup is the caller's business)
+static bool decode_base(const std::vector<uint8_t>& raw, Affine<Fq>* p) { return raw.size() == 64 && sc_decode_point(raw.data(), p) != SC_POINT_BAD; }
+static bool decode_base(const std::vector<uint8_t>& raw, Affine<Fq2>* p) {
+  const Fq2 twist_b = Fq2{Fq::from_u64(3), Fq::zero()} * Fq2{Fq::from_u64(9), Fq::one()}.inv();
+  return raw.size() == 128 && pt_decode_g2(raw.data(), twist_b, p) != SC_POINT_BAD;
+}
+static void print_point(const Affine<Fq>& r) { print_g1(r); }
+static void print_point(const Affine<Fq2>& r) { print_g2(r); }
+// the modes gather (F = Fq) and gather2 (F = Fq2): the planner, then the text of k_col_gather<F> and k_col_combine<F>
+template <class F>
+static int run_gather(FILE* f) {
+  unsigned nbases, ncoef, ncols, nentries;
+  if (fscanf(f, "%u %u %u %u", &nbases, &ncoef, &ncols, &nentries) != 4) return 2;
+  static char sp[300];
+  std::vector<Affine<F>> bases(nbases);
+  std::vector<uint32_t> mags((size_t)8 * ncoef), meta(ncoef);
+  for (unsigned i = 0; i < nbases; i++) {
+    std::vector<uint8_t> raw;
+    if (fscanf(f, "%299s", sp) != 1 || !unhex(sp, raw) || !decode_base(raw, &bases[i])) return 2;
+  }
+  for (unsigned i = 0; i < ncoef; i++) {
+    std::vector<uint8_t> kb;
+    uint32_t c[8];
+    if (fscanf(f, "%299s", sp) != 1 || !unhex(sp, kb) || kb.size() != 32) return 2;
+    limbs_of(kb.data(), c);
+    meta[i] = pt_signed_coeff(c, &mags[(size_t)8 * i]);
+  }
+  std::vector<ColEntry> entries(nentries);
+  for (auto& e : entries)
+    if (fscanf(f, "%u %u %u", &e.col, &e.row, &e.coeff) != 3) return 2;
+  ColPlan plan;
+  if (!col_plan(ncols, nbases, ncoef, entries, &plan)) { printf("PLAN 0\n"); return 0; }
+  printf("PLAN 1 |");
+  for (uint32_t v : plan.terms) printf(" %u", v);
+  printf(" |");
+  for (uint32_t v : plan.chunk_ptr) printf(" %u", v);
+  printf(" |");
+  for (uint32_t v : plan.col_ptr) printf(" %u", v);
+  printf("\n");
+  std::vector<XYZZ<F>> partial(plan.chunk_ptr.size() - 1);
+  for (size_t c = 0; c + 1 < plan.chunk_ptr.size(); c++)
+    partial[c] = pt_gather_chunk(bases.data(), plan.terms.data(), plan.chunk_ptr[c], plan.chunk_ptr[c + 1], mags.data(), meta.data());
+  for (uint32_t j = 0; j < ncols; j++) {
+    printf("COL ");
+    print_point(pt_gather_combine(partial.data(), plan.col_ptr[j], plan.col_ptr[j + 1]));
+    printf("\n");
+  }
+  return 0;
 }
 
 int main(int argc, char** argv) {
@@ -160,47 +211,12 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  if (argc == 3 && !strcmp(argv[1], "gather")) {
+  if (argc == 3 && (!strcmp(argv[1], "gather") || !strcmp(argv[1], "gather2"))) {
     FILE* f = fopen(argv[2], "r");
     if (!f) return 2;
-    unsigned nbases, ncoef, ncols, nentries;
-    if (fscanf(f, "%u %u %u %u", &nbases, &ncoef, &ncols, &nentries) != 4) return 2;
-    static char sp[300];
-    std::vector<Affine<Fq>> bases(nbases);
-    std::vector<uint32_t> mags((size_t)8 * ncoef), meta(ncoef);
-    for (unsigned i = 0; i < nbases; i++) {
-      std::vector<uint8_t> raw;
-      if (fscanf(f, "%299s", sp) != 1 || !unhex(sp, raw) || raw.size() != 64 || sc_decode_point(raw.data(), &bases[i]) == SC_POINT_BAD) return 2;
-    }
-    for (unsigned i = 0; i < ncoef; i++) {
-      std::vector<uint8_t> kb;
-      uint32_t c[8];
-      if (fscanf(f, "%299s", sp) != 1 || !unhex(sp, kb) || kb.size() != 32) return 2;
-      limbs_of(kb.data(), c);
-      meta[i] = pt_signed_coeff(c, &mags[(size_t)8 * i]);
-    }
-    std::vector<ColEntry> entries(nentries);
-    for (auto& e : entries)
-      if (fscanf(f, "%u %u %u", &e.col, &e.row, &e.coeff) != 3) return 2;
+    const int rc = strcmp(argv[1], "gather") ? run_gather<Fq2>(f) : run_gather<Fq>(f);
     fclose(f);
-    ColPlan plan;
-    if (!col_plan(ncols, nbases, ncoef, entries, &plan)) { printf("PLAN 0\n"); return 0; }
-    printf("PLAN 1 |");
-    for (uint32_t v : plan.terms) printf(" %u", v);
-    printf(" |");
-    for (uint32_t v : plan.chunk_ptr) printf(" %u", v);
-    printf(" |");
-    for (uint32_t v : plan.col_ptr) printf(" %u", v);
-    printf("\n");
-    std::vector<XYZZ<Fq>> partial(plan.chunk_ptr.size() - 1);
-    for (size_t c = 0; c + 1 < plan.chunk_ptr.size(); c++)
-      partial[c] = pt_gather_chunk(bases.data(), plan.terms.data(), plan.chunk_ptr[c], plan.chunk_ptr[c + 1], mags.data(), meta.data());
-    for (uint32_t j = 0; j < ncols; j++) {
-      printf("COL ");
-      print_g1(pt_gather_combine(partial.data(), plan.col_ptr[j], plan.col_ptr[j + 1]));
-      printf("\n");
-    }
-    return 0;
+    return rc;
   }
   if (argc == 3 && !strcmp(argv[1], "intt")) {
     FILE* f = fopen(argv[2], "r");
@@ -244,6 +260,6 @@ int main(int argc, char** argv) {
     for (uint32_t k = 0; k < n; k++) { printf("PT "); print_g1(out[k]); printf("\n"); }
     return 0;
   }
-  fprintf(stderr, "usage: ec_ntt_check layout|mul|scalar|bfly|intt|coeff|gather ...\n");
+  fprintf(stderr, "usage: ec_ntt_check layout|mul|scalar|bfly|intt|coeff|gather|gather2 ...\n");
   return 2;
 }
