@@ -24,6 +24,9 @@
  *   spp_shamir_reconstruct / spp_rlwe_decrypt_batch   scripts/rlwe_decrypt.py:61-132, demo-frontend/app/lib/shamir.ts:97-169
  *   spp_rlwe_sample_key / spp_rlwe_keygen_batch / spp_rlwe_key_check / spp_shamir_split
  *                             scripts/rlwe_keygen.py:98-182 (the audit key pair and its files) and :51-65 (shamir_share_field)
+ *   spp_vss_deal              scripts/rlwe_keygen.py:51-65 (shamir_share_field) by every auditor for its own part of the key, with
+ *                             public commitments (no counterpart in the reference, whose :98-182 draw and share the key in one place)
+ *   spp_vss_receive           the check of those commitments and the sum that is a share file of :157-171
  *   spp_prove_audit_records   scripts/generate_audit.py:468-691 with the ciphertext.json of :590-606: the audit RECORD
  *                             (proof, public witness, ciphertext) from the prover's raw secrets
  *   spp_audit_open_batch      scripts/rlwe_decrypt.py:61-149 for a batch of such records, after `sunspot verify`
@@ -454,6 +457,54 @@ int spp_rlwe_key_check(spp_ctx* ctx, size_t count, const uint32_t* pk_a, const u
  * ys = m*n*32, share-major.  t == 1: every share equals the secret. */
 int spp_shamir_split(spp_ctx* ctx, uint32_t t, uint32_t m, const uint32_t* xs, size_t n, const uint8_t* secrets_be,
                      const uint8_t* coeffs_be, uint8_t* ys);
+
+/* ---- the auditors' key without a dealer: verifiable (Pedersen) sharing, the joint key, share refresh ----
+ * spp_rlwe_keygen_batch + spp_shamir_split run on ONE machine, which sees the whole key.  Here each of the m auditors i draws its
+ * own s_i, e_i, computes b_i = e_i - a*s_i (spp_rlwe_keygen_batch, a from spp_dkg_a_from_seed) and deals s_i mod r to the others:
+ *   C_k[v] = c_k[v] G + c'_k[v] H, k < t, public, c_0 = s_i, c'_0 and every higher coefficient random below r;
+ *   y_j[v] = sum_k c_k[v] x_j^k,  y'_j[v] = sum_k c'_k[v] x_j^k, for receiver j alone.
+ * G = (1, 2); H = (x, the smaller y) at the first ctr = 0, 1, ... for which x = SHA-256("spp-vss-pedersen-h" | ctr, 4 B big-endian)
+ * mod p has x^3 + 3 a square (ctr = 1): nobody knows log_G H, which plain Feldman commitments s G of a coefficient in [-3, 3] would
+ * need nobody to look up.  Receiver j accepts value v of dealer i iff y G + y' H == sum_k x_j^k C_k[v].  The key is
+ * (a, sum_i b_i mod q), auditor j's share sum_i y_{i->j} mod r: a share file of spp_shamir_split's format for a key nobody ever held.
+ * The same dealing with s = 0 refreshes shares: the dealer also publishes c'_0, the receiver also checks C_0 == c'_0 H and adds the
+ * sum to its old share; the key stays.  Each dealer publishes the SHA-256 of its public values before any are revealed (else the
+ * last one chooses b_i as a function of the others'); that, and who talks to whom, is the caller's (spp dkg-deal / dkg-receive).
+ * a: SHA-256("spp-dkg-a" | seed | ctr, 4 B big-endian), ctr = 0, 1, ..., each digest eight big-endian words masked to 28 bits and
+ * kept when below q, the first 1024 kept.
+ * Refusals as in the key-generation block (SPP_ERR_BAD_INPUT before any device work, the index named in spp_last_error()): NULL
+ * required pointers, t == 0, t > 64, m < t, m > 255, an x equal to 0 or repeated, a field element >= r, n > 2^20, dealers == 0,
+ * dealers > 255.  n == 0 is SPP_OK.  Synchronous and serialised on the context; device buffers that held secrets, blinds,
+ * coefficients or sub-shares are zeroed before they are freed.  The commitments are sums of entries of a table of multiples of G
+ * and H (built on the device by the first call, freed with the context) selected by the bytes of the scalars: the addresses read
+ * depend on the secrets. */
+#define SPP_VSS_BAD_POINT 1   /* a commitment is not 64 canonical bytes of a curve point or of infinity */
+#define SPP_VSS_BAD_SHARE 2   /* y G + y' H != sum_k x^k C_k */
+#define SPP_VSS_NOT_ZERO  4   /* refresh only: C_0 != s' H */
+/* host-only: the two generators as X | Y big-endian; a of the joint key from the agreed seed */
+int spp_vss_generators(uint8_t g[64], uint8_t h[64]);
+int spp_dkg_a_from_seed(const uint8_t seed[32], uint32_t a[1024]);
+/* commitments: t*n*64, C_k[v] at (k*n + v)*64 (infinity: 64 zero bytes)
+ * ys, ys_blind: m*n*32 share-major, as spp_shamir_split writes ys
+ * blinds_be (n*32): NULL = OS randomness
+ * coeffs_be, coeffs_blind_be ((t-1)*n*32, layout of spp_shamir_split): NULL = OS randomness
+ * blinds_out (optional, n*32): the constant-term blinds that were used, for a refresh dealer to publish */
+int spp_vss_deal(spp_ctx* ctx, uint32_t t, uint32_t m, const uint32_t* xs, size_t n, const uint8_t* secrets_be, const uint8_t* blinds_be,
+                 const uint8_t* coeffs_be, const uint8_t* coeffs_blind_be, uint8_t* ys, uint8_t* ys_blind, uint8_t* commitments,
+                 uint8_t* blinds_out);
+/* The same; ms (optional) receives the device times of the two evaluations together and of the commitment kernel, in milliseconds */
+int spp_vss_deal_timed(spp_ctx* ctx, uint32_t t, uint32_t m, const uint32_t* xs, size_t n, const uint8_t* secrets_be,
+                       const uint8_t* blinds_be, const uint8_t* coeffs_be, const uint8_t* coeffs_blind_be, uint8_t* ys, uint8_t* ys_blind,
+                       uint8_t* commitments, uint8_t* blinds_out, float ms[2]);
+/* The receiver at x.
+ * commitments: dealers*t*n*64;  ys, ys_blind: dealers*n*32
+ * zero_blinds (optional): dealers*n*32, the refresh check
+ * flags: dealers*n SPP_VSS_* bits, always written; a commitment that is no point ends that value's check (SPP_VSS_BAD_POINT alone)
+ * share_out (optional, n*32) = base_be (optional, else 0) + sum over dealers of ys
+ *   written only when every flag is 0; *bad = number of non-zero flags */
+int spp_vss_receive(spp_ctx* ctx, uint32_t t, uint32_t x, uint32_t dealers, size_t n, const uint8_t* commitments, const uint8_t* ys,
+                    const uint8_t* ys_blind, const uint8_t* zero_blinds, const uint8_t* base_be, uint32_t* flags, uint8_t* share_out,
+                    size_t* bad);
 
 /* Opening audit records in one pass: what an auditor replaying submit_audit logs asks of every record (proof, public witness,
  * ciphertext) -- does the proof verify, is this the ciphertext the proof committed to, is the decrypted identity the one the

@@ -154,6 +154,17 @@ void launch_rlwe_key_noise(hipStream_t st, const RlweDev& rd, const uint32_t* a,
 // t-of-m sharing of n values: xs m share indices as Fr, coeffs_be (t - 1) * n * 32 B, ys_be m * n * 32 B share-major
 void launch_shamir_split(hipStream_t st, const Fr* xs, const uint8_t* secrets_be, const uint8_t* coeffs_be, uint32_t t, uint32_t m,
                          uint32_t n, uint8_t* ys_be);
+// verifiable sharing of the auditors' key (vss.hpp; kernels_vss.hip).  table: VSS_TABLE_POINTS affine points, built once from the 64
+// window bases; every scalar is 32 B big-endian and canonical (the caller's check)
+//   launch_vss_commit  commitments t * n * 64 B, C_k[v] at (k n + v) * 64; coeffs (t - 1) * n * 32 B as launch_shamir_split reads them
+//   launch_vss_check   flags dealers * n; commitments dealers * t * n * 64 B; ys, ys_blind, zero_blinds (optional) dealers * n * 32 B
+//   launch_vss_sum     out[v] = base[v] (optional) + sum over dealers of ys[d][v]
+void launch_vss_table(hipStream_t st, const G1Affine* wbases, G1Affine* table);
+void launch_vss_commit(hipStream_t st, const G1Affine* table, const uint8_t* secrets_be, const uint8_t* coeffs_be, const uint8_t* blinds_be,
+                       const uint8_t* coeffs_blind_be, uint32_t t, uint32_t n, uint8_t* commitments);
+void launch_vss_check(hipStream_t st, const G1Affine* table, uint32_t t, uint32_t x, uint32_t dealers, uint32_t n, const uint8_t* commitments,
+                      const uint8_t* ys_be, const uint8_t* ys_blind_be, const uint8_t* zero_blinds_be, uint32_t* flags);
+void launch_vss_sum(hipStream_t st, const uint8_t* base_be, const uint8_t* ys_be, uint32_t dealers, uint32_t n, uint8_t* out_be);
 // one wave per 64 audit records (audit_open.hpp): owners count * 64 B, flags[i] = SPP_AUDIT_* bits; proof_ok (optional): the verdicts
 // of launch_verify for the same records, enqueued before on `st`
 void launch_audit_open(hipStream_t st, HashConsts hc, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, const uint8_t* pws,

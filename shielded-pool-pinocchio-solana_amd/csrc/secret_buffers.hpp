@@ -1,5 +1,5 @@
 // Host-side handling of secrets, shared by the units that take key material (spp_witness_api.cpp: key generation and sharing;
-// spp_partial_api.cpp: an auditor's share and pair seeds): wiping, the operating system's randomness, and device buffers that are
+// spp_partial_api.cpp: an auditor's share and pair seeds; spp_vss_api.cpp: a dealer's part of the key and its sharing): wiping, the operating system's randomness, and device buffers that are
 // zeroed before they are freed.
 #pragma once
 #include "spp_internal.hpp"
@@ -33,6 +33,21 @@ struct OsRandom {
     return true;
   }
 };
+// host scratch of secrets, wiped when it goes
+struct WipedBytes {
+  std::vector<uint8_t> v;
+  ~WipedBytes() { wipe(v.data(), v.size()); }
+};
+// count field elements below r, 32 B big-endian each: 254 random bits, kept when below r (3 of 4 are)
+int draw_field_elements(OsRandom& rnd, uint8_t* out, size_t count) {
+  for (size_t i = 0; i < count;) {
+    uint8_t* c = out + 32 * i;
+    if (!rnd.next(c, 32)) return fail(SPP_ERR_IO, "cannot read /dev/urandom");
+    c[0] &= 0x3f;
+    if (be_is_canonical<FrParams>(c)) i++;
+  }
+  return SPP_OK;
+}
 // device buffer of secrets: zeroed on its stream before DevBuf's destructor frees it, on every return path
 struct WipedDevBuf : DevBuf {
   size_t bytes = 0;

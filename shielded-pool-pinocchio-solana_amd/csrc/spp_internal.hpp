@@ -12,6 +12,7 @@
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
 //   spp_withdrawals_api.cpp  the withdrawal plan: which notes of a batch still need an audit record (spp_prove_withdrawals itself is in spp_prove.cpp)
 //   spp_ceremony_api.cpp the setup ceremony: contributions to a key's delta and to its sigma, their receipts and verifiers, the scaling unit call
+//   spp_vss_api.cpp      the auditors' key without a dealer: verifiable sharing, the receiver's check, the sum of sub-shares
 //   spp_ptau_api.cpp     the ceremony's first phase: the powers-of-tau transcript, the derivation of a circuit's keys from it, unit calls
 //   spp_micro_api.cpp    the NTT / Pippenger unit and micro-benchmark entry points, the raw-word arithmetic probe (spp_debug_arith)
 #pragma once
@@ -154,6 +155,7 @@ struct spp_ctx {
   GkAffine* gk_table = nullptr;
   bool rlwe_ready = false;
   RlweDev rlwe{};              // NTT tables of the RLWE witness kernel (rlwe_ntt.hpp)
+  G1Affine* vss_table = nullptr;   // window table of the sharing's two generators (vss.hpp), built by the first spp_vss_* call
   // temporaries of spp_audit_inputs_batch(_device), kept between calls (grow only): a hipFree per call would drain every
   // stream of the device, the proving streams of the batch in flight included
   void* audit_scratch = nullptr;

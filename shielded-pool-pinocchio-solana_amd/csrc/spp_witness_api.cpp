@@ -1067,20 +1067,12 @@ extern "C" int spp_shamir_split(spp_ctx* ctx, uint32_t t, uint32_t m, const uint
     for (size_t i = 0; i < ncoef; i++)
       if (!be_is_canonical<FrParams>(coeffs_be + 32 * i))
         return fail(SPP_ERR_BAD_INPUT, "coefficient %zu (x^%zu of value %zu) is not a canonical field element", i, i / n + 1, i % n);
-  // the sharing polynomials from the OS when the caller brings none: 254 random bits, kept when below r (3 of 4 are)
-  struct WipedBytes {
-    std::vector<uint8_t> v;
-    ~WipedBytes() { wipe(v.data(), v.size()); }
-  } drawn;
+  // the sharing polynomials from the OS when the caller brings none
+  WipedBytes drawn;
   if (!coeffs_be && ncoef) {
     drawn.v.resize(ncoef * 32);
     OsRandom rnd;
-    for (size_t i = 0; i < ncoef;) {
-      uint8_t* c = drawn.v.data() + 32 * i;
-      if (!rnd.next(c, 32)) return fail(SPP_ERR_IO, "cannot read /dev/urandom");
-      c[0] &= 0x3f;
-      if (be_is_canonical<FrParams>(c)) i++;
-    }
+    if (int rc = draw_field_elements(rnd, drawn.v.data(), ncoef)) return rc;
     coeffs_be = drawn.v.data();
   }
   std::vector<Fr> x(m);

@@ -33,6 +33,20 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
     python -m spp.cli rlwe-key-check rlwe_pk.json --shares share_1.json share_2.json [--params rlwe_params.json]
                               # are these shares the secret of this public key?  prints max |b + a*sk| and max |sk| (centred),
                               # exit 0 iff both are within the noise bound of rlwe_params.json (next to rlwe_pk.json; default 3)
+    python -m spp.cli dkg-deal --index I --threshold T --shares M --a-seed HEX32 --out DIR [--refresh]
+                              # auditor I's part of a key that no dealer ever holds: draws its own s_I, e_I from the operating system,
+                              # computes b_I = e_I - a*s_I (a from the seed the auditors agreed on) and deals s_I to the auditors 1..M
+                              # with public commitments.  Writes DIR/deal_<I>.json (public), DIR/deal_<I>.hash (its SHA-256: every
+                              # auditor publishes this BEFORE any deal file is revealed) and DIR/private/subshare_<I>_to_<J>.json
+                              # (for auditor J alone).  --refresh: a dealing of zero that renews the shares of an existing key.
+                              # M <= 10: the noise of M summed keys, M * 18432 + 3, and the smudging limit 2^17 stay below delta / 2
+    python -m spp.cli dkg-receive --index J --deals deal_1.json ... --hashes deal_1.hash ... --subshares subshare_1_to_J.json ...
+                              --out DIR [--refresh share_J.json]
+                              # auditor J checks every dealer's file against the hash published first (--hashes in the order of
+                              # --deals) and every sub-share against the commitments, on the GPU; then writes DIR/rlwe_pk.json,
+                              # DIR/rlwe_params.json and DIR/rlwe_sk_shares/share_<J>.json, the files of rlwe-keygen (--refresh: only
+                              # the share, the old one plus the dealt zeros).  exit 1 names the first failing dealer, the check
+                              # (hash, missing, agreement, point, share, not-zero) and the value; nothing is written then
     python -m spp.cli pool-replay withdraw.vk audit.vk log.jsonl [--capacity N] [--verifier each|rlc [--group N]]
                               # the pool program's decisions for a log of instructions, one JSON object per line, values in hex:
                               #   {"deposit": {"root"}}  {"submit_audit": {"proof", "pw"}}  {"withdraw": {"proof", "pw", "recipient"}}
@@ -356,6 +370,208 @@ def _rlwe_key_check(a):
     ok = noise <= bound and skmax <= bound
     print("key: %s" % ("the shares hold the secret of this public key" if ok else "NOT a key pair within the bound"))
     return 0 if ok else 1
+
+
+DKG_MAX_SHARES = 10
+_DKG_NOISE_PER_KEY, _DKG_SMUDGE_LIMIT, _DKG_HALF_DELTA = 18432, 1 << 17, (167772161 // 256) // 2
+
+
+def _dkg_refuses_size(cmd, t, m):
+    """the message for a committee this command does not serve, or None"""
+    if not (1 <= t <= 64 and t <= m <= 255):
+        return "spp %s: need 1 <= threshold <= 64 and threshold <= shares <= 255" % cmd
+    if m > DKG_MAX_SHARES:
+        return ("spp %s: at most %d auditors: a ciphertext under %d summed keys has noise up to %d * %d + 3 = %d, and with the "
+                "smudging limit %d that is %d, not below delta / 2 = %d (%d auditors: %d)"
+                % (cmd, DKG_MAX_SHARES, m, m, _DKG_NOISE_PER_KEY, m * _DKG_NOISE_PER_KEY + 3, _DKG_SMUDGE_LIMIT,
+                   m * _DKG_NOISE_PER_KEY + 3 + _DKG_SMUDGE_LIMIT, _DKG_HALF_DELTA, DKG_MAX_SHARES,
+                   DKG_MAX_SHARES * _DKG_NOISE_PER_KEY + 3 + _DKG_SMUDGE_LIMIT))
+    return None
+
+
+def _hex_seed(text):
+    seed = bytes.fromhex(text[2:] if text.lower().startswith("0x") else text)
+    if len(seed) != 32:
+        raise ValueError("--a-seed is 32 bytes in hex")
+    return seed
+
+
+def _dkg_deal(a):
+    import hashlib
+    from . import witness
+    t, m, i = a.threshold, a.shares, a.index
+    msg = _dkg_refuses_size("dkg-deal", t, m)
+    if msg is None and not 1 <= i <= m:
+        msg = "spp dkg-deal: --index is one of the auditors 1..%d" % m
+    if msg:
+        print(msg, file=sys.stderr)
+        return 2
+    private = os.path.join(a.out, "private")
+    try:
+        seed = _hex_seed(a.a_seed)
+        os.makedirs(private, exist_ok=True)
+    except (OSError, ValueError) as e:
+        print("spp dkg-deal: %s" % e, file=sys.stderr)
+        return 2
+    L = lib.load_library()
+    ctx = Context(a.device)
+    try:
+        deal = {"version": 1, "kind": "refresh" if a.refresh else "key", "index": i, "threshold": t, "num_shares": m, "a_seed": seed.hex()}
+        if a.refresh:
+            secrets = [0] * witness.RLWE_N
+        else:
+            sk, _, e = (x[0] for x in witness.rlwe_sample_key(L, 1, witness.NOISE_BOUND))   # its a is not used: a comes from the seed
+            pk_b, _ = witness.rlwe_keygen(ctx, sk, witness.dkg_a_from_seed(L, seed), e)
+            deal["b"] = ["0x%08x" % int(v) for v in pk_b[0]]
+            secrets = [int(v) % R for v in sk]
+        d = witness.vss_deal(ctx, secrets, t, m)
+        deal["commitments"] = d["commitments"].hex()
+        if a.refresh:
+            deal["zero_blinds"] = ["%064x" % v for v in d["blinds"]]
+        text = json.dumps(deal).encode()
+        deal_path = os.path.join(a.out, "deal_%d.json" % i)
+        with open(deal_path, "wb") as f:
+            f.write(text)
+        digest = hashlib.sha256(text).hexdigest()
+        with open(os.path.join(a.out, "deal_%d.hash" % i), "w") as f:
+            f.write(digest + "\n")
+        for sh in d["shares"]:
+            with open(os.path.join(private, "subshare_%d_to_%d.json" % (i, sh["x"])), "w") as f:
+                json.dump({"from": i, "to": sh["x"], "y": ["%064x" % v for v in sh["y"]], "y_blind": ["%064x" % v for v in sh["y_blind"]]}, f)
+    except (OSError, ValueError, lib.SppError) as e:
+        print("spp dkg-deal: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    print("dkg-deal: %s (%s, threshold %d of %d) and %d sub-shares in %s" % (deal_path, deal["kind"], t, m, m, private))
+    print("publish first: %s" % digest)
+    return 0
+
+
+def _dkg_fail(dealer, check_name, detail):
+    print("spp dkg-receive: dealer %d: %s check failed%s" % (dealer, check_name, ": " + detail if detail else ""), file=sys.stderr)
+    return 1
+
+
+def _dkg_receive(a):
+    import hashlib
+    from . import witness
+    j, n = a.index, witness.RLWE_N
+    if len(a.hashes) != len(a.deals):
+        print("spp dkg-receive: one --hashes file per --deals file, in the same order", file=sys.stderr)
+        return 2
+    try:   # everything that can be wrong with the files is found before a device is opened
+        raw = [open(p, "rb").read() for p in a.deals]
+        published = [open(p).read().split()[0].lower() for p in a.hashes]
+        subs = [json.load(open(p)) for p in a.subshares]
+        old = witness.load_share_json(a.refresh) if a.refresh else None
+    except (OSError, ValueError, IndexError) as e:
+        print("spp dkg-receive: %s" % e, file=sys.stderr)
+        return 2
+    deals = {}
+    for path, body, want in zip(a.deals, raw, published):
+        try:
+            d = json.loads(body)
+            idx, kind, t, m = int(d["index"]), d["kind"], int(d["threshold"]), int(d["num_shares"])
+            if int(d["version"]) != 1 or kind not in ("key", "refresh"):
+                raise ValueError("version %r, kind %r" % (d["version"], kind))
+            entry = {"kind": kind, "t": t, "m": m, "a_seed": _hex_seed(d["a_seed"]), "commitments": bytes.fromhex(d["commitments"])}
+            if kind == "key":
+                entry["b"] = [int(v, 16) for v in d["b"]]
+                if len(entry["b"]) != n or not all(0 <= v < witness.RLWE_Q for v in entry["b"]):
+                    raise ValueError("b is 1024 coefficients in [0, q)")
+            else:
+                entry["zero_blinds"] = [int(v, 16) for v in d["zero_blinds"]]
+                if len(entry["zero_blinds"]) != n:
+                    raise ValueError("zero_blinds is 1024 field elements")
+        except (KeyError, TypeError, ValueError) as e:
+            print("spp dkg-receive: %s: not a deal file (%s)" % (path, e), file=sys.stderr)
+            return 2
+        if hashlib.sha256(body).hexdigest() != want:
+            return _dkg_fail(idx, "hash", "%s is not the file whose SHA-256 was published" % path)
+        if idx in deals:
+            return _dkg_fail(idx, "missing", "dealt twice")
+        deals[idx] = entry
+    first = deals[min(deals)] if deals else None
+    if first is None:
+        print("spp dkg-receive: no deal files", file=sys.stderr)
+        return 2
+    t, m, kind = first["t"], first["m"], first["kind"]
+    msg = _dkg_refuses_size("dkg-receive", t, m)
+    if msg is None and not 1 <= j <= m:
+        msg = "spp dkg-receive: --index is one of the auditors 1..%d" % m
+    if msg is None and (kind == "refresh") != (old is not None):
+        msg = "spp dkg-receive: these are %s dealings: %s" % (kind, "give --refresh share_%d.json" % j if old is None else "--refresh takes refresh dealings")
+    if msg is None and old is not None and old["x"] != j:
+        msg = "spp dkg-receive: %s is the share at x = %d, not auditor %d's" % (a.refresh, old["x"], j)
+    if msg:
+        print(msg, file=sys.stderr)
+        return 2
+    for i in range(1, m + 1):
+        if i not in deals:
+            return _dkg_fail(i, "missing", "no deal file of this dealer among --deals")
+        for key, what in (("t", "threshold"), ("m", "num_shares"), ("a_seed", "a_seed"), ("kind", "kind")):
+            if deals[i][key] != first[key]:
+                return _dkg_fail(i, "agreement", "its %s differs from dealer %d's" % (what, min(deals)))
+        if len(deals[i]["commitments"]) != t * n * 64:
+            return _dkg_fail(i, "point", "%d commitment bytes, not %d" % (len(deals[i]["commitments"]), t * n * 64))
+    if len(deals) != m:
+        return _dkg_fail(max(deals), "missing", "not one of the auditors 1..%d" % m)
+    ys, yb = {}, {}
+    for path, sub in zip(a.subshares, subs):
+        try:
+            src, dst = int(sub["from"]), int(sub["to"])
+            y, b = [int(v, 16) for v in sub["y"]], [int(v, 16) for v in sub["y_blind"]]
+        except (KeyError, TypeError, ValueError) as e:
+            print("spp dkg-receive: %s: not a sub-share file (%s)" % (path, e), file=sys.stderr)
+            return 2
+        if dst != j or src in ys or len(y) != n or len(b) != n:
+            print("spp dkg-receive: %s: need one sub-share of 1024 values per dealer, addressed to auditor %d" % (path, j), file=sys.stderr)
+            return 2
+        ys[src], yb[src] = y, b
+    for i in range(1, m + 1):
+        if i not in ys:
+            return _dkg_fail(i, "missing", "no sub-share of this dealer among --subshares")
+        for row in (ys[i], yb[i]):
+            for v, val in enumerate(row):
+                if not 0 <= val < R:
+                    return _dkg_fail(i, "share", "value %d is no field element" % v)
+        if kind == "refresh":
+            for v, val in enumerate(deals[i]["zero_blinds"]):
+                if not 0 <= val < R:
+                    return _dkg_fail(i, "not-zero", "published blind %d is no field element" % v)
+    order = list(range(1, m + 1))
+    ctx = Context(a.device)
+    try:
+        flags, bad, share = witness.vss_receive(ctx, t, j, [deals[i]["commitments"] for i in order], [ys[i] for i in order], [yb[i] for i in order],
+                                                zero_blinds=[deals[i]["zero_blinds"] for i in order] if kind == "refresh" else None,
+                                                base=old["y"] if old is not None else None)
+    except lib.SppError as e:
+        print("spp dkg-receive: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    if bad:
+        for i, row in zip(order, flags):
+            for v, fl in enumerate(row):
+                if fl:
+                    name = next(nm for bit, nm in witness.VSS_FLAG_NAMES if fl & bit)
+                    return _dkg_fail(i, name, "value %d (%d values refused in all)" % (v, bad))
+    shares_dir = os.path.join(a.out, "rlwe_sk_shares")
+    share_path = os.path.join(shares_dir, "share_%d.json" % j)
+    try:
+        os.makedirs(shares_dir, exist_ok=True)
+        if kind == "key":
+            pk_b = [sum(deals[i]["b"][v] for i in order) % witness.RLWE_Q for v in range(n)]
+            witness.write_rlwe_pk_json(os.path.join(a.out, "rlwe_pk.json"), witness.dkg_a_from_seed(lib.load_library(), first["a_seed"]), pk_b)
+            witness.write_rlwe_params_json(os.path.join(a.out, "rlwe_params.json"), t, m, witness.NOISE_BOUND * m)
+        witness.write_share_json(share_path, j, t, m, j, share)
+    except (OSError, ValueError, lib.SppError) as e:
+        print("spp dkg-receive: %s" % e, file=sys.stderr)
+        return 2
+    print("dkg-receive: %d dealers, every hash and all %d values of each accepted; %s%s"
+          % (m, n, "refreshed " if kind == "refresh" else "rlwe_pk.json, rlwe_params.json and ", share_path))
+    return 0
 
 
 _POOL_FIELDS = {"deposit": (("root", 32),), "submit_audit": (("proof", lib.PROOF_LEN), ("pw", lib.AUDIT_PW_LEN)),
@@ -936,6 +1152,16 @@ def main(argv=None):
     kc.add_argument("--shares", nargs="+", required=True, metavar="SHARE.json", help="threshold many share files")
     kc.add_argument("--params", default=None, help="rlwe_params.json (default: next to the public key; without one the bound is 3)")
     kc.add_argument("--device", type=int, default=0)
+    dd = sub.add_parser("dkg-deal"); dd.add_argument("--index", type=int, required=True, metavar="I", help="this auditor, 1..M")
+    dd.add_argument("--threshold", type=int, required=True); dd.add_argument("--shares", type=int, required=True, metavar="M")
+    dd.add_argument("--a-seed", required=True, metavar="HEX32", help="the seed of the common a, agreed beforehand")
+    dd.add_argument("--out", required=True, metavar="DIR"); dd.add_argument("--refresh", action="store_true", help="deal zeros: renews shares, keeps the key")
+    dd.add_argument("--device", type=int, default=0)
+    dr = sub.add_parser("dkg-receive"); dr.add_argument("--index", type=int, required=True, metavar="J", help="this auditor, 1..M")
+    dr.add_argument("--deals", nargs="+", required=True, metavar="DEAL.json"); dr.add_argument("--hashes", nargs="+", required=True, metavar="DEAL.hash")
+    dr.add_argument("--subshares", nargs="+", required=True, metavar="SUBSHARE.json"); dr.add_argument("--out", required=True, metavar="DIR")
+    dr.add_argument("--refresh", default=None, metavar="SHARE.json", help="this auditor's current share: the dealings are refresh dealings")
+    dr.add_argument("--device", type=int, default=0)
     sc = sub.add_parser("setup-contribute"); sc.add_argument("pk"); sc.add_argument("vk")
     sc.add_argument("--out", required=True, metavar="DIR", help="<name>.pk, <name>.vk and <name>.receipt go here (not the key's own directory)")
     sc.add_argument("--entropy", default=None, metavar="HEX32", help="for reproducible tests only: the default draws from the operating system")
@@ -974,6 +1200,10 @@ def main(argv=None):
         return _setup_contribute(a)
     if a.cmd == "setup-verify":
         return _setup_verify(a)
+    if a.cmd == "dkg-deal":
+        return _dkg_deal(a)
+    if a.cmd == "dkg-receive":
+        return _dkg_receive(a)
     if a.cmd == "rlwe-keygen":
         return _rlwe_keygen(a)
     if a.cmd == "rlwe-key-check":

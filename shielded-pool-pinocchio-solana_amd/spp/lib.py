@@ -216,6 +216,12 @@ def load_library():
     L.spp_rlwe_keygen_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.spp_rlwe_key_check.argtypes = [vp, sz, vp, vp, vp, vp]
     L.spp_shamir_split.argtypes = [vp, u32, u32, vp, sz, cp, cp, vp]
+    # the auditors' key without a dealer (include/spp.h)
+    L.spp_vss_generators.argtypes = [vp, vp]
+    L.spp_dkg_a_from_seed.argtypes = [cp, vp]
+    L.spp_vss_deal.argtypes = [vp, u32, u32, vp, sz, cp, cp, cp, cp, vp, vp, vp, vp]
+    L.spp_vss_deal_timed.argtypes = [vp, u32, u32, vp, sz, cp, cp, cp, cp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
+    L.spp_vss_receive.argtypes = [vp, u32, u32, u32, sz, cp, cp, cp, cp, cp, vp, vp, ctypes.POINTER(sz)]
     # threshold opening (include/spp.h)
     L.spp_rlwe_sample_smudge.argtypes = [sz, u32, vp, vp]
     L.spp_rlwe_partial_decrypt_batch.argtypes = [vp, u32, vp, u32, cp, sz, vp, vp, vp, vp, cp, vp, vp]

@@ -22,6 +22,9 @@
     load_share_json(...)     scripts/rlwe_keygen.py:157-171 (keys/rlwe_sk_shares/share_<i>.json)
     rlwe_sample_key / rlwe_keygen / rlwe_key_check / shamir_split
                              scripts/rlwe_keygen.py:98-116 (the audit key pair) and :51-65 (shamir_share_field)
+    vss_generators / dkg_a_from_seed / vss_deal / vss_receive
+                             scripts/rlwe_keygen.py:51-65, 98-182 by the auditors together: every auditor deals its own part of
+                             the key with public commitments, nobody draws the whole (no counterpart in the reference)
     write_rlwe_pk_json / write_rlwe_params_json / write_share_json
                              scripts/rlwe_keygen.py:124-127, 133-142, 161-169: the files `cli compile --rlwe-pk` and
                              load_share_json read
@@ -875,3 +878,83 @@ def reference_key_draws(seed, threshold=2, n=RLWE_N):
         for k in range(threshold - 1):
             coeffs[k][i] = rng.randint(0, FR_MODULUS - 1)
     return sk, a, e, coeffs
+
+
+# ---- the auditors' key without a dealer: verifiable sharing, joint key, share refresh (include/spp.h) ----
+VSS_BAD_POINT, VSS_BAD_SHARE, VSS_NOT_ZERO = 1, 2, 4
+VSS_FLAG_NAMES = ((VSS_BAD_POINT, "point"), (VSS_BAD_SHARE, "share"), (VSS_NOT_ZERO, "not-zero"))
+
+
+def vss_generators(L):
+    """(G, H) of the Pedersen commitments as (x, y) pairs of ints (host only; L: the loaded library)"""
+    g, h = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+    check(L.spp_vss_generators(ctypes.cast(g, ctypes.c_void_p), ctypes.cast(h, ctypes.c_void_p)))
+    return tuple((int.from_bytes(b.raw[:32], "big"), int.from_bytes(b.raw[32:], "big")) for b in (g, h))
+
+
+def dkg_a_from_seed(L, seed):
+    """the common a of a joint key from the 32-byte seed the auditors agreed on (host only): 1024 ints in [0, q)"""
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed of a is 32 bytes")
+    out = (ctypes.c_uint32 * RLWE_N)()
+    check(L.spp_dkg_a_from_seed(seed, ctypes.cast(out, ctypes.c_void_p)))
+    return list(out)
+
+
+def vss_deal(ctx, secrets, threshold, num_shares, xs=None, blinds=None, coeffs=None, coeffs_blind=None, times=None):
+    """One dealer's verifiable sharing of a list of field elements.  xs, coeffs as in shamir_split; blinds: the constant-term blinds;
+    coeffs_blind: the blinding polynomial's higher coefficients; whatever is None the library draws from the operating system.
+    Returns {"commitments": bytes (C_k[v] at (k n + v) * 64), "shares": [{"x", "y", "y_blind"}] per receiver, "blinds": [int] * n}.
+    times (a list, optional) receives the device milliseconds of the two evaluations and of the commitment kernel."""
+    secrets = [int(v) for v in secrets]
+    n, t, m = len(secrets), int(threshold), int(num_shares)
+    if xs is not None and len(xs) != m:
+        raise ValueError("xs must name %d shares" % m)
+    for name, rows in (("coeffs", coeffs), ("coeffs_blind", coeffs_blind)):
+        if rows is not None and (len(rows) != t - 1 or any(len(row) != n for row in rows)):
+            raise ValueError("%s must be %d rows of %d field elements" % (name, t - 1, n))
+    if blinds is not None and len(blinds) != n:
+        raise ValueError("blinds must be %d field elements" % n)
+    cx = None if xs is None else (ctypes.c_uint32 * m)(*[int(x) for x in xs])
+    flat = lambda rows: None if rows is None else _be(v for row in rows for v in row)
+    ys, yb = (ctypes.create_string_buffer(max(1, m * n * 32)) for _ in range(2))
+    cm = ctypes.create_string_buffer(max(1, t * n * 64))
+    bo = ctypes.create_string_buffer(max(1, n * 32))
+    p = lambda b: ctypes.cast(b, ctypes.c_void_p)
+    args = (ctx.h, t, m, None if cx is None else p(cx), n, _be(secrets), None if blinds is None else _be(blinds), flat(coeffs),
+            flat(coeffs_blind), p(ys), p(yb), p(cm), p(bo))
+    if times is None:
+        check(ctx.L.spp_vss_deal(*args))
+    else:
+        ms = (ctypes.c_float * 2)()
+        check(ctx.L.spp_vss_deal_timed(*args, ms))
+        times[:] = [float(ms[0]), float(ms[1])]
+    y, b = _unbe(ys.raw, m * n), _unbe(yb.raw, m * n)
+    return {"commitments": cm.raw[:t * n * 64],
+            "shares": [{"x": int(xs[j]) if xs is not None else j + 1, "y": y[j * n:(j + 1) * n], "y_blind": b[j * n:(j + 1) * n]}
+                       for j in range(m)],
+            "blinds": _unbe(bo.raw, n)}
+
+
+def vss_receive(ctx, threshold, x, commitments, ys, ys_blind, zero_blinds=None, base=None, want_share=True):
+    """The receiver at x checks every dealer's values: commitments [bytes] per dealer, ys / ys_blind / zero_blinds [[int] * n] per
+    dealer.  Returns (flags [[int] * n] per dealer, bad, share): share = base (default 0) + the sum over dealers, None when a check
+    failed (or want_share is False)."""
+    dealers, n, t = len(commitments), len(ys[0]) if ys else 0, int(threshold)
+    if len(ys) != dealers or len(ys_blind) != dealers or (zero_blinds is not None and len(zero_blinds) != dealers):
+        raise ValueError("one commitment string, one y row and one y_blind row per dealer")
+    if any(len(c) != t * n * 64 for c in commitments) or any(len(r) != n for r in list(ys) + list(ys_blind) + list(zero_blinds or [])):
+        raise ValueError("a dealing of %d values at threshold %d is %d commitment bytes and %d sub-shares" % (n, t, t * n * 64, n))
+    if base is not None and len(base) != n:
+        raise ValueError("base must be %d field elements" % n)
+    flat = lambda rows: _be(v for row in rows for v in row)
+    flags = (ctypes.c_uint32 * max(1, dealers * n))()
+    out = ctypes.create_string_buffer(max(1, n * 32))
+    bad = ctypes.c_size_t(0)
+    check(ctx.L.spp_vss_receive(ctx.h, t, int(x), dealers, n, b"".join(commitments), flat(ys), flat(ys_blind),
+                                None if zero_blinds is None else flat(zero_blinds), None if base is None else _be(base),
+                                ctypes.cast(flags, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p) if want_share else None,
+                                ctypes.byref(bad)))
+    fl = [list(flags[d * n:(d + 1) * n]) for d in range(dealers)]
+    return fl, int(bad.value), (_unbe(out.raw, n) if want_share and bad.value == 0 else None)
