@@ -27,6 +27,8 @@
  *   spp_vss_deal              scripts/rlwe_keygen.py:51-65 (shamir_share_field) by every auditor for its own part of the key, with
  *                             public commitments (no counterpart in the reference, whose :98-182 draw and share the key in one place)
  *   spp_vss_receive           the check of those commitments and the sum that is a share file of :157-171
+ *   spp_vss_combine_commitments / spp_vss_share_commitments / spp_vss_reshare_receive
+ *                             the committee's commitments and handing the key to a new committee (no counterpart in the reference)
  *   spp_prove_audit_records   scripts/generate_audit.py:468-691 with the ciphertext.json of :590-606: the audit RECORD
  *                             (proof, public witness, ciphertext) from the prover's raw secrets
  *   spp_audit_open_batch      scripts/rlwe_decrypt.py:61-149 for a batch of such records, after `sunspot verify`
@@ -505,6 +507,48 @@ int spp_vss_deal_timed(spp_ctx* ctx, uint32_t t, uint32_t m, const uint32_t* xs,
 int spp_vss_receive(spp_ctx* ctx, uint32_t t, uint32_t x, uint32_t dealers, size_t n, const uint8_t* commitments, const uint8_t* ys,
                     const uint8_t* ys_blind, const uint8_t* zero_blinds, const uint8_t* base_be, uint32_t* flags, uint8_t* share_out,
                     size_t* bad);
+
+/* ---- the committee's commitments, and handing the key to a new committee (verifiable resharing) ----
+ * The Pedersen commitments of the dealings are public, and their sums D_k[v] = sum_i C_{i,k}[v], k < t, commit to the ONE polynomial
+ * whose value at 0 is the key coefficient sk[v] and whose value at x_j is auditor j's share.  A refresh round adds its dealers'
+ * commitments to D: D_0[v] then commits to the same sk[v] under another blind.  E_x[v] = sum_k x^k D_k[v] is the public commitment of the share at x:
+ * share_j[v] G + blind_j[v] H == E_{x_j}[v], where blind_j is the sum of every y_blind auditor j was ever dealt.  A member checks
+ * its own (share, blind) against the committee with spp_vss_receive itself, called with dealers = 1, commitments = D, x = x_j: no
+ * other call is needed for that.
+ * Resharing from a set S of exactly t old members to a new committee (t', m'): member j of S deals secret = share_j, blinds =
+ * blind_j at threshold t' with spp_vss_deal (blinds_be), not scaled by anything, so its C'_{j,0}[v] is exactly E_{x_j}[v].  The
+ * new member at x' checks each sub-share against C'_j (as spp_vss_receive does), checks C'_{j,0} == E_{x_j} (SPP_VSS_NOT_SHARE), and
+ * takes share' = sum_{j in S} lambda_j y_j mod r, the blind alike, lambda_j the Lagrange coefficient at 0 of x_j in S; the new
+ * committee's commitments are D'_k[v] = sum_{j in S} lambda_j C'_{j,k}[v], k < t', with D'_0 == D_0: the key stays, nobody held it,
+ * and old and new shares do not combine.
+ * Refusals as in the block above (SPP_ERR_BAD_INPUT before any device work, the index named in spp_last_error()): NULL pointers,
+ * a threshold of 0 or above 64, dealers == 0 or > 255 (> 64 with weights), count == 0 or > 255, an index equal to 0 or repeated,
+ * a weight or a sub-share >= r, n > 2^20, and a base or a committee entry that is no point (they are the caller's own earlier
+ * outputs).  n == 0 is SPP_OK.  Synchronous and serialised on the context; device buffers that held sub-shares, blinds, the new
+ * share or the new blind are zeroed before they are freed. */
+#define SPP_VSS_NOT_SHARE 8   /* reshare: an old member's C'_0 is not its public share commitment E_x */
+/* out_k[v] = base_k[v] + sum_d w_d C_{d,k}[v].
+ * commitments: dealers*t*n*64, dealer after dealer;  weights_be: dealers*32 canonical, or NULL (every weight 1; dealers <= 255)
+ * base (optional), out: t*n*64
+ * flags: dealers*t*n, SPP_VSS_BAD_POINT for every input that is no point, always written; *bad = number of non-zero flags
+ * out is written only when *bad == 0 */
+int spp_vss_combine_commitments(spp_ctx* ctx, uint32_t t, uint32_t dealers, size_t n, const uint8_t* commitments, const uint8_t* weights_be,
+                                const uint8_t* base, uint8_t* out, uint32_t* flags, size_t* bad);
+/* The same; kernel_ms (optional) receives the device time of the kernels (decoding the points, the sum), in milliseconds */
+int spp_vss_combine_commitments_timed(spp_ctx* ctx, uint32_t t, uint32_t dealers, size_t n, const uint8_t* commitments,
+                                      const uint8_t* weights_be, const uint8_t* base, uint8_t* out, uint32_t* flags, size_t* bad,
+                                      float* kernel_ms);
+/* out[(i*n + v)*64 ..] = sum_k xs[i]^k D_k[v];  committee: t*n*64;  xs: count <= 255 non-zero distinct indices */
+int spp_vss_share_commitments(spp_ctx* ctx, uint32_t t, size_t n, const uint8_t* committee, uint32_t count, const uint32_t* xs,
+                              uint8_t* out);
+/* The new member at x_new.
+ * xs_old: the set S, t_old indices;  committee: the old committee's D, t_old*n*64
+ * commitments: t_old * t_new*n*64, the dealings of the members of S in xs_old order;  ys, ys_blind: t_old*n*32, in that order
+ * flags: t_old*n, SPP_VSS_BAD_POINT (alone) / SPP_VSS_BAD_SHARE / SPP_VSS_NOT_SHARE, always written; *bad = number of non-zero flags
+ * share_out, blind_out (n*32) and committee_out (t_new*n*64) are written only when *bad == 0 */
+int spp_vss_reshare_receive(spp_ctx* ctx, uint32_t t_old, const uint32_t* xs_old, uint32_t t_new, uint32_t x_new, size_t n,
+                            const uint8_t* committee, const uint8_t* commitments, const uint8_t* ys, const uint8_t* ys_blind, uint32_t* flags,
+                            uint8_t* share_out, uint8_t* blind_out, uint8_t* committee_out, size_t* bad);
 
 /* Opening audit records in one pass: what an auditor replaying submit_audit logs asks of every record (proof, public witness,
  * ciphertext) -- does the proof verify, is this the ciphertext the proof committed to, is the decrypted identity the one the

@@ -165,6 +165,21 @@ void launch_vss_commit(hipStream_t st, const G1Affine* table, const uint8_t* sec
 void launch_vss_check(hipStream_t st, const G1Affine* table, uint32_t t, uint32_t x, uint32_t dealers, uint32_t n, const uint8_t* commitments,
                       const uint8_t* ys_be, const uint8_t* ys_blind_be, const uint8_t* zero_blinds_be, uint32_t* flags);
 void launch_vss_sum(hipStream_t st, const uint8_t* base_be, const uint8_t* ys_be, uint32_t dealers, uint32_t n, uint8_t* out_be);
+// the committee's commitments and resharing (vss.hpp, last section)
+//   launch_vss_decode         points[i], flags[i] (SPP_VSS_BAD_POINT or 0) from raw[i * 64 ..], i < count
+//   launch_vss_lincomb        out[i] = base[i] (optional) + sum_d w_d points[d * count + i], i < count = t n; weights dealers * 8
+//                             canonical words, the same for every lane, or nullptr: plain sums
+//   launch_vss_share_commit   out[(i n + v) 64 ..] = sum_k xs[i]^k committee[(k n + v) 64 ..], i < count
+//   launch_vss_reshare_check  flags t_old * n: vss_check_value at (t_new, x_new) of each old member's dealing | SPP_VSS_NOT_SHARE
+//   launch_vss_weighted_sum   out[v] = sum_d weights[d] ys[d][v]
+void launch_vss_decode(hipStream_t st, const uint8_t* raw, size_t count, G1Affine* points, uint32_t* flags);
+void launch_vss_lincomb(hipStream_t st, uint32_t dealers, const uint32_t* weights, const G1Affine* points, const G1Affine* base, uint32_t count,
+                        uint8_t* out);
+void launch_vss_share_commit(hipStream_t st, uint32_t t, const uint32_t* xs, uint32_t count, uint32_t n, const uint8_t* committee, uint8_t* out);
+void launch_vss_reshare_check(hipStream_t st, const G1Affine* table, uint32_t t_old, const uint32_t* xs_old, uint32_t t_new, uint32_t x_new,
+                              uint32_t n, const uint8_t* committee, const uint8_t* commitments, const uint8_t* ys_be, const uint8_t* ys_blind_be,
+                              uint32_t* flags);
+void launch_vss_weighted_sum(hipStream_t st, const Fr* weights, const uint8_t* ys_be, uint32_t dealers, uint32_t n, uint8_t* out_be);
 // one wave per 64 audit records (audit_open.hpp): owners count * 64 B, flags[i] = SPP_AUDIT_* bits; proof_ok (optional): the verdicts
 // of launch_verify for the same records, enqueued before on `st`
 void launch_audit_open(hipStream_t st, HashConsts hc, const uint32_t* sk_mod_q, const uint32_t* c0, const uint32_t* c1, const uint8_t* pws,

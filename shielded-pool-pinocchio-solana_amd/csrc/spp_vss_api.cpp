@@ -179,3 +179,186 @@ extern "C" int spp_vss_receive(spp_ctx* ctx, uint32_t t, uint32_t x, uint32_t de
   HIP_TRY(hipGetLastError());
   return SPP_OK;
 }
+
+// ---- the committee's commitments, and handing the key to a new committee (include/spp.h, the block after spp_vss_receive) ----
+namespace {
+int check_threshold(const char* what, uint32_t t) {
+  if (t == 0 || t > 64) return fail(SPP_ERR_BAD_INPUT, "%s %u is not in [1, 64]", what, t);
+  return SPP_OK;
+}
+int check_indices(const char* what, const uint32_t* xs, uint32_t count) {
+  for (uint32_t j = 0; j < count; j++) {
+    if (xs[j] == 0) return fail(SPP_ERR_BAD_INPUT, "%s[%u] is 0: that share would be the secret", what, j);
+    for (uint32_t k = 0; k < j; k++)
+      if (xs[k] == xs[j]) return fail(SPP_ERR_BAD_INPUT, "%s[%u] repeats %s[%u] = %u", what, j, what, k, xs[j]);
+  }
+  return SPP_OK;
+}
+// the caller's own earlier output (a base, a committee file): every entry a point, checked on the host before any device work
+int check_points(const char* what, const uint8_t* raw, size_t count) {
+  G1Affine p;
+  for (size_t i = 0; i < count; i++)
+    if (sc_decode_point(raw + 64 * i, &p) == SC_POINT_BAD) return fail(SPP_ERR_BAD_INPUT, "%s %zu is not a curve point", what, i);
+  return SPP_OK;
+}
+// weights as the scan reads them: 8 canonical words each, least significant first
+void weight_words(const Fr* w, uint32_t count, std::vector<uint32_t>& out) {
+  out.resize((size_t)8 * count);
+  for (uint32_t d = 0; d < count; d++) w[d].to_canonical(out.data() + 8 * d);
+}
+}  // namespace
+
+extern "C" int spp_vss_combine_commitments_timed(spp_ctx* ctx, uint32_t t, uint32_t dealers, size_t n, const uint8_t* commitments,
+                                                 const uint8_t* weights_be, const uint8_t* base, uint8_t* out, uint32_t* flags, size_t* bad,
+                                                 float* kernel_ms) {
+  if (!ctx || !commitments || !out || !flags || !bad) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int rc = check_threshold("threshold", t)) return rc;
+  if (dealers == 0 || dealers > 255) return fail(SPP_ERR_BAD_INPUT, "%u dealers: need between 1 and 255", dealers);
+  if (weights_be && dealers > VSS_LINCOMB_MAX) return fail(SPP_ERR_BAD_INPUT, "%u dealers: a weighted sum takes at most %u", dealers, VSS_LINCOMB_MAX);
+  if (n > VSS_MAX_VALUES) return fail(SPP_ERR_BAD_INPUT, "n %zu: at most 2^20 values in one call", n);
+  if (kernel_ms) *kernel_ms = 0;
+  if (n == 0) {
+    *bad = 0;
+    return SPP_OK;
+  }
+  const size_t count = (size_t)t * n, inputs = count * dealers;
+  std::vector<uint32_t> words;
+  if (weights_be) {
+    if (int rc = check_elements("weight", weights_be, dealers)) return rc;
+    std::vector<Fr> w(dealers);
+    for (uint32_t d = 0; d < dealers; d++) w[d] = Fr::from_bytes_be(weights_be + 32 * d);
+    weight_words(w.data(), dealers, words);
+  }
+  if (base)
+    if (int rc = check_points("base point", base, count)) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
+  } ev;
+  if (kernel_ms)
+    for (hipEvent_t& v : ev.e) HIP_TRY(hipEventCreate(&v));
+  DevBuf draw, dpts, df, dw, dbraw, dbase, dbf, dout;
+  UP(draw, commitments, inputs * 64);
+  HIP_TRY(dpts.alloc(inputs * sizeof(G1Affine)));
+  HIP_TRY(df.alloc(inputs * 4));
+  if (weights_be) UP(dw, words.data(), words.size() * 4);
+  if (base) {
+    UP(dbraw, base, count * 64);
+    HIP_TRY(dbase.alloc(count * sizeof(G1Affine)));
+    HIP_TRY(dbf.alloc(count * 4));
+  }
+  HIP_TRY(dout.alloc(count * 64));
+  if (kernel_ms) HIP_TRY(hipEventRecord(ev.e[0], st));
+  launch_vss_decode(st, draw.as<uint8_t>(), inputs, dpts.as<G1Affine>(), df.as<uint32_t>());
+  if (base) launch_vss_decode(st, dbraw.as<uint8_t>(), count, dbase.as<G1Affine>(), dbf.as<uint32_t>());
+  // a non-point decodes as infinity: the sum below is then of no use, is computed all the same and is not copied out
+  launch_vss_lincomb(st, dealers, weights_be ? dw.as<uint32_t>() : nullptr, dpts.as<G1Affine>(), base ? dbase.as<G1Affine>() : nullptr,
+                     (uint32_t)count, dout.as<uint8_t>());
+  if (kernel_ms) HIP_TRY(hipEventRecord(ev.e[1], st));
+  HIP_TRY(hipMemcpyAsync(flags, df.p, inputs * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.e[0], ev.e[1]));
+  size_t nbad = 0;
+  for (size_t i = 0; i < inputs; i++) nbad += flags[i] != 0;
+  *bad = nbad;
+  if (nbad) return SPP_OK;
+  HIP_TRY(hipMemcpyAsync(out, dout.p, count * 64, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SPP_OK;
+}
+extern "C" int spp_vss_combine_commitments(spp_ctx* ctx, uint32_t t, uint32_t dealers, size_t n, const uint8_t* commitments,
+                                           const uint8_t* weights_be, const uint8_t* base, uint8_t* out, uint32_t* flags, size_t* bad) {
+  return spp_vss_combine_commitments_timed(ctx, t, dealers, n, commitments, weights_be, base, out, flags, bad, nullptr);
+}
+
+extern "C" int spp_vss_share_commitments(spp_ctx* ctx, uint32_t t, size_t n, const uint8_t* committee, uint32_t count, const uint32_t* xs,
+                                         uint8_t* out) {
+  if (!ctx || !committee || !xs || !out) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int rc = check_threshold("threshold", t)) return rc;
+  if (count == 0 || count > 255) return fail(SPP_ERR_BAD_INPUT, "%u indices: need between 1 and 255", count);
+  if (int rc = check_indices("xs", xs, count)) return rc;
+  if (n > VSS_MAX_VALUES) return fail(SPP_ERR_BAD_INPUT, "n %zu: at most 2^20 values in one call", n);
+  if (n == 0) return SPP_OK;
+  if (int rc = check_points("committee commitment", committee, (size_t)t * n)) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf dcm, dx, dout;
+  UP(dcm, committee, (size_t)t * n * 64);
+  UP(dx, xs, (size_t)count * 4);
+  HIP_TRY(dout.alloc((size_t)count * n * 64));
+  launch_vss_share_commit(st, t, dx.as<uint32_t>(), count, (uint32_t)n, dcm.as<uint8_t>(), dout.as<uint8_t>());
+  HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)count * n * 64, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}
+
+extern "C" int spp_vss_reshare_receive(spp_ctx* ctx, uint32_t t_old, const uint32_t* xs_old, uint32_t t_new, uint32_t x_new, size_t n,
+                                       const uint8_t* committee, const uint8_t* commitments, const uint8_t* ys, const uint8_t* ys_blind,
+                                       uint32_t* flags, uint8_t* share_out, uint8_t* blind_out, uint8_t* committee_out, size_t* bad) {
+  if (!ctx || !xs_old || !committee || !commitments || !ys || !ys_blind || !flags || !share_out || !blind_out || !committee_out || !bad)
+    return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int rc = check_threshold("old threshold", t_old)) return rc;
+  if (int rc = check_threshold("new threshold", t_new)) return rc;
+  if (x_new == 0) return fail(SPP_ERR_BAD_INPUT, "x_new is 0: that share would be the secret");
+  if (int rc = check_indices("xs_old", xs_old, t_old)) return rc;
+  if (n > VSS_MAX_VALUES) return fail(SPP_ERR_BAD_INPUT, "n %zu: at most 2^20 values in one call", n);
+  if (n == 0) {
+    *bad = 0;
+    return SPP_OK;
+  }
+  const size_t lanes = (size_t)t_old * n, count = (size_t)t_new * n, inputs = count * t_old;
+  if (int rc = check_elements("sub-share", ys, lanes)) return rc;
+  if (int rc = check_elements("sub-share blind", ys_blind, lanes)) return rc;
+  if (int rc = check_points("committee commitment", committee, lanes)) return rc;
+  std::vector<Fr> lambda(t_old);
+  vss_lagrange_at_zero(xs_old, t_old, lambda.data());
+  std::vector<uint32_t> words;
+  weight_words(lambda.data(), t_old, words);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (int rc = ensure_vss_table(ctx)) return rc;
+  WipedDevBuf dy, dyb, dso, dbo;
+  DevBuf dold, dcm, dx, df, dl, dw, dpts, dpf, dout;
+  UP(dold, committee, lanes * 64);
+  UP(dcm, commitments, inputs * 64);
+  UP(dx, xs_old, (size_t)t_old * 4);
+  UP_SECRET(dy, ys, lanes * 32);
+  UP_SECRET(dyb, ys_blind, lanes * 32);
+  HIP_TRY(df.alloc(lanes * 4));
+  launch_vss_reshare_check(st, ctx->vss_table, t_old, dx.as<uint32_t>(), t_new, x_new, (uint32_t)n, dold.as<uint8_t>(), dcm.as<uint8_t>(),
+                           dy.as<uint8_t>(), dyb.as<uint8_t>(), df.as<uint32_t>());
+  HIP_TRY(hipMemcpyAsync(flags, df.p, lanes * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  size_t nbad = 0;
+  for (size_t i = 0; i < lanes; i++) nbad += flags[i] != 0;
+  *bad = nbad;
+  if (nbad) return SPP_OK;
+  // every check passed: the new share and blind (Lagrange-weighted sums of the sub-shares), the new committee's commitments
+  UP(dl, lambda.data(), sizeof(Fr) * t_old);
+  UP(dw, words.data(), words.size() * 4);
+  dso.bytes = dbo.bytes = n * 32;
+  dso.st = dbo.st = st;
+  HIP_TRY(dso.alloc(n * 32));
+  HIP_TRY(dbo.alloc(n * 32));
+  HIP_TRY(dpts.alloc(inputs * sizeof(G1Affine)));
+  HIP_TRY(dpf.alloc(inputs * 4));
+  HIP_TRY(dout.alloc(count * 64));
+  launch_vss_weighted_sum(st, dl.as<Fr>(), dy.as<uint8_t>(), t_old, (uint32_t)n, dso.as<uint8_t>());
+  launch_vss_weighted_sum(st, dl.as<Fr>(), dyb.as<uint8_t>(), t_old, (uint32_t)n, dbo.as<uint8_t>());
+  launch_vss_decode(st, dcm.as<uint8_t>(), inputs, dpts.as<G1Affine>(), dpf.as<uint32_t>());   // points all: the check above read every one
+  launch_vss_lincomb(st, t_old, dw.as<uint32_t>(), dpts.as<G1Affine>(), nullptr, (uint32_t)count, dout.as<uint8_t>());
+  HIP_TRY(hipMemcpyAsync(share_out, dso.p, n * 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(blind_out, dbo.p, n * 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(committee_out, dout.p, count * 64, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  return SPP_OK;
+}

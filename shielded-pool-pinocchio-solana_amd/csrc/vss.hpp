@@ -20,7 +20,10 @@
 //
 // The table is indexed by bytes of secret scalars, so the addresses a dealing reads depend on them.
 //
-// Host and device: everything below is SPP_HD or plain C++, so that tests/host/vss_check.cpp pins it against big integers.
+// The last section is the committee's view of the same commitments and the hand-over of the key to a new committee.
+//
+// Host and device: everything below is SPP_HD or plain C++, so that tests/host/vss_check.cpp and tests/host/reshare_check.cpp pin
+// it against big integers.
 #pragma once
 #include <string.h>
 #include "bn254.hpp"
@@ -168,8 +171,9 @@ SPP_HD G1XYZZ vss_mul_small(const G1XYZZ& p, uint32_t x, uint32_t xbits) {
 // commitments: C_k of this value at commitments + k * stride (64 B each), k < t; y_be, yb_be: the sub-share and its blind;
 // zero_be: the published constant-term blind of a refresh, or nullptr.  Returns the VSS_FLAG_* bits; a commitment that is no
 // point ends the check (VSS_FLAG_BAD_POINT alone).
-SPP_HD uint32_t vss_check_value(const G1Affine* table, uint32_t t, uint32_t x, const uint8_t* commitments, size_t stride, const uint8_t* y_be,
-                                const uint8_t* yb_be, const uint8_t* zero_be) {
+// The Horner walk both the receiver's check and the share commitments use: *acc = sum_k x^k C_k, *c0 = C_0; false (and nothing
+// more read) at the first commitment that is no point.
+SPP_HD bool vss_eval_commitments(uint32_t t, uint32_t x, const uint8_t* commitments, size_t stride, G1XYZZ* acc_out, G1Affine* c0) {
   const uint32_t xbits = vss_bit_length(x);
   G1XYZZ acc = G1XYZZ::infinity();
   G1Affine c;
@@ -177,10 +181,19 @@ SPP_HD uint32_t vss_check_value(const G1Affine* table, uint32_t t, uint32_t x, c
 #pragma unroll 1
 #endif
   for (uint32_t k = t; k-- > 0;) {
-    if (sc_decode_point(commitments + (size_t)k * stride, &c) == SC_POINT_BAD) return VSS_FLAG_BAD_POINT;
+    if (sc_decode_point(commitments + (size_t)k * stride, &c) == SC_POINT_BAD) return false;
     if (!acc.is_inf()) acc = vss_mul_small(acc, x, xbits);
     acc.madd(c);
   }
+  *acc_out = acc;
+  *c0 = c;
+  return true;
+}
+SPP_HD uint32_t vss_check_value(const G1Affine* table, uint32_t t, uint32_t x, const uint8_t* commitments, size_t stride, const uint8_t* y_be,
+                                const uint8_t* yb_be, const uint8_t* zero_be) {
+  G1XYZZ acc;
+  G1Affine c;
+  if (!vss_eval_commitments(t, x, commitments, stride, &acc, &c)) return VSS_FLAG_BAD_POINT;
   uint32_t flags = 0;
   if (!vss_same_point(vss_commit(table, y_be, yb_be), acc)) flags |= VSS_FLAG_BAD_SHARE;
   if (zero_be) {   // c holds C_0
@@ -189,6 +202,84 @@ SPP_HD uint32_t vss_check_value(const G1Affine* table, uint32_t t, uint32_t x, c
     if (!vss_same_point(zh, G1XYZZ::from_affine(c))) flags |= VSS_FLAG_NOT_ZERO;
   }
   return flags;
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
+// the committee's commitments, and handing the key to a new committee
+// ----------------------------------------------------------------------------------------------------------------------
+// D_k[v] = sum_i C_{i,k}[v] commits to coefficient k of the ONE polynomial whose value at 0 is the key and at x_j auditor j's
+// share; E_x[v] = sum_k x^k D_k[v] (vss_eval_commitments) is what share_j G + blind_j H must equal.  A member j of a set S of t old
+// members deals (share_j, blind_j) to the new committee, so its C'_{j,0} is E_{x_j}; the new committee's commitments are
+// D'_k[v] = sum_{j in S} lambda_j C'_{j,k}[v] with lambda_j the Lagrange coefficient at 0 of x_j in S.
+//
+// That last sum is the only one here with full-size scalars on variable points, and its scalars are the same for every output
+// point: the weight of dealer d does not depend on (k, v).  So the lanes of a wave share ONE MSB-first scan over the 254 bits:
+// one doubling per bit, and for each dealer whose bit is set one mixed addition of the lane's own point of that dealer.  The
+// weights are read through a pointer that is the same in every lane (scalar loads), every branch on a bit is the wave's, and
+// nothing diverges but the equal / opposite / infinity branches inside madd.  pt_mul_each per dealer would pay the 254 doublings
+// `dealers` times over, and a general addition per dealer on top.  weights == nullptr is the sum itself (the committee of a key
+// or of a refresh round): `dealers` mixed additions and no scan.  A weight of 0 has no bit set and adds nothing.
+static constexpr uint32_t VSS_FLAG_NOT_SHARE = 8;   // SPP_VSS_NOT_SHARE
+static constexpr uint32_t VSS_LINCOMB_MAX = 64;      // dealers of a weighted sum
+
+// raw[64] -> Montgomery form for the sums below; SPP_VSS_BAD_POINT (and infinity in *out) when it is no point, else 0
+SPP_HD uint32_t vss_decode(const uint8_t raw[64], G1Affine* out) {
+  return sc_decode_point(raw, out) == SC_POINT_BAD ? VSS_FLAG_BAD_POINT : 0u;
+}
+// base (optional) + sum_d w_d points[d * stride]; weights: dealers * 8 canonical words, least significant first, or nullptr (all 1)
+SPP_HD G1XYZZ vss_lincomb(uint32_t dealers, const uint32_t* weights, const G1Affine* points, size_t stride, const G1Affine* base) {
+  G1XYZZ acc = G1XYZZ::infinity();
+  if (weights) {
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (uint32_t b = 254; b-- > 0;) {   // r < 2^254
+      acc.dbl_inplace();
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+      for (uint32_t d = 0; d < dealers; d++)
+        if ((weights[8u * d + (b >> 5)] >> (b & 31u)) & 1u) acc.madd(points[(size_t)d * stride]);
+    }
+  } else {
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (uint32_t d = 0; d < dealers; d++) acc.madd(points[(size_t)d * stride]);
+  }
+  if (base) acc.madd(*base);
+  return acc;
+}
+// the new member's extra check of old member x_old's dealing: is its constant term C'_0 (c0_raw) the public share commitment
+// E_{x_old} under the old committee's commitments?  0 or VSS_FLAG_NOT_SHARE; a committee entry or a C'_0 that is no point: BAD_POINT
+SPP_HD uint32_t vss_is_share(uint32_t t_old, uint32_t x_old, const uint8_t* committee, size_t stride, const uint8_t* c0_raw) {
+  G1XYZZ e;
+  G1Affine d0, c0;
+  if (!vss_eval_commitments(t_old, x_old, committee, stride, &e, &d0)) return VSS_FLAG_BAD_POINT;
+  if (sc_decode_point(c0_raw, &c0) == SC_POINT_BAD) return VSS_FLAG_BAD_POINT;
+  return vss_same_point(e, G1XYZZ::from_affine(c0)) ? 0u : VSS_FLAG_NOT_SHARE;
+}
+// lambda_j = prod_{i != j} x_i / (x_i - x_j) for distinct non-zero xs (host only)
+inline void vss_lagrange_at_zero(const uint32_t* xs, uint32_t count, Fr* out) {
+  for (uint32_t j = 0; j < count; j++) {
+    Fr num = Fr::one(), den = Fr::one();
+    for (uint32_t i = 0; i < count; i++)
+      if (i != j) {
+        num = num * Fr::from_u64(xs[i]);
+        den = den * (Fr::from_u64(xs[i]) - Fr::from_u64(xs[j]));
+      }
+    out[j] = num * den.inv();
+  }
+}
+// out = sum_d w_d y_d mod r over big-endian values `stride` bytes apart
+SPP_HD void vss_weighted_sum(uint32_t dealers, const Fr* weights, const uint8_t* ys_be, size_t stride, uint8_t out_be[32]) {
+  uint8_t buf[32];
+  Fr acc = Fr::zero();
+  for (uint32_t d = 0; d < dealers; d++) {
+    for (int i = 0; i < 32; i++) buf[i] = ys_be[(size_t)d * stride + i];
+    acc = acc + weights[d] * Fr::from_bytes_be(buf);
+  }
+  acc.to_bytes_be(out_be);
 }
 
 }  // namespace spp

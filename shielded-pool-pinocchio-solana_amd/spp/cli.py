@@ -47,6 +47,22 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # DIR/rlwe_params.json and DIR/rlwe_sk_shares/share_<J>.json, the files of rlwe-keygen (--refresh: only
                               # the share, the old one plus the dealt zeros).  exit 1 names the first failing dealer, the check
                               # (hash, missing, agreement, point, share, not-zero) and the value; nothing is written then
+    python -m spp.cli dkg-committee --deals deal_1.json ... [--base committee.json] --out committee.json
+                              # the committee's commitments, the sums of the dealers' (no secrets): key dealings make the file,
+                              # refresh dealings are added to --base.  Checks what dkg-receive checks of the public files; exit 1
+                              # names the dealer and the value of a commitment that is no point
+    python -m spp.cli dkg-reshare-deal --share share_J.json (--blind blind_J.json | --subshares F...) --committee committee.json
+                              --set X1 .. Xt --new-threshold T --new-shares M --out DIR
+                              # old member J of the set deals its share to a new committee of M at threshold T (M <= 255: the key and
+                              # its noise stay, so dkg-deal's limit of 10 does not apply).  First checks (share, blind) against the
+                              # committee file on the GPU: exit 1 `share-mismatch`, nothing written.  Writes DIR/reshare_<J>.json
+                              # (public) and DIR/private/subshare_<J>_to_<K>.json
+    python -m spp.cli dkg-reshare-receive --index K --committee committee.json --deals reshare_*.json --subshares ... --out DIR
+                              # new member K checks every sub-share against its dealer's commitments and every dealer's constant
+                              # terms against the old committee file, on the GPU; then writes DIR/rlwe_sk_shares/share_<K>.json,
+                              # DIR/private/blind_<K>.json, DIR/committee.json and DIR/rlwe_params.json (rlwe_pk.json stays).  exit 1
+                              # names the first failing old member, the check (set, missing, agreement, point, share, not-share)
+                              # and the value; nothing is written then
     python -m spp.cli pool-replay withdraw.vk audit.vk log.jsonl [--capacity N] [--verifier each|rlc [--group N]]
                               # the pool program's decisions for a log of instructions, one JSON object per line, values in hex:
                               #   {"deposit": {"root"}}  {"submit_audit": {"proof", "pw"}}  {"withdraw": {"proof", "pw", "recipient"}}
@@ -571,6 +587,280 @@ def _dkg_receive(a):
         return 2
     print("dkg-receive: %d dealers, every hash and all %d values of each accepted; %s%s"
           % (m, n, "refreshed " if kind == "refresh" else "rlwe_pk.json, rlwe_params.json and ", share_path))
+    return 0
+
+
+# ---- the committee's commitments and handing the key to a new committee (include/spp.h, the block after spp_vss_receive) ----
+_RESHARE_NO_NOISE_LIMIT = ("dkg-deal's limit of %d auditors does not apply here: a reshared key is the same key, so the noise of its "
+                           "ciphertexts does not change however many hold it" % DKG_MAX_SHARES)
+
+
+def _committee_size_refused(cmd, t, m, what="threshold and shares"):
+    if not (1 <= t <= 64 and t <= m <= 255):
+        return "spp %s: %s: need 1 <= threshold <= 64 and threshold <= shares <= 255" % (cmd, what)
+    return None
+
+
+def _load_committee(path):
+    """a committee.json as a dict with bytes for a_seed and commitments; ValueError if it is not one"""
+    from . import witness
+    try:
+        d = json.load(open(path))
+        c = {"t": int(d["threshold"]), "m": int(d["num_shares"]), "xs": [int(x) for x in d["xs"]], "a_seed": _hex_seed(d["a_seed"]),
+             "commitments": bytes.fromhex(d["commitments"]), "noise_bound": int(d["noise_bound"])}
+        if int(d["version"]) != 1:
+            raise ValueError("version %r" % d["version"])
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError("%s: not a committee file (%s)" % (path, e))
+    if _committee_size_refused("", c["t"], c["m"]) or c["xs"] != list(range(1, c["m"] + 1)) or len(c["commitments"]) != c["t"] * witness.RLWE_N * 64:
+        raise ValueError("%s: a committee file holds threshold * 1024 commitments for the auditors 1..num_shares" % path)
+    return c
+
+
+def _write_committee(path, t, m, a_seed, commitments, noise_bound):
+    with open(path, "w") as f:
+        json.dump({"version": 1, "threshold": t, "num_shares": m, "xs": list(range(1, m + 1)), "a_seed": a_seed.hex(),
+                   "noise_bound": int(noise_bound), "commitments": commitments.hex()}, f)
+
+
+def _load_public_deal(path):
+    """the public fields of a deal file of any kind; ValueError if it is not one"""
+    try:
+        d = json.load(open(path))
+        if int(d["version"]) != 1 or d["kind"] not in ("key", "refresh", "reshare"):
+            raise ValueError("version %r, kind %r" % (d["version"], d["kind"]))
+        out = {"index": int(d["index"]), "kind": d["kind"], "t": int(d["threshold"]), "m": int(d["num_shares"]), "a_seed": _hex_seed(d["a_seed"]),
+               "commitments": bytes.fromhex(d["commitments"])}
+        if d["kind"] == "reshare":
+            out.update({"set": [int(x) for x in d["set"]], "t_new": int(d["new_threshold"]), "m_new": int(d["new_shares"])})
+        return out
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError("%s: not a deal file (%s)" % (path, e))
+
+
+def _fail_named(cmd, who, number, check_name, detail):
+    print("spp %s: %s %d: %s check failed%s" % (cmd, who, number, check_name, ": " + detail if detail else ""), file=sys.stderr)
+    return 1
+
+
+def _dkg_committee(a):
+    from . import witness
+    n = witness.RLWE_N
+    try:   # everything that can be wrong with the files is found before a device is opened
+        loaded = [_load_public_deal(p) for p in a.deals]
+        base = _load_committee(a.base) if a.base else None
+    except (OSError, ValueError) as e:
+        print("spp dkg-committee: %s" % e, file=sys.stderr)
+        return 2
+    first = loaded[0]
+    t, m, kind = first["t"], first["m"], first["kind"]
+    msg = _committee_size_refused("dkg-committee", t, m)
+    if msg is None and kind == "reshare":
+        msg = "spp dkg-committee: the committee file of a reshared key is written by dkg-reshare-receive"
+    if msg is None and (kind == "refresh") != (base is not None):
+        msg = "spp dkg-committee: %s" % ("refresh dealings are added to a committee file: give --base" if base is None
+                                         else "key dealings make a committee file of their own: --base is for refresh dealings")
+    if msg is None and base is not None and (base["t"], base["m"], base["a_seed"]) != (t, m, first["a_seed"]):
+        msg = "spp dkg-committee: %s is the committee file of another key or committee" % a.base
+    if msg:
+        print(msg, file=sys.stderr)
+        return 2
+    deals = {}
+    for d in loaded:
+        if d["index"] in deals:
+            return _fail_named("dkg-committee", "dealer", d["index"], "missing", "dealt twice")
+        deals[d["index"]] = d
+    for i in range(1, m + 1):
+        if i not in deals:
+            return _fail_named("dkg-committee", "dealer", i, "missing", "no deal file of this dealer among --deals")
+        for key, what in (("t", "threshold"), ("m", "num_shares"), ("a_seed", "a_seed"), ("kind", "kind")):
+            if deals[i][key] != first[key]:
+                return _fail_named("dkg-committee", "dealer", i, "agreement", "its %s differs from dealer %d's" % (what, first["index"]))
+        if len(deals[i]["commitments"]) != t * n * 64:
+            return _fail_named("dkg-committee", "dealer", i, "point", "%d commitment bytes, not %d" % (len(deals[i]["commitments"]), t * n * 64))
+    if len(deals) != m:
+        return _fail_named("dkg-committee", "dealer", max(deals), "missing", "not one of the auditors 1..%d" % m)
+    ctx = Context(a.device)
+    try:
+        flags, bad, out = witness.vss_combine_commitments(ctx, t, [deals[i]["commitments"] for i in range(1, m + 1)],
+                                                          base=base["commitments"] if base else None)
+    except lib.SppError as e:
+        print("spp dkg-committee: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    if bad:
+        for i, row in enumerate(flags, 1):
+            for at, fl in enumerate(row):
+                if fl:
+                    return _fail_named("dkg-committee", "dealer", i, "point", "value %d, coefficient %d (%d commitments refused in all)" % (at % n, at // n, bad))
+    try:
+        _write_committee(a.out, t, m, first["a_seed"], out, base["noise_bound"] if base else witness.NOISE_BOUND * m)
+    except OSError as e:
+        print("spp dkg-committee: %s" % e, file=sys.stderr)
+        return 2
+    print("dkg-committee: %s: the commitments of %d %s dealings%s, threshold %d of %d" % (a.out, m, kind, " added to %s" % a.base if base else "", t, m))
+    return 0
+
+
+def _load_subshare(path, to):
+    """(from, y, y_blind) of a sub-share file addressed to auditor `to`; ValueError otherwise"""
+    from . import witness
+    try:
+        sub = json.load(open(path))
+        src, dst = int(sub["from"]), int(sub["to"])
+        y, b = [int(v, 16) for v in sub["y"]], [int(v, 16) for v in sub["y_blind"]]
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError("%s: not a sub-share file (%s)" % (path, e))
+    if dst != to or len(y) != witness.RLWE_N or len(b) != witness.RLWE_N:
+        raise ValueError("%s: need a sub-share of 1024 values addressed to auditor %d" % (path, to))
+    return src, y, b
+
+
+def _dkg_reshare_deal(a):
+    from . import witness
+    T, M = a.new_threshold, a.new_shares
+    msg = _committee_size_refused("dkg-reshare-deal", T, M, "--new-threshold and --new-shares")
+    if msg is None and not a.blind and not a.subshares:
+        msg = "spp dkg-reshare-deal: the blind of the share is needed: --blind blind_J.json, --subshares of every round it was dealt in, or both"
+    if msg:
+        print(msg, file=sys.stderr)
+        return 2
+    try:   # everything that can be wrong with the files is found before a device is opened
+        share = witness.load_share_json(a.share)
+        j = share["x"]
+        com = _load_committee(a.committee)
+        blind = [0] * witness.RLWE_N
+        if a.blind:
+            bf = witness.load_share_json(a.blind)
+            if bf["x"] != j:
+                raise ValueError("%s is the blind at x = %d, not auditor %d's" % (a.blind, bf["x"], j))
+            blind = list(bf["y"])
+        for path in a.subshares or []:
+            _, _, yb = _load_subshare(path, j)
+            if not all(0 <= v < R for v in yb):
+                raise ValueError("%s: a y_blind is no field element" % path)
+            blind = [(x + y) % R for x, y in zip(blind, yb)]
+        S = list(a.set)
+        if len(S) != com["t"] or len(set(S)) != len(S) or not all(1 <= x <= com["m"] for x in S):
+            raise ValueError("--set names exactly the threshold (%d) of distinct old members 1..%d" % (com["t"], com["m"]))
+        if j not in S:
+            raise ValueError("%s is auditor %d's share, and %d is not in --set" % (a.share, j, j))
+    except (OSError, ValueError) as e:
+        print("spp dkg-reshare-deal: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        _, bad, _ = witness.vss_receive(ctx, com["t"], j, [com["commitments"]], [share["y"]], [blind], want_share=False)
+        if bad:
+            print("spp dkg-reshare-deal: share-mismatch: %d of 1024 values of (share, blind) are not what %s commits auditor %d to; "
+                  "the likely cause is a forgotten sub-share file of a refresh round (or a committee file from before it): nothing written"
+                  % (bad, a.committee, j), file=sys.stderr)
+            return 1
+        d = witness.vss_deal(ctx, share["y"], T, M, blinds=blind)
+        private = os.path.join(a.out, "private")
+        os.makedirs(private, exist_ok=True)
+        deal_path = os.path.join(a.out, "reshare_%d.json" % j)
+        with open(deal_path, "w") as f:
+            json.dump({"version": 1, "kind": "reshare", "index": j, "set": S, "threshold": com["t"], "num_shares": com["m"], "new_threshold": T,
+                       "new_shares": M, "a_seed": com["a_seed"].hex(), "commitments": d["commitments"].hex()}, f)
+        for sh in d["shares"]:
+            with open(os.path.join(private, "subshare_%d_to_%d.json" % (j, sh["x"])), "w") as f:
+                json.dump({"from": j, "to": sh["x"], "y": ["%064x" % v for v in sh["y"]], "y_blind": ["%064x" % v for v in sh["y_blind"]]}, f)
+    except (OSError, ValueError, lib.SppError) as e:
+        print("spp dkg-reshare-deal: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    print("dkg-reshare-deal: %s (old member %d of the set %s, threshold %d of %d -> %d of %d) and %d sub-shares in %s"
+          % (deal_path, j, S, com["t"], com["m"], T, M, M, private))
+    return 0
+
+
+def _dkg_reshare_receive(a):
+    from . import witness
+    k, n, cmd = a.index, witness.RLWE_N, "dkg-reshare-receive"
+    try:   # everything that can be wrong with the files is found before a device is opened
+        com = _load_committee(a.committee)
+        loaded = [_load_public_deal(p) for p in a.deals]
+        for path, d in zip(a.deals, loaded):
+            if d["kind"] != "reshare":
+                raise ValueError("%s is a %s dealing: dkg-reshare-receive takes the reshare_<j>.json files of dkg-reshare-deal" % (path, d["kind"]))
+        subs = [_load_subshare(p, k) for p in a.subshares]
+    except (OSError, ValueError) as e:
+        print("spp %s: %s" % (cmd, e), file=sys.stderr)
+        return 2
+    first = loaded[0]
+    T, M, S = first["t_new"], first["m_new"], first["set"]
+    msg = _committee_size_refused(cmd, T, M, "the deals' new_threshold and new_shares")
+    if msg is None and not 1 <= k <= M:
+        msg = "spp %s: --index is one of the new members 1..%d" % (cmd, M)
+    if msg:
+        print(msg, file=sys.stderr)
+        return 2
+    deals = {}
+    for d in loaded:
+        if d["set"] != S:
+            return _fail_named(cmd, "old member", d["index"], "set", "its set %s differs from old member %d's %s" % (d["set"], first["index"], S))
+        if d["index"] in deals:
+            return _fail_named(cmd, "old member", d["index"], "missing", "dealt twice")
+        deals[d["index"]] = d
+    if len(S) != com["t"] or len(set(S)) != len(S) or not all(1 <= x <= com["m"] for x in S):
+        return _fail_named(cmd, "old member", first["index"], "set", "%s is not exactly the threshold (%d) of distinct old members 1..%d" % (S, com["t"], com["m"]))
+    for i in sorted(deals):
+        if i not in S:
+            return _fail_named(cmd, "old member", i, "set", "not a member of the set %s" % S)
+    ys, yb = {}, {}
+    for src, y, b in subs:
+        ys[src], yb[src] = y, b
+    for i in S:
+        if i not in deals:
+            return _fail_named(cmd, "old member", i, "missing", "no deal file of this member among --deals")
+        d = deals[i]
+        for got, want, what in ((d["t"], com["t"], "threshold"), (d["m"], com["m"], "num_shares"), (d["a_seed"], com["a_seed"], "a_seed")):
+            if got != want:
+                return _fail_named(cmd, "old member", i, "agreement", "its %s is not the committee file's" % what)
+        for key, what in (("t_new", "new_threshold"), ("m_new", "new_shares")):
+            if d[key] != first[key]:
+                return _fail_named(cmd, "old member", i, "agreement", "its %s differs from old member %d's" % (what, first["index"]))
+        if len(d["commitments"]) != T * n * 64:
+            return _fail_named(cmd, "old member", i, "point", "%d commitment bytes, not %d" % (len(d["commitments"]), T * n * 64))
+        if i not in ys:
+            return _fail_named(cmd, "old member", i, "missing", "no sub-share of this member among --subshares")
+        for row in (ys[i], yb[i]):
+            for v, val in enumerate(row):
+                if not 0 <= val < R:
+                    return _fail_named(cmd, "old member", i, "share", "value %d is no field element" % v)
+    ctx = Context(a.device)
+    try:
+        flags, bad, share, blind, out = witness.vss_reshare_receive(ctx, S, T, k, com["commitments"], [deals[i]["commitments"] for i in S],
+                                                                    [ys[i] for i in S], [yb[i] for i in S])
+    except lib.SppError as e:
+        print("spp %s: %s" % (cmd, e), file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    if bad:
+        for i, row in zip(S, flags):
+            for v, fl in enumerate(row):
+                if fl:
+                    name = next(nm for bit, nm in witness.VSS_RESHARE_FLAG_NAMES if fl & bit)
+                    return _fail_named(cmd, "old member", i, name, "value %d (%d values refused in all)" % (v, bad))
+    shares_dir, private = os.path.join(a.out, "rlwe_sk_shares"), os.path.join(a.out, "private")
+    share_path = os.path.join(shares_dir, "share_%d.json" % k)
+    try:
+        os.makedirs(shares_dir, exist_ok=True)
+        os.makedirs(private, exist_ok=True)
+        witness.write_share_json(share_path, k, T, M, k, share)
+        witness.write_share_json(os.path.join(private, "blind_%d.json" % k), k, T, M, k, blind)
+        _write_committee(os.path.join(a.out, "committee.json"), T, M, com["a_seed"], out, com["noise_bound"])
+        witness.write_rlwe_params_json(os.path.join(a.out, "rlwe_params.json"), T, M, com["noise_bound"])
+    except (OSError, ValueError) as e:
+        print("spp %s: %s" % (cmd, e), file=sys.stderr)
+        return 2
+    print("dkg-reshare-receive: %d old members, all %d values of each accepted and each constant term the member's own share commitment; "
+          "%s, private/blind_%d.json, committee.json (threshold %d of %d) and rlwe_params.json; rlwe_pk.json stays as it is"
+          % (len(S), n, share_path, k, T, M))
     return 0
 
 
@@ -1162,6 +1452,24 @@ def main(argv=None):
     dr.add_argument("--subshares", nargs="+", required=True, metavar="SUBSHARE.json"); dr.add_argument("--out", required=True, metavar="DIR")
     dr.add_argument("--refresh", default=None, metavar="SHARE.json", help="this auditor's current share: the dealings are refresh dealings")
     dr.add_argument("--device", type=int, default=0)
+    dc = sub.add_parser("dkg-committee", description="The committee's commitments from the public deal files: holds no secrets.")
+    dc.add_argument("--deals", nargs="+", required=True, metavar="DEAL.json", help="one deal file per auditor, all key or all refresh dealings")
+    dc.add_argument("--base", default=None, metavar="COMMITTEE.json", help="refresh dealings: the committee file they are added to")
+    dc.add_argument("--out", required=True, metavar="COMMITTEE.json"); dc.add_argument("--device", type=int, default=0)
+    rd = sub.add_parser("dkg-reshare-deal", description="An old member deals its share to a new committee. " + _RESHARE_NO_NOISE_LIMIT + ".")
+    rd.add_argument("--share", required=True, metavar="SHARE_J.json")
+    rd.add_argument("--blind", default=None, metavar="BLIND_J.json", help="the blind a dkg-reshare-receive wrote")
+    rd.add_argument("--subshares", nargs="+", default=None, metavar="SUBSHARE.json",
+                    help="every sub-share file addressed to this auditor since the key round (or since --blind): their y_blind sum to the blind")
+    rd.add_argument("--committee", required=True, metavar="COMMITTEE.json")
+    rd.add_argument("--set", nargs="+", type=int, required=True, metavar="X", help="the old members who deal: exactly the old threshold")
+    rd.add_argument("--new-threshold", type=int, required=True, metavar="T", help="1 <= T <= 64")
+    rd.add_argument("--new-shares", type=int, required=True, metavar="M", help="T <= M <= 255; " + _RESHARE_NO_NOISE_LIMIT)
+    rd.add_argument("--out", required=True, metavar="DIR"); rd.add_argument("--device", type=int, default=0)
+    rr = sub.add_parser("dkg-reshare-receive"); rr.add_argument("--index", type=int, required=True, metavar="K", help="this new member, 1..M")
+    rr.add_argument("--committee", required=True, metavar="COMMITTEE.json", help="the old committee's file")
+    rr.add_argument("--deals", nargs="+", required=True, metavar="RESHARE.json"); rr.add_argument("--subshares", nargs="+", required=True, metavar="SUBSHARE.json")
+    rr.add_argument("--out", required=True, metavar="DIR"); rr.add_argument("--device", type=int, default=0)
     sc = sub.add_parser("setup-contribute"); sc.add_argument("pk"); sc.add_argument("vk")
     sc.add_argument("--out", required=True, metavar="DIR", help="<name>.pk, <name>.vk and <name>.receipt go here (not the key's own directory)")
     sc.add_argument("--entropy", default=None, metavar="HEX32", help="for reproducible tests only: the default draws from the operating system")
@@ -1204,6 +1512,12 @@ def main(argv=None):
         return _dkg_deal(a)
     if a.cmd == "dkg-receive":
         return _dkg_receive(a)
+    if a.cmd == "dkg-committee":
+        return _dkg_committee(a)
+    if a.cmd == "dkg-reshare-deal":
+        return _dkg_reshare_deal(a)
+    if a.cmd == "dkg-reshare-receive":
+        return _dkg_reshare_receive(a)
     if a.cmd == "rlwe-keygen":
         return _rlwe_keygen(a)
     if a.cmd == "rlwe-key-check":

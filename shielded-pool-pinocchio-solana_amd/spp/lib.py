@@ -222,6 +222,11 @@ def load_library():
     L.spp_vss_deal.argtypes = [vp, u32, u32, vp, sz, cp, cp, cp, cp, vp, vp, vp, vp]
     L.spp_vss_deal_timed.argtypes = [vp, u32, u32, vp, sz, cp, cp, cp, cp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.spp_vss_receive.argtypes = [vp, u32, u32, u32, sz, cp, cp, cp, cp, cp, vp, vp, ctypes.POINTER(sz)]
+    # the committee's commitments and verifiable resharing (include/spp.h)
+    L.spp_vss_combine_commitments.argtypes = [vp, u32, u32, sz, cp, cp, cp, vp, vp, ctypes.POINTER(sz)]
+    L.spp_vss_combine_commitments_timed.argtypes = [vp, u32, u32, sz, cp, cp, cp, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_float)]
+    L.spp_vss_share_commitments.argtypes = [vp, u32, sz, cp, u32, vp, vp]
+    L.spp_vss_reshare_receive.argtypes = [vp, u32, vp, u32, u32, sz, cp, cp, cp, cp, vp, vp, vp, vp, ctypes.POINTER(sz)]
     # threshold opening (include/spp.h)
     L.spp_rlwe_sample_smudge.argtypes = [sz, u32, vp, vp]
     L.spp_rlwe_partial_decrypt_batch.argtypes = [vp, u32, vp, u32, cp, sz, vp, vp, vp, vp, cp, vp, vp]

@@ -25,6 +25,8 @@
     vss_generators / dkg_a_from_seed / vss_deal / vss_receive
                              scripts/rlwe_keygen.py:51-65, 98-182 by the auditors together: every auditor deals its own part of
                              the key with public commitments, nobody draws the whole (no counterpart in the reference)
+    vss_combine_commitments / vss_share_commitments / vss_reshare_receive
+                             the committee's commitments and handing the key to a new committee (no counterpart either)
     write_rlwe_pk_json / write_rlwe_params_json / write_share_json
                              scripts/rlwe_keygen.py:124-127, 133-142, 161-169: the files `cli compile --rlwe-pk` and
                              load_share_json read
@@ -958,3 +960,87 @@ def vss_receive(ctx, threshold, x, commitments, ys, ys_blind, zero_blinds=None, 
                                 ctypes.byref(bad)))
     fl = [list(flags[d * n:(d + 1) * n]) for d in range(dealers)]
     return fl, int(bad.value), (_unbe(out.raw, n) if want_share and bad.value == 0 else None)
+
+
+# ---- the committee's commitments and verifiable resharing (include/spp.h) ----
+VSS_NOT_SHARE = 8
+VSS_RESHARE_FLAG_NAMES = ((VSS_BAD_POINT, "point"), (VSS_BAD_SHARE, "share"), (VSS_NOT_SHARE, "not-share"))
+
+
+def lagrange_at_zero(xs):
+    """the Lagrange coefficients at 0 of the distinct non-zero indices xs, as ints mod r"""
+    xs = [int(x) for x in xs]
+    lam = []
+    for j, xj in enumerate(xs):
+        num = den = 1
+        for i, xi in enumerate(xs):
+            if i != j:
+                num = num * xi % FR_MODULUS
+                den = den * (xi - xj) % FR_MODULUS
+        lam.append(num * pow(den, -1, FR_MODULUS) % FR_MODULUS)
+    return lam
+
+
+def vss_combine_commitments(ctx, threshold, commitments, weights=None, base=None, times=None):
+    """base + sum_d w_d C_d over the dealers' commitment strings (bytes of threshold * n * 64 each); weights: one int per dealer
+    or None (plain sums: the committee's commitments of a key, or of a refresh round on top of base).  Returns (flags [[int] *
+    (threshold * n)] per dealer, bad, out bytes or None when an input is no point).  times (a list, optional) receives the device
+    milliseconds of the kernels."""
+    dealers, t = len(commitments), int(threshold)
+    size = len(commitments[0]) if commitments else 0
+    n = size // (64 * t) if t else 0
+    if size != n * t * 64 or any(len(c) != size for c in commitments) or (base is not None and len(base) != size):
+        raise ValueError("every dealer's commitments (and base) are threshold * n * 64 bytes")
+    if weights is not None and len(weights) != dealers:
+        raise ValueError("one weight per dealer")
+    flags = (ctypes.c_uint32 * max(1, dealers * t * n))()
+    out = ctypes.create_string_buffer(max(1, size))
+    bad = ctypes.c_size_t(0)
+    args = (ctx.h, t, dealers, n, b"".join(commitments), None if weights is None else _be(weights), base, ctypes.cast(out, ctypes.c_void_p),
+            ctypes.cast(flags, ctypes.c_void_p), ctypes.byref(bad))
+    if times is None:
+        check(ctx.L.spp_vss_combine_commitments(*args))
+    else:
+        ms = ctypes.c_float(0)
+        check(ctx.L.spp_vss_combine_commitments_timed(*args, ctypes.byref(ms)))
+        times[:] = [float(ms.value)]
+    fl = [list(flags[d * t * n:(d + 1) * t * n]) for d in range(dealers)]
+    return fl, int(bad.value), (out.raw[:size] if bad.value == 0 else None)
+
+
+def vss_share_commitments(ctx, threshold, committee, xs):
+    """E_x = sum_k x^k D_k for every x in xs: a list of n * 64 bytes per x (committee: threshold * n * 64 bytes)"""
+    t, xs = int(threshold), [int(x) for x in xs]
+    n = len(committee) // (64 * t) if t else 0
+    if len(committee) != t * n * 64:
+        raise ValueError("a committee's commitments are threshold * n * 64 bytes")
+    cx = (ctypes.c_uint32 * max(1, len(xs)))(*xs)
+    out = ctypes.create_string_buffer(max(1, len(xs) * n * 64))
+    check(ctx.L.spp_vss_share_commitments(ctx.h, t, n, committee, len(xs), ctypes.cast(cx, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+    return [out.raw[i * n * 64:(i + 1) * n * 64] for i in range(len(xs))]
+
+
+def vss_reshare_receive(ctx, xs_old, threshold_new, x_new, committee, commitments, ys, ys_blind):
+    """The new member at x_new takes the dealings of the old members xs_old (the set S, as many as the old threshold): committee
+    the old committee's commitments, commitments [bytes] / ys / ys_blind [[int] * n] per old member in xs_old order.  Returns
+    (flags [[int] * n] per old member, bad, share, blind, committee_out); the last three are None when a check failed."""
+    xs_old, t_new = [int(x) for x in xs_old], int(threshold_new)
+    t_old, n = len(xs_old), len(ys[0]) if ys else 0
+    if len(commitments) != t_old or len(ys) != t_old or len(ys_blind) != t_old:
+        raise ValueError("one commitment string, one y row and one y_blind row per old member")
+    if any(len(c) != t_new * n * 64 for c in commitments) or any(len(r) != n for r in list(ys) + list(ys_blind)) or len(committee) != t_old * n * 64:
+        raise ValueError("a dealing of %d values at threshold %d is %d commitment bytes; the old committee's are %d"
+                         % (n, t_new, t_new * n * 64, t_old * n * 64))
+    flat = lambda rows: _be(v for row in rows for v in row)
+    cx = (ctypes.c_uint32 * max(1, t_old))(*xs_old)
+    flags = (ctypes.c_uint32 * max(1, t_old * n))()
+    share, blind = (ctypes.create_string_buffer(max(1, n * 32)) for _ in range(2))
+    out = ctypes.create_string_buffer(max(1, t_new * n * 64))
+    bad = ctypes.c_size_t(0)
+    p = lambda b: ctypes.cast(b, ctypes.c_void_p)
+    check(ctx.L.spp_vss_reshare_receive(ctx.h, t_old, p(cx), t_new, int(x_new), n, committee, b"".join(commitments), flat(ys), flat(ys_blind),
+                                        p(flags), p(share), p(blind), p(out), ctypes.byref(bad)))
+    fl = [list(flags[j * n:(j + 1) * n]) for j in range(t_old)]
+    if bad.value:
+        return fl, int(bad.value), None, None, None
+    return fl, 0, _unbe(share.raw, n), _unbe(blind.raw, n), out.raw[:t_new * n * 64]
