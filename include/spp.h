@@ -18,6 +18,11 @@
  *                             resident tree (spp_merkle_tree_*)
  *   spp_merkle_tree_deposit   client/payroll-demo.ts:264-292 (generateIdentityKeypair / calculateCommitment / insert / getRoot
  *                             per deposit) into the same tree
+ *   spp_deposit_rows_from_tree / spp_prove_deposits(_device) / spp_verify_deposit_chain
+ *                             no counterpart: the reference's deposit carries no proof -- the program ignores the commitment, pushes
+ *                             the new_root it is sent and transfers an amount nothing binds to the note
+ *                             (shielded_pool_program/src/instructions/deposit.rs:31-36,73).  A proof per deposit of the root before,
+ *                             the root after, the commitment, its amount and its index, and the check of a log of them
  *   spp_verify                `sunspot verify` noir_circuit/prove_linux.sh:86-87, audit_circuit/prove_audit.sh:98-99
  *   spp_verify_batch          the same for many proofs on the GPU
  *   spp_verify_batch_rlc      the same by random linear combination: key-side pairings once per group of proofs
@@ -134,6 +139,14 @@ int spp_circuit_build(int circuit_id, const uint32_t* aux, const char* out_path,
  * reference's OWN compiled circuit is what gets set up and proved.  blob: the decoded opcode list written by
  * spp/acir.py:to_blob (bincode decoding stays on the host side).  circuit_id: id stored in the container (0 = generic;
  * SPP_CIRCUIT_WITHDRAW when the program has the withdraw circuit's ABI, so that spp_prove_withdraw accepts it). */
+/* The deposit statement (csrc/circuit_deposit.cpp; no counterpart in the reference, whose program checks nothing about a deposit,
+ * shielded_pool_program/src/instructions/deposit.rs:31-36,73).  aux NULL.  Depth SPP_TREE_DEPTH.
+ *   public  (.pw order): old_root | new_root | commitment | amount | index
+ *   private            : owner_x | owner_y | randomness | siblings[SPP_TREE_DEPTH]
+ * amount is a u64; commitment == H(owner_x, owner_y, amount, randomness) (main.nr:69-70); index < 2^depth; over the bits of index and
+ * ONE set of siblings the path from the empty leaf 0 (client/merkle.ts:152) ends in old_root and the path from commitment in new_root.
+ * No secret key: one may deposit to an owner whose key one does not hold; an owner off the curve is an unspendable note. */
+#define SPP_CIRCUIT_DEPOSIT 6
 #define SPP_CIRCUIT_ACIR 5
 int spp_circuit_build_acir(const uint8_t* blob, size_t blob_len, int circuit_id, const char* out_path, uint32_t* n_constraints);
 
@@ -386,6 +399,57 @@ int spp_prove_withdraw_notes_device(spp_circuit* c, spp_merkle_tree* t, size_t c
  * the proving (large batches in chunks); rs NULL = OS randomness.  Returns SPP_ERR_UNSAT if any note was refused. */
 int spp_prove_withdraw_notes(spp_circuit* c, spp_merkle_tree* t, size_t count, const uint8_t* notes, const uint8_t* rs, uint8_t* proofs,
                              uint8_t* pws, int32_t* status);
+
+/* ---- deposit proofs ----
+ * The reference's deposit is unchecked: process_deposit reads the commitment and ignores it, pushes whatever new_root the client sent
+ * and transfers `amount` lamports that nothing ties to the amount inside the commitment (shielded_pool_program/src/instructions/
+ * deposit.rs:31-36,73).  Its program does NOT verify the proofs made here; they serve a pool program that does, and any indexer,
+ * relayer or auditor who wants to check a deposit log without rebuilding the tree.
+ *   deposit = secret_key | amount | randomness                       (SPP_DEPOSIT_LEN, as spp_merkle_tree_deposit)
+ *   row     = old_root | new_root | commitment | amount | index | owner_x | owner_y | randomness | siblings[depth]
+ * for leaf i = first_index + k of the tree, which must already hold it (spp_merkle_tree_deposit first): owner = secret_key * G, the
+ * key as given; commitment = H(owner_x, owner_y, amount, randomness), computed from the RECORD, never read from the tree; sibling l is
+ * the stored node to the left of the path when (i >> l) is odd -- a subtree of leaves below i, final -- and the level default
+ * otherwise; old_root and new_root are the path from 0 and from the commitment over those siblings: the roots of sizes i and i + 1
+ * (spp_merkle_tree_root_at), whatever the tree's size is now, unchanged by later inserts.
+ * A record that is not the deposit at that index (other key, amount or randomness) still gives a self-consistent row and a proof
+ * that verifies, of "this commitment at this index after old_root"; its new_root is then not the tree's.  What binds a proof to the
+ * real tree is the chain check below, not the row builder.  amount >= 2^64 is not refused here: the row is made and the circuit
+ * refuses it in place (status != 0, proof bytes zero), the rest of the batch is proved.
+ * Refused with SPP_ERR_BAD_INPUT before any device work, the index named in spp_last_error(): NULL pointers, a circuit that is not
+ * SPP_CIRCUIT_DEPOSIT or whose input count is not SPP_DEPOSIT_INPUTS, a tree of another spp_ctx or of a depth other than
+ * SPP_TREE_DEPTH (rows only: any depth), first_index + count > the tree's size, count > 2^24; by the host entry points also a field >= r
+ * and secret_key == 0.  count == 0 is SPP_OK.
+ * Snapshot: the rows are gathered on the tree's stream, in stream order with inserts, as spp_prove_withdraw_notes_device does. */
+#define SPP_DEPOSIT_PW_LEN 172
+#define SPP_DEPOSIT_INPUTS 24     /* fields per row */
+/* rows only, host buffers; leaves first_index .. first_index+count-1 must already be in the tree; rows = count * (8 + depth) * 32 B */
+int spp_deposit_rows_from_tree(spp_merkle_tree* t, uint64_t first_index, size_t count, const uint8_t* deposits, uint8_t* rows);
+/* end to end on the device, asynchronous until spp_sync(); contract of spp_prove_withdraw_notes_device (no field check on the records) */
+int spp_prove_deposits_device(spp_circuit* c, spp_merkle_tree* t, uint64_t first_index, size_t count, const void* d_deposits,
+                              const void* d_rs, void* d_proofs, void* d_pws, void* d_status);
+/* host convenience, chunked like spp_prove_withdraw_notes; rs NULL = OS randomness; SPP_ERR_UNSAT if any row was refused */
+int spp_prove_deposits(spp_circuit* c, spp_merkle_tree* t, uint64_t first_index, size_t count, const uint8_t* deposits,
+                       const uint8_t* rs, uint8_t* proofs, uint8_t* pws, int32_t* status);
+
+/* Checking a log of proved deposits, as a program that keeps (current_root, leaf count) would: the instructions are taken one after
+ * another from (start_root, start_index); codes[i] is the FIRST failing check in the order below, words compared bytewise as the pool
+ * ledger compares them.  An accepted instruction advances (current_root, count) to (its new_root, its index + 1); a rejected one
+ * advances nothing, so a deposit built on a rejected one is STALE_ROOT.  end_root / end_index (optional) receive the state after the
+ * last accepted instruction.  lamports (optional): the amount each instruction transfers; NULL skips the amount check.
+ * The proofs are verified once for the whole batch, independent of position, by spp_verify_batch (SPP_DEPOSIT_BAD_PROOF is its
+ * decision, a malformed witness header included); the chain is a sequential scan of 76 bytes per instruction on the host after one
+ * download of the flags.  No spp_pool is read or changed: feed the accepted new_roots to spp_pool_add_roots.
+ * SPP_ERR_FORMAT: a vk that does not parse or whose public-input count is not 5.  SPP_ERR_BAD_INPUT: NULL ctx, vk, codes or
+ * start_root, NULL proofs or pws with count > 0, count > 2^24.  count == 0 is SPP_OK with the end state = the start state. */
+#define SPP_DEPOSIT_OK 0
+#define SPP_DEPOSIT_BAD_AMOUNT 1   /* pw amount != the instruction's lamports */
+#define SPP_DEPOSIT_STALE_ROOT 2   /* pw old_root != the current root at this position */
+#define SPP_DEPOSIT_BAD_INDEX 3    /* pw index != the leaf count at this position */
+#define SPP_DEPOSIT_BAD_PROOF 4    /* the decision of spp_verify_batch, witness header included */
+int spp_verify_deposit_chain(spp_ctx* ctx, const uint8_t* vk, size_t vk_len, size_t count, const uint8_t* proofs, const uint8_t* pws,
+                             const uint64_t* lamports /* optional */, const uint8_t start_root[32], uint64_t start_index,
+                             uint32_t* codes, uint8_t end_root[32], uint64_t* end_index);
 
 /* Batched verification on the GPU (`sunspot verify` for many proofs against one key, the checks of the
  * deployed verifier withdraw.rs:63-90 / submit_audit.rs:41-54): proofs = count * 388 B, pws = count * pw_len B (host

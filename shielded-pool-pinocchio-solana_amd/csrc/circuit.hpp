@@ -57,7 +57,7 @@ enum : uint32_t {
                       //                +4..+7 remainder, +8..+13 carries
 };
 
-enum : uint32_t { CIRCUIT_WITHDRAW = 1, CIRCUIT_AUDIT = 2, CIRCUIT_ACIR = 5 };
+enum : uint32_t { CIRCUIT_WITHDRAW = 1, CIRCUIT_AUDIT = 2, CIRCUIT_ACIR = 5, CIRCUIT_DEPOSIT = 6 };
 
 struct Term {
   uint32_t wire;
@@ -366,5 +366,7 @@ Circuit build_withdraw_circuit(bool native_hints, uint32_t pad_to_constraints = 
 // Returns false and sets *err on an unsupported construct.  csrc/circuit_acir.cpp
 bool build_acir_circuit(const uint8_t* blob, size_t len, uint32_t circuit_id, Circuit* out, std::string* err);
 Circuit build_audit_circuit(const uint32_t* pk_a, const uint32_t* pk_b, bool native_hints);
+// old_root | new_root | commitment | amount | index public, owner_x | owner_y | randomness | siblings[depth] private.  csrc/circuit_deposit.cpp
+Circuit build_deposit_circuit(bool native_hints, uint32_t depth = 16);
 
 }  // namespace spp

@@ -120,6 +120,10 @@ void launch_withdraw_rows(hipStream_t st, const GkAffine* table, HashConsts hc, 
 void launch_deposit_leaves(hipStream_t st, const GkAffine* table, HashConsts hc, const uint8_t* deposits, Fr* leaves, uint32_t count);
 void launch_deposit_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first, uint32_t count, uint8_t* roots_be,
                           uint8_t* commitments_be);
+// rows for the deposit circuit (deposit_rows.hpp): leaves first .. first+count-1 must be in the tree (first + count <= t->count[0], checked
+// by the caller); rows = count * (8 + depth) * 32 B
+void launch_deposit_rows(hipStream_t st, const GkAffine* table, HashConsts hc, const MerkleTreeDev* t, uint64_t first, const uint8_t* deposits,
+                         uint8_t* rows, uint32_t count);
 // The resident tree as of an earlier size (merkle_prefix.hpp has the rule).  size <= t->count[0], checked by the caller.
 //   launch_merkle_frontier   one lane: frontier[0..depth] of `size`; the as-of launches below read it in a LATER launch on the stream
 //   launch_merkle_gather_at / launch_withdraw_rows_at   launch_merkle_gather / launch_withdraw_rows with the three-case selection

@@ -10,6 +10,7 @@
 //   k_withdraw_rows       client/payroll-demo.ts:323-340 (keygen, wa_commitment, nullifier, getRoot, getProof -> one withdraw row)
 //   k_deposit_leaves      client/payroll-demo.ts:264-292 (keygen, calculateCommitment, mt.insert)
 //   k_deposit_roots       the same deposits' mt.getRoot() after each insert
+//   k_deposit_rows        a deposit's row for the deposit circuit: the roots before and after its insert, one set of siblings
 //   k_leaf_index_insert / k_leaf_find / k_wallet_identity / k_wallet_locate
 //                         demo-frontend/app/lib/storage.ts:9-26,45-50 (leafIndex, nullifier, waCommitment, status of a DepositRecord
 //                         from the secrets, the leaf list and the pool's accounts; the leaf index is leaf_index.hpp)
@@ -32,6 +33,7 @@
 #include "rlwe_keygen.hpp"
 #include "leaf_index.hpp"
 #include "merkle_prefix.hpp"
+#include "deposit_rows.hpp"
 
 namespace spp {
 
@@ -564,6 +566,54 @@ void launch_deposit_leaves(hipStream_t st, const GkAffine* table, HashConsts hc,
 void launch_deposit_roots(hipStream_t st, HashConsts hc, const MerkleTreeDev* t, uint64_t first, uint32_t count, uint8_t* roots_be,
                           uint8_t* commitments_be) {
   if (count) hipLaunchKernelGGL(k_deposit_roots, dim3((count + 63) / 64), dim3(64), 0, st, hc, t, first, count, roots_be, commitments_be);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Deposit rows (circuit_deposit.cpp): one lane per deposit; leaf i = first + g of the tree, which must already hold it.
+// row = old_root | new_root | commitment | amount | index | owner_x | owner_y | randomness | siblings[depth], 32 B big-endian each.
+// The owner and the commitment are k_deposit_leaves' (the commitment computed from the record, never read from the tree); the walk
+// up is deposit_rows.hpp: k_deposit_roots' walk twice over one set of siblings, from the empty leaf to the root of size i and from
+// the commitment to the root of size i + 1.  It reads stored nodes to the LEFT of the path only, at positions below count[l]
+// whenever i < count[0], which the callers check on the host.  An amount >= 2^64 is copied as it is: the circuit refuses the row.
+// Two permutation call sites, t = 5 once and t = 3 in the rolled two-trip loop of the walk, both inlined (see k_withdraw_rows).
+// ----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_deposit_rows(const GkAffine* __restrict__ table, HashConsts hc, const MerkleTreeDev* __restrict__ t,
+                                                     uint64_t first, const uint8_t* __restrict__ deposits, uint8_t* __restrict__ rows,
+                                                     uint32_t count) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const uint32_t depth = t->depth;
+  const uint64_t i = first + g;
+  const uint8_t* d = deposits + (size_t)g * DEPOSIT_BYTES;
+  uint8_t* o = rows + (size_t)g * (DEPOSIT_ROW_FIXED + depth) * 32;
+  Fr c;
+  {
+    const GkAffine pk = grumpkin_mul_g(table, load_be(d));           // the key as given, as k_deposit_leaves
+    store_be(o + 5 * 32, pk.x);
+    store_be(o + 6 * 32, pk.y);
+    Fr s[5] = {Fr::zero(), pk.x, pk.y, load_be(d + 32), load_be(d + 64)};
+    poseidon_permute29<5, false>(s, hc.pos5_rc, hc.pos5_mds29, 60, PoseidonNoEmit{});
+    c = s[0];
+  }
+  store_be(o + 2 * 32, c);
+  copy32(o + 3 * 32, d + 32);                                        // amount
+  for (int b = 0; b < 24; b++) o[4 * 32 + b] = 0;                    // index
+  for (int b = 0; b < 8; b++) o[4 * 32 + 24 + b] = (uint8_t)(i >> (8 * (7 - b)));
+  copy32(o + 7 * 32, d + 64);                                        // randomness
+  Fr roots[2];
+  deposit_walk(i, depth, [&](uint32_t l) { return (const Fr*)t->level[l]; }, t->dflt, Fr::zero(), c,
+               [&](const Fr& a, const Fr& b) {
+                 Fr s[3] = {Fr::zero(), a, b};
+                 poseidon_permute29<3, false>(s, hc.pos3_rc, hc.pos3_mds29, 57, PoseidonNoEmit{});
+                 return s[0];
+               },
+               [&](uint32_t l, const Fr& sib) { store_be(o + (DEPOSIT_ROW_FIXED + l) * 32, sib); }, roots);
+  store_be(o, roots[0]);
+  store_be(o + 32, roots[1]);
+}
+void launch_deposit_rows(hipStream_t st, const GkAffine* table, HashConsts hc, const MerkleTreeDev* t, uint64_t first, const uint8_t* deposits,
+                         uint8_t* rows, uint32_t count) {
+  if (count) hipLaunchKernelGGL(k_deposit_rows, dim3((count + 63) / 64), dim3(64), 0, st, table, hc, t, first, deposits, rows, count);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 //   spp_verify_api.cpp   verification and pairing checks
 //   spp_audit_api.cpp    opening audit records: verification, ciphertext binding, decryption, identity binding in one pass
 //   spp_pool_api.cpp     the pool ledger: root ring, nullifier and audit-record sets, settling submit_audit / withdraw batches
+//   spp_deposit_api.cpp  deposit proofs: rows from the resident tree, the check of a log of proved deposits (spp_prove_deposits itself is in spp_prove.cpp)
 //   spp_withdrawals_api.cpp  the withdrawal plan: which notes of a batch still need an audit record (spp_prove_withdrawals itself is in spp_prove.cpp)
 //   spp_ceremony_api.cpp the setup ceremony: contributions to a key's delta and to its sigma, their receipts and verifiers, the scaling unit call
 //   spp_vss_api.cpp      the auditors' key without a dealer: verifiable sharing, the receiver's check, the sum of sub-shares
@@ -249,6 +250,10 @@ int spp_audit_inputs_enqueue(spp_ctx* ctx, hipStream_t st, void* scratch, const 
                              uint32_t* d_c1_out);
 // withdraw notes (spp_witness_api.cpp): SPP_ERR_BAD_INPUT unless every field of every note is canonical
 int spp_check_notes(size_t count, const uint8_t* notes);
+// deposit proofs (spp_deposit_api.cpp): SPP_ERR_BAD_INPUT unless every field of every record is canonical and no secret_key is 0;
+// unless leaves first_index .. first_index+count-1 are in the tree (ctx->mu held)
+int spp_check_deposit_records(size_t count, const uint8_t* deposits);
+int spp_check_deposit_range(const spp_merkle_tree* t, uint64_t first_index, size_t count);
 // threshold opening (spp_partial_api.cpp): SPP_ERR_BAD_INPUT unless t is in [1, 64] and xs (optional) holds t distinct nonzero
 // indices; unless every one of the t * count * 64 partials is a canonical field element
 int spp_check_share_set(uint32_t t, const uint32_t* xs);

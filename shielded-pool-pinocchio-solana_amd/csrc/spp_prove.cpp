@@ -507,6 +507,57 @@ extern "C" int spp_prove_withdraw_notes_at(spp_circuit* c, spp_merkle_tree* t, u
   if (count == 0) return SPP_OK;
   return spp_prove_batch(c, count, rows.data(), rs, proofs, pws, status);
 }
+// Deposit proofs from records against the resident tree (include/spp.h): spp_prove_withdraw_notes_device's scheme with k_deposit_rows
+// as the rows kernel -- gathered on the tree's stream under the context lock, body and tail into their own workspaces' d_inputs.
+// The range check reads the tree's size under that lock, before a workspace is taken.
+static int deposit_args(spp_circuit* c, spp_merkle_tree* t) {
+  if (c->circ.id != SPP_CIRCUIT_DEPOSIT) return fail(SPP_ERR_BAD_INPUT, "not a deposit circuit");
+  if (t->ctx != c->ctx) return fail(SPP_ERR_BAD_INPUT, "the tree belongs to another context");
+  if (c->circ.n_inputs() != SPP_DEPOSIT_INPUTS || t->depth != SPP_TREE_DEPTH)
+    return fail(SPP_ERR_BAD_INPUT, "the circuit takes %u inputs and the tree has depth %u; a deposit row has %d fields over a depth-%d tree",
+                c->circ.n_inputs(), t->depth, SPP_DEPOSIT_INPUTS, SPP_TREE_DEPTH);
+  return SPP_OK;
+}
+extern "C" int spp_prove_deposits_device(spp_circuit* c, spp_merkle_tree* t, uint64_t first_index, size_t count, const void* d_deposits,
+                                         const void* d_rs, void* d_proofs, void* d_pws, void* d_status) {
+  if (!c || !t || !d_deposits || !d_rs || !d_proofs || !d_pws || !d_status) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int e = deposit_args(c, t)) return e;
+  if (count > (1u << 20)) return fail(SPP_ERR_BAD_INPUT, "batch too large");
+  spp_ctx* ctx = c->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int e = spp_check_deposit_range(t, first_index, count)) return e;
+  if (count == 0) return SPP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (int e = spp_ensure_ctx_consts(ctx)) return e;
+  Workspace* wp;
+  if (int e = take_sized_workspace(c, count, c->generic_solver, &wp)) return e;
+  Workspace &w = *wp, &wt = c->ws[c->next_ws];
+  const size_t tail = batch_tail(c, count), body = count - tail;
+  const uint8_t* deposits = (const uint8_t*)d_deposits;
+  HIP_TRY(hipStreamWaitEvent(ctx->stream, w.ev_in, 0));
+  if (tail) HIP_TRY(hipStreamWaitEvent(ctx->stream, wt.ev_in, 0));
+  launch_deposit_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, first_index, deposits, w.d_inputs, (uint32_t)body);
+  if (tail)
+    launch_deposit_rows(ctx->stream, ctx->gk_table, ctx->hc, t->dev, first_index + body, deposits + body * SPP_DEPOSIT_LEN, wt.d_inputs, (uint32_t)tail);
+  HIP_TRY(hipEventRecord(w.ev_rows, ctx->stream));
+  HIP_TRY(hipStreamWaitEvent(w.st, w.ev_rows, 0));
+  if (tail) HIP_TRY(hipStreamWaitEvent(wt.st, w.ev_rows, 0));
+  const BatchIO io{(const uint8_t*)d_rs, (uint8_t*)d_proofs, (uint8_t*)d_pws, (uint32_t*)d_status};
+  if (int e = prove_on_device(c, w, body, w.d_inputs, io)) return e;
+  if (!tail) return SPP_OK;
+  return prove_on_device(c, wt, tail, wt.d_inputs, io.at(c, body));
+}
+// Host form: all rows are built (one launch) before spp_prove_batch proves them in chunks.
+extern "C" int spp_prove_deposits(spp_circuit* c, spp_merkle_tree* t, uint64_t first_index, size_t count, const uint8_t* deposits, const uint8_t* rs,
+                                  uint8_t* proofs, uint8_t* pws, int32_t* status) {
+  if (!c || !t || (count && (!deposits || !proofs || !pws))) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
+  if (int e = deposit_args(c, t)) return e;
+  if (count > (1u << 24)) return fail(SPP_ERR_BAD_INPUT, "too many deposits in one call (%zu; at most 2^24)", count);
+  std::vector<uint8_t> rows(std::max<size_t>(count, 1) * c->in_stride);
+  if (int e = spp_deposit_rows_from_tree(t, first_index, count, deposits, rows.data())) return e;   // the field and range refusals, also for count == 0
+  if (count == 0) return SPP_OK;
+  return spp_prove_batch(c, count, rows.data(), rs, proofs, pws, status);
+}
 extern "C" int spp_commitment_challenge(spp_circuit* c, size_t count, const uint8_t* inputs, uint8_t* challenges) {
   if (!c || !inputs || !challenges) return fail(SPP_ERR_BAD_INPUT, "NULL argument");
   if (count == 0) return SPP_OK;

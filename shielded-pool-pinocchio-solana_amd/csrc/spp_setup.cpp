@@ -17,6 +17,8 @@ extern "C" int spp_circuit_build(int circuit_id, const uint32_t* aux, const char
   } else if (circuit_id == SPP_CIRCUIT_AUDIT) {
     if (!aux) return fail(SPP_ERR_BAD_INPUT, "audit circuit needs the RLWE public key (aux)");
     c = build_audit_circuit(aux, aux + 1024, true);
+  } else if (circuit_id == SPP_CIRCUIT_DEPOSIT) {
+    c = build_deposit_circuit(true, SPP_TREE_DEPTH);
   } else {
     return fail(SPP_ERR_BAD_INPUT, "unknown circuit id %d", circuit_id);
   }

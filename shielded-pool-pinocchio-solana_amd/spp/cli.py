@@ -91,6 +91,21 @@ output-file naming (outputs land next to the circuit file, as sunspot writes the
                               # identity's record, then its withdraw), which pool-replay takes, and per record DIR/record_<s>.proof,
                               # record_<s>.pw and ciphertext_<s>.json, which audit-open takes.  --with-deposits: the log begins with
                               # the deposits of all leaves.  exit 1 if the circuit refused a row
+    python -m spp.cli compile deposit -o deposit.sppc                                           # the deposit circuit (include/spp.h)
+    python -m spp.cli deposit-prove deposits.jsonl deposit.sppc deposit.pk leaves.txt --out DIR
+                              # deposits.jsonl: one {"secretKey", "amount", "randomness"} per line; leaves.txt: the chain's leaves so
+                              # far, one hex leaf per line (may be empty).  Appends the deposits to a resident depth-16 tree and proves
+                              # each one (old_root, new_root, commitment, amount, index public).  Writes DIR/deposit_<i>.proof / .pw,
+                              # i = the leaf index, and DIR/log.jsonl with one line per deposit
+                              #   {"deposit": {"root", "commitment", "amount", "proof", "pw"}}
+                              # which deposit-verify takes and pool-replay reads as a deposit with a commitment (it ignores the other
+                              # keys).  The reference's program does not verify these proofs.  exit 1 if the circuit refused a row
+    python -m spp.cli deposit-verify deposit.vk log.jsonl [--start-root HEX --start-index N]
+                              # the log checked as a program keeping (current_root, leaf count) would, from the empty tree or the
+                              # given state: per line the pw amount against "amount", old_root against the current root, index
+                              # against the count, the proof; an accepted line advances the state, a rejected one does not.  Prints
+                              # one result name per line (OK, BAD_AMOUNT, STALE_ROOT, BAD_INDEX, BAD_PROOF); exit 1 names the first
+                              # line that is not OK
     python -m spp.cli setup-contribute <name>.pk <name>.vk --out DIR [--entropy HEX32]
                               # one contribution to a setup ceremony: multiplies the key's delta by a secret drawn from the operating
                               # system (--entropy: for reproducible tests only) and writes DIR/<name>.pk, DIR/<name>.vk and
@@ -1176,6 +1191,129 @@ def _withdraw_bundle(a):
     return 1 if refused else 0
 
 
+def parse_deposit_records(lines):
+    """[(secret_key, amount, randomness)] from the lines of a deposits.jsonl; ValueError names the line the library would refuse"""
+    out = []
+    for no, line in enumerate(lines, 1):
+        if not line.strip():
+            continue
+        try:
+            d = json.loads(line)
+            sk, amount, rnd = (_num(str(d[k])) for k in ("secretKey", "amount", "randomness"))
+        except (ValueError, KeyError, TypeError) as e:
+            raise ValueError("line %d: not a {secretKey, amount, randomness} record (%s)" % (no, e))
+        if not (0 < sk < R and 0 <= rnd < R and 0 <= amount < 1 << 64):
+            raise ValueError("line %d: secretKey in [1, r), randomness in [0, r), a 64-bit amount" % no)
+        out.append((sk, amount, rnd))
+    return out
+
+
+def parse_deposit_log(lines):
+    """[(line number, proof, pw, amount)] from the deposit lines of a deposit-prove log, other kinds skipped; ValueError names the line"""
+    out = []
+    for no, line in enumerate(lines, 1):
+        if not line.strip():
+            continue
+        try:
+            d = json.loads(line)
+            (kind, body), = d.items()
+            if kind != "deposit":
+                continue
+            unhex = lambda t: bytes.fromhex(t[2:] if t.lower().startswith("0x") else t)
+            proof, pw, amount = unhex(body["proof"]), unhex(body["pw"]), _num(str(body["amount"]))
+        except (ValueError, KeyError, TypeError, AttributeError) as e:
+            raise ValueError("line %d: not a proved deposit {root, commitment, amount, proof, pw} (%s)" % (no, e))
+        if len(proof) != lib.PROOF_LEN or len(pw) != lib.DEPOSIT_PW_LEN:
+            raise ValueError("line %d: deposit.proof must be %d bytes and deposit.pw %d" % (no, lib.PROOF_LEN, lib.DEPOSIT_PW_LEN))
+        if not 0 <= amount < 1 << 64:
+            raise ValueError("line %d: deposit.amount does not fit 64 bits" % no)
+        out.append((no, proof, pw, amount))
+    return out
+
+
+def _deposit_prove(a):
+    from . import witness
+    try:   # everything that can be wrong with the arguments and the files is found before a device is opened
+        deposits = parse_deposit_records(open(a.deposits).readlines())
+        if not deposits:
+            raise ValueError("%s holds no deposit" % a.deposits)
+        leaves = _hex_lines(a.leaves, "leaf")
+        if any(v >= R for v in leaves):
+            raise ValueError("%s: leaf %d is not a canonical field element" % (a.leaves, next(i for i, v in enumerate(leaves) if v >= R)))
+        if len(leaves) + len(deposits) > 1 << 16:
+            raise ValueError("%d leaves and %d deposits do not fit a tree of depth 16" % (len(leaves), len(deposits)))
+        for p in (a.sppc, a.pk):
+            open(p, "rb").close()
+        os.makedirs(a.out, exist_ok=True)
+    except (OSError, ValueError) as e:
+        print("spp deposit-prove: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    h = None
+    try:
+        h = ctx.load_circuit(a.sppc, a.pk, a.window)
+        with witness.ShieldedPoolMerkleTree(ctx, 16) as tree:
+            tree.insert_many(leaves)
+            first, commitments, roots, proofs, pws, status = tree.deposit_proved(h, deposits)
+    except (lib.SppError, ValueError) as e:
+        print("spp deposit-prove: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        if h is not None:
+            h.close()
+        ctx.close()
+    with open(os.path.join(a.out, "log.jsonl"), "w") as f:
+        for k, dep in enumerate(deposits):
+            open(os.path.join(a.out, "deposit_%d.proof" % (first + k)), "wb").write(proofs[k])
+            open(os.path.join(a.out, "deposit_%d.pw" % (first + k)), "wb").write(pws[k])
+            f.write(json.dumps({"deposit": {"root": "%064x" % roots[k], "commitment": "%064x" % commitments[k], "amount": dep[1],
+                                            "proof": proofs[k].hex(), "pw": pws[k].hex()}}) + "\n")
+    refused = [k for k, v in enumerate(status) if v]
+    print("deposit-prove: %d deposits at leaves %d .. %d, %d rows refused; %s" %
+          (len(deposits), first, first + len(deposits) - 1, len(refused), os.path.join(a.out, "log.jsonl")))
+    for k in refused:
+        print("deposit %d: the deposit circuit refuses it" % k)
+    return 1 if refused else 0
+
+
+def _deposit_verify(a):
+    from . import witness
+    try:   # everything that can be wrong with the files is found before a device is opened
+        vk = open(a.vk, "rb").read()
+        entries = parse_deposit_log(open(a.log).readlines())
+        start_root = None if a.start_root is None else _hex32(a.start_root, "--start-root")
+        if a.start_index < 0 or a.start_index >= 1 << 64:
+            raise ValueError("--start-index is a leaf count")
+    except (OSError, ValueError) as e:
+        print("spp deposit-verify: %s" % e, file=sys.stderr)
+        return 2
+    ctx = Context(a.device)
+    try:
+        if start_root is None:                       # the empty depth-16 tree (client/merkle.ts:150-156)
+            with witness.ShieldedPoolMerkleTree(ctx, 16) as tree:
+                start_root = tree.getRoot().to_bytes(32, "big")
+        codes = []
+        root, index = start_root, a.start_index
+        for i in range(0, len(entries), _POOL_LOG_CHUNK):
+            part = entries[i:i + _POOL_LOG_CHUNK]
+            c, root, index = witness.verify_deposit_chain(ctx, vk, [e[1] for e in part], [e[2] for e in part], root, index,
+                                                          lamports=[e[3] for e in part])
+            codes += c
+    except lib.SppError as e:
+        print("spp deposit-verify: %s" % e, file=sys.stderr)
+        return 2
+    finally:
+        ctx.close()
+    for c in codes:
+        print(lib.DEPOSIT_RESULT_NAMES[c])
+    bad = [(e[0], c) for e, c in zip(entries, codes) if c]
+    if bad:
+        print("spp deposit-verify: line %d: %s (%d of %d deposits not OK)" % (bad[0][0], lib.DEPOSIT_RESULT_NAMES[bad[0][1]], len(bad), len(codes)),
+              file=sys.stderr)
+        return 1
+    return 0
+
+
 def _verify_batch(a):
     try:   # everything that can be wrong with the files is found before a device is opened
         if not a.files or len(a.files) % 2:
@@ -1383,7 +1521,7 @@ def _ptau_verify(a):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="spp")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    c = sub.add_parser("compile"); c.add_argument("circuit", help="withdraw | audit | path of a nargo-compiled target/<name>.json (ACIR)")
+    c = sub.add_parser("compile"); c.add_argument("circuit", help="withdraw | audit | deposit | path of a nargo-compiled target/<name>.json (ACIR)")
     c.add_argument("--rlwe-pk"); c.add_argument("-o", "--out", default=None)
     s = sub.add_parser("setup"); s.add_argument("sppc"); s.add_argument("--seed", default=None); s.add_argument("--device", type=int, default=0)
     s.add_argument("--force", action="store_true", help="redo the setup even when matching keys exist")
@@ -1432,6 +1570,14 @@ def main(argv=None):
     wb.add_argument("--size", type=int, default=None, help="prove against the tree of the first SIZE leaves (a root the pool still holds)")
     wb.add_argument("--with-deposits", action="store_true", help="begin the log with one deposit line per leaf, so that it replays on a fresh pool")
     wb.add_argument("--window", type=int, default=0); wb.add_argument("--depth", type=int, default=16); wb.add_argument("--device", type=int, default=0)
+    dp = sub.add_parser("deposit-prove"); dp.add_argument("deposits", help="one {secretKey, amount, randomness} per line (JSON)")
+    dp.add_argument("sppc"); dp.add_argument("pk"); dp.add_argument("leaves", help="the leaves so far, one hex leaf per line, in chain order")
+    dp.add_argument("--out", required=True, metavar="DIR", help="log.jsonl and deposit_<i>.proof / .pw go here")
+    dp.add_argument("--window", type=int, default=0); dp.add_argument("--device", type=int, default=0)
+    dv = sub.add_parser("deposit-verify"); dv.add_argument("vk"); dv.add_argument("log", help="the log.jsonl of deposit-prove")
+    dv.add_argument("--start-root", default=None, metavar="HEX", help="the root before the first line (default: the empty depth-16 tree)")
+    dv.add_argument("--start-index", type=int, default=0, metavar="N", help="the leaf count before the first line")
+    dv.add_argument("--device", type=int, default=0)
     k = sub.add_parser("rlwe-keygen"); k.add_argument("--out", required=True, metavar="DIR")
     k.add_argument("--threshold", type=int, default=2); k.add_argument("--shares", type=int, default=3)
     k.add_argument("--reference-seed", type=int, default=None, metavar="N",
@@ -1536,6 +1682,10 @@ def main(argv=None):
         return _wallet_sync(a)
     if a.cmd == "withdraw-bundle":
         return _withdraw_bundle(a)
+    if a.cmd == "deposit-prove":
+        return _deposit_prove(a)
+    if a.cmd == "deposit-verify":
+        return _deposit_verify(a)
     if a.cmd == "compile" and a.circuit.endswith(".ccs"):
         from . import ccs
         c = ccs.load_ccs(a.circuit)
@@ -1548,7 +1698,7 @@ def main(argv=None):
         a.sppc = os.path.splitext(a.sppc)[0] + ".sppc"
         ccs.to_sppc(ccs.decode_system(c), c, a.sppc)
     if a.cmd == "compile":
-        if a.circuit not in ("withdraw", "audit"):
+        if a.circuit not in ("withdraw", "audit", "deposit"):
             # `sunspot compile target/<name>.json` (prove_linux.sh:66-70): the reference's own compiled ACIR -> R1CS
             from . import acir
             out = a.out or os.path.splitext(a.circuit)[0] + ".sppc"
@@ -1567,7 +1717,7 @@ def main(argv=None):
                 ap.error("audit needs --rlwe-pk (demo-frontend/public/rlwe/rlwe_pk.json)")
             pk = json.load(open(a.rlwe_pk))
             aux = [_num(str(x)) for x in pk["a"]] + [_num(str(x)) for x in pk["b"]]
-        n = build_circuit(lib.SPP_CIRCUIT_WITHDRAW if a.circuit == "withdraw" else lib.SPP_CIRCUIT_AUDIT, a.out, aux)
+        n = build_circuit({"withdraw": lib.SPP_CIRCUIT_WITHDRAW, "audit": lib.SPP_CIRCUIT_AUDIT, "deposit": lib.SPP_CIRCUIT_DEPOSIT}[a.circuit], a.out, aux)
         print("nbConstraints=%d" % n)
         return 0
     if a.cmd == "setup":

@@ -14,9 +14,18 @@ SPP_CIRCUIT_WITHDRAW = 1
 SPP_CIRCUIT_AUDIT = 2
 SPP_CIRCUIT_WITHDRAW_DEPTH20 = 4     # build only: withdraw over a depth-20 tree (synthetic variant)
 SPP_CIRCUIT_WITHDRAW_REFSHAPE = 3   # build only: withdraw padded to the reference's R1CS size (12 452 constraints)
+SPP_CIRCUIT_DEPOSIT = 6             # old_root | new_root | commitment | amount | index public; owner, randomness, siblings private
 PROOF_LEN = 388
 NOTE_LEN = 160                      # withdraw note: recipient | amount | secret_key | randomness | index
 DEPOSIT_LEN = 96                    # deposit: secret_key | amount | randomness
+DEPOSIT_PW_LEN = 172                # deposit public witness: header | old_root | new_root | commitment | amount | index
+DEPOSIT_INPUTS = 24                 # fields of a deposit row
+SPP_DEPOSIT_OK = 0                  # spp_verify_deposit_chain (include/spp.h)
+SPP_DEPOSIT_BAD_AMOUNT = 1
+SPP_DEPOSIT_STALE_ROOT = 2
+SPP_DEPOSIT_BAD_INDEX = 3
+SPP_DEPOSIT_BAD_PROOF = 4
+DEPOSIT_RESULT_NAMES = ("OK", "BAD_AMOUNT", "STALE_ROOT", "BAD_INDEX", "BAD_PROOF")
 AUDIT_PW_LEN = 76                   # audit public witness: header | wa_commitment | ct_commitment
 # spp_audit_open_batch: bits of flags[i] (include/spp.h)
 SPP_RLC_SERIAL_TAIL = 1     # spp_verify_batch_rlc flags (include/spp.h)
@@ -206,6 +215,11 @@ def load_library():
     L.spp_prove_withdraw_notes_at_device.argtypes = [vp, vp, u64, sz, vp, vp, vp, vp, vp]
     L.spp_prove_withdraw_notes_at.argtypes = [vp, vp, u64, sz, cp, cp, vp, vp, vp]
     L.spp_pool_root_sizes.argtypes = [vp, vp, vp, ctypes.POINTER(u64)]
+    # deposit proofs (include/spp.h)
+    L.spp_deposit_rows_from_tree.argtypes = [vp, u64, sz, cp, vp]
+    L.spp_prove_deposits_device.argtypes = [vp, vp, u64, sz, vp, vp, vp, vp, vp]
+    L.spp_prove_deposits.argtypes = [vp, vp, u64, sz, cp, cp, vp, vp, vp]
+    L.spp_verify_deposit_chain.argtypes = [vp, cp, sz, sz, cp, cp, vp, cp, u64, vp, vp, ctypes.POINTER(u64)]
     # withdrawals from notes: the audit plan, and both proofs in one call (include/spp.h)
     L.spp_withdrawal_audit_plan.argtypes = [vp, vp, sz, cp, vp, vp, ctypes.POINTER(u32)]
     L.spp_prove_withdrawals.argtypes = [vp, vp, vp, vp, u64, vp, vp, sz, cp, vp, vp, vp, cp, cp, vp, vp, vp, vp, vp, ctypes.POINTER(u32),

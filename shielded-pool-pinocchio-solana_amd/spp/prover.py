@@ -559,6 +559,31 @@ class CircuitHandle:
         else:
             check(self.L.spp_prove_withdraw_notes_at_device(self.h, tree.h, int(size), count, d_notes, d_rs, d_proofs, d_pws, d_status))
 
+    def prove_deposits(self, tree, first_index, deposits, rs=None):
+        """Deposit proofs (spp_prove_deposits) for leaves first_index .. first_index + len(deposits) - 1 of `tree`, which must already
+        hold them (tree.deposit first; ShieldedPoolMerkleTree.deposit_proved does both).  deposits: (secret_key, amount, randomness)
+        tuples.  Same return shape as prove_batch; the public witness is old_root | new_root | commitment | amount | index."""
+        from .witness import pack_deposits
+        count = len(deposits)
+        buf = pack_deposits(deposits)
+        rsb = None
+        if rs is not None:
+            rsb = b"".join(int(r).to_bytes(32, "big") + int(s).to_bytes(32, "big") for r, s in rs)
+        proofs = ctypes.create_string_buffer(PROOF_LEN * max(count, 1))
+        pws = ctypes.create_string_buffer(self.pw_len * max(count, 1))
+        status = (ctypes.c_int32 * max(count, 1))()
+        rc = self.L.spp_prove_deposits(self.h, tree.h, int(first_index), count, buf, rsb, ctypes.cast(proofs, ctypes.c_void_p),
+                                       ctypes.cast(pws, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p))
+        if rc != 0 and rc != SPP_ERR_UNSAT:
+            check(rc)
+        return ([proofs.raw[PROOF_LEN * i:PROOF_LEN * (i + 1)] for i in range(count)],
+                [pws.raw[self.pw_len * i:self.pw_len * (i + 1)] for i in range(count)], list(status)[:count])
+
+    def prove_deposits_device(self, tree, first_index, count, d_deposits, d_rs, d_proofs, d_pws, d_status):
+        """Deposit proofs from records resident on the device (spp_prove_deposits_device): asynchronous until sync().  Raw device
+        pointers (ints)."""
+        check(self.L.spp_prove_deposits_device(self.h, tree.h, int(first_index), count, d_deposits, d_rs, d_proofs, d_pws, d_status))
+
     def sync(self):
         check(self.L.spp_sync(self.h))
 

@@ -238,6 +238,27 @@ class ShieldedPoolMerkleTree:
             check(self.ctx.L.spp_withdraw_rows_from_tree_at(self.h, int(size), len(notes), buf, ctypes.cast(rows, ctypes.c_void_p)))
         return [_unbe(rows.raw[32 * n_in * i:], n_in) for i in range(len(notes))]
 
+    # ---- deposit proofs (include/spp.h): the reference's program checks nothing about a deposit
+    # (shielded_pool_program/src/instructions/deposit.rs:31-36,73) and does not verify these proofs; a program that does, an indexer or
+    # an auditor can ----
+    def deposit_rows(self, first_index, deposits):
+        """Rows of the deposit circuit for leaves first_index .. first_index + len(deposits) - 1, which the tree must already hold
+        (spp_deposit_rows_from_tree): per deposit [old_root, new_root, commitment, amount, index, owner_x, owner_y, randomness,
+        *siblings], the commitment computed from the record.  A record that is not the deposit at that index still gives a
+        self-consistent row; its new_root is then not the tree's (verify_deposit_chain is what binds a log to one tree)."""
+        buf = pack_deposits(deposits)
+        n_in = 8 + self.depth
+        rows = ctypes.create_string_buffer(32 * n_in * max(len(deposits), 1))
+        check(self.ctx.L.spp_deposit_rows_from_tree(self.h, int(first_index), len(deposits), buf, ctypes.cast(rows, ctypes.c_void_p)))
+        return [_unbe(rows.raw[32 * n_in * i:], n_in) for i in range(len(deposits))]
+
+    def deposit_proved(self, handle, deposits, rs=None):
+        """deposit(), then the proof of every one of those deposits with the deposit circuit `handle` (CircuitHandle.prove_deposits).
+        Returns (first, commitments, roots, proofs, pws, status)."""
+        first, commitments, roots = self.deposit(deposits)
+        proofs, pws, status = handle.prove_deposits(self, first, deposits, rs)
+        return first, commitments, roots, proofs, pws, status
+
     # ---- the tree as of an earlier size (include/spp.h): the root a deposit pushed is the root of the leaves its client knew,
     # client/payroll-demo.ts:285-292, and the program takes it as sent, shielded_pool_program/src/instructions/deposit.rs:31-36,73.
     # size: 0 .. len(self), or SPP_TREE_SIZE_NOW ----
@@ -493,6 +514,31 @@ class Pool:
         check(self.ctx.L.spp_pool_settle_log(self.h, n, bytes(kinds), nd, roots, na, ap, aw, nw, wp, ww, rb, ctypes.cast(res, ctypes.c_void_p),
                                              ctypes.cast(amounts, ctypes.c_void_p)))
         return list(res)[:n], [int(a) for a in amounts][:n]
+
+
+def verify_deposit_chain(ctx, vk, proofs, pws, start_root, start_index, lamports=None):
+    """A log of proved deposits checked as a program that keeps (current_root, leaf count) would (spp_verify_deposit_chain): every
+    proof through the batch verifier, then one after another -- the pw amount against lamports[i] (when given), old_root against the
+    current root, index against the count, the proof.  An accepted deposit moves the state to (its new_root, index + 1), a rejected
+    one moves nothing.  proofs, pws: lists of bytes (or one buffer each); start_root: int or 32 bytes.  Returns (codes, end_root int, end_index); codes
+    index lib.DEPOSIT_RESULT_NAMES.  No Pool is touched: feed the accepted new_roots to Pool.add_roots."""
+    from .lib import DEPOSIT_PW_LEN, PROOF_LEN
+    pb = _joined(proofs, PROOF_LEN, "proof")
+    wb = _joined(pws, DEPOSIT_PW_LEN, "public witness")
+    n = len(pb) // PROOF_LEN
+    if len(wb) != n * DEPOSIT_PW_LEN or (lamports is not None and len(lamports) != n):
+        raise ValueError("proofs, pws and lamports must have one entry per instruction")
+    start = start_root if isinstance(start_root, (bytes, bytearray)) else int(start_root).to_bytes(32, "big")
+    if len(start) != 32:
+        raise ValueError("start_root is 32 bytes")
+    lam = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in lamports]) if lamports is not None else None
+    codes = (ctypes.c_uint32 * max(n, 1))()
+    end_root = ctypes.create_string_buffer(32)
+    end_index = ctypes.c_uint64(0)
+    check(ctx.L.spp_verify_deposit_chain(ctx.h, bytes(vk), len(vk), n, pb, wb, ctypes.cast(lam, ctypes.c_void_p) if lam is not None else None,
+                                         bytes(start), int(start_index), ctypes.cast(codes, ctypes.c_void_p),
+                                         ctypes.cast(end_root, ctypes.c_void_p), ctypes.byref(end_index)))
+    return list(codes)[:n], int.from_bytes(end_root.raw, "big"), int(end_index.value)
 
 
 def merkle_build(ctx, leaves, queries, depth=TREE_DEPTH):
