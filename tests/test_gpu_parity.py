@@ -962,22 +962,9 @@ def test_pippenger_matches_oracle_and_is_linear(ctx):
     assert B.g1_to_bytes(B.g1_mul(B.g1_from_bytes(r1), k)) == r2
     # and against the oracle on a 2^12 prefix-sized instance of the same generator
     r3, _, _ = ctx.msm_g1_pippenger_bench(1 << 12, seed=9)
-    x = (9 * 6364136223846793005 + 1442695040888963407) % (1 << 64)
-    def nxt():
-        nonlocal x
-        x = (x * 6364136223846793005 + 1442695040888963407) % (1 << 64)
-        return x
-    ks, ss = [], []
-    for _ in range(1 << 12):
-        ks.append(nxt() | 1)
-        w = []
-        for _ in range(4):
-            v = nxt(); w += [v & 0xffffffff, v >> 32]
-        w[7] &= 0x1fffffff
-        ss.append(sum(l << (32 * i) for i, l in enumerate(w)))
-    # the generator writes raw limbs into Montgomery storage: the field element is limbs * 2^-256
-    rinv = pow(1 << 256, -1, B.R)
-    ss = [s * rinv % B.R for s in ss]
+    # (the generator writes raw limbs into Montgomery storage: the field element is limbs * 2^-256 -- tests/pippenger_model.py)
+    from pippenger_model import bench_points
+    ks, ss = zip(*bench_points(1 << 12, 9, 0))
     out = ctypes.create_string_buffer(64)
     basesb = b"".join(B.g1_to_bytes(B.g1_mul(B.G1_GEN, kk)) for kk in ks)
     native.lib().orc_msm_g1(basesb, b"".join(s.to_bytes(32, "big") for s in ss), 1 << 12, ctypes.cast(out, ctypes.c_void_p))
@@ -1046,23 +1033,8 @@ def test_pippenger_skewed_scalars(ctx):
     assert ctx.msm_g1_pippenger(bases[:64 * 512], sc2) == out.raw
     # the synthetic generator with 70 % byte-sized scalars: oracle on 2^12, linearity on 2^18
     r3, _, _ = ctx.msm_g1_pippenger_bench(1 << 12, seed=9, small_permille=700)
-    x = (9 * 6364136223846793005 + 1442695040888963407) % (1 << 64)
-    def nxt():
-        nonlocal x
-        x = (x * 6364136223846793005 + 1442695040888963407) % (1 << 64)
-        return x
-    rinv = pow(1 << 256, -1, B.R)
-    ks, ss = [], []
-    for _ in range(1 << 12):
-        ks.append(nxt() | 1)
-        w = []
-        for _ in range(4):
-            v = nxt(); w += [v & 0xffffffff, v >> 32]
-        w[7] &= 0x1fffffff
-        if (nxt() >> 20) % 1000 < 700:
-            ss.append(w[0] & 0xff)
-        else:
-            ss.append(sum(l << (32 * i) for i, l in enumerate(w)) * rinv % B.R)
+    from pippenger_model import bench_points
+    ks, ss = zip(*bench_points(1 << 12, 9, 700))
     assert sum(1 for v in ss if v < 256) > 2500
     basesb = b"".join(B.g1_to_bytes(B.g1_mul(B.G1_GEN, kk)) for kk in ks)
     native.lib().orc_msm_g1(basesb, b"".join(s.to_bytes(32, "big") for s in ss), 1 << 12, ctypes.cast(out, ctypes.c_void_p))
